@@ -1,10 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X UIS-RNN decode path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (uisrnn.UISRNN.predict over a list,
-uisrnn/uisrnn.py:564-590) over one batch of synthetic utterances.  --config picks
+uisrnn/uisrnn.py:564-590) over one batch of synthetic utterances.  A plain run sets up,
+warms up, times exactly K steps of the timed leg and prints the line; everything else the
+line can carry (the other two legs, roofline, cpu_baseline, extra_configs and the counter
+sub-runs behind roofline.traffic) is measured only with --full.  --dump-outputs DIR writes
+what the timed leg returned in its last step (rank 0) as DIR/<name>.npy: labels and scores,
+float32, and with more than one rank the gathered labels of every rank; the inputs are
+seeded, so two builds can be compared array for array.  --config picks
 the BASELINE.json `configs[i]` workload (per GPU):
 
   1 (default)  64 utterances x 500 frames x 256-dim, beam 10, look_ahead 1   <- the metric's config
@@ -21,7 +27,8 @@ torchrun (the driver's launch) it reads RANK / LOCAL_RANK / WORLD_SIZE.  It refu
 run when fewer than N HIP devices are visible.  Every rank pins itself to its share of the
 host cores (the library's float64 -> float32 cast threads follow the affinity mask).
 
-What the ONE JSON line (rank 0) says, field by field:
+What the ONE JSON line (rank 0) says, field by field (the fields of the other legs, roofline,
+cpu_baseline and extra_configs are null without --full):
   value                 frames/s of the whole job through the entry UISRNN.predict uses
                         (uis_decode_f64: the list of float64 arrays the caller holds; cast + H2D of
                         the frames + decode + D2H of the labels inside the clock) -- the quantity
@@ -173,11 +180,11 @@ def measured_traffic(argv, timeout_s=180):
     if skip_next:
       skip_next = False
       continue
-    if a in ('--steps', '--warmup', '--gpus', '--timed', '--cpu_sample', '--backend'):
+    if a in ('--steps', '--warmup', '--gpus', '--timed', '--cpu_sample', '--backend', '--dump-outputs'):
       skip_next = True
       continue
     if a in ('--no_cpu_baseline', '--no_host_buffers', '--no_extra_configs', '--force_dist', '--check_gather',
-             '--allow_shared_device'):
+             '--allow_shared_device', '--full') or a.startswith('--dump-outputs='):
       continue
     keep.append(a)
   env = dict(os.environ, UIS_BENCH_CHILD='1', TMPDIR='/tmp')
@@ -186,8 +193,9 @@ def measured_traffic(argv, timeout_s=180):
   for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
     out_dir = tempfile.mkdtemp(prefix='uis_pmc_', dir='/tmp')
     try:
+      # (--full: the sub-run's line must name its kernel, roofline.kernel)
       cmd = [prof, '--kernel-trace', '--pmc', counter, '-d', out_dir, '-o', 'p', '--output-format', 'csv', '--',
-             sys.executable, os.path.abspath(__file__)] + keep + [
+             sys.executable, os.path.abspath(__file__)] + keep + ['--full',
                  '--timed', 'device', '--steps', '1', '--warmup', '0', '--no_cpu_baseline', '--no_host_buffers', '--no_extra_configs']
       # (no check of the exit status: under --pmc the profiled interpreter can die in its exit handlers AFTER the counter
       # files are complete -- seen on this image, also from a shell; what decides is whether the kernel's rows are there)
@@ -306,6 +314,11 @@ def parse(argv=None):
   ap.add_argument('--check_gather', action='store_true',
                   help='rank 0 compares the gathered labels of EVERY rank, all utterances, with the CPU oracle '
                        '(outside the timed regions) and puts the verdict into the line (`gather_check`)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline does not need: the other two legs, roofline (with the '
+                       'counter sub-runs), cpu_baseline and extra_configs')
+  ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                  help='write what the timed leg returned in its last step as DIR/<name>.npy (rank 0)')
   return ap.parse_args(argv)
 
 
@@ -316,12 +329,15 @@ def free_port():
 
 
 def respawn_under_torchrun(n_gpus, argv):
-  """--gpus N without a launcher: one rank per GPU through torch.distributed.run."""
+  """--gpus N without a launcher: one rank per GPU through torch.distributed.run, started as a child
+  process (this one has already asked the HIP runtime for its devices); exits with the launcher's status."""
+  import subprocess  # pylint: disable=import-outside-toplevel
   cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', str(n_gpus), '--master-addr', '127.0.0.1',
          '--master-port', str(free_port()), os.path.abspath(__file__)] + list(argv)
-  os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-  os.execv(sys.executable, cmd)
+  env = dict(os.environ)
+  env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
+  raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def pin_rank_to_cores(local_rank, local_world):
@@ -608,6 +624,25 @@ def run_extra_config(index, args, rank, dev, dev_index, sync_fn):
   return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+  """--dump-outputs: every array as float32 DIR/<name>.npy (labels are small integers: exact).  Should they
+  hold more than `budget` bytes in all, each keeps the same fixed share of its elements, drawn with a fixed
+  seed; the positions drawn go to DIR/<name>_index.npy (float64)."""
+  os.makedirs(out_dir, exist_ok=True)
+  arrays = {k: np.ascontiguousarray(v, dtype=np.float32).ravel() for k, v in arrays.items() if v is not None}
+  total = sum(v.nbytes for v in arrays.values())
+  keep = min(1.0, budget / (3.0 * total)) if total else 1.0   # (3x: a float64 position beside every float32 kept)
+  for name, v in arrays.items():
+    if keep < 1.0:
+      idx = np.sort(np.random.default_rng(0).choice(v.size, int(v.size * keep), replace=False))
+      np.save(os.path.join(out_dir, name + '_index.npy'), idx.astype(np.float64))
+      v = v[idx]
+    np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def main(argv=None):
   args = parse(argv)
   env_world = os.environ.get('WORLD_SIZE')
@@ -629,7 +664,7 @@ def main(argv=None):
   # HBM traffic of the dominant kernel, measured for THIS command where rocprofv3 is there (two counter sub-runs of a
   # few seconds each, BEFORE this process creates its HIP context); otherwise the newest committed record stays
   live_traffic = None
-  if world == 1 and rank == 0 and args.device == 'cuda':
+  if args.full and world == 1 and rank == 0 and args.device == 'cuda':
     live_traffic = measured_traffic(sys.argv[1:] if argv is None else list(argv))
 
   import torch  # device memory + torch.distributed only
@@ -702,16 +737,23 @@ def main(argv=None):
     if w.d_labels.numel() < width:
       w.d_labels = torch.empty(width, dtype=torch.int32, device=dev)
   gathered = (torch.empty(world * max(width, 1), dtype=torch.int32, device=gather_dev) if use_dist else None)
+  rank_frames = [w.rank_frames]
+  if use_dist and args.dump_outputs:  # (--dump-outputs: every rank's share of the padded gather, padding left out)
+    every = torch.empty(world, dtype=torch.int64, device=gather_dev)
+    dist.all_gather_into_tensor(every, torch.tensor([w.rank_frames], dtype=torch.int64, device=gather_dev))
+    rank_frames = every.tolist()
 
   # ---- the three legs of one pass (all end with the labels of this rank's utterances):
   #   predict_f64   uis_decode_f64 from the float64 arrays predict() receives (cast + H2D + decode + D2H)
   #   host_buffers  uis_decode from pinned float32 (H2D + decode + D2H)
   #   device        uis_decode_device, frames and labels resident in HBM
   # (which legs run is a JOB-wide decision -- every leg's timed region issues barriers and gathers, so a rank
-  # without utterances still enters every leg and takes part in its collectives with an empty decode)
+  # without utterances still enters every leg and takes part in its collectives with an empty decode; without
+  # --full only the timed leg runs)
   want_host = not args.no_host_buffers
+  timed_leg = args.timed if want_host else 'device'
   host = {}
-  if w.n_utt and want_host:
+  if w.n_utt and want_host and (args.full or timed_leg == 'host_buffers'):
     pin = (lambda t: t.pin_memory()) if on_gpu else (lambda t: t)
     host['frames'] = pin(torch.from_numpy(w.frames))
     host['labels'] = pin(torch.empty(max(w.rank_frames, 1), dtype=torch.int32))
@@ -755,7 +797,6 @@ def main(argv=None):
   if want_host:
     legs['host_buffers'] = host_step
     legs['predict_f64'] = f64_step
-  timed_leg = args.timed if args.timed in legs else 'device'   # (--no_host_buffers)
 
   setup_passes, setup_ms = w.setup(sync_fn)
   w.timing = True
@@ -764,13 +805,27 @@ def main(argv=None):
   ms_per_step = 1e3 * elapsed / max(steps, 1)
   value = w.job_frames * steps / elapsed
   rates = {timed_leg: value}
+  if args.dump_outputs and rank == 0:
+    # what the timed leg's last step returned to its caller (before any other leg overwrites the buffers)
+    if timed_leg == 'predict_f64':
+      last = f64_out.get('r', {})
+      outputs = {'labels': last.get('labels'), 'scores': last.get('scores')}
+    elif timed_leg == 'host_buffers':
+      outputs = ({'labels': host['labels'].numpy()[:w.rank_frames], 'scores': host['scores'].numpy()[:w.n_utt]}
+                 if host else {})
+    else:
+      outputs = {'labels': w.d_labels[:w.rank_frames].cpu().numpy(), 'scores': w.d_scores[:w.n_utt].cpu().numpy()}
+    if gathered is not None:
+      every = gathered.cpu().numpy().reshape(world, max(width, 1))
+      outputs['labels_all_ranks'] = np.concatenate([every[r, :n] for r, n in enumerate(rank_frames)])
+    dump_outputs(args.dump_outputs, outputs)
   # ---- the other legs, same passes, every rank (a multi-GPU line carries all three rates too)
   n_other = max(steps // 2, 1)
   for name in ('device', 'host_buffers', 'predict_f64'):
-    if name in legs and name not in rates:
+    if args.full and name in legs and name not in rates:
       el = timed_region(legs[name], sync_fn, n_other, 1, dist, gather_dev)
       rates[name] = w.job_frames * n_other / el
-  if host:  # the three legs decoded the same utterances: same labels
+  if host and args.full:  # the three legs decoded the same utterances: same labels
     dev_labels = w.d_labels[:w.rank_frames].cpu().numpy()
     if w.rank_frames and not (np.array_equal(host['labels'].numpy()[:w.rank_frames], dev_labels) and
                               np.array_equal(f64_out['r']['labels'], dev_labels)):
@@ -779,12 +834,14 @@ def main(argv=None):
 
   result = None
   if rank == 0:
-    roofline = w.roofline(rates['device'] / world)  # (the path fractions are the HBM-resident leg's)
-    if live_traffic and live_traffic.pop('kernel') == roofline['kernel']:
-      roofline['traffic'] = live_traffic   # (measured for this very command, before this process took the device)
+    roofline = None
+    if args.full:
+      roofline = w.roofline(rates['device'] / world)  # (the path fractions are the HBM-resident leg's)
+      if live_traffic and live_traffic.pop('kernel') == roofline['kernel']:
+        roofline['traffic'] = live_traffic   # (measured for this very command, before this process took the device)
     # ---- CPU baseline: the oracle on this box's cores, bounded sample
     cpu = None
-    if not args.no_cpu_baseline and on_gpu:
+    if args.full and not args.no_cpu_baseline and on_gpu:
       # (N > 1: the timed regions are closed; the other ranks wait at the final barrier while rank 0
       # times the oracle on ITS share of the host cores)
       cores = rank_cores if world > 1 else (os.cpu_count() or 1)
@@ -809,7 +866,7 @@ def main(argv=None):
     if args.check_gather:
       gather_check = check_gathered_labels(cfg, args, world, w, gathered, width)
     extras = None
-    if (not args.no_extra_configs and world == 1 and on_gpu and args.config == 1 and not args.ragged and
+    if (args.full and not args.no_extra_configs and world == 1 and on_gpu and args.config == 1 and not args.ragged and
         args.utterances is None and args.frames is None and args.beam_size is None and args.rnn_depth is None and
         args.look_ahead is None and args.max_clusters is None and args.rnn_hidden_size is None):
       first = w.last

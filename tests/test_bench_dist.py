@@ -108,14 +108,8 @@ _MAIN_SCRIPT = textwrap.dedent('''
 import pytest
 
 
-@pytest.mark.parametrize('extra', [[], ['--config', '3'], ['--timed', 'device']],
-                         ids=['config1_predict_f64', 'config3_ragged', 'timed_device'])
-def test_bench_main_world_2_gloo_with_a_stand_in_decoder(tmp_path, extra):
-  """bench.main() itself, two ranks over gloo: launch plumbing, per-rank core pinning, ragged
-  utterances dealt by shard_utterances, the padded label gather, the timed region over the
-  float64-list leg on EVERY rank (the multi-GPU line is PCIe-inclusive), the other two legs, ONE
-  JSON line from rank 0 with the per-rank spread -- for configs[1] and for the configs[3] share
-  (`--config 3 --ragged`, the driver's 8-GPU workload).  (The decode is a stand-in: no GPU here.)"""
+def _bench_main_world_2(tmp_path, extra):
+  """_MAIN_SCRIPT under torch.distributed.run, two ranks over gloo: rank 0's JSON line."""
   script = tmp_path / 'main_rank.py'
   script.write_text(_MAIN_SCRIPT.format(root=ROOT, extra=extra))
   import json
@@ -134,7 +128,57 @@ def test_bench_main_world_2_gloo_with_a_stand_in_decoder(tmp_path, extra):
   assert out.returncode == 0, out.stderr[-3000:]
   lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
   assert len(lines) == 1, out.stdout[-2000:]
-  rec = json.loads(lines[0])
+  return json.loads(lines[0])
+
+
+def test_plain_run_times_only_its_leg_and_dumps_what_it_returned(tmp_path):
+  """Without --full the line carries the timed leg alone (no other legs, roofline, CPU baseline or extra configs),
+  and --dump-outputs writes what that leg returned in its last step: rank 0's labels and the gathered labels of
+  both ranks, the padding of the ragged gather left out, float32."""
+  import numpy as np
+  out_dir = tmp_path / 'out'
+  rec = _bench_main_world_2(tmp_path, ['--dump-outputs', str(out_dir)])
+  assert rec['steps'] == 2 and rec['warmup'] == 1 and rec['ms_per_step'] > 0
+  assert rec['value_leg'] == 'predict_f64' and rec['value'] == rec['value_predict_f64'] > 0
+  assert rec['value_host_buffers'] is None and rec['value_device'] is None
+  assert rec['roofline'] is None and rec['cpu_baseline'] is None and rec['extra_configs'] is None
+  assert sorted(os.listdir(out_dir)) == ['labels.npy', 'labels_all_ranks.npy']
+  own = np.load(out_dir / 'labels.npy')
+  every = np.load(out_dir / 'labels_all_ranks.npy')
+  assert own.dtype == every.dtype == np.float32
+  assert 3 * 12 <= own.size <= 3 * 24 and (own == 7).all()            # the stand-in's labels: rank + 7
+  assert 6 * 12 <= every.size <= 6 * 24
+  assert (every[:own.size] == 7).all() and (every[own.size:] == 8).all()
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_its_budget(tmp_path):
+  sys.path.insert(0, ROOT)
+  import bench
+  import numpy as np
+  big = np.arange(100_000, dtype=np.int32)
+  for sub in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / sub), {'labels': big, 'scores': np.ones(10, np.float32), 'none': None},
+                       budget=120_000)
+  files = sorted(os.listdir(tmp_path / 'a'))
+  assert files == ['labels.npy', 'labels_index.npy', 'scores.npy', 'scores_index.npy']
+  assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 120_000 + 4 * 128   # (+ the .npy headers)
+  for f in files:
+    assert np.array_equal(np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f))   # the same sample every time
+  idx, kept = np.load(tmp_path / 'a' / 'labels_index.npy'), np.load(tmp_path / 'a' / 'labels.npy')
+  assert idx.dtype == np.float64 and kept.dtype == np.float32 and np.array_equal(kept, idx.astype(np.float32))
+  bench.dump_outputs(str(tmp_path / 'c'), {'labels': big[:10]})
+  assert os.listdir(tmp_path / 'c') == ['labels.npy'] and np.array_equal(np.load(tmp_path / 'c' / 'labels.npy'), big[:10])
+
+
+@pytest.mark.parametrize('extra', [[], ['--config', '3'], ['--timed', 'device']],
+                         ids=['config1_predict_f64', 'config3_ragged', 'timed_device'])
+def test_bench_main_world_2_gloo_with_a_stand_in_decoder(tmp_path, extra):
+  """bench.main() itself, two ranks over gloo: launch plumbing, per-rank core pinning, ragged
+  utterances dealt by shard_utterances, the padded label gather, the timed region over the
+  float64-list leg on EVERY rank (the multi-GPU line is PCIe-inclusive), the other two legs, ONE
+  JSON line from rank 0 with the per-rank spread -- for configs[1] and for the configs[3] share
+  (`--config 3 --ragged`, the driver's 8-GPU workload), with `--full`.  (The decode is a stand-in: no GPU here.)"""
+  rec = _bench_main_world_2(tmp_path, ['--full'] + extra)
   assert rec['n_gpus'] == 2 and rec['steps'] == 2 and rec['warmup'] == 1
   assert rec['scaling'] == 'weak' and rec['unit'] == 'frames/s'
   assert rec['per_rank_ms']['min'] <= rec['per_rank_ms']['max'] <= rec['ms_per_step'] * 1.5

@@ -178,7 +178,7 @@ def _torchrun_bench(extra, backend='gloo', nproc=2, timeout=900):
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(nproc),
          '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(_ROOT, 'bench.py'),
          '--gpus', str(nproc), '--allow_shared_device', '--backend', backend, '--check_gather',
-         '--no_cpu_baseline', '--no_extra_configs'] + list(extra),
+         '--full', '--no_cpu_baseline', '--no_extra_configs'] + list(extra),
         capture_output=True, text=True, timeout=timeout, cwd=_ROOT, env=env)
     if out.returncode == 0:
       break
@@ -192,6 +192,31 @@ def _record(name, text):
       f.write(text)
   except OSError:
     pass
+
+
+def test_plain_benchmark_run_dumps_what_it_timed(oracle_lib, tmp_path):
+  """bench.py without --full: one line for exactly the steps asked for, nothing measured beside the timed leg, and
+  --dump-outputs holds what that leg (uis_decode_f64) returned in its last step -- labels and scores identical to
+  the CPU oracle on the same seeded utterances and the same model."""
+  out_dir = tmp_path / 'out'
+  out = subprocess.run([sys.executable, os.path.join(_ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--utterances', '8', '--frames', '120', '--dump-outputs', str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=_ROOT)
+  assert out.returncode == 0, out.stderr[-3000:]
+  rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
+  assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['ms_per_step'] > 0
+  assert rec['value_leg'] == 'predict_f64' and rec['value_device'] is None and rec['roofline'] is None
+  if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+  import bench  # pylint: disable=import-outside-toplevel
+  cfg = dict(bench.CONFIGS[1], utterances_per_gpu=8, frames=120)
+  params, _ = bench.load_model(cfg, 'auto')
+  seqs, _ = bench.rank_sequences(cfg, bench.parse([]), 0, 1)
+  ref = oracle_lib.decode(params, seqs, 10, 1, 2, n_threads=8)
+  labels, scores = np.load(out_dir / 'labels.npy'), np.load(out_dir / 'scores.npy')
+  assert labels.dtype == scores.dtype == np.float32
+  assert np.array_equal(labels, np.concatenate(ref['labels']).astype(np.float32))
+  assert np.array_equal(scores.view(np.uint32), ref['scores'].view(np.uint32))
 
 
 @pytest.mark.parametrize('extra', [['--steps', '3', '--warmup', '1'],

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-Q="--no_cpu_baseline --no_host_buffers --no_extra_configs"
+Q="--full --no_cpu_baseline --no_host_buffers --no_extra_configs"
 val() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline'].get('frac'))" "$1" 2>/dev/null; }
 echo "=== suite"; timeout 200 python -m pytest tests -m gpu -x -q > gpurun_out/refill_pytest.log 2>&1; echo "pytest rc=$?" >> gpurun_out/refill_pytest.log; tail -4 gpurun_out/refill_pytest.log
 echo "=== default bench"; timeout 200 python bench.py > gpurun_out/refill_bench_c1.json 2> gpurun_out/refill_bench_c1.err; echo "rc=$? $(val gpurun_out/refill_bench_c1.json)"

@@ -28,9 +28,9 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$REPO" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-BENCH_QUIET="--no_cpu_baseline --no_host_buffers --no_extra_configs"
+BENCH_QUIET="--full --no_cpu_baseline --no_host_buffers --no_extra_configs"   # (--full: the lines name roofline.kernel / frac)
 
-value_of() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline'].get('frac'))" "$1" 2>/dev/null; }
+value_of() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d['roofline'] or {}; print(d['value'], d['ms_per_step'], r.get('kernel'), r.get('frac'))" "$1" 2>/dev/null; }
 
 run_one() {
   local exp=$1; shift
@@ -91,7 +91,7 @@ for u in us:
       k, _, v = a.partition('=')
       e[k] = v
     r = subprocess.run([sys.executable, 'bench.py', '--utterances', str(u), '--frames', frames, '--timed', 'device', '--steps', '3', '--warmup', '1',
-                        '--no_cpu_baseline', '--no_host_buffers', '--no_extra_configs'] + os.environ.get('SWEEP_ARGS', '').split(),
+                        '--full', '--no_cpu_baseline', '--no_host_buffers', '--no_extra_configs'] + os.environ.get('SWEEP_ARGS', '').split(),
                        capture_output=True, text=True, env=e)
     try:
       d = json.loads(r.stdout.strip().splitlines()[-1])
