@@ -150,14 +150,9 @@ typedef struct uis_decode_opts {
                                     cluster-wide barriers between GRU, linear_mean1 and linear_mean2 instead of
                                     the per-producer phase words (a consumer wave waits for the four workgroups
                                     that produce its K-slice); A/B switch, results are bit-identical either way */
-#define UIS_FLAG_COHORTS 0x10000u /* one-launch decode with many utterances per XCD (where k_decode_big<WS> applies): run an
-                                    XCD's utterances as TWO cohorts whose stages alternate on every workgroup, the selects
-                                    riding on the other cohort's dense phases, row tiles pulled from LDS counters, no
-                                    workgroup barrier in the step loop (k_decode_coh, UIS_DK_BIG_COH).  Bit-identical;
-                                    measured SLOWER than the lock-step batch on MI355X (3.8 against 4.0 M frames/s at
-                                    1024 utterances: DESIGN.md / LABNOTES.md): since round 6 the kernel is compiled only
-                                    into builds with -DUIS_WITH_COHORTS (uis_build_flags() & UIS_BUILD_COHORTS; the test
-                                    variant build/variants/cohorts.so); the product library ignores the flag          */
+#define UIS_FLAG_COHORTS 0x10000u /* accepted and ignored: the bit is reserved.  It once selected k_decode_coh (two utterance
+                                    cohorts in flight per XCD), which measured slower than k_decode_big<WS> and was removed;
+                                    a decode with the flag runs exactly as one without it                               */
 #define UIS_FLAG_AGENT_FLAGS 0x20000u /* one-launch decode: publish the per-producer phase words of the dense-stage hand-offs
                                     with an AGENT-scope store (`global_store sc1`: the HIP memory model's by-the-book form for
                                     a word other workgroups read) instead of the workgroup-scope store that stays in the
@@ -212,11 +207,11 @@ enum {
   UIS_DK_SMALL = 6,      /* one launch, one workgroup per utterance: small models, any rnn_depth, any look_ahead (k_decode_small) */
   UIS_DK_WINDOW = 7,     /* one launch, look_ahead >= 2: a window sub-step as the select stage (k_decode_big<WIN>) */
   UIS_DK_DEEP = 8,       /* one launch, rnn_depth >= 2 at hidden size 128 / 256 / 512: the weight slot refilled per stage (k_decode_deep) */
-  UIS_DK_BIG_COH = 9     /* one launch, a wave per row tile, two utterance cohorts in flight per XCD (k_decode_coh; UIS_FLAG_COHORTS) */
+  UIS_DK_BIG_COH = 9     /* reserved, never reported (was k_decode_coh, removed)                 */
 };
 /* ... in bits 16..23 for UIS_DK_RS its instantiation: 1 base, 2 base with the shape of BASELINE configs[1] as
  * compile-time constants, 3 two utterances per wave (9 .. 16 per XCD), 4 wide (beam_size <= 32 / observation
- * dim 512); and, in bits 8..15 for UIS_DK_STEPWISE, the dense kernels' family */
+ * dim 512); 5 and 6 are reserved (never reported); and, in bits 8..15 for UIS_DK_STEPWISE, the dense kernels' family */
 enum { UIS_DF_DENSE = 1 /* k_dense_* split-K */, UIS_DF_BIG = 2 /* k_big_* */, UIS_DF_WT = 3 /* k_wt_* */ };
 
 /* kernel classes for uis_stats.kernel_ms */
@@ -238,8 +233,8 @@ int32_t uis_abi_version(void);
 /* UIS_NUMERICS_VERSION of include/uis_numerics.h this library was built with. */
 int32_t uis_numerics_version(void);
 
-/* What this binary was built with (round 6): a mask of UIS_BUILD_*. */
-#define UIS_BUILD_COHORTS 0x1u  /* -DUIS_WITH_COHORTS: k_decode_coh is there and UIS_FLAG_COHORTS selects it */
+/* What this binary was built with: a mask of UIS_BUILD_* (none is defined at present: always 0). */
+#define UIS_BUILD_COHORTS 0x1u  /* reserved, never set (was: k_decode_coh compiled in) */
 uint32_t uis_build_flags(void);
 
 /* Number of visible HIP devices (0 if none / runtime unusable). */

@@ -375,9 +375,8 @@ struct Launcher {
 // One batched CoreRNN evaluation over the rows emitted for step parity `par`.
 // Which family of dense kernels the launch-per-step path runs for a step of at most `max_rows`
 // rnn rows (UIS_DF_*; uis_stats.decode_kernel reports it).
-int dense_family(const uis_handle* h, uint32_t flags, long max_rows) {
-  const DevModel& m = h->m;
-  if (max_rows > UIS_WT_ROWS && (m.Hp == 512 || m.Hp == 256) && m.Dp % 16 == 0 && !(flags & UIS_FLAG_SMALL_TILES) && h->n_cu >= 64)
+int dense_family(const DevModel& m, int n_cu, uint32_t flags, long max_rows) {
+  if (max_rows > UIS_WT_ROWS && (m.Hp == 512 || m.Hp == 256) && m.Dp % 16 == 0 && !(flags & UIS_FLAG_SMALL_TILES) && n_cu >= 64)
     return UIS_DF_WT;
   if (max_rows > UIS_WIDE_TILE_ROWS && (m.Hp / 16) % 4 == 0 && (m.Dp / 16) % 4 == 0 && !(flags & UIS_FLAG_SMALL_TILES))
     return UIS_DF_BIG;
@@ -388,7 +387,7 @@ int launch_rnn(uis_handle* h, Launcher& lch, const DecodeState& st, int par, lon
   const DevModel& m = h->m;
   const int mr = (int)max_rows;
   const bool wide = max_rows > UIS_WIDE_TILE_ROWS;  // tile shape, see uis_kernels.hip
-  const int family = dense_family(h, st.flags, max_rows);
+  const int family = dense_family(m, h->n_cu, st.flags, max_rows);
   // thousands of rows: the big-tile kernels (4 row tiles x several feature tiles per workgroup,
   // full-K chains per wave) where the feature-tile counts divide
   // thousands of rows and hidden size 256 / 512: weights in LDS, a wave per row tile (k_wt_*)
@@ -674,10 +673,458 @@ struct CastPool {
   }
 };
 
+// ---- which kernels decode a list: plan_decode() decides, decode_once() carries the plan out
+
+// The environment switches the decode path honours, read once per decode, at the top of decode_once (tests change
+// os.environ between calls).
+//   UIS_MAX_STATE_BYTES   a smaller ceiling on the decode state, for tests of the host layer's answer (halving)
+//   UIS_SPLIT_MIN_MB      list size from which a host list is decoded in slices (tests, experiments)
+//   UIS_SPLIT_FRAMES      a,b,..: the slice boundaries instead of the library's schedule
+//   UIS_NO_SPLIT          one launch (A/B switch, bit-identical)
+//   UIS_NO_ARENA, UIS_ARENA_SHIFT, UIS_NO_CTL_TUNE, UIS_CTL_OFFSET   buffer placement (tools/experiments/bimodal.py)
+//   UIS_AGENT_FLAGS       (read once per process) UIS_FLAG_AGENT_FLAGS on every decode
+struct DecodeKnobs {
+  double max_state_bytes = 200e9, split_min_bytes = 0.0;
+  bool split_min_set = false, split_frames_set = false, no_split = false, no_arena = false, no_ctl_tune = false;
+  bool ctl_offset_set = false, agent_flags = false;
+  std::vector<long> split_frames;
+  size_t arena_shift = 0, ctl_offset = 0;
+};
+
+DecodeKnobs read_knobs() {
+  DecodeKnobs k;
+  if (const char* e = getenv("UIS_MAX_STATE_BYTES")) k.max_state_bytes = atof(e);
+  if (const char* e = getenv("UIS_SPLIT_MIN_MB")) { k.split_min_set = true; k.split_min_bytes = 1e6 * atof(e); }
+  if (const char* e = getenv("UIS_SPLIT_FRAMES")) {
+    k.split_frames_set = true;
+    for (const char* p = e; *p;) {
+      char* end = nullptr;
+      const long v = strtol(p, &end, 10);
+      if (end == p) break;
+      k.split_frames.push_back(v);
+      p = *end ? end + 1 : end;
+    }
+  }
+  k.no_split = getenv("UIS_NO_SPLIT") != nullptr;
+  k.no_arena = getenv("UIS_NO_ARENA") != nullptr;
+  if (const char* e = getenv("UIS_ARENA_SHIFT")) k.arena_shift = (size_t)atol(e) & ~(size_t)4095;
+  k.no_ctl_tune = getenv("UIS_NO_CTL_TUNE") != nullptr;
+  if (const char* e = getenv("UIS_CTL_OFFSET")) { k.ctl_offset_set = true; k.ctl_offset = (size_t)atol(e) & ~(size_t)127; }
+  k.agent_flags = agent_flags_env();
+  return k;
+}
+
+// What the planner needs to know about a decode besides the model.
+struct DecodeShape {
+  int U, G, B, Kmax, L, S;     // utterances, utterance groups (streams), beam, cluster cap, look_ahead, slots per utterance
+  int64_t F, maxN, maxT, NC;   // frames, longest utterance, its steps (test_iteration x), level capacity
+  bool ragged;                 // utterances of different lengths
+  bool f64;                    // uis_decode_f64: float64 utterances, cast by the library
+  bool host_frames;            // the frames are in host memory (uis_decode / uis_decode_f64)
+  bool wnd;                    // the window machinery decodes (look_ahead >= 2, wide beams, select tables beyond LDS)
+  size_t select_lds;           // select_lds_layout(...).total (without wnd)
+  size_t window_scratch;       // window_scratch_layout(...).total
+};
+
+enum class DecodePath { STEPWISE, GRAPH, RESIDENT, RS, BIG, BIG_WS, WINDOW, DEEP, SMALL };
+// the shapes of BASELINE's configs as compile-time constants
+enum { CLS_NONE = 0, CLS_C1 /* configs[1] / [3]: beam 10, cap 16 */, CLS_C4 /* configs[4]: beam 20, cap 11 */,
+       CLS_C2 /* configs[2]: beam 50, cap 12, look_ahead 2 */ };
+// k_decode_rs's instantiations (uis_stats.decode_kernel bits 16..23; 5 and 6 are reserved):
+//   RS_BASE   beam_size <= 16, <= 192 candidates, observation dim <= 256, at most 8 utterances per XCD
+//   RS_C1     ... with beam_size 10 / max_clusters 16 as compile-time constants (BASELINE configs[1])
+//   RS_UPW2   ... 9 .. 16 utterances per XCD: two utterances per wave
+//   RS_WIDE   beam_size <= 32, <= 256 candidates, observation dim 256 or 512 (configs[4]), at most 8 per XCD
+enum { RS_NONE = 0, RS_BASE, RS_C1, RS_UPW2, RS_WIDE };
+
+struct DecodePlan {
+  DecodePath path = DecodePath::STEPWISE;
+  int rs_kind = RS_NONE;
+  int cls = CLS_NONE;     // the shape class of the instantiation that runs (CLS_*)
+  size_t lds = 0;         // dynamic LDS bytes of the decode kernel (stepwise: of the select)
+  int decode_kernel = 0;  // uis_stats.decode_kernel
+  bool split = false;     // several launches, the later frames travelling behind the earlier launches ...
+  std::vector<int64_t> cuts;  // ... at these frame indices (empty without split)
+  // geometry the workspace shares with the choice
+  int ncl = 0, nclq = 1;  // clusters of 32 CUs (0: the device has none), and at least 1
+  int rx_stride = 0;      // rows of one cluster's row region
+  long max_rows = 0, rows_cap = 0;
+  bool hst = false;       // rnn_depth >= 2 at the cluster kernels' shapes: k_decode_deep's hand-off buffers
+  bool stage = false;     // a ragged float64 list big enough to split: the device's copy of the staging block
+  bool resident() const { return path == DecodePath::RESIDENT || path == DecodePath::RS || path == DecodePath::BIG || path == DecodePath::BIG_WS; }
+  bool clustered() const { return resident() || path == DecodePath::WINDOW || path == DecodePath::DEEP; }
+  bool one_launch() const { return clustered() || path == DecodePath::SMALL; }
+};
+
+// The dispatch rule.  No HIP call, no allocation, no global state: the same inputs give the same plan.
+DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, const DecodeKnobs& k, int n_cu,
+                       bool resident_off) {
+  DecodePlan p;
+  const int U = s.U, B = s.B, Kmax = s.Kmax, L = s.L, S = s.S;
+  const bool use_graph = !(flags & UIS_FLAG_PROFILE) && (flags & UIS_FLAG_GRAPH);
+  const bool per_step = (flags & UIS_FLAG_STEPWISE) != 0, generic = (flags & UIS_FLAG_GENERIC_SELECT) != 0;
+  // (after a failed placement check the handle keeps to the launch-per-step path, unless UIS_FLAG_RESIDENT asks)
+  const bool allowed = !resident_off || (flags & UIS_FLAG_RESIDENT);
+  const bool cl_dims = (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512);
+  // the one-launch kernels: the CUs form ncl clusters of 32 (one per XCD: 8 on a whole MI355X, 1 in CPX mode); one
+  // row region per cluster, a multiple of 16 rows (rows an utterance can emit per step: beam_size, or a level's
+  // capacity inside a look-ahead window)
+  p.ncl = (n_cu >= 32 && n_cu % 32 == 0 && n_cu / 32 <= UIS_MAX_CLUSTERS) ? n_cu / 32 : 0;
+  p.nclq = std::max(p.ncl, 1);
+  p.max_rows = (long)U * (L == 1 ? B : (long)s.NC);
+  // (+ 16 at look_ahead 1: room that a since removed kernel cut into two cohorts per cluster.  Kept: every buffer behind
+  // `rows` in the workspace arena would move, and placement alone has measured a 4 % mode switch -- DESIGN.md section 5)
+  p.rx_stride = (int)(((((long)U + p.nclq - 1) / p.nclq) * (L == 1 ? (long)B : (long)s.NC) + 15) / 16 * 16) + (L == 1 ? 16 : 0);
+  p.rows_cap = std::max(p.max_rows + 48L * s.G, (long)p.nclq * p.rx_stride);  // every group's last row tile may run past its rows
+  p.hst = m.depth >= 2 && s.G == 1 &&
+          ((m.Hp == 512 && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512)) ||
+           (m.Hp == 256 && (m.Dp == 128 || m.Dp == 256)) || (m.Hp == 128 && (m.Dp == 128 || m.Dp == 256)));
+  // (the compile-time shape classes: unpadded models, and the embedded hidden sizes 257 .. 384, whose H_units is Hp)
+  const bool exact = m.D == m.Dp && m.H_units == m.Hp;
+  const bool c1 = exact && m.Hp == 512 && m.Dp == 256 && B == 10 && Kmax == 16;
+  const bool c4 = exact && m.Hp == 512 && m.Dp == 512 && B == 20 && Kmax == 11;
+  // (a model of the cluster kernels' shapes -- hidden size 128 with a small observation dim also counts as "small" --
+  // goes to them: k_decode_big<WIN>)
+  const bool cluster_shape = m.depth == 1 && cl_dims;
+
+  // the whole decode in one launch with register-resident weights (k_decode_resident and its relatives below); the
+  // default wherever it applies.  (Its state is addressed through 2 GB buffer descriptors.)
+  const bool resident_ok = L == 1 && cluster_shape && s.G == 1 && select_fast_ok(B, Kmax, S) && !generic && p.ncl >= 1 &&
+                           ((double)U * S + 1) * m.Hp * 4.0 < 2.0e9 && (double)p.rows_cap * m.Hp * 4.0 < 2.0e9 &&
+                           (double)U * S * m.Dp * 4.0 < 2.0e9 && resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
+  const bool resident = resident_ok && !use_graph && allowed && !per_step;
+  // SMALL models (small_model_ok: hidden size up to about 64, any rnn_depth -- the shapes of the reference's own tests):
+  // the whole beam search of an utterance on ONE workgroup (k_decode_small); look_ahead >= 2 with a sub-step of the
+  // window kernel in the select's place
+  const bool small_shape = s.G == 1 && !use_graph && !per_step && !generic && small_model_ok(m.Hp, m.Dp, m.depth);
+  // rnn_depth >= 2 at the cluster kernels' shapes: k_decode_big's stages with the weight slot refilled per stage
+  // (look_ahead >= 2: with the window's sub-step as the select stage, for the shapes instantiated)
+  const bool deep_win_shape = (m.Hp == 512 && m.Dp == 256) || (m.Hp == 256 && (m.Dp == 128 || m.Dp == 256)) || (m.Hp == 128 && m.Dp == 128);
+  const bool deep = p.hst && !small_shape && !use_graph && p.ncl >= 1 &&
+                    (L == 1 ? select_fast_ok(B, Kmax, S) : deep_win_shape && big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B) <= 157 * 1024) &&
+                    !per_step && !generic && allowed &&
+                    ((double)U * S + 1) * m.depth * m.Hp * 4.0 < 2.0e9 && (double)p.rows_cap * m.G * 4.0 < 2.0e9 &&
+                    (double)U * S * m.Dp * 4.0 < 2.0e9 && (L > 1 || deep_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 157 * 1024);
+  const bool small = !resident_ok && small_shape &&
+                     (L == 1 ? select_fast_ok(B, Kmax, S) && small_lds_bytes(m.Dp, B, Kmax, S) <= 160 * 1024
+                             : !cluster_shape && s.window_scratch <= 128 * 1024 && (double)U * s.NC * std::max(m.G, m.Hp) * 4.0 < 2.0e9);
+  // look_ahead >= 2 in one launch (k_decode_big<WIN>: the window kernel's sub-step as the select stage of the
+  // wave-per-row-tile decode; its state through 4 GB descriptors with unsigned offsets, element counts below 2^31)
+  const bool win = !small && L > 1 && cluster_shape && s.G == 1 && !use_graph && p.ncl >= 1 && !per_step && allowed &&
+                   ((double)U * S + 1) * m.Hp * 4.0 < 4.0e9 && (double)p.rows_cap * m.Hp * 4.0 < 4.0e9 &&
+                   ((double)U * S + 1) * m.Hp < 2.0e9 && (double)U * S * m.Dp * 4.0 < 4.0e9 &&
+                   big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B) <= 157 * 1024;
+
+  if (resident) {
+    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0, replicated = (flags & UIS_FLAG_REPLICATED_SELECT) != 0;
+    const int per_xcd = (U + p.ncl - 1) / p.ncl;
+    const bool frames32 = s.F < 0x7fffffffLL;  // (k_decode_rs keeps frame numbers in 32 bits)
+    const bool base_shape = m.Dp <= 256 && rs_select_ok(B, Kmax, S, (long)s.maxT, 3) && frames32;
+    // the REPLICATED select (k_decode_rs, uis_select_rs.hip): every workgroup of an XCD decides all of the cluster's
+    // utterances, one wave each; the default where it applies (UIS_FLAG_OWNER_SELECT keeps k_decode_resident)
+    if (!owner) {
+      if (base_shape && per_xcd <= UIS_RS_UTT && resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024)
+        p.rs_kind = c1 ? RS_C1 : RS_BASE;
+      // (only on request: 1.20 / 1.40 / 1.60 M frames/s at 65 / 96 / 128 utterances against the owner select's
+      // 1.37 / 1.67 / 1.94 M, profiles/r04_rs_shape_classes.txt)
+      else if (replicated && base_shape && per_xcd <= 2 * UIS_RS_UTT && m.Hp == 512 && m.Dp == 256 &&
+               resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, 2, true) <= 160 * 1024)
+        p.rs_kind = RS_UPW2;
+      // (only on request: configs[4] 0.80 M frames/s against the owner select's 0.84 M)
+      else if (replicated && per_xcd <= UIS_RS_UTT && m.Hp == 512 && (m.Dp == 256 || m.Dp == 512) &&
+               rs_select_ok(B, Kmax, S, (long)s.maxT, 4) && frames32 && resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, 1, true) <= 160 * 1024)
+        p.rs_kind = RS_WIDE;
+    }
+    // more utterances than workgroups: k_decode_big, whose dense stages give a wave a whole row tile (+6 % at 288
+    // utterances, +17 % at 768 / 1024; UIS_FLAG_SMALL_TILES keeps the split-K passes: A/B switch, bit-identical) --
+    // with the selects of a rank's utterances running concurrently, one wave each (k_decode_big<WS>), where the
+    // single-wave select applies.  It takes over (round 5, profiles/r05_usweep_dispatch.json: 128 utterances 2.03
+    // against 1.89 M frames/s, 160: 2.20 / 2.22, 192: 2.31 / 2.46, 224: 2.42 / 2.52, 256: 2.43 / 2.65) from 21
+    // utterances per XCD with the concurrent selects, from 33 without them (profiles/r05_usweep_c4_shape.json: a tie at 128)
+    const int per_rank = ((U + p.nclq - 1) / p.nclq + 31) / 32;
+    const bool ws_shape = !owner && m.Dp <= 256 && per_rank <= 8 && rs_select_ok(B, Kmax, S, (long)s.maxT, 3) &&
+                          big_ws_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank) <= 160 * 1024;
+    const bool big = U >= (ws_shape ? 20 : 32) * p.ncl + 1 && !(flags & UIS_FLAG_SMALL_TILES) &&
+                     big_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
+    if (p.rs_kind != RS_NONE) {
+      const bool two = p.rs_kind == RS_UPW2, wide = p.rs_kind == RS_WIDE;
+      p.path = DecodePath::RS;
+      p.cls = p.rs_kind == RS_C1 ? CLS_C1 : CLS_NONE;
+      p.lds = resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, two ? 2 : 1, two || wide);
+      p.decode_kernel = UIS_DK_RS | (p.rs_kind << 16);
+    } else if (big && ws_shape) {
+      p.path = DecodePath::BIG_WS;
+      p.cls = c1 ? CLS_C1 : CLS_NONE;
+      p.lds = big_ws_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank);
+      p.decode_kernel = UIS_DK_BIG_WS;
+    } else if (big) {
+      p.path = DecodePath::BIG;
+      p.lds = big_lds_bytes(m.Hp, m.Dp, B, Kmax, S);
+      p.decode_kernel = UIS_DK_BIG;
+    } else {
+      p.path = DecodePath::RESIDENT;
+      p.cls = c1 ? CLS_C1 : c4 ? CLS_C4 : CLS_NONE;
+      p.lds = resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S);
+      p.decode_kernel = UIS_DK_RESIDENT;
+    }
+    p.lds = std::max<size_t>(p.lds, 96 * 1024);  // one workgroup per CU
+  } else if (win) {
+    p.path = DecodePath::WINDOW;
+    p.cls = exact && m.Hp == 512 && m.Dp == 256 && B == 50 && Kmax == 12 && L == 2 && s.NC == (int64_t)B * (Kmax + 1) &&
+                    S == B * Kmax + B + B * (Kmax + 1) ? CLS_C2 : CLS_NONE;
+    p.lds = big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B);
+    p.decode_kernel = UIS_DK_WINDOW;
+  } else if (deep) {
+    p.path = DecodePath::DEEP;
+    p.lds = L == 1 ? deep_lds_bytes(m.Hp, m.Dp, B, Kmax, S) : big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B);
+    p.decode_kernel = UIS_DK_DEEP;
+  } else if (small) {
+    p.path = DecodePath::SMALL;
+    p.lds = L == 1 ? small_lds_bytes(m.Dp, B, Kmax, S) : small_win_lds_bytes(S, (int)s.NC, Kmax, B);
+    p.decode_kernel = UIS_DK_SMALL;
+  } else {
+    p.path = use_graph ? DecodePath::GRAPH : DecodePath::STEPWISE;
+    p.lds = s.select_lds;
+    p.decode_kernel = UIS_DK_STEPWISE | (dense_family(m, n_cu, flags, (long)(U / s.G) * (L == 1 ? B : (long)s.NC)) << 8);
+  }
+
+  // ---- (round 5) ingestion overlapped with the decode.  The one-launch kernels own every CU, so nothing can be
+  // copied-and-projected "behind" them -- but k_decode_rs / k_decode_big<WS> / k_decode_resident (one utterance per
+  // workgroup) can stop after any step and pick up again (DecodeState::step0 / step1 / resume).  For a list of
+  // equal-length utterances given in HOST memory the decode is several launches: the first slice of every utterance's
+  // frames travels (one strided copy) and is projected, the first launch decodes the steps that need nothing else (a
+  // step looks one frame ahead: the early MSEs and the partial sums of the next select), the next slice travels and is
+  // projected behind it, and so on.  What is left exposed of the PCIe leg is the first slice.
+  // (utterances of equal length: a slice is ONE strided copy and the projection's batches are a constant stride apart.
+  // A ragged list: only through the float64 entry, whose staging block the library lays out itself -- slice after
+  // slice, so that a slice is one copy too, scattered to the utterance-major frame stream on the device; a copy per
+  // utterance and slice measured 2.48 against 3.59 M frames/s at a ragged configs[3] share -- and from 64 MB of frames
+  // on: a ragged configs[1] (24 MB) loses 3-5 % to the extra launches, 256 ragged utterances (96 MB) gain 2 %)
+  // (... and a list too small to spend a launch on keeps one: below 8 MB of frames the whole copy takes less than the
+  // ~0.15 ms a further launch costs)
+  const double split_min_bytes = k.split_min_set ? k.split_min_bytes : (s.ragged ? 64e6 : 8e6);
+  const bool big_enough = (double)s.F * m.D * 4.0 >= split_min_bytes;
+  p.stage = s.f64 && s.host_frames && s.F > 0 && s.ragged && big_enough;
+  const bool can_split = (!s.ragged || s.f64) && big_enough && s.host_frames && s.F > 0 &&
+                         (p.path == DecodePath::RS ? p.rs_kind == RS_BASE || p.rs_kind == RS_C1
+                                                   : p.path == DecodePath::BIG_WS || (p.path == DecodePath::RESIDENT && U <= 32 * p.nclq)) &&
+                         !(flags & (UIS_FLAG_PROFILE | UIS_FLAG_DEBUG_SCORES | UIS_FLAG_SMALL_TILES)) && m.D == m.Dp && !k.no_split;
+  const int64_t uniN = s.maxN;  // the longest utterance: slice boundaries are frame indices inside an utterance
+  if (can_split && uniN >= 128) {
+    std::vector<int64_t>& cuts = p.cuts;
+    if (k.split_frames_set) {
+      for (long v : k.split_frames) {
+        const int64_t lo = cuts.empty() ? 32 : cuts.back() + 32;
+        if (lo <= uniN - 32 && cuts.size() < 7) cuts.push_back(std::max<int64_t>(lo, std::min<int64_t>(v, uniN - 32)));
+      }
+    } else {
+      // A launch must last as long as the next slice travels, and every further launch costs ~0.15 ms (measured:
+      // configs[1] with cuts 32 | 32,128 | 32,96,288: 1.622 / 1.604 / 1.591 M frames/s from pinned float32).  Model:
+      // a decode step takes ~(11.7 + 0.108 U) us (profiles/r05_usweep.json), a frame of every utterance U D 4 bytes at
+      // ~45 GB/s (a quarter more through the float64 cast); slice k + 1 = what travels during 0.9 of launch k, and a
+      // last slice below a quarter of the utterance is not worth a launch of its own.
+      const double step_us = 11.7 + 0.108 * U, frame_us = (double)U * m.D * 4.0 / 45e3 * (s.f64 ? 1.25 : 1.0);
+      // (round 6) ... and no further cut once everything that is left travels within the launch in front of it plus two
+      // relaunches' worth (0.3 ms): configs[1] got the cuts {32, 326} and paid a second relaunch for frames that had
+      // arrived five milliseconds earlier -- 1.607 M frames/s through the float64 list against 1.629 M with the one cut
+      // at 32 (profiles/r06_f64_leg_knobs.txt); the configs[3] share keeps its slices (a launch there lasts 4 ms, the rest 28)
+      int64_t prev = 0, cur = 32;
+      while (cur <= uniN - 32 && (int)cuts.size() < 6) {
+        if (!cuts.empty() && uniN - cur < uniN / 4) break;
+        cuts.push_back(cur);
+        if ((double)(uniN - cur) * frame_us <= (double)(cur - prev) * step_us + 300.0) break;
+        const int64_t next = cur + std::max<int64_t>(32, (int64_t)(0.9 * (double)(cur - prev) * step_us / frame_us));
+        prev = cur; cur = next;
+      }
+    }
+  }
+  p.split = !p.cuts.empty();
+  return p;
+}
+
+typedef void (*DecodeKernel)(DevModel, DecodeState);
+struct KernelEntry { int Hp, Dp, variant; DecodeKernel fn; };
+
+template <size_t N>
+DecodeKernel find_kernel(const KernelEntry (&table)[N], int Hp, int Dp, int variant) {
+  for (const KernelEntry& e : table)
+    if (e.Hp == Hp && e.Dp == Dp && e.variant == variant) return e.fn;
+  return nullptr;
+}
+
+// The instantiations of the cluster-wide one-launch kernels, family by family, keyed by (Hp, Dp, variant): variant =
+// the shape class (CLS_*), for k_decode_rs its kind (RS_*), for k_decode_deep look_ahead >= 2.
+DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L) {
+  static const KernelEntry big_ws[] = {
+      {512, 256, CLS_C1, &k_decode_big<512, 256, true, 10, 16>},
+      {512, 256, CLS_NONE, &k_decode_big<512, 256, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, true>},
+      {256, 256, CLS_NONE, &k_decode_big<256, 256, true>}, {256, 128, CLS_NONE, &k_decode_big<256, 128, true>},
+      {128, 256, CLS_NONE, &k_decode_big<128, 256, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, true>}};
+  //                     HP   DP   NPOS UPW CB  CK  SPLIT2
+  static const KernelEntry rs[] = {
+      {512, 256, RS_BASE, &k_decode_rs<512, 256, 3, 1, 0, 0, false>}, {512, 128, RS_BASE, &k_decode_rs<512, 128, 3, 1, 0, 0, false>},
+      {256, 256, RS_BASE, &k_decode_rs<256, 256, 3, 1, 0, 0, false>}, {256, 128, RS_BASE, &k_decode_rs<256, 128, 3, 1, 0, 0, false>},
+      {128, 256, RS_BASE, &k_decode_rs<128, 256, 3, 1, 0, 0, false>}, {128, 128, RS_BASE, &k_decode_rs<128, 128, 3, 1, 0, 0, false>},
+      {512, 256, RS_C1, &k_decode_rs<512, 256, 3, 1, 10, 16, false>},
+      {512, 256, RS_UPW2, &k_decode_rs<512, 256, 3, 2, 0, 0, true>},
+      {512, 256, RS_WIDE, &k_decode_rs<512, 256, 4, 1, 0, 0, true>}, {512, 512, RS_WIDE, &k_decode_rs<512, 512, 4, 1, 0, 0, true>}};
+  static const KernelEntry resident[] = {
+      {512, 256, CLS_C1, &k_decode_resident<512, 256, false, 10, 16>}, {512, 512, CLS_C4, &k_decode_resident<512, 512, false, 20, 11>},
+      {512, 256, CLS_NONE, &k_decode_resident<512, 256>}, {512, 512, CLS_NONE, &k_decode_resident<512, 512>},
+      {512, 128, CLS_NONE, &k_decode_resident<512, 128>}, {256, 256, CLS_NONE, &k_decode_resident<256, 256>},
+      {256, 128, CLS_NONE, &k_decode_resident<256, 128>}, {256, 512, CLS_NONE, &k_decode_resident<256, 512>},
+      {128, 256, CLS_NONE, &k_decode_resident<128, 256>}, {128, 128, CLS_NONE, &k_decode_resident<128, 128>},
+      {128, 512, CLS_NONE, &k_decode_resident<128, 512>}};
+  static const KernelEntry big[] = {
+      {512, 256, CLS_NONE, &k_decode_big<512, 256>}, {512, 512, CLS_NONE, &k_decode_big<512, 512>},
+      {512, 128, CLS_NONE, &k_decode_big<512, 128>}, {256, 256, CLS_NONE, &k_decode_big<256, 256>},
+      {256, 128, CLS_NONE, &k_decode_big<256, 128>}, {256, 512, CLS_NONE, &k_decode_big<256, 512>},
+      {128, 256, CLS_NONE, &k_decode_big<128, 256>}, {128, 128, CLS_NONE, &k_decode_big<128, 128>},
+      {128, 512, CLS_NONE, &k_decode_big<128, 512>}};
+  static const KernelEntry window[] = {
+      {512, 256, CLS_C2, &k_decode_big<512, 256, false, 50, 12, true>},
+      {512, 256, CLS_NONE, &k_decode_big<512, 256, false, 0, 0, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, false, 0, 0, true>},
+      {512, 512, CLS_NONE, &k_decode_big<512, 512, false, 0, 0, true>}, {256, 256, CLS_NONE, &k_decode_big<256, 256, false, 0, 0, true>},
+      {256, 128, CLS_NONE, &k_decode_big<256, 128, false, 0, 0, true>}, {256, 512, CLS_NONE, &k_decode_big<256, 512, false, 0, 0, true>},
+      {128, 256, CLS_NONE, &k_decode_big<128, 256, false, 0, 0, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, false, 0, 0, true>},
+      {128, 512, CLS_NONE, &k_decode_big<128, 512, false, 0, 0, true>}};
+  static const KernelEntry deep[] = {
+      {512, 256, 0, &k_decode_deep<512, 256>}, {512, 128, 0, &k_decode_deep<512, 128>}, {512, 512, 0, &k_decode_deep<512, 512>},
+      {256, 256, 0, &k_decode_deep<256, 256>}, {256, 128, 0, &k_decode_deep<256, 128>}, {128, 128, 0, &k_decode_deep<128, 128>},
+      {128, 256, 0, &k_decode_deep<128, 256>},
+      {512, 256, 1, &k_decode_deep<512, 256, true>}, {256, 256, 1, &k_decode_deep<256, 256, true>},
+      {256, 128, 1, &k_decode_deep<256, 128, true>}, {128, 128, 1, &k_decode_deep<128, 128, true>}};
+  switch (p.path) {
+    case DecodePath::BIG_WS: return find_kernel(big_ws, m.Hp, m.Dp, p.cls);
+    case DecodePath::RS: return find_kernel(rs, m.Hp, m.Dp, p.rs_kind);
+    case DecodePath::RESIDENT: return find_kernel(resident, m.Hp, m.Dp, p.cls);
+    case DecodePath::BIG: return find_kernel(big, m.Hp, m.Dp, p.cls);
+    case DecodePath::WINDOW: return find_kernel(window, m.Hp, m.Dp, p.cls);
+    case DecodePath::DEEP: return find_kernel(deep, m.Hp, m.Dp, L > 1 ? 1 : 0);
+    default: return nullptr;
+  }
+}
+
+// One launch of a cluster-wide decode kernel: a workgroup of 512 threads on every CU of the ncl clusters.
+int launch_cluster_kernel(Launcher& lch, DecodeKernel kern, int n_cu, int ncl, size_t lds, const DevModel& m, const DecodeState& st) {
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, m, st);
+}
+
+#if defined(UIS_SELECT_TIMING) || defined(UIS_RESIDENT_PROBE) || defined(UIS_RS_COUNT_PATHS) || defined(UIS_RESIDENT_TIMING)
+// Diagnostic builds: what the device-side counters of the decode just run recorded, on stderr.
+int report_diagnostics(uis_handle* h, const DecodePlan& plan, int U, int64_t maxT, int L) {
+#if defined(UIS_SELECT_TIMING)
+  {
+    unsigned long long tc[48];
+    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
+    const double launches = (double)maxT * U;
+    if (L == 1) {
+      fprintf(stderr, "[select timing] cycles per workgroup-launch:");
+      for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.0f", k, (double)tc[16 + k] / launches);
+      fprintf(stderr, "\n");
+    } else {
+      static const char* names[7] = {"live+offsets", "mse", "scores", "expand/prune", "leaders+slots", "tables", "records+rows"};
+      for (int half = 0; half < 2; ++half) {
+        const unsigned long long* c = tc + (half ? 32 : 16);
+        const double n = (double)std::max<unsigned long long>(c[7], 1);
+        fprintf(stderr, "[window timing] %s sub-steps, us per workgroup-launch:", half ? "pruning" : "expanding");
+        double sum = 0.0;
+        for (int k = 0; k < 7; ++k) { fprintf(stderr, " %s=%.2f", names[k], (double)c[k] * 0.01 / n); sum += (double)c[k] * 0.01 / n; }
+        fprintf(stderr, " | total=%.2f; per launch: candidates=%.0f live=%.0f hypotheses in=%.0f rows=%.1f\n", sum, (double)c[8] / n,
+                (double)c[9] / n, (double)c[10] / n, (double)c[11] / n);
+      }
+    }
+  }
+#endif
+#if defined(UIS_RESIDENT_PROBE)
+  if (plan.resident()) {
+    unsigned long long tc[88];
+    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[resident probe] cycles per dependent load: own-table(nt)=%.0f mean(sc1)=%.0f wgt(plain)=%.0f wgt-again=%.0f\n",
+            (double)tc[80] / (double)maxT, (double)tc[81] / (double)maxT, (double)tc[82] / (double)maxT, (double)tc[83] / (double)maxT);
+  }
+#endif
+#if defined(UIS_RS_COUNT_PATHS)
+  if (plan.path == DecodePath::RS) {
+    unsigned long long tc[96];
+    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[rs short lists] selects with <= 16 / <= 32 / <= 64 / more survivors: %llu %llu %llu %llu\n", tc[88], tc[89], tc[90], tc[91]);
+  }
+#endif
+#if defined(UIS_RESIDENT_TIMING)
+  if (plan.path == DecodePath::WINDOW) {  // even sub-steps (expanding, at look_ahead 2) and odd ones (pruning) apart
+    const int ncl = plan.ncl;
+    unsigned long long tc[88];
+    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
+    static const char* names[8] = {"window", "barA", "gru", "barB", "head1", "barC", "head2", "barD"};
+    for (int wg = 0; wg < 2; ++wg)
+      for (int odd = 0; odd < 2; ++odd) {
+        fprintf(stderr, "[window launch timing] workgroup %3d, %s sub-steps, us per sub-step:", wg ? 248 : 0, odd ? "odd" : "even");
+        double sum = 0.0;
+        for (int k = 0; k < 8; ++k) {
+          const double us = (double)tc[(wg ? 64 : 48) + 8 * odd + k] * 0.01 / ((double)maxT * 0.5);
+          fprintf(stderr, " %s=%.2f", names[k], us);
+          sum += us;
+        }
+        fprintf(stderr, " | total=%.2f\n", sum);
+      }
+    std::vector<unsigned long long> per((size_t)96 + 1024);
+    HIPCHK(hipMemcpy(per.data(), h->counters.as<unsigned long long>(), per.size() * 8, hipMemcpyDeviceToHost));
+    for (int wg = 0; wg < 2; ++wg) {
+      fprintf(stderr, "[window launch timing] workgroup %3d, gru of the even sub-steps, us by wave:", wg ? 248 : 0);
+      for (int w = 0; w < 8; ++w) fprintf(stderr, " %.1f", (double)per[80 + 8 * wg + w] * 0.01 / ((double)maxT * 0.5));
+      fprintf(stderr, "\n");
+    }
+    static const char* what[4] = {"gru", "wait B", "head1", "head2"};
+    for (int k = 0; k < 4; ++k) {
+      fprintf(stderr, "[window launch timing] %s, even sub-steps, us by rank (mean over the clusters):", what[k]);
+      for (int r = 0; r < 32; ++r) {
+        double sum = 0.0;
+        for (int c = 0; c < ncl; ++c) sum += (double)per[(size_t)96 + 256 * k + c + ncl * r];
+        fprintf(stderr, " %.1f", sum / ncl * 0.01 / ((double)maxT * 0.5));
+      }
+      fprintf(stderr, "\n");
+    }
+  }
+  if (plan.resident()) {
+    unsigned long long tc[88];
+    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
+    static const char* names[8] = {"select", "barA", "gru", "barB", "head1", "barC", "head2", "barD"};
+    for (int wg = 0; wg < 2; ++wg) {
+      fprintf(stderr, "[resident timing] workgroup %3d, us per step:", wg ? 248 : 0);
+      for (int k = 0; k < 8; ++k) fprintf(stderr, " %s=%.2f", names[k], (double)tc[(wg ? 64 : 48) + k] * 0.01 / (double)maxT);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "[resident timing] select phases (wg 0), us per step:");
+    for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.2f", k, (double)tc[80 + k] * 0.01 / (double)maxT);
+    fprintf(stderr, "\n");
+    fprintf(stderr, "[resident timing] gru fine (wg 248): other=%.2f tile=%.2f combine=%.2f sync=%.2f\n",
+            (double)tc[72] * 0.01 / (double)maxT, (double)tc[73] * 0.01 / (double)maxT, (double)tc[74] * 0.01 / (double)maxT,
+            (double)tc[75] * 0.01 / (double)maxT);
+    if (plan.path == DecodePath::BIG || plan.path == DecodePath::BIG_WS) {  // k_decode_big: the GRU stage wave by wave, the row tiles per step
+      unsigned long long wv[32];
+      HIPCHK(hipMemcpy(wv, h->counters.as<unsigned long long>() + 96, sizeof(wv), hipMemcpyDeviceToHost));
+      for (int wg = 0; wg < 2; ++wg) {
+        fprintf(stderr, "[resident timing] workgroup %3d, gru us per step by wave:", wg ? 248 : 0);
+        for (int w = 0; w < 8; ++w) fprintf(stderr, " %.1f", (double)wv[8 * wg + w] * 0.01 / (double)maxT);
+        fprintf(stderr, "\n");
+      }
+      fprintf(stderr, "[resident timing] cluster 0: row tiles per step mean %.2f; steps by (row tiles mod 8):", (double)wv[24] / (double)maxT);
+      for (int k = 0; k < 8; ++k) fprintf(stderr, " %d:%llu", k, wv[16 + k]);
+      fprintf(stderr, "\n");
+    }
+  }
+#endif
+  return UIS_OK;
+}
+#endif
+
 int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
                 const uis_decode_opts* opts, int32_t* d_labels, float* d_scores, uis_stats* stats,
                 const float* h_frames = nullptr) {
   if (!h || !offsets || !opts || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets/opts or negative n_utt");
+  const DecodeKnobs knobs = read_knobs();
   // (whatever refuses this decode below: uis_last_decode_info must not hand out the PREVIOUS decode's arrays)
   h->last_U = 0; h->last_B = 0;
   h->last_overflow.clear(); h->last_beam_scores.clear();
@@ -731,7 +1178,6 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   if (S64 > 0x3fffffff) return fail(UIS_ERR_UNSUPPORTED, "beam_size * max_clusters ^ look_ahead too large");
   const int S = (int)S64;
   const bool profile = (opts->flags & UIS_FLAG_PROFILE) != 0;
-  const bool use_graph = !profile && (opts->flags & UIS_FLAG_GRAPH) != 0;
   Launcher lch{h, h->stream, profile};
   h->prof.used = 0; h->prof.cls.clear();
 
@@ -754,9 +1200,7 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   {  // refuse configurations whose state would not fit the device instead of failing in hipMalloc
     const double bytes = (double)U * S * (m.Dp + (double)m.depth * m.Hp) * 4.0 +
                          (wnd ? (double)U * (wsl.total + 2.0 * NC * (Kmax * 8.0 + 32.0) + NC * (m.Hp + m.G) * 4.0) : 0.0);
-    // (UIS_MAX_STATE_BYTES: a smaller ceiling, for tests of the host layer's answer -- it decodes the list in halves)
-    const char* lim = getenv("UIS_MAX_STATE_BYTES");
-    if (bytes > (lim ? atof(lim) : 200e9))
+    if (bytes > knobs.max_state_bytes)
       return fail(UIS_ERR_OOM, "decode state would need " + std::to_string((long long)(bytes / 1e9)) + " GB");
   }
 
@@ -775,23 +1219,43 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     h->gdone.push_back(e);
     h->gcache.emplace_back();
   }
-  std::vector<GroupPlan> plan(G);
+  std::vector<GroupPlan> groups(G);
   for (int g = 0; g < G; ++g) {
-    plan[g].u0 = (int)((int64_t)U * g / G);
-    plan[g].U = (int)((int64_t)U * (g + 1) / G) - plan[g].u0;
-    for (int u = plan[g].u0; u < plan[g].u0 + plan[g].U; ++u)
-      plan[g].maxT = std::max<int64_t>(plan[g].maxT, (int64_t)tau * (offsets[u + 1] - offsets[u]));
+    groups[g].u0 = (int)((int64_t)U * g / G);
+    groups[g].U = (int)((int64_t)U * (g + 1) / G) - groups[g].u0;
+    for (int u = groups[g].u0; u < groups[g].u0 + groups[g].U; ++u)
+      groups[g].maxT = std::max<int64_t>(groups[g].maxT, (int64_t)tau * (offsets[u + 1] - offsets[u]));
   }
-  const long max_rows = (long)U * (L == 1 ? B : (long)NC);
+
+  // ---- the plan: which kernels decode this list
+  const DecodeShape shape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, h_frames != nullptr,
+                          wnd, (size_t)lds.total, wsl.total};
+  const DecodePlan plan = plan_decode(m, shape, opts->flags, knobs, h->n_cu, h->resident_off);
+  if ((opts->flags & UIS_FLAG_RESIDENT) && !plan.one_launch())
+    return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT needs (look_ahead 1:) one stream, beam_size * (max_clusters + 1) <= 256, no "
+                                     "per-step path flag and either a small model (rnn_hidden_size up to about 64, any rnn_depth) "
+                                     "or rnn_depth 1 with rnn_hidden_size 128, 256 or 512 (padded), observation_dim 128, "
+                                     "256 or 512 (padded) and a device whose CU count is a multiple of 32");
+  const bool rs = plan.path == DecodePath::RS, split = plan.split;
+  const std::vector<int64_t>& cuts = plan.cuts;
+  const long rows_cap = plan.rows_cap;
+  const bool dbg = (opts->flags & UIS_FLAG_DEBUG_SCORES) != 0;
+  // one array per window: [windows][U][B][Kmax + 1] ^ look_ahead
+  double dbg_want = dbg ? (double)((maxT + L - 1) / L) * U * B : 0.0;
+  for (int k = 0; k < L; ++k) dbg_want *= (double)(Kmax + 1);
+  if (dbg_want > 1e9) return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_DEBUG_SCORES: more than 1e9 candidate scores (a test hook for small decodes)");
+  const size_t dbg_floats = (size_t)dbg_want;
+  h->dbg_floats = 0;
+
   // back-pointer records per utterance (look_ahead >= 2): windows x B
   std::vector<int64_t> bp_base(U + 1, 0);
   if (wnd)
     for (int u = 0; u < U; ++u)
       bp_base[u + 1] = bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
 
-  // ---- workspace
+  // ---- workspace: every buffer is a 4 KB-aligned view into ONE allocation (h->arena), laid out in the order of the
+  // ENSUREs below -- which is part of the measured speed: keep the order and the sizes
   int rc;
-  // every buffer is a 4 KB-aligned view into ONE allocation (h->arena), sized first
   std::vector<std::pair<DevBuf*, size_t>> want;
 #define ENSURE(buf, bytes) want.emplace_back(&h->buf, (size_t)(bytes))
   ENSURE(off, (size_t)(U + 1) * 8);
@@ -815,25 +1279,13 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   ENSURE(beam_slot, (size_t)2 * U * B * Kmax * 4);
   ENSURE(beam_blk, (size_t)2 * U * B * Kmax * 4);
   ENSURE(bp, !wnd ? (size_t)std::max<int64_t>(tau * F, 1) * B * 4 : 16);
-  // k_decode_resident: the CUs form ncl clusters of 32 (one per XCD: 8 on a whole MI355X, 1 in
-  // CPX mode); one row region per cluster, a multiple of 16 rows
-  const int ncl = (h->n_cu >= 32 && h->n_cu % 32 == 0 && h->n_cu / 32 <= UIS_MAX_CLUSTERS) ? h->n_cu / 32 : 0;
-  const int nclq = std::max(ncl, 1);
-  // (rows an utterance can emit per step: beam_size, or a level's capacity inside a look-ahead window)
-  // (+ 16 at look_ahead 1: k_decode_coh cuts a cluster's region into two cohorts, each rounded up to a row tile)
-  const int rx_stride = (int)(((((long)U + nclq - 1) / nclq) * (L == 1 ? (long)B : (long)NC) + 15) / 16 * 16) + (L == 1 ? 16 : 0);
-  const long rows_cap = std::max(max_rows + 48L * G, (long)nclq * rx_stride);  // every group's last row tile may run past its rows
   ENSURE(rows, (size_t)rows_cap * sizeof(RnnRow));
   ENSURE(nrows, (size_t)UIS_MAX_GROUPS * 2 * 4);
   // depth 1: k_decode_resident's h' staging buffer
   ENSURE(gi_up, m.depth > 1 ? (size_t)rows_cap * m.G * 4 : (size_t)rows_cap * m.Hp * 4);
   ENSURE(a1, (size_t)rows_cap * m.Hp * 4);
-  // rnn_depth >= 2 in one launch (k_decode_deep): the cluster kernels' shapes, the select's LDS budget; the
-  // two hand-off buffers a layer's h' goes through
-  const bool deep_shape = m.depth >= 2 && G == 1 &&
-                          ((m.Hp == 512 && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512)) ||
-                           (m.Hp == 256 && (m.Dp == 128 || m.Dp == 256)) || (m.Hp == 128 && (m.Dp == 128 || m.Dp == 256)));
-  if (deep_shape) ENSURE(hst, (size_t)2 * rows_cap * m.Hp * 4);
+  // rnn_depth >= 2 in one launch (k_decode_deep): the two hand-off buffers a layer's h' goes through
+  if (plan.hst) ENSURE(hst, (size_t)2 * rows_cap * m.Hp * 4);
 #if defined(UIS_RESIDENT_TIMING)
   ENSURE(counters, (size_t)UIS_MAX_GROUPS * 4 * 8 + (96 + 1024) * 8);
 #else
@@ -844,102 +1296,18 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // (a decode in several launches: DecodeState::resume -- only lists given in host memory can split, and never through
   // the window machinery: wide beams, large caps and look-ahead decodes do not pay for it)
   ENSURE(resume, (h_frames && !wnd) ? (size_t)U * (rs_lds_layout(B, Kmax, S).persist_stride + 4) + 16 : (size_t)16);
-  ENSURE(split_tab, (size_t)8 * U * 2 * sizeof(long));
+  ENSURE(split_tab, (size_t)8 * U * 2 * sizeof(long));                                     // (... of a ragged list: batch tables of up to 8 slices)
   ENSURE(scatter_tab, (size_t)64 * U * 3 * sizeof(long));                                  // (... and of its copy units: the scatter's tables)
-  if (h->src64 && h_frames && F > 0 && ragged_list && (double)F * m.D * 4.0 >= (getenv("UIS_SPLIT_MIN_MB") ? 1e6 * atof(getenv("UIS_SPLIT_MIN_MB")) : 64e6))
-    ENSURE(stage, (size_t)F * m.D * 4);                   // (... the device's copy of the time-major staging block)
-                                     // (... of a ragged list: batch tables of up to 8 slices)
-  // the whole decode in one launch with register-resident weights (k_decode_resident)
-  const bool resident_ok = L == 1 && m.depth == 1 && (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) &&
-                           (m.Dp == 128 || m.Dp == 256 || m.Dp == 512) && G == 1 &&
-                           select_fast_ok(B, Kmax, S) && !(opts->flags & UIS_FLAG_GENERIC_SELECT) && ncl >= 1 &&
-                           ((double)U * S + 1) * m.Hp * 4.0 < 2.0e9 && (double)rows_cap * m.Hp * 4.0 < 2.0e9 &&
-                           (double)U * S * m.Dp * 4.0 < 2.0e9 &&  // (the cluster means too are addressed through a 2 GB buffer descriptor)
-                           resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
-  // the default wherever it applies; UIS_FLAG_STEPWISE (or any of the per-step experiments) keeps
-  // the launch-per-step path, UIS_FLAG_RESIDENT turns "does not apply" into an error
-  const bool resident = resident_ok && !use_graph && (!h->resident_off || (opts->flags & UIS_FLAG_RESIDENT)) &&
-                        !(opts->flags & UIS_FLAG_STEPWISE);
-  // ... and for SMALL models (small_model_ok: hidden size up to about 64, any rnn_depth -- the shapes of
-  // the reference's own tests) the whole beam search of an utterance on ONE workgroup, one launch per decode
-  // (k_decode_small); the default where the kernels above do not apply
-  // (look_ahead >= 2: with a sub-step of the window kernel in the select's place, its work arrays in LDS)
-  const bool small_shape = G == 1 && !use_graph && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) &&
-                           small_model_ok(m.Hp, m.Dp, m.depth) && !getenv("UIS_NO_SMALL_KERNEL");
-  // (a model of the cluster kernels' shapes -- hidden size 128 with a small observation dim also counts as
-  // "small" -- goes to them: k_decode_big<WIN> below)
-  const bool cluster_shape = m.depth == 1 && (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512);
-  // rnn_depth >= 2 at the cluster kernels' shapes: k_decode_big's stages with the weight slot refilled per stage
-  // (look_ahead >= 2: with the window's sub-step as the select stage, for the shapes instantiated below)
-  const bool deep_win_shape = (m.Hp == 512 && m.Dp == 256) || (m.Hp == 256 && (m.Dp == 128 || m.Dp == 256)) || (m.Hp == 128 && m.Dp == 128);
-  const bool deep = deep_shape && !small_shape && !use_graph && ncl >= 1 &&
-                    (L == 1 ? select_fast_ok(B, Kmax, S)
-                            : deep_win_shape && big_win_lds_bytes(m.Hp, S, (int)NC, Kmax, B) <= 157 * 1024 && !getenv("UIS_NO_WINDOW_LAUNCH")) &&
-                    !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) &&
-                    (!h->resident_off || (opts->flags & UIS_FLAG_RESIDENT)) &&
-                    ((double)U * S + 1) * m.depth * m.Hp * 4.0 < 2.0e9 && (double)rows_cap * m.G * 4.0 < 2.0e9 &&
-                    (double)U * S * m.Dp * 4.0 < 2.0e9 && (L > 1 || deep_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 157 * 1024) &&
-                    !getenv("UIS_NO_DEEP_KERNEL");  // (look_ahead >= 2: the window's layout, checked above, not the fast select's)
-  const bool small = !resident_ok && small_shape &&
-                     (L == 1 ? select_fast_ok(B, Kmax, S) && small_lds_bytes(m.Dp, B, Kmax, S) <= 160 * 1024
-                             : !cluster_shape && wsl.total <= 128 * 1024 && (double)U * NC * std::max(m.G, m.Hp) * 4.0 < 2.0e9);
-  // ... and look_ahead >= 2 in one launch (k_decode_big<WIN>: the window kernel's sub-step as the select stage
-  // of the wave-per-row-tile decode)
-  const bool win = !small && L > 1 && m.depth == 1 && G == 1 && !use_graph && ncl >= 1 &&
-                   (U <= 32 * ncl || !getenv("UIS_WINDOW_LAUNCH_ONE_EACH")) &&
-                   cluster_shape &&
-                   !(opts->flags & UIS_FLAG_STEPWISE) && (!h->resident_off || (opts->flags & UIS_FLAG_RESIDENT)) &&
-                   // (k_decode_big addresses its state through 4 GB descriptors with unsigned offsets since round 5; element
-                   // counts stay below 2^31 for its int arithmetic)
-                   ((double)U * S + 1) * m.Hp * 4.0 < 4.0e9 && (double)rows_cap * m.Hp * 4.0 < 4.0e9 &&
-                   ((double)U * S + 1) * m.Hp < 2.0e9 && (double)U * S * m.Dp * 4.0 < 4.0e9 &&
-                   big_win_lds_bytes(m.Hp, S, (int)NC, Kmax, B) <= 157 * 1024 &&
-                   !getenv("UIS_NO_WINDOW_LAUNCH");
-  if ((opts->flags & UIS_FLAG_RESIDENT) && !resident && !small && !win && !deep)
-    return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT needs (look_ahead 1:) one stream, beam_size * (max_clusters + 1) <= 256, no "
-                                     "per-step path flag and either a small model (rnn_hidden_size up to about 64, any rnn_depth) "
-                                     "or rnn_depth 1 with rnn_hidden_size 128, 256 or 512 (padded), observation_dim 128, "
-                                     "256 or 512 (padded) and a device whose CU count is a multiple of 32");
+  if (plan.stage) ENSURE(stage, (size_t)F * m.D * 4);                                      // (... the device's copy of the time-major staging block)
   // control words: [0, 16) XCC id per cluster, [16] abort, [32, 32 + 32 ncl) row counters,
   // then 32 ncl barrier counters, then 32 ncl phase words (one 128-byte line per cluster each)
   const size_t ctl_words = (size_t)32 + 3 * UIS_MAX_CLUSTERS * 32;
   static const size_t ctl_place[4] = {0, 8192, (size_t)1 << 20, ((size_t)1 << 20) + 8192};
   ENSURE(cluster_ctl, ctl_place[3] + ((ctl_words * 4 + 4095) & ~(size_t)4095));
-  // the one-launch decode with the REPLICATED select (k_decode_rs, uis_select_rs.hip): every workgroup of
-  // an XCD decides all of the cluster's utterances, one wave each; the default where it applies.
-  // Its instantiations (shape classes), in the order tried:
-  //   RS_BASE   beam_size <= 16, <= 192 candidates, observation dim <= 256, at most 8 utterances per XCD
-  //   RS_C1     ... with beam_size 10 / max_clusters 16 as compile-time constants (BASELINE configs[1])
-  //   RS_UPW2   ... 9 .. 16 utterances per XCD: two utterances per wave
-  //   RS_WIDE   beam_size <= 32, <= 256 candidates, observation dim 256 or 512 (configs[4]), at most 8 per XCD
-  enum { RS_NONE = 0, RS_BASE, RS_C1, RS_UPW2, RS_WIDE, RS_UPW2_C1, RS_WIDE_C4 };
-  int rs_kind = RS_NONE;
-  if (resident && !(opts->flags & UIS_FLAG_OWNER_SELECT) && (UIS_RS_DEFAULT || (opts->flags & UIS_FLAG_REPLICATED_SELECT))) {
-    const int per_xcd = (U + ncl - 1) / ncl;
-    const bool base_shape = m.Dp <= 256 && rs_select_ok(B, Kmax, S, (long)maxT, 3) && F < 0x7fffffffLL;  // (k_decode_rs keeps frame numbers in 32 bits)
-    if (base_shape && per_xcd <= UIS_RS_UTT && resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024)
-      rs_kind = (m.Hp == 512 && m.Dp == 256 && m.H == 512 && m.D == 256 && B == 10 && Kmax == 16 && !getenv("UIS_RS_NO_C1") && !getenv("UIS_NO_SHAPE_CLASSES")) ? RS_C1 : RS_BASE;
-    else if (base_shape && per_xcd <= 2 * UIS_RS_UTT && m.Hp == 512 && m.Dp == 256 &&
-             ((UIS_RS_UPW2_DEFAULT && !getenv("UIS_RS_NO_UPW2")) || (opts->flags & UIS_FLAG_REPLICATED_SELECT)) &&
-             resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, 2, true) <= 160 * 1024)
-      rs_kind = (m.H == 512 && m.D == 256 && B == 10 && Kmax == 16 && getenv("UIS_RS_UPW2_C1")) ? RS_UPW2_C1 : RS_UPW2;
-    else if (per_xcd <= UIS_RS_UTT && m.Hp == 512 && (m.Dp == 256 || m.Dp == 512) &&
-             ((UIS_RS_WIDE_DEFAULT && !getenv("UIS_RS_NO_WIDE")) || (opts->flags & UIS_FLAG_REPLICATED_SELECT)) &&
-             rs_select_ok(B, Kmax, S, (long)maxT, 4) && F < 0x7fffffffLL && resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, 1, true) <= 160 * 1024)
-      rs_kind = (m.Dp == 512 && m.D == 512 && m.H == 512 && B == 20 && Kmax == 11 && getenv("UIS_RS_WIDE_C4")) ? RS_WIDE_C4 : RS_WIDE;
-  }
-  const bool rs = rs_kind != RS_NONE;
   const size_t mse_tab_bytes = ((size_t)2 * U * S * 4 + 255) & ~(size_t)255;
-  const size_t mse_part_bytes = (size_t)nclq * rx_stride * rs_part_stride(m.Dp) * 4;
+  const size_t mse_part_bytes = (size_t)plan.nclq * plan.rx_stride * rs_part_stride(m.Dp) * 4;
   if (rs) ENSURE(mse_tab, mse_tab_bytes + mse_part_bytes);
-  const bool dbg = (opts->flags & UIS_FLAG_DEBUG_SCORES) != 0;
-  // one array per window: [windows][U][B][Kmax + 1] ^ look_ahead
-  double dbg_want = dbg ? (double)((maxT + L - 1) / L) * U * B : 0.0;
-  for (int k = 0; k < L; ++k) dbg_want *= (double)(Kmax + 1);
-  if (dbg_want > 1e9) return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_DEBUG_SCORES: more than 1e9 candidate scores (a test hook for small decodes)");
-  const size_t dbg_floats = (size_t)dbg_want;
   if (dbg) ENSURE(dbg_scores, std::max<size_t>(dbg_floats, 1) * 4);
-  h->dbg_floats = 0;
   if (wnd) {
     ENSURE(lv_n, (size_t)2 * U * 4);
     ENSURE(lv_K, (size_t)2 * U * NC * 4);
@@ -956,13 +1324,12 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   }
 #undef ENSURE
   {
-    const bool use_arena = getenv("UIS_NO_ARENA") == nullptr;
     size_t total = 0;
     for (auto& w : want) total += (w.second + 4095) & ~(size_t)4095;
-    if (use_arena) {
-      // (experiment knob, tools/experiments/bimodal.py: the one-launch decode runs in one of two modes
+    if (!knobs.no_arena) {
+      // (UIS_ARENA_SHIFT, tools/experiments/bimodal.py: the one-launch decode runs in one of two modes
       // 4 % apart depending on where its buffers land)
-      const size_t shift = getenv("UIS_ARENA_SHIFT") ? ((size_t)atol(getenv("UIS_ARENA_SHIFT")) & ~(size_t)4095) : 0;
+      const size_t shift = knobs.arena_shift;
       if ((rc = h->arena.ensure(total + shift))) return rc;
       size_t o = shift;
       for (auto& w : want) {
@@ -984,94 +1351,20 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // (not for k_decode_rs: its row descriptors and row counters live in LDS, only the barrier
   // counters are polled in memory, and what is left of the placement effect is 1 % --
   // profiles/r03_bimodal.txt -- against 5 % for the kernels that keep them in global memory)
-  if (resident && !rs && !getenv("UIS_NO_CTL_TUNE")) {
+  const bool ctl_tune = plan.resident() && !rs && !knobs.no_ctl_tune;
+  if (ctl_tune) {
     const uint64_t sig = ((uint64_t)U << 44) ^ ((uint64_t)F << 16) ^ ((uint64_t)maxT << 6) ^ ((uint64_t)B << 1) ^ ((uint64_t)Kmax << 54);
     if (tn.sig != sig) { tn = uis_handle::CtlTune{}; tn.sig = sig; }
     ctl_cand = (tn.phase >= 1 && tn.phase <= 4) ? tn.phase - 1 : tn.best;
   }
   size_t ctl_off = ctl_place[ctl_cand];
-  if (const char* e = getenv("UIS_CTL_OFFSET")) ctl_off = std::min<size_t>((size_t)atol(e) & ~(size_t)127, ctl_place[3]);  // experiments
+  if (knobs.ctl_offset_set) ctl_off = std::min<size_t>(knobs.ctl_offset, ctl_place[3]);  // experiments
   uint32_t* const ctl = reinterpret_cast<uint32_t*>(h->cluster_ctl.as<char>() + ctl_off);
 
-  // ... with the selects of a rank's utterances running concurrently, one wave each (k_decode_big<.., true>),
-  // where the single-wave select applies; UIS_FLAG_OWNER_SELECT keeps them one after the other
-  const int per_rank = (((U + nclq - 1) / nclq) + 31) / 32;
-  const bool ws_shape = !(opts->flags & UIS_FLAG_OWNER_SELECT) && m.Dp <= 256 && per_rank <= 8 &&
-                        rs_select_ok(B, Kmax, S, (long)maxT, 3) &&
-                        big_ws_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank) <= 160 * 1024;
-  // Where k_decode_big takes over from k_decode_resident (round 5, from the sweep profiles/r05_usweep_dispatch.json:
-  // 128 utterances 2.03 against 1.89 M frames/s, 160: 2.20 / 2.22, 192: 2.31 / 2.46, 224: 2.42 / 2.52, 256: 2.43 /
-  // 2.65): with the concurrent single-wave selects from 21 utterances per XCD on (rounds 2-4 switched at "more
-  // utterances than workgroups", 33 per XCD); without them (observation dim 512, wide beams) the sequential
-  // selects keep the old switch (profiles/r05_usweep_c4_shape.json: a tie at 128).  UIS_BIG_MIN_U: experiments.
-  const int big_from = getenv("UIS_BIG_MIN_U") ? atoi(getenv("UIS_BIG_MIN_U")) : (ws_shape ? 20 : 32) * ncl + 1;
-  const bool big = resident && U >= big_from && !(opts->flags & UIS_FLAG_SMALL_TILES) &&
-                   big_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
-  const bool big_ws = big && ws_shape;
-  // ... or, on request (UIS_FLAG_COHORTS / UIS_COHORTS=1: measured slower, an experiment that stays tested), as two
-  // utterance cohorts in flight per XCD (k_decode_coh: a cohort's select and hand-off waits filled with the other
-  // cohort's dense stages)
-#if defined(UIS_WITH_COHORTS)
-  const bool coh = big_ws && ((opts->flags & UIS_FLAG_COHORTS) || getenv("UIS_COHORTS")) &&
-                   coh_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank) <= 160 * 1024;
-#else
-  const bool coh = false;  // (round 6: the cohort kernel lost every measurement; it lives on in the -DUIS_WITH_COHORTS test variant)
-#endif
-  // ---- (round 5) ingestion overlapped with the decode.  The one-launch kernels own every CU, so nothing can be
-  // copied-and-projected "behind" them -- but k_decode_rs / k_decode_big<WS> / k_decode_resident (one utterance per
-  // workgroup) can stop after any step and pick up again
-  // (DecodeState::step0 / step1 / resume).  For a list of equal-length utterances given in HOST memory the decode is
-  // several launches: the first slice of every utterance's frames travels (one strided copy) and is projected, the
-  // first launch decodes the steps that need nothing else (a step looks one frame ahead: the early MSEs and the
-  // partial sums of the next select), the next slice travels and is projected behind it, and so on.  What is left
-  // exposed of the PCIe leg is the first slice.  UIS_NO_SPLIT=1 keeps one launch (A/B switch, bit-identical).
-  // (utterances of equal length: a slice is ONE strided copy and the projection's batches are a constant stride apart.
-  // A ragged list: only through the float64 entry, whose staging block the library lays out itself -- slice after
-  // slice, so that a slice is one copy too, scattered to the utterance-major frame stream on the device; a copy per
-  // utterance and slice measured 2.48 against 3.59 M frames/s at a ragged configs[3] share -- and from 64 MB of frames on:
-  // a ragged configs[1] (24 MB) loses 3-5 % to the extra launches, 256 ragged utterances (96 MB) gain 2 %)
-  const bool uniform = n_utt > 0 && !ragged_list;
+  // ---- ingestion: the frames onto the device, the input projection and the fresh-cluster MSEs
+  const bool uniform = !ragged_list;
   const int64_t uniN = maxN;  // the longest utterance: slice boundaries are frame indices inside an utterance
-  // (... and a list too small to spend a launch on keeps one: below 8 MB of frames the whole copy takes less than the
-  // ~0.15 ms a further launch costs.  UIS_SPLIT_MIN_MB moves both sizes: tests, experiments)
-  const double split_min_bytes = getenv("UIS_SPLIT_MIN_MB") ? 1e6 * atof(getenv("UIS_SPLIT_MIN_MB")) : (uniform ? 8e6 : 64e6);
-  const bool split_shape = (uniform || h->src64 != nullptr) && (double)F * m.D * 4.0 >= split_min_bytes;
-  std::vector<int64_t> cuts;
-  if (uniN >= 128) {
-    if (const char* e = getenv("UIS_SPLIT_FRAMES")) {
-      for (const char* p2 = e; *p2;) {
-        char* end = nullptr;
-        const long v = strtol(p2, &end, 10);
-        if (end == p2) break;
-        const int64_t lo = cuts.empty() ? 32 : cuts.back() + 32;
-        if (lo <= uniN - 32 && cuts.size() < 7) cuts.push_back(std::max<int64_t>(lo, std::min<int64_t>(v, uniN - 32)));
-        p2 = *end ? end + 1 : end;
-      }
-    } else {
-      // A launch must last as long as the next slice travels, and every further launch costs ~0.15 ms (measured:
-      // configs[1] with cuts 32 | 32,128 | 32,96,288: 1.622 / 1.604 / 1.591 M frames/s from pinned float32).  Model:
-      // a decode step takes ~(11.7 + 0.108 U) us (profiles/r05_usweep.json), a frame of every utterance U D 4 bytes at
-      // ~45 GB/s (a quarter more through the float64 cast); slice k + 1 = what travels during 0.9 of launch k, and a
-      // last slice below a quarter of the utterance is not worth a launch of its own.
-      const double step_us = 11.7 + 0.108 * U, frame_us = (double)U * m.D * 4.0 / 45e3 * (h->src64 ? 1.25 : 1.0);
-      // (round 6) ... and no further cut once everything that is left travels within the launch in front of it plus two
-      // relaunches' worth (0.3 ms): configs[1] got the cuts {32, 326} and paid a second relaunch for frames that had
-      // arrived five milliseconds earlier -- 1.607 M frames/s through the float64 list against 1.629 M with the one cut
-      // at 32 (profiles/r06_f64_leg_knobs.txt); the configs[3] share keeps its slices (a launch there lasts 4 ms, the rest 28)
-      int64_t prev = 0, cur = 32;
-      while (cur <= uniN - 32 && (int)cuts.size() < 6) {
-        if (!cuts.empty() && uniN - cur < uniN / 4) break;
-        cuts.push_back(cur);
-        if ((double)(uniN - cur) * frame_us <= (double)(cur - prev) * step_us + 300.0) break;
-        const int64_t next = cur + std::max<int64_t>(32, (int64_t)(0.9 * (double)(cur - prev) * step_us / frame_us));
-        prev = cur; cur = next;
-      }
-    }
-  }
-  const int64_t T1 = cuts.empty() ? 0 : cuts[0];
-  const bool split = T1 > 0 && split_shape && h_frames && F > 0 && resident && (rs_kind == RS_BASE || rs_kind == RS_C1 || (big_ws && !coh) || (!rs && !big && U <= 32 * nclq)) && !profile &&
-                     !dbg && m.D == m.Dp && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512) && !(opts->flags & UIS_FLAG_SMALL_TILES) &&
-                     !getenv("UIS_NO_SPLIT");
+  const int64_t T1 = split ? cuts[0] : 0;
   std::unique_ptr<CastTeam> team;
   struct TeamGuard {  // nobody may still be inside the team when it goes out of scope
     CastPool* pool = nullptr;
@@ -1284,10 +1577,10 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // ---- group views of the shared buffers
   const size_t rows_per_utt = (size_t)(L == 1 ? B : NC);
   for (int g = 0; g < G; ++g) {
-    GroupPlan& gp = plan[g];
+    GroupPlan& gp = groups[g];
     DecodeState& st = gp.st;
     const size_t u0 = (size_t)gp.u0;
-    st.U = gp.U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = L; st.tau = tau; st.flags = opts->flags | (agent_flags_env() ? UIS_FLAG_AGENT_FLAGS : 0u); st.wnd = wnd ? 1 : 0;
+    st.U = gp.U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = L; st.tau = tau; st.flags = opts->flags | (knobs.agent_flags ? UIS_FLAG_AGENT_FLAGS : 0u); st.wnd = wnd ? 1 : 0;
     st.max_rows = (int)((size_t)gp.U * rows_per_utt);
     st.off = h->off.as<int64_t>() + u0;
     st.utt_step = h->utt_step.as<int32_t>() + u0;
@@ -1313,18 +1606,18 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     st.counters = h->counters.as<unsigned long long>() + 4 * g;
     st.cl_abort = ctl + 16;
     st.utt_nrows = h->utt_nrows.as<int32_t>() + 2 * u0;
-    st.hst = deep_shape ? h->hst.as<float>() : nullptr;
+    st.hst = plan.hst ? h->hst.as<float>() : nullptr;
     st.step0 = 0; st.step1 = 0; st.resume = h->resume.as<unsigned char>(); st.resume_stride = 0;
     st.hst_elems = (size_t)rows_cap * m.Hp;
     st.dbg_scores = dbg ? h->dbg_scores.as<float>() + 0 : nullptr;  // (one group: groups would need their own utterance offset)
-    if (resident || win || deep) {
-      st.ncl = ncl;
+    if (plan.clustered()) {
+      st.ncl = plan.ncl;
       st.cl_xcc = ctl;
-      st.rx_stride = rx_stride;
+      st.rx_stride = plan.rx_stride;
       st.rx_nrows = reinterpret_cast<int32_t*>(ctl) + 32;
       st.rx_bar = ctl + 32 + UIS_MAX_CLUSTERS * 32;
       st.rx_flags = ctl + 32 + 2 * UIS_MAX_CLUSTERS * 32;
-      if (rs) {  // (one group: resident_ok)
+      if (rs) {  // (one group)
         st.mse_tab = h->mse_tab.as<float>();
         st.mse_part = reinterpret_cast<float*>(h->mse_tab.as<char>() + mse_tab_bytes);
       }
@@ -1347,247 +1640,66 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     }
   }
 
-  // ---- lock-step decode of every group on its own stream
-  int decode_kernel = UIS_DK_STEPWISE | (dense_family(h, opts->flags, (long)plan[0].st.max_rows) << 8);
+  // ---- the decode of every group on its own stream
+  const DecodeKernel cluster_kern = plan.clustered() ? cluster_kernel(plan, m, L) : nullptr;
+  if (plan.clustered() && !cluster_kern) return fail(UIS_ERR_HIP, "no one-launch kernel instantiated for this shape");
   for (int g = 0; g < G; ++g) {
-    GroupPlan& gp = plan[g];
+    GroupPlan& gp = groups[g];
     hipStream_t sg = h->gstreams[g];
     Launcher gl{h, sg, profile};
     Launcher& lch = gl;  // LAUNCH() below targets this group's stream
     HIPCHK(hipStreamWaitEvent(sg, h->ev_pre, 0));
     LAUNCH(-1, k_init_state, dim3((gp.U + 255) / 256), dim3(256), 0, gp.st);
-    if (resident) {
-      // h1 into the extra slot, then ONE launch for every step of every utterance
-      HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)U * S * m.Hp, m.h1, (size_t)m.Hp * 4, hipMemcpyDeviceToDevice, sg));
-      // more utterances than workgroups: the variant whose dense stages give a wave a whole row tile
-      // (k_decode_big: +6 % at 288 utterances, +17 % at 768 / 1024; up to 256 the LDS-resident beam of
-      // k_decode_resident wins); UIS_FLAG_SMALL_TILES keeps the split-K passes (A/B switch, bit-identical)
-      const bool rs_two = rs_kind == RS_UPW2 || rs_kind == RS_UPW2_C1, rs_wide = rs_kind == RS_WIDE || rs_kind == RS_WIDE_C4;
-      const size_t shmem = std::max<size_t>(rs       ? resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S, rs_two ? 2 : 1, rs_two || rs_wide)
-#if defined(UIS_WITH_COHORTS)
-                                            : coh    ? coh_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank)
-#endif
-                                            : big_ws ? big_ws_lds_bytes(m.Hp, m.Dp, B, Kmax, S, per_rank)
-                                            : big    ? big_lds_bytes(m.Hp, m.Dp, B, Kmax, S)
-                                                     : resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S),
-                                            96 * 1024);  // one workgroup per CU
-      decode_kernel = rs ? (UIS_DK_RS | (rs_kind << 16)) : coh ? UIS_DK_BIG_COH : big_ws ? UIS_DK_BIG_WS : big ? UIS_DK_BIG : UIS_DK_RESIDENT;
-      // the shapes of BASELINE's configs as compile-time constants (unpadded models only; UIS_NO_SHAPE_CLASSES=1
-      // keeps the run-time instantiations: A/B switch, bit-identical)
-      const bool exact = m.D == m.Dp && m.H == m.Hp && !getenv("UIS_NO_SHAPE_CLASSES");
-      const bool cls_c1 = exact && m.Hp == 512 && m.Dp == 256 && B == 10 && Kmax == 16;   // configs[1] / [3]: beam 10, cap 16
-      const bool cls_c4 = exact && m.Hp == 512 && m.Dp == 512 && B == 20 && Kmax == 11;   // configs[4]: beam 20, cap 11
-      // (round 5) the launch as a function of the step range: once for the whole decode, or twice with the rest of the
-      // frames arriving behind the first launch (split, above)
-      auto launch_resident = [&]() -> int {
-#if defined(UIS_WITH_COHORTS)
-#define UIS_COH_CASE(HPV, DPV, COND, ...)                                                                             \
-  if (m.Hp == HPV && m.Dp == DPV && coh && (COND)) {                                                                 \
-    void (*kern)(DevModel, DecodeState) = &k_decode_coh<HPV, DPV, ##__VA_ARGS__>;                                    \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_COH_CASE(512, 256, cls_c1, 10, 16)
-      UIS_COH_CASE(512, 256, !cls_c1)
-      UIS_COH_CASE(512, 128, true)
-      UIS_COH_CASE(256, 256, true)
-      UIS_COH_CASE(256, 128, true)
-      UIS_COH_CASE(128, 256, true)
-      UIS_COH_CASE(128, 128, true)
-#undef UIS_COH_CASE
-#endif
-#define UIS_BIGWS_CASE(HPV, DPV, COND, ...)                                                                           \
-  if (m.Hp == HPV && m.Dp == DPV && big_ws && !coh && (COND)) {                                                              \
-    void (*kern)(DevModel, DecodeState) = &k_decode_big<HPV, DPV, true, ##__VA_ARGS__>;                              \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_BIGWS_CASE(512, 256, cls_c1, 10, 16)
-      UIS_BIGWS_CASE(512, 256, !cls_c1)
-      UIS_BIGWS_CASE(512, 128, true)
-      UIS_BIGWS_CASE(256, 256, true)
-      UIS_BIGWS_CASE(256, 128, true)
-      UIS_BIGWS_CASE(128, 256, true)
-      UIS_BIGWS_CASE(128, 128, true)
-#undef UIS_BIGWS_CASE
-#define UIS_RS_CASE(KIND, HPV, DPV, ...)                                                                              \
-  if (m.Hp == HPV && m.Dp == DPV && rs_kind == KIND) {                                                               \
-    void (*kern)(DevModel, DecodeState) = &k_decode_rs<HPV, DPV, __VA_ARGS__>;                                      \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      //          kind      HP   DP   NPOS UPW CB  CK  SPLIT2
-      UIS_RS_CASE(RS_BASE, 512, 256, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_BASE, 512, 128, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_BASE, 256, 256, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_BASE, 256, 128, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_BASE, 128, 256, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_BASE, 128, 128, 3, 1, 0, 0, false)
-      UIS_RS_CASE(RS_C1, 512, 256, 3, 1, 10, 16, false)
-      UIS_RS_CASE(RS_UPW2, 512, 256, 3, 2, 0, 0, true)
-      UIS_RS_CASE(RS_UPW2_C1, 512, 256, 3, 2, 10, 16, true)
-      UIS_RS_CASE(RS_WIDE, 512, 256, 4, 1, 0, 0, true)
-      UIS_RS_CASE(RS_WIDE, 512, 512, 4, 1, 0, 0, true)
-      UIS_RS_CASE(RS_WIDE_C4, 512, 512, 4, 1, 20, 11, true)
-#undef UIS_RS_CASE
-#define UIS_RESIDENT_CLASS(HPV, DPV, COND, CBV, CKV)                                                                  \
-  if (m.Hp == HPV && m.Dp == DPV && !rs && !big_ws && !big && (COND)) {                                              \
-    void (*kern)(DevModel, DecodeState) = &k_decode_resident<HPV, DPV, false, CBV, CKV>;                            \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_RESIDENT_CLASS(512, 256, cls_c1, 10, 16)
-      UIS_RESIDENT_CLASS(512, 512, cls_c4, 20, 11)
-#undef UIS_RESIDENT_CLASS
-      const bool in_class = !big && (cls_c1 || cls_c4);
-#define UIS_RESIDENT_CASE(HPV, DPV)                                                                                   \
-  if (m.Hp == HPV && m.Dp == DPV && !rs && !big_ws && !in_class) {                                                   \
-    void (*kern)(DevModel, DecodeState) = big ? &k_decode_big<HPV, DPV> : &k_decode_resident<HPV, DPV>;             \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_RESIDENT_CASE(512, 256)
-      UIS_RESIDENT_CASE(512, 512)
-      UIS_RESIDENT_CASE(512, 128)
-      UIS_RESIDENT_CASE(256, 256)
-      UIS_RESIDENT_CASE(256, 128)
-      UIS_RESIDENT_CASE(256, 512)
-      UIS_RESIDENT_CASE(128, 256)
-      UIS_RESIDENT_CASE(128, 128)
-      UIS_RESIDENT_CASE(128, 512)
-#undef UIS_RESIDENT_CASE
-        return UIS_OK;
-      };
-      if (!split) {
-        if ((rc = launch_resident())) return rc;
-      } else {
-        for (size_t k = 0; k <= cuts.size(); ++k) {
-          if (k > 0) {
-            // slice k of every utterance: cast (float64 lists), one strided copy, projection -- behind launch k - 1
-            const int64_t t0 = cuts[k - 1], t1 = k < cuts.size() ? cuts[k] : uniN;
-            for (size_t un = unit_first[k]; un < unit_first[k + 1]; ++un) {
-              if (team) team->wait_blocks(cast_blocks_upto[un]);
-              if ((rc = copy_rows(un))) return rc;
-            }
-            HIPCHK(hipEventRecord(h->h2d_done[k], h->copy_stream));
-            HIPCHK(hipStreamWaitEvent(sg, h->h2d_done[k], 0));
-            if ((rc = pre_rows(gl, k, t0, t1))) return rc;
-            // (k_decode_big<WS> counts its barriers and rows from zero in every launch; the abort word and the XCC ids stay)
-            if (!rs) HIPCHK(hipMemsetAsync(ctl + 32, 0, (ctl_words - 32) * 4, sg));
+    if (plan.clustered()) {
+      // h1 (of every layer) into the extra slot, then ONE launch for every step of every utterance -- or (split) one
+      // per slice of the frames, the next slice arriving behind it
+      HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)U * S * m.depth * m.Hp, m.h1, (size_t)m.depth * m.Hp * 4, hipMemcpyDeviceToDevice, sg));
+      for (size_t k = 0; k <= cuts.size(); ++k) {
+        if (k > 0) {
+          // slice k of every utterance: cast (float64 lists), one strided copy, projection -- behind launch k - 1
+          const int64_t t0 = cuts[k - 1], t1 = k < cuts.size() ? cuts[k] : uniN;
+          for (size_t un = unit_first[k]; un < unit_first[k + 1]; ++un) {
+            if (team) team->wait_blocks(cast_blocks_upto[un]);
+            if ((rc = copy_rows(un))) return rc;
           }
+          HIPCHK(hipEventRecord(h->h2d_done[k], h->copy_stream));
+          HIPCHK(hipStreamWaitEvent(sg, h->h2d_done[k], 0));
+          if ((rc = pre_rows(gl, k, t0, t1))) return rc;
+          // (k_decode_big<WS> counts its barriers and rows from zero in every launch; the abort word and the XCC ids stay)
+          if (!rs) HIPCHK(hipMemsetAsync(ctl + 32, 0, (ctl_words - 32) * 4, sg));
+        }
+        if (split) {
           gp.st.step0 = k ? (int)cuts[k - 1] - 1 : 0;
           gp.st.step1 = k < cuts.size() ? (int)cuts[k] - 1 : 0;
-          if ((rc = launch_resident())) return rc;
         }
+        if ((rc = launch_cluster_kernel(gl, cluster_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st))) return rc;
       }
-    } else if (win) {
-      // h1 into the extra slot, then ONE launch for every sub-step of every window
-      HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)U * S * m.Hp, m.h1, (size_t)m.Hp * 4, hipMemcpyDeviceToDevice, sg));
-      const size_t shmem = big_win_lds_bytes(m.Hp, S, (int)NC, Kmax, B);
-      decode_kernel = UIS_DK_WINDOW;
-      // (BASELINE configs[2]'s shape as compile-time constants: beam 50, cap 12, look_ahead 2, one level of 650 hypotheses;
-      // UIS_NO_SHAPE_CLASSES=1 keeps the run-time instantiation: A/B switch, bit-identical)
-      const bool win_c2 = m.D == m.Dp && m.H == m.Hp && m.Hp == 512 && m.Dp == 256 && B == 50 && Kmax == 12 && L == 2 &&
-                          NC == (int64_t)B * (Kmax + 1) && S == B * Kmax + B + B * (Kmax + 1) && !getenv("UIS_NO_SHAPE_CLASSES");
-      if (win_c2) {
-        void (*kern)(DevModel, DecodeState) = &k_decode_big<512, 256, false, 50, 12, true>;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st))) return rc;
-      }
-#define UIS_WIN_CASE(HPV, DPV)                                                                                        \
-  if (m.Hp == HPV && m.Dp == DPV && !win_c2) {                                                                       \
-    void (*kern)(DevModel, DecodeState) = &k_decode_big<HPV, DPV, false, 0, 0, true>;                               \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_WIN_CASE(512, 256)
-      UIS_WIN_CASE(512, 128)
-      UIS_WIN_CASE(512, 512)
-      UIS_WIN_CASE(256, 256)
-      UIS_WIN_CASE(256, 128)
-      UIS_WIN_CASE(256, 512)
-      UIS_WIN_CASE(128, 256)
-      UIS_WIN_CASE(128, 128)
-      UIS_WIN_CASE(128, 512)
-#undef UIS_WIN_CASE
-    } else if (deep) {
-      // h1 of every layer into the extra slot, then ONE launch for every step of every utterance
-      HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)U * S * m.depth * m.Hp, m.h1, (size_t)m.depth * m.Hp * 4, hipMemcpyDeviceToDevice, sg));
-      const size_t shmem = L == 1 ? deep_lds_bytes(m.Hp, m.Dp, B, Kmax, S) : big_win_lds_bytes(m.Hp, S, (int)NC, Kmax, B);
-      decode_kernel = UIS_DK_DEEP;
-#define UIS_DEEP_CASE(HPV, DPV)                                                                                       \
-  if (m.Hp == HPV && m.Dp == DPV && L == 1) {                                                                        \
-    void (*kern)(DevModel, DecodeState) = &k_decode_deep<HPV, DPV>;                                                 \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_DEEP_CASE(512, 256)
-      UIS_DEEP_CASE(512, 128)
-      UIS_DEEP_CASE(512, 512)
-      UIS_DEEP_CASE(256, 256)
-      UIS_DEEP_CASE(256, 128)
-      UIS_DEEP_CASE(128, 128)
-      UIS_DEEP_CASE(128, 256)
-#undef UIS_DEEP_CASE
-#define UIS_DEEPW_CASE(HPV, DPV)                                                                                      \
-  if (m.Hp == HPV && m.Dp == DPV && L > 1) {                                                                         \
-    void (*kern)(DevModel, DecodeState) = &k_decode_deep<HPV, DPV, true>;                                           \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                               (int)shmem));                                                                         \
-    if ((rc = gl.run_cooperative(UIS_K_GRU, kern, h->n_cu, dim3(32 * ncl), dim3(512), shmem, m, gp.st)))           \
-      return rc;                                                                                                     \
-  }
-      UIS_DEEPW_CASE(512, 256)
-      UIS_DEEPW_CASE(256, 256)
-      UIS_DEEPW_CASE(256, 128)
-      UIS_DEEPW_CASE(128, 128)
-#undef UIS_DEEPW_CASE
-    } else if (small) {
-      const size_t shmem = L == 1 ? small_lds_bytes(m.Dp, B, Kmax, S) : small_win_lds_bytes(S, (int)NC, Kmax, B);
-      decode_kernel = UIS_DK_SMALL;
-      if (L == 1) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_small<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        LAUNCH(UIS_K_GRU, k_decode_small<false>, dim3(gp.U), dim3(512), shmem, m, gp.st);
-      } else {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_small<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        LAUNCH(UIS_K_GRU, k_decode_small<true>, dim3(gp.U), dim3(512), shmem, m, gp.st);
-      }
-    } else if (use_graph && gp.maxT >= UIS_GRAPH_STEPS) {
+    } else if (plan.path == DecodePath::SMALL) {
+      DecodeKernel kern = L == 1 ? &k_decode_small<false> : &k_decode_small<true>;
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+      LAUNCH(UIS_K_GRU, kern, dim3(gp.U), dim3(512), plan.lds, m, gp.st);
+    } else if (plan.path == DecodePath::GRAPH && gp.maxT >= UIS_GRAPH_STEPS) {
       GraphCache& gc = h->gcache[g];
-      const bool same = gc.exec && gc.lds == (size_t)lds.total && memcmp(&gc.st, &gp.st, sizeof(DecodeState)) == 0;
+      const bool same = gc.exec && gc.lds == plan.lds && memcmp(&gc.st, &gp.st, sizeof(DecodeState)) == 0;
       if (!same) {
         if (gc.exec) { (void)hipGraphExecDestroy(gc.exec); gc.exec = nullptr; }
         hipGraph_t graph = nullptr;
         HIPCHK(hipStreamBeginCapture(sg, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_steps(h, gl, gp.st, lds.total, UIS_GRAPH_STEPS);
+        rc = enqueue_steps(h, gl, gp.st, plan.lds, UIS_GRAPH_STEPS);
         hipError_t ce = hipStreamEndCapture(sg, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (ce != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
         ce = hipGraphInstantiate(&gc.exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (ce != hipSuccess) { gc.exec = nullptr; return fail(UIS_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ce)); }
-        gc.st = gp.st; gc.lds = (size_t)lds.total;
+        gc.st = gp.st; gc.lds = plan.lds;
       }
       const int64_t nlaunch = (gp.maxT + UIS_GRAPH_STEPS - 1) / UIS_GRAPH_STEPS;  // the tail steps are no-ops
       for (int64_t i = 0; i < nlaunch; ++i) HIPCHK(hipGraphLaunch(gc.exec, sg));
     } else {
       const int64_t nsteps = gp.maxT + (gp.maxT & 1);
       for (int64_t s0 = 0; s0 < nsteps; s0 += 2)
-        if ((rc = enqueue_steps(h, gl, gp.st, lds.total, 2))) return rc;
+        if ((rc = enqueue_steps(h, gl, gp.st, plan.lds, 2))) return rc;
     }
     if (!wnd)
       LAUNCH(UIS_K_BACKTRACE, k_backtrace, dim3(gp.U), dim3(64), (size_t)64 * B, gp.st, d_labels,
@@ -1600,6 +1712,7 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(h->stream, h->gdone[g], 0));
   HIPCHK(hipEventRecord(h->ev_end, h->stream));
 
+  // ---- stats
   std::vector<unsigned long long> counters((size_t)UIS_MAX_GROUPS * 4, 0ull);
   HIPCHK(hipMemcpyAsync(counters.data(), h->counters.p, (size_t)G * 4 * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(h->last_overflow.data(), h->overflow.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1614,124 +1727,10 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     return fail(UIS_ERR_HIP, abort_word == 2 ? "workgroup cluster not placed on one XCD (in-launch barrier path)"
                                              : "in-launch barrier timed out");
   }
-#if defined(UIS_SELECT_TIMING)
-  {
-    unsigned long long tc[48];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-
-    const double launches = (double)maxT * U;
-    if (L == 1) {
-      fprintf(stderr, "[select timing] cycles per workgroup-launch:");
-      for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.0f", k, (double)tc[16 + k] / launches);
-      fprintf(stderr, "\n");
-    } else {
-      static const char* names[7] = {"live+offsets", "mse", "scores", "expand/prune", "leaders+slots", "tables", "records+rows"};
-      for (int half = 0; half < 2; ++half) {
-        const unsigned long long* c = tc + (half ? 32 : 16);
-        const double n = (double)std::max<unsigned long long>(c[7], 1);
-        fprintf(stderr, "[window timing] %s sub-steps, us per workgroup-launch:", half ? "pruning" : "expanding");
-        double sum = 0.0;
-        for (int k = 0; k < 7; ++k) { fprintf(stderr, " %s=%.2f", names[k], (double)c[k] * 0.01 / n); sum += (double)c[k] * 0.01 / n; }
-        fprintf(stderr, " | total=%.2f; per launch: candidates=%.0f live=%.0f hypotheses in=%.0f rows=%.1f\n", sum, (double)c[8] / n,
-                (double)c[9] / n, (double)c[10] / n, (double)c[11] / n);
-      }
-    }
-  }
+#if defined(UIS_SELECT_TIMING) || defined(UIS_RESIDENT_PROBE) || defined(UIS_RS_COUNT_PATHS) || defined(UIS_RESIDENT_TIMING)
+  if ((rc = report_diagnostics(h, plan, U, maxT, L))) return rc;
 #endif
-#if defined(UIS_RESIDENT_PROBE)
-  if (resident) {
-    unsigned long long tc[88];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[resident probe] cycles per dependent load: own-table(nt)=%.0f mean(sc1)=%.0f wgt(plain)=%.0f wgt-again=%.0f\n",
-            (double)tc[80] / (double)maxT, (double)tc[81] / (double)maxT, (double)tc[82] / (double)maxT, (double)tc[83] / (double)maxT);
-  }
-#endif
-#if defined(UIS_RS_COUNT_PATHS)
-  if (rs) {
-    unsigned long long tc[96];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[rs short lists] selects with <= 16 / <= 32 / <= 64 / more survivors: %llu %llu %llu %llu\n", tc[88], tc[89], tc[90], tc[91]);
-  }
-#endif
-#if defined(UIS_RESIDENT_TIMING)
-  if (win) {  // even sub-steps (expanding, at look_ahead 2) and odd ones (pruning) apart
-    unsigned long long tc[88];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-    static const char* names[8] = {"window", "barA", "gru", "barB", "head1", "barC", "head2", "barD"};
-    for (int wg = 0; wg < 2; ++wg)
-      for (int odd = 0; odd < 2; ++odd) {
-        fprintf(stderr, "[window launch timing] workgroup %3d, %s sub-steps, us per sub-step:", wg ? 248 : 0, odd ? "odd" : "even");
-        double sum = 0.0;
-        for (int k = 0; k < 8; ++k) {
-          const double us = (double)tc[(wg ? 64 : 48) + 8 * odd + k] * 0.01 / ((double)maxT * 0.5);
-          fprintf(stderr, " %s=%.2f", names[k], us);
-          sum += us;
-        }
-        fprintf(stderr, " | total=%.2f\n", sum);
-      }
-    std::vector<unsigned long long> per((size_t)96 + 1024);
-    HIPCHK(hipMemcpy(per.data(), h->counters.as<unsigned long long>(), per.size() * 8, hipMemcpyDeviceToHost));
-    for (int wg = 0; wg < 2; ++wg) {
-      fprintf(stderr, "[window launch timing] workgroup %3d, gru of the even sub-steps, us by wave:", wg ? 248 : 0);
-      for (int w = 0; w < 8; ++w) fprintf(stderr, " %.1f", (double)per[80 + 8 * wg + w] * 0.01 / ((double)maxT * 0.5));
-      fprintf(stderr, "\n");
-    }
-    static const char* what[4] = {"gru", "wait B", "head1", "head2"};
-    for (int k = 0; k < 4; ++k) {
-      fprintf(stderr, "[window launch timing] %s, even sub-steps, us by rank (mean over the clusters):", what[k]);
-      for (int r = 0; r < 32; ++r) {
-        double sum = 0.0;
-        for (int c = 0; c < ncl; ++c) sum += (double)per[(size_t)96 + 256 * k + c + ncl * r];
-        fprintf(stderr, " %.1f", sum / ncl * 0.01 / ((double)maxT * 0.5));
-      }
-      fprintf(stderr, "\n");
-    }
-  }
-  if (resident && (decode_kernel & 0xff) == UIS_DK_BIG_COH) {  // k_decode_coh: waves 0 (cohort A), 1 (cohort B) and 7 (no utterance at <= 7 per rank) of workgroup 0
-    unsigned long long tc[96];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-    static const char* names[16] = {"wait select A", "-", "-", "gru", "mean1", "mean2", "select", "early mse", "slot", "leave", "-", "-", "-", "-", "-", "-"};
-    for (int k3 = 0; k3 < 3; ++k3) {
-      fprintf(stderr, "[cohort timing] workgroup 0 wave %d, us per step:", k3 == 0 ? 0 : k3 == 1 ? 1 : 7);
-      double sum = 0.0;
-      for (int k = 0; k < 10; ++k) {
-        if (k == 1 || k == 2) continue;
-        const double us = (double)tc[48 + 16 * k3 + k] * 0.01 / (double)maxT;
-        fprintf(stderr, " %s=%.2f", names[k], us);
-        sum += us;
-      }
-      fprintf(stderr, " | total=%.2f\n", sum);
-    }
-  } else if (resident) {
-    unsigned long long tc[88];
-    HIPCHK(hipMemcpy(tc, h->counters.as<unsigned long long>(), sizeof(tc), hipMemcpyDeviceToHost));
-    static const char* names[8] = {"select", "barA", "gru", "barB", "head1", "barC", "head2", "barD"};
-    for (int wg = 0; wg < 2; ++wg) {
-      fprintf(stderr, "[resident timing] workgroup %3d, us per step:", wg ? 248 : 0);
-      for (int k = 0; k < 8; ++k) fprintf(stderr, " %s=%.2f", names[k], (double)tc[(wg ? 64 : 48) + k] * 0.01 / (double)maxT);
-      fprintf(stderr, "\n");
-    }
-    fprintf(stderr, "[resident timing] select phases (wg 0), us per step:");
-    for (int k = 0; k < 8; ++k) fprintf(stderr, " p%d=%.2f", k, (double)tc[80 + k] * 0.01 / (double)maxT);
-    fprintf(stderr, "\n");
-    fprintf(stderr, "[resident timing] gru fine (wg 248): other=%.2f tile=%.2f combine=%.2f sync=%.2f\n",
-            (double)tc[72] * 0.01 / (double)maxT, (double)tc[73] * 0.01 / (double)maxT, (double)tc[74] * 0.01 / (double)maxT,
-            (double)tc[75] * 0.01 / (double)maxT);
-    if ((decode_kernel & 0xff) == UIS_DK_BIG || (decode_kernel & 0xff) == UIS_DK_BIG_WS) {  // k_decode_big: the GRU stage wave by wave, the row tiles per step
-      unsigned long long wv[32];
-      HIPCHK(hipMemcpy(wv, h->counters.as<unsigned long long>() + 96, sizeof(wv), hipMemcpyDeviceToHost));
-      for (int wg = 0; wg < 2; ++wg) {
-        fprintf(stderr, "[resident timing] workgroup %3d, gru us per step by wave:", wg ? 248 : 0);
-        for (int w = 0; w < 8; ++w) fprintf(stderr, " %.1f", (double)wv[8 * wg + w] * 0.01 / (double)maxT);
-        fprintf(stderr, "\n");
-      }
-      fprintf(stderr, "[resident timing] cluster 0: row tiles per step mean %.2f; steps by (row tiles mod 8):", (double)wv[24] / (double)maxT);
-      for (int k = 0; k < 8; ++k) fprintf(stderr, " %d:%llu", k, wv[16 + k]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
-  if (resident && !rs && tn.sig != 0 && tn.phase <= 4 && !getenv("UIS_NO_CTL_TUNE")) {  // the decode's device time goes to the placement it ran with
+  if (ctl_tune && tn.sig != 0 && tn.phase <= 4) {  // the decode's device time goes to the placement it ran with
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, h->ev_begin, h->ev_end));
     if (tn.phase >= 1) tn.ms[tn.phase - 1] = ms;
@@ -1759,8 +1758,8 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     }
     stats->n_overflow = n_over;
     stats->n_streams = G;
-    stats->decode_kernel = decode_kernel;
-    stats->decode_launches = (resident || win || deep || small) ? (split ? (int)cuts.size() + 1 : 1) : 0;
+    stats->decode_kernel = plan.decode_kernel;
+    stats->decode_launches = plan.one_launch() ? (int)cuts.size() + 1 : 0;
     if (profile) {
       for (size_t i = 0; i + 1 < h->prof.used; i += 2) {
         float t = 0.0f;
@@ -1804,13 +1803,7 @@ int decode_impl(uis_handle* h, const float* d_frames, const int64_t* offsets, in
 
 UIS_EXPORT int32_t uis_abi_version(void) { return UIS_ABI_VERSION; }
 UIS_EXPORT int32_t uis_numerics_version(void) { return UIS_NUMERICS_VERSION; }
-UIS_EXPORT uint32_t uis_build_flags(void) {
-  uint32_t f = 0;
-#if defined(UIS_WITH_COHORTS)
-  f |= UIS_BUILD_COHORTS;
-#endif
-  return f;
-}
+UIS_EXPORT uint32_t uis_build_flags(void) { return 0; }
 
 UIS_EXPORT int32_t uis_device_count(void) {
   int n = 0;
@@ -1895,7 +1888,7 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
       hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming) != hipSuccess)
     return bail(fail(UIS_ERR_HIP, "event create failed"));
   DevModel& m = h->m;
-  m.D = D; m.H = H; m.depth = depth;
+  m.D = D; m.H_units = H; m.depth = depth;
   m.Dp = round_up(D, 16); m.Hp = round_up(H, 16);
   // The one-launch cluster kernels exist for padded hidden sizes 256 / 512 and observation dims 128 / 256 /
   // 512.  Padding further than to 16 is free of numerical consequences exactly where it keeps the canonical
@@ -1915,7 +1908,7 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
       m.Hp = hp; m.Dp = dp;
       if (seg3) {
         hmap.seg = 3 * 16; hmap.seg_p = 4 * 16;
-        m.H = m.Hp;  // (the kernels' `unit < H` masks: the model's units are spread over the whole padded vector; the rest stay 0 by themselves)
+        m.H_units = m.Hp;  // (the kernels' `unit < H_units` masks: the model's units are spread over the whole padded vector; the rest stay 0 by themselves)
       }
     }
   }

@@ -42,7 +42,9 @@ struct RnnRow {
 #define UIS_PM_CTL_WORDS 832
 
 struct DevModel {
-  int D, H, depth, Dp, Hp, G;  // G = 3*Hp (gates r|z|n, each padded to Hp)
+  // H_units: the hidden units the kernels compute (rnn_hidden_size, or Hp where a model is embedded in a larger
+  // shape: hidden sizes 257 .. 384); units from H_units to Hp stay 0.  The model's own size is uis_handle::H_model.
+  int D, H_units, depth, Dp, Hp, G;  // G = 3*Hp (gates r|z|n, each padded to Hp)
   // weights in MFMA tile order: [feature tile][k block][lane 0..63][4]
   const float* wih[UIS_MAX_DEPTH];
   const float* whh[UIS_MAX_DEPTH];

@@ -11,6 +11,7 @@
 // Written for wave64 / MFMA f32 16x16x4 / 8 XCDs; no other target.
 #include "uis_kernels.h"
 #include "uis_numerics.h"
+#include "uisrnn_hip.h"  // (UIS_FLAG_* the kernels test in DecodeState::flags)
 
 
 // ------------------------------------------------------------------ helpers
@@ -529,7 +530,7 @@ __global__ __launch_bounds__(512) void k_dense_gru(DevModel m, DecodeState st, i
     const float ghr = splitk_combine<RT, 3>(spart, r, 0, e);
     const float ghz = splitk_combine<RT, 3>(spart, r, 1, e);
     const float ghn = splitk_combine<RT, 3>(spart, r, 2, e);
-    const float out = j < m.H ? uis_gru_unit(gir[k], giz[k], gin[k], ghr, ghz, ghn, hprev[k]) : 0.0f;
+    const float out = j < m.H_units ? uis_gru_unit(gir[k], giz[k], gin[k], ghr, ghz, ghn, hprev[k]) : 0.0f;
     const_cast<float*>(hid_ptr(m, st, re[k], re[k].dst, layer))[j] = out;
   }
 }
@@ -718,7 +719,7 @@ __global__ __launch_bounds__(256) void k_big_gru(DevModel m, DecodeState st, int
     f32x4 out;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      out[i] = j4 + i < m.H ? uis_gru_unit(gir[c][i], giz[c][i], gin[c][i], total[c * 3 + 0][i], total[c * 3 + 1][i],
+      out[i] = j4 + i < m.H_units ? uis_gru_unit(gir[c][i], giz[c][i], gin[c][i], total[c * 3 + 0][i], total[c * 3 + 1][i],
                                            total[c * 3 + 2][i], hprev[c][i])
                             : 0.0f;
     *reinterpret_cast<f32x4*>(hd + j4) = out;
@@ -2052,7 +2053,7 @@ __device__ __forceinline__ f32x4 sys_load_f32x4(const float* p) {
 template <int HP, int DP, bool PERSIST = false, int CB = 0, int CK = 0>
 __global__ __launch_bounds__(512) void k_decode_resident(DevModel m, DecodeState st) {
   m.Hp = HP; m.Dp = DP; m.G = 3 * HP;  // (what the template arguments say)
-  if (CB) { st.B = CB; st.Kmax = CK; st.S = CB * CK + CB; m.H = HP; m.D = DP; }
+  if (CB) { st.B = CB; st.Kmax = CK; st.S = CB * CK + CB; m.H_units = HP; m.D = DP; }
   constexpr int NKB = HP / 16, PER = NKB / UIS_KSPLIT, RC = UIS_RES_RC;
   constexpr int NFT1 = HP / 16, SH1 = 32 / NFT1;  // ranks sharing one GRU / linear_mean1 feature tile
   constexpr int NFT2 = DP / 16, SH2 = 32 / NFT2;  // ranks sharing one linear_mean2 feature tile
@@ -2532,7 +2533,7 @@ __global__ __launch_bounds__(512) void k_decode_resident(DevModel m, DecodeState
           const float ghr = splitk_combine<RC, 3>(spart, r, 0, e);
           const float ghz = splitk_combine<RC, 3>(spart, r, 1, e);
           const float ghn = splitk_combine<RC, 3>(spart, r, 2, e);
-          const float out = j < m.H ? uis_gru_unit(gir[k], giz[k], gin[k], ghr, ghz, ghn, hprev[k]) : 0.0f;
+          const float out = j < m.H_units ? uis_gru_unit(gir[k], giz[k], gin[k], ghr, ghz, ghn, hprev[k]) : 0.0f;
           rs_buf_store_f32(rs_hid, (uint32_t)(((re[k].utt * S + re[k].dst) * HP + j) * 4), out);
           rs_buf_store_f32(rs_hst, (uint32_t)((((int)tile0 + c0 + tpar1 + SH1 * (i0 + r)) * NFT1 + ft1) * 256 + e) * 4u, out);  // the copy linear_mean1 streams
         }
@@ -2547,7 +2548,7 @@ __global__ __launch_bounds__(512) void k_decode_resident(DevModel m, DecodeState
     if (flag_handoff) {
       // publish; the first half of the next step's select preparation (this workgroup's own LDS tables:
       // nobody else's data); then every wave waits for the four producers of its K-slice
-      rs_flag_publish(flags_c, rank, fphase, (st.flags & 0x20000u) != 0u);
+      rs_flag_publish(flags_c, rank, fphase, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
       if (prep_next)
         select_fast_body<512, true, true, DP, 1>(m, st, upar ^ 1, cluster + ncl * rank, smem_raw, sink, ustep + 1, my_off0, my_off1,
                                                  SelectNoHook(), first_step);
@@ -2590,7 +2591,7 @@ __global__ __launch_bounds__(512) void k_decode_resident(DevModel m, DecodeState
     RSTAMP(4);
     ++fphase;
     if (flag_handoff) {  // ... and the second half inside the next hand-off
-      rs_flag_publish(flags_c, rank, fphase, (st.flags & 0x20000u) != 0u);
+      rs_flag_publish(flags_c, rank, fphase, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
       if (prep_next)
         select_fast_body<512, true, true, DP, 4>(m, st, upar ^ 1, cluster + ncl * rank, smem_raw, sink, ustep + 1, my_off0, my_off1,
                                                  SelectNoHook(), first_step);
@@ -2860,7 +2861,7 @@ __global__ __launch_bounds__(512) void k_wt_gru(DevModel m, DecodeState st, int 
       f32x4 out;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        out[i] = j4 + i < m.H ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
+        out[i] = j4 + i < m.H_units ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
       *reinterpret_cast<f32x4*>(const_cast<float*>(hid_ptr(m, st, me, me.dst, layer)) + j4) = out;
     }
     tile = next; me = me_n; hs = hs_n;
@@ -3612,7 +3613,7 @@ __global__ __launch_bounds__(512) void k_decode_small(DevModel m, DecodeState st
             const float ghr = splitk_combine<1, 3>(spart, 0, 0, t);
             const float ghz = splitk_combine<1, 3>(spart, 0, 1, t);
             const float ghn = splitk_combine<1, 3>(spart, 0, 2, t);
-            const float out = j < m.H ? uis_gru_unit(gi[j], gi[m.Hp + j], gi[2 * m.Hp + j], ghr, ghz, ghn, hs[j]) : 0.0f;
+            const float out = j < m.H_units ? uis_gru_unit(gi[j], gi[m.Hp + j], gi[2 * m.Hp + j], ghr, ghz, ghn, hs[j]) : 0.0f;
             const_cast<float*>(hid_ptr(m, st, re, re.dst, l))[j] = out;
           }
           __syncthreads();
@@ -3821,10 +3822,10 @@ template <int HP, int DP, bool WS = false, int CB = 0, int CK = 0, bool WIN = fa
 __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) {
   static_assert(!(WIN && WS), "one kind of select stage");
   m.Hp = HP; m.Dp = DP; m.G = 3 * HP;  // (what the template arguments say)
-  if (CB && !WIN) { st.B = CB; st.Kmax = CK; st.S = CB * CK + CB; m.H = HP; m.D = DP; }  // (see k_decode_resident)
+  if (CB && !WIN) { st.B = CB; st.Kmax = CK; st.S = CB * CK + CB; m.H_units = HP; m.D = DP; }  // (see k_decode_resident)
   // WIN with a fixed shape (round 5: BASELINE configs[2], beam 50 / cap 12): look_ahead 2, one intermediate level of
   // beam_size * (max_clusters + 1) hypotheses (below the level capacity: the host checks), its slots behind the beam's
-  if (CB && WIN) { st.B = CB; st.Kmax = CK; st.L = 2; st.NC = CB * (CK + 1); st.S = CB * CK + CB + CB * (CK + 1); m.H = HP; m.D = DP; }
+  if (CB && WIN) { st.B = CB; st.Kmax = CK; st.L = 2; st.NC = CB * (CK + 1); st.S = CB * CK + CB + CB * (CK + 1); m.H_units = HP; m.D = DP; }
   constexpr int NKB = HP / 16;
   constexpr int NFT1 = HP / 16, SH1 = 32 / NFT1;  // ranks sharing one GRU / linear_mean1 feature tile
   constexpr int NFT2 = DP / 16, SH2 = 32 / NFT2;  // ranks sharing one linear_mean2 feature tile
@@ -4067,7 +4068,7 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
           f32x4 out;
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            out[i] = j4 + i < m.H ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
+            out[i] = j4 + i < m.H_units ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
           rs_buf_store_f32x4(rs_hid, (uint32_t)((rh.utt * S + rh.dst) * HP + j4) * 4u, out);
           // ... and the copy linear_mean1 streams: [row tile][feature tile][16 rows][16], so that a
           // consumer wave's 16-byte-per-lane load is one contiguous KiB (plain rows cost one 64-byte L2
@@ -4169,10 +4170,6 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
     atomicMax(&st.counters[3], acc[3]);
   }
 }
-
-#if defined(UIS_WITH_COHORTS)
-#include "uis_decode_coh.hip"
-#endif
 
 // rnn_depth >= 2 in ONE launch (round 4): k_decode_big's grid, barriers and wave-per-row-tile stages with one
 // more pair of stages per upper layer.  A workgroup's 96 KB weight slot cannot hold W_hh of every layer and
@@ -4348,7 +4345,7 @@ __global__ __launch_bounds__(512) void k_decode_deep(DevModel m, DecodeState st)
             f32x4 out;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              out[i] = j4 + i < m.H ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
+              out[i] = j4 + i < m.H_units ? uis_gru_unit(gir[i], giz[i], gin[i], gh[0][i], gh[1][i], gh[2][i], hprev[i]) : 0.0f;
             rs_buf_store_f32x4(rs_hid, (uint32_t)((((size_t)rh.utt * S + rh.dst) * depth * HP + j4) * 4) + lay, out);
             rs_buf_store_f32x4(rs_out, (uint32_t)((((int)tile0 + tile) * NFT1 + ft1) * 256 + (lane & 15) * 16 + 4 * q) * 4u, out);
           }

@@ -35,20 +35,6 @@
 //     step's last hand-off all 32.
 #pragma once
 
-// 1: k_decode_rs is the default wherever it applies (UIS_FLAG_OWNER_SELECT keeps k_decode_resident);
-// 0: it runs only with UIS_FLAG_REPLICATED_SELECT
-#ifndef UIS_RS_DEFAULT
-#define UIS_RS_DEFAULT 1
-#endif
-// 1: two utterances per wave (9 .. 16 utterances per XCD) is the default where it applies; 0: only with
-// UIS_FLAG_REPLICATED_SELECT (k_decode_resident keeps those batches)
-#ifndef UIS_RS_UPW2_DEFAULT
-#define UIS_RS_UPW2_DEFAULT 0   // measured (profiles/r04_rs_shape_classes.txt): 1.20 / 1.40 / 1.60 M frames/s at 65 / 96 / 128 utterances against 1.37 / 1.67 / 1.94 M
-#endif
-// ... and the same switch for the wide class (beam_size 17 .. 32, observation dim 512)
-#ifndef UIS_RS_WIDE_DEFAULT
-#define UIS_RS_WIDE_DEFAULT 0   // measured: configs[4] 0.80 M against k_decode_resident's 0.84 M
-#endif
 #define UIS_RS_UTT 8        // waves per workgroup = utterance slots per cluster and UPW (utterances per wave)
 #define UIS_RS_MAXS 256     // slots per utterance (four 64-bit masks)
 #define UIS_RS_LOGTAB 128   // entries of the LDS copies of the log tables (larger counts: global)
@@ -928,7 +914,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   const int U = st.U;
   // (the fixed-shape classes are dispatched for unpadded models only: observation_dim = DP, rnn_hidden_size = HP)
   const RsDims dm{CB ? CB : st.B, CB ? CK : st.Kmax, CB ? CB * CK + CB : st.S, CB ? DP : m.D};
-  const int Hreal = CB ? HP : m.H;
+  const int Hreal = CB ? HP : m.H_units;
   const int S = dm.S, B = dm.B;
   const RsLds L = rs_lds_layout(dm.B, dm.Kmax, dm.S);
   float* swgt = reinterpret_cast<float*>(smem_raw);
@@ -1188,7 +1174,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // for); the first look at the producers' words is requested from inside it, so that its round
     // trip is over when the wave gets there; then wait
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 1u) & live_mask, (st.flags & 0x20000u) != 0u);
+      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 1u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
       u32x4 pk = u32x4{0u, 0u, 0u, 0u};
       auto peek = [&]() { pk = rs_flag_peek4(rs_flags, (uint32_t)(16 * w)); };
       bool peeked = false;
@@ -1243,7 +1229,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // publish; then the next step's MSEs of the clusters this step did not rewrite (every workgroup
     // its share of every utterance's; visible to all behind the step's last hand-off); then wait
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 2u) & live_mask, (st.flags & 0x20000u) != 0u);
+      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 2u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
       u32x4 pk = u32x4{0u, 0u, 0u, 0u};
       auto peek = [&]() { pk = rs_flag_peek4(rs_flags, (uint32_t)(16 * w)); };
       bool peeked = false;
@@ -1322,7 +1308,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // publish; then the next step's candidate grid (this wave's own tables: nobody else's data); then
     // wait -- every wave, every step, for all 32 producers (rs_flag_wait_all)
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 3u) & live_mask, (st.flags & 0x20000u) != 0u);
+      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 3u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
       uint32_t pk = 0u;
       auto peek = [&]() { pk = rs_flag_peek_all(flags_c); };
       bool peeked = false;
