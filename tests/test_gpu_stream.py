@@ -276,6 +276,43 @@ def test_persistent_flag_is_refused_where_it_cannot_work():
   dec.stream_end()
 
 
+# Which sessions uis_stream_begin accepts, per (rnn_hidden_size, observation_dim, rnn_depth, beam_size, n_utt): the return
+# codes for UIS_FLAG_RESIDENT, UIS_FLAG_PERSISTENT and UIS_FLAG_RESIDENT | UIS_FLAG_STEPWISE (0 = accepted, -7 =
+# UIS_ERR_UNSUPPORTED), recorded on a whole MI355X (256 compute units: 8 clusters of 32).
+_SESSION_ACCEPTANCE = {
+    (128, 128, 1, 10, 8): (-7, -7, -7),
+    (128, 256, 1, 10, 8): (-7, -7, -7),
+    (128, 512, 1, 10, 8): (-7, -7, -7),
+    (256, 128, 1, 10, 8): (0, -7, -7),
+    (256, 256, 1, 10, 8): (0, 0, -7),
+    (256, 512, 1, 10, 8): (0, -7, -7),
+    (512, 128, 1, 10, 8): (0, -7, -7),
+    (512, 256, 1, 10, 8): (0, 0, -7),
+    (512, 512, 1, 10, 8): (0, 0, -7),
+    (256, 256, 2, 10, 8): (-7, -7, -7),     # rnn_depth 2
+    (512, 200, 1, 10, 8): (0, -7, -7),      # a padded observation dim
+    (512, 256, 1, 40, 8): (-7, -7, -7),     # a beam too wide for the fast select
+    (512, 256, 1, 10, 257): (0, -7, -7)}    # more utterances than 32 x clusters
+
+
+def test_session_kernel_choice_is_pinned():
+  """The one-launch and persistent sessions are offered for exactly the shapes recorded above; after a refusal the
+  handle still opens a plain session."""
+  import torch  # (only for the device's compute-unit count)
+  if torch.cuda.get_device_properties(0).multi_processor_count != 256:
+    pytest.skip('the recorded matrix is for a whole MI355X (256 compute units)')
+  flags = (_capi.UIS_FLAG_RESIDENT, _capi.UIS_FLAG_PERSISTENT, _capi.UIS_FLAG_RESIDENT | _capi.UIS_FLAG_STEPWISE)
+  for (hidden, dim, depth, beam, n_utt), want in _SESSION_ACCEPTANCE.items():
+    dec = _capi.Decoder(weights.init_params(dim, hidden, depth, sigma2=0.08, transition_bias=0.2, seed=5))
+    got = []
+    for f in flags:
+      got.append(dec._lib.uis_stream_begin(dec._handle, n_utt, _capi.make_opts(beam, 1, 1, 0, f, 0), 16))
+      if got[-1] != _capi.UIS_OK:
+        dec.stream_begin(n_utt, beam, 16)
+      dec.stream_end()
+    assert tuple(got) == want, (hidden, dim, depth, beam, n_utt)
+
+
 def test_odd_model_shapes_general_select_and_depth(oracle_lib):
   """Padded dims, depth 2 (k_dense_upper_in), a beam too wide for the fast select kernel."""
   rng = np.random.default_rng(3)

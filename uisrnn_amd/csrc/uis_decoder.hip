@@ -372,6 +372,13 @@ struct Launcher {
     if (rc_) return rc_;                  \
   } while (0)
 
+// The input projection of n frames with the plain kernels: gi0 = W_ih0 x + b_ih0, then mse0.
+int plain_input_proj(Launcher& lch, const DevModel& m, const float* x, float* gi0, float* mse0, long n) {
+  LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj, dense_grid(n, m.G / 16), dim3(256), 0, m, x, gi0, n);
+  LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, x, mse0, n, 0L, (const long*)nullptr);
+  return UIS_OK;
+}
+
 // One batched CoreRNN evaluation over the rows emitted for step parity `par`.
 // Which family of dense kernels the launch-per-step path runs for a step of at most `max_rows`
 // rnn rows (UIS_DF_*; uis_stats.decode_kernel reports it).
@@ -737,7 +744,16 @@ enum { CLS_NONE = 0, CLS_C1 /* configs[1] / [3]: beam 10, cap 16 */, CLS_C4 /* c
 //   RS_WIDE   beam_size <= 32, <= 256 candidates, observation dim 256 or 512 (configs[4]), at most 8 per XCD
 enum { RS_NONE = 0, RS_BASE, RS_C1, RS_UPW2, RS_WIDE };
 
-struct DecodePlan {
+// Where the one-launch kernels put their rows: the CUs form ncl clusters of 32 (one per XCD: 8 on a whole MI355X, 1 in
+// CPX mode); one row region per cluster of rx_stride rows, a multiple of 16 (rows an utterance can emit per step:
+// beam_size, or a level's capacity inside a look-ahead window) plus `slack`; rows_cap rows in all.
+struct ClusterGeometry {
+  int ncl = 0, nclq = 1;  // clusters of 32 CUs (0: the device has none), and at least 1
+  int rx_stride = 0;      // rows of one cluster's row region
+  long rows_cap = 0;
+};
+
+struct DecodePlan : ClusterGeometry {  // (the geometry the workspace shares with the choice)
   DecodePath path = DecodePath::STEPWISE;
   int rs_kind = RS_NONE;
   int cls = CLS_NONE;     // the shape class of the instantiation that runs (CLS_*)
@@ -745,16 +761,34 @@ struct DecodePlan {
   int decode_kernel = 0;  // uis_stats.decode_kernel
   bool split = false;     // several launches, the later frames travelling behind the earlier launches ...
   std::vector<int64_t> cuts;  // ... at these frame indices (empty without split)
-  // geometry the workspace shares with the choice
-  int ncl = 0, nclq = 1;  // clusters of 32 CUs (0: the device has none), and at least 1
-  int rx_stride = 0;      // rows of one cluster's row region
-  long max_rows = 0, rows_cap = 0;
+  long max_rows = 0;
   bool hst = false;       // rnn_depth >= 2 at the cluster kernels' shapes: k_decode_deep's hand-off buffers
   bool stage = false;     // a ragged float64 list big enough to split: the device's copy of the staging block
   bool resident() const { return path == DecodePath::RESIDENT || path == DecodePath::RS || path == DecodePath::BIG || path == DecodePath::BIG_WS; }
   bool clustered() const { return resident() || path == DecodePath::WINDOW || path == DecodePath::DEEP; }
   bool one_launch() const { return clustered() || path == DecodePath::SMALL; }
 };
+
+ClusterGeometry cluster_geometry(int n_cu, int U, long rows_per_utt, int slack, int G) {
+  ClusterGeometry g;
+  g.ncl = (n_cu >= 32 && n_cu % 32 == 0 && n_cu / 32 <= UIS_MAX_CLUSTERS) ? n_cu / 32 : 0;
+  g.nclq = std::max(g.ncl, 1);
+  g.rx_stride = (int)(((((long)U + g.nclq - 1) / g.nclq) * rows_per_utt + 15) / 16 * 16) + slack;
+  g.rows_cap = std::max((long)U * rows_per_utt + 48L * G, (long)g.nclq * g.rx_stride);  // every group's last row tile may run past its rows
+  return g;
+}
+
+// What a one-launch decode with register-resident weights (k_decode_resident and its relatives) needs, before the
+// callers' own terms: rnn_depth 1 at the instantiated dims, the fast select, a cluster, 2 GB descriptors, the LDS budget.
+bool resident_fits(const DevModel& m, int U, int B, int Kmax, int S, const ClusterGeometry& g) {
+  return m.depth == 1 && (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512) &&
+         select_fast_ok(B, Kmax, S) && g.ncl >= 1 && ((double)U * S + 1) * m.Hp * 4.0 < 2.0e9 &&
+         (double)g.rows_cap * m.Hp * 4.0 < 2.0e9 && (double)U * S * m.Dp * 4.0 < 2.0e9 &&
+         resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
+}
+
+// The dynamic LDS of a one-launch kernel: at least 96 KB, so that a CU holds one workgroup.
+size_t one_launch_lds(size_t lds) { return std::max<size_t>(lds, 96 * 1024); }
 
 // The dispatch rule.  No HIP call, no allocation, no global state: the same inputs give the same plan.
 DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, const DecodeKnobs& k, int n_cu,
@@ -765,17 +799,11 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
   const bool per_step = (flags & UIS_FLAG_STEPWISE) != 0, generic = (flags & UIS_FLAG_GENERIC_SELECT) != 0;
   // (after a failed placement check the handle keeps to the launch-per-step path, unless UIS_FLAG_RESIDENT asks)
   const bool allowed = !resident_off || (flags & UIS_FLAG_RESIDENT);
-  const bool cl_dims = (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512);
-  // the one-launch kernels: the CUs form ncl clusters of 32 (one per XCD: 8 on a whole MI355X, 1 in CPX mode); one
-  // row region per cluster, a multiple of 16 rows (rows an utterance can emit per step: beam_size, or a level's
-  // capacity inside a look-ahead window)
-  p.ncl = (n_cu >= 32 && n_cu % 32 == 0 && n_cu / 32 <= UIS_MAX_CLUSTERS) ? n_cu / 32 : 0;
-  p.nclq = std::max(p.ncl, 1);
-  p.max_rows = (long)U * (L == 1 ? B : (long)s.NC);
-  // (+ 16 at look_ahead 1: room that a since removed kernel cut into two cohorts per cluster.  Kept: every buffer behind
+  const long rows_per_utt = L == 1 ? (long)B : (long)s.NC;
+  // (+ 16 rows of slack at look_ahead 1: room that a since removed kernel cut into two cohorts.  Kept: every buffer behind
   // `rows` in the workspace arena would move, and placement alone has measured a 4 % mode switch -- DESIGN.md section 5)
-  p.rx_stride = (int)(((((long)U + p.nclq - 1) / p.nclq) * (L == 1 ? (long)B : (long)s.NC) + 15) / 16 * 16) + (L == 1 ? 16 : 0);
-  p.rows_cap = std::max(p.max_rows + 48L * s.G, (long)p.nclq * p.rx_stride);  // every group's last row tile may run past its rows
+  static_cast<ClusterGeometry&>(p) = cluster_geometry(n_cu, U, rows_per_utt, L == 1 ? 16 : 0, s.G);
+  p.max_rows = (long)U * rows_per_utt;
   p.hst = m.depth >= 2 && s.G == 1 &&
           ((m.Hp == 512 && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512)) ||
            (m.Hp == 256 && (m.Dp == 128 || m.Dp == 256)) || (m.Hp == 128 && (m.Dp == 128 || m.Dp == 256)));
@@ -785,13 +813,11 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
   const bool c4 = exact && m.Hp == 512 && m.Dp == 512 && B == 20 && Kmax == 11;
   // (a model of the cluster kernels' shapes -- hidden size 128 with a small observation dim also counts as "small" --
   // goes to them: k_decode_big<WIN>)
-  const bool cluster_shape = m.depth == 1 && cl_dims;
+  const bool cluster_shape = m.depth == 1 && (m.Hp == 128 || m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512);
 
   // the whole decode in one launch with register-resident weights (k_decode_resident and its relatives below); the
   // default wherever it applies.  (Its state is addressed through 2 GB buffer descriptors.)
-  const bool resident_ok = L == 1 && cluster_shape && s.G == 1 && select_fast_ok(B, Kmax, S) && !generic && p.ncl >= 1 &&
-                           ((double)U * S + 1) * m.Hp * 4.0 < 2.0e9 && (double)p.rows_cap * m.Hp * 4.0 < 2.0e9 &&
-                           (double)U * S * m.Dp * 4.0 < 2.0e9 && resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
+  const bool resident_ok = L == 1 && s.G == 1 && !generic && resident_fits(m, U, B, Kmax, S, p);
   const bool resident = resident_ok && !use_graph && allowed && !per_step;
   // SMALL models (small_model_ok: hidden size up to about 64, any rnn_depth -- the shapes of the reference's own tests):
   // the whole beam search of an utterance on ONE workgroup (k_decode_small); look_ahead >= 2 with a sub-step of the
@@ -867,7 +893,7 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
       p.lds = resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S);
       p.decode_kernel = UIS_DK_RESIDENT;
     }
-    p.lds = std::max<size_t>(p.lds, 96 * 1024);  // one workgroup per CU
+    p.lds = one_launch_lds(p.lds);
   } else if (win) {
     p.path = DecodePath::WINDOW;
     p.cls = exact && m.Hp == 512 && m.Dp == 256 && B == 50 && Kmax == 12 && L == 2 && s.NC == (int64_t)B * (Kmax + 1) &&
@@ -952,63 +978,71 @@ DecodeKernel find_kernel(const KernelEntry (&table)[N], int Hp, int Dp, int vari
   return nullptr;
 }
 
-// The instantiations of the cluster-wide one-launch kernels, family by family, keyed by (Hp, Dp, variant): variant =
-// the shape class (CLS_*), for k_decode_rs its kind (RS_*), for k_decode_deep look_ahead >= 2.
+// The instantiations of the cluster-wide one-launch kernels, family by family (persist: a UIS_FLAG_PERSISTENT session's
+// launch), keyed by (Hp, Dp, variant): variant = the shape class (CLS_*), for k_decode_rs its kind (RS_*), for
+// k_decode_deep look_ahead >= 2.
+namespace kernels {
+const KernelEntry big_ws[] = {
+    {512, 256, CLS_C1, &k_decode_big<512, 256, true, 10, 16>},
+    {512, 256, CLS_NONE, &k_decode_big<512, 256, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, true>},
+    {256, 256, CLS_NONE, &k_decode_big<256, 256, true>}, {256, 128, CLS_NONE, &k_decode_big<256, 128, true>},
+    {128, 256, CLS_NONE, &k_decode_big<128, 256, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, true>}};
+//                     HP   DP   NPOS UPW CB  CK  SPLIT2
+const KernelEntry rs[] = {
+    {512, 256, RS_BASE, &k_decode_rs<512, 256, 3, 1, 0, 0, false>}, {512, 128, RS_BASE, &k_decode_rs<512, 128, 3, 1, 0, 0, false>},
+    {256, 256, RS_BASE, &k_decode_rs<256, 256, 3, 1, 0, 0, false>}, {256, 128, RS_BASE, &k_decode_rs<256, 128, 3, 1, 0, 0, false>},
+    {128, 256, RS_BASE, &k_decode_rs<128, 256, 3, 1, 0, 0, false>}, {128, 128, RS_BASE, &k_decode_rs<128, 128, 3, 1, 0, 0, false>},
+    {512, 256, RS_C1, &k_decode_rs<512, 256, 3, 1, 10, 16, false>},
+    {512, 256, RS_UPW2, &k_decode_rs<512, 256, 3, 2, 0, 0, true>},
+    {512, 256, RS_WIDE, &k_decode_rs<512, 256, 4, 1, 0, 0, true>}, {512, 512, RS_WIDE, &k_decode_rs<512, 512, 4, 1, 0, 0, true>}};
+const KernelEntry resident[] = {
+    {512, 256, CLS_C1, &k_decode_resident<512, 256, false, 10, 16>}, {512, 512, CLS_C4, &k_decode_resident<512, 512, false, 20, 11>},
+    {512, 256, CLS_NONE, &k_decode_resident<512, 256>}, {512, 512, CLS_NONE, &k_decode_resident<512, 512>},
+    {512, 128, CLS_NONE, &k_decode_resident<512, 128>}, {256, 256, CLS_NONE, &k_decode_resident<256, 256>},
+    {256, 128, CLS_NONE, &k_decode_resident<256, 128>}, {256, 512, CLS_NONE, &k_decode_resident<256, 512>},
+    {128, 256, CLS_NONE, &k_decode_resident<128, 256>}, {128, 128, CLS_NONE, &k_decode_resident<128, 128>},
+    {128, 512, CLS_NONE, &k_decode_resident<128, 512>}};
+const KernelEntry big[] = {
+    {512, 256, CLS_NONE, &k_decode_big<512, 256>}, {512, 512, CLS_NONE, &k_decode_big<512, 512>},
+    {512, 128, CLS_NONE, &k_decode_big<512, 128>}, {256, 256, CLS_NONE, &k_decode_big<256, 256>},
+    {256, 128, CLS_NONE, &k_decode_big<256, 128>}, {256, 512, CLS_NONE, &k_decode_big<256, 512>},
+    {128, 256, CLS_NONE, &k_decode_big<128, 256>}, {128, 128, CLS_NONE, &k_decode_big<128, 128>},
+    {128, 512, CLS_NONE, &k_decode_big<128, 512>}};
+const KernelEntry window[] = {
+    {512, 256, CLS_C2, &k_decode_big<512, 256, false, 50, 12, true>},
+    {512, 256, CLS_NONE, &k_decode_big<512, 256, false, 0, 0, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, false, 0, 0, true>},
+    {512, 512, CLS_NONE, &k_decode_big<512, 512, false, 0, 0, true>}, {256, 256, CLS_NONE, &k_decode_big<256, 256, false, 0, 0, true>},
+    {256, 128, CLS_NONE, &k_decode_big<256, 128, false, 0, 0, true>}, {256, 512, CLS_NONE, &k_decode_big<256, 512, false, 0, 0, true>},
+    {128, 256, CLS_NONE, &k_decode_big<128, 256, false, 0, 0, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, false, 0, 0, true>},
+    {128, 512, CLS_NONE, &k_decode_big<128, 512, false, 0, 0, true>}};
+const KernelEntry deep[] = {
+    {512, 256, 0, &k_decode_deep<512, 256>}, {512, 128, 0, &k_decode_deep<512, 128>}, {512, 512, 0, &k_decode_deep<512, 512>},
+    {256, 256, 0, &k_decode_deep<256, 256>}, {256, 128, 0, &k_decode_deep<256, 128>}, {128, 128, 0, &k_decode_deep<128, 128>},
+    {128, 256, 0, &k_decode_deep<128, 256>},
+    {512, 256, 1, &k_decode_deep<512, 256, true>}, {256, 256, 1, &k_decode_deep<256, 256, true>},
+    {256, 128, 1, &k_decode_deep<256, 128, true>}, {128, 128, 1, &k_decode_deep<128, 128, true>}};
+const KernelEntry persist[] = {
+    {512, 256, CLS_NONE, &k_decode_resident<512, 256, true>}, {512, 512, CLS_NONE, &k_decode_resident<512, 512, true>},
+    {256, 256, CLS_NONE, &k_decode_resident<256, 256, true>}};
+}  // namespace kernels
+
 DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L) {
-  static const KernelEntry big_ws[] = {
-      {512, 256, CLS_C1, &k_decode_big<512, 256, true, 10, 16>},
-      {512, 256, CLS_NONE, &k_decode_big<512, 256, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, true>},
-      {256, 256, CLS_NONE, &k_decode_big<256, 256, true>}, {256, 128, CLS_NONE, &k_decode_big<256, 128, true>},
-      {128, 256, CLS_NONE, &k_decode_big<128, 256, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, true>}};
-  //                     HP   DP   NPOS UPW CB  CK  SPLIT2
-  static const KernelEntry rs[] = {
-      {512, 256, RS_BASE, &k_decode_rs<512, 256, 3, 1, 0, 0, false>}, {512, 128, RS_BASE, &k_decode_rs<512, 128, 3, 1, 0, 0, false>},
-      {256, 256, RS_BASE, &k_decode_rs<256, 256, 3, 1, 0, 0, false>}, {256, 128, RS_BASE, &k_decode_rs<256, 128, 3, 1, 0, 0, false>},
-      {128, 256, RS_BASE, &k_decode_rs<128, 256, 3, 1, 0, 0, false>}, {128, 128, RS_BASE, &k_decode_rs<128, 128, 3, 1, 0, 0, false>},
-      {512, 256, RS_C1, &k_decode_rs<512, 256, 3, 1, 10, 16, false>},
-      {512, 256, RS_UPW2, &k_decode_rs<512, 256, 3, 2, 0, 0, true>},
-      {512, 256, RS_WIDE, &k_decode_rs<512, 256, 4, 1, 0, 0, true>}, {512, 512, RS_WIDE, &k_decode_rs<512, 512, 4, 1, 0, 0, true>}};
-  static const KernelEntry resident[] = {
-      {512, 256, CLS_C1, &k_decode_resident<512, 256, false, 10, 16>}, {512, 512, CLS_C4, &k_decode_resident<512, 512, false, 20, 11>},
-      {512, 256, CLS_NONE, &k_decode_resident<512, 256>}, {512, 512, CLS_NONE, &k_decode_resident<512, 512>},
-      {512, 128, CLS_NONE, &k_decode_resident<512, 128>}, {256, 256, CLS_NONE, &k_decode_resident<256, 256>},
-      {256, 128, CLS_NONE, &k_decode_resident<256, 128>}, {256, 512, CLS_NONE, &k_decode_resident<256, 512>},
-      {128, 256, CLS_NONE, &k_decode_resident<128, 256>}, {128, 128, CLS_NONE, &k_decode_resident<128, 128>},
-      {128, 512, CLS_NONE, &k_decode_resident<128, 512>}};
-  static const KernelEntry big[] = {
-      {512, 256, CLS_NONE, &k_decode_big<512, 256>}, {512, 512, CLS_NONE, &k_decode_big<512, 512>},
-      {512, 128, CLS_NONE, &k_decode_big<512, 128>}, {256, 256, CLS_NONE, &k_decode_big<256, 256>},
-      {256, 128, CLS_NONE, &k_decode_big<256, 128>}, {256, 512, CLS_NONE, &k_decode_big<256, 512>},
-      {128, 256, CLS_NONE, &k_decode_big<128, 256>}, {128, 128, CLS_NONE, &k_decode_big<128, 128>},
-      {128, 512, CLS_NONE, &k_decode_big<128, 512>}};
-  static const KernelEntry window[] = {
-      {512, 256, CLS_C2, &k_decode_big<512, 256, false, 50, 12, true>},
-      {512, 256, CLS_NONE, &k_decode_big<512, 256, false, 0, 0, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, false, 0, 0, true>},
-      {512, 512, CLS_NONE, &k_decode_big<512, 512, false, 0, 0, true>}, {256, 256, CLS_NONE, &k_decode_big<256, 256, false, 0, 0, true>},
-      {256, 128, CLS_NONE, &k_decode_big<256, 128, false, 0, 0, true>}, {256, 512, CLS_NONE, &k_decode_big<256, 512, false, 0, 0, true>},
-      {128, 256, CLS_NONE, &k_decode_big<128, 256, false, 0, 0, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, false, 0, 0, true>},
-      {128, 512, CLS_NONE, &k_decode_big<128, 512, false, 0, 0, true>}};
-  static const KernelEntry deep[] = {
-      {512, 256, 0, &k_decode_deep<512, 256>}, {512, 128, 0, &k_decode_deep<512, 128>}, {512, 512, 0, &k_decode_deep<512, 512>},
-      {256, 256, 0, &k_decode_deep<256, 256>}, {256, 128, 0, &k_decode_deep<256, 128>}, {128, 128, 0, &k_decode_deep<128, 128>},
-      {128, 256, 0, &k_decode_deep<128, 256>},
-      {512, 256, 1, &k_decode_deep<512, 256, true>}, {256, 256, 1, &k_decode_deep<256, 256, true>},
-      {256, 128, 1, &k_decode_deep<256, 128, true>}, {128, 128, 1, &k_decode_deep<128, 128, true>}};
   switch (p.path) {
-    case DecodePath::BIG_WS: return find_kernel(big_ws, m.Hp, m.Dp, p.cls);
-    case DecodePath::RS: return find_kernel(rs, m.Hp, m.Dp, p.rs_kind);
-    case DecodePath::RESIDENT: return find_kernel(resident, m.Hp, m.Dp, p.cls);
-    case DecodePath::BIG: return find_kernel(big, m.Hp, m.Dp, p.cls);
-    case DecodePath::WINDOW: return find_kernel(window, m.Hp, m.Dp, p.cls);
-    case DecodePath::DEEP: return find_kernel(deep, m.Hp, m.Dp, L > 1 ? 1 : 0);
+    case DecodePath::BIG_WS: return find_kernel(kernels::big_ws, m.Hp, m.Dp, p.cls);
+    case DecodePath::RS: return find_kernel(kernels::rs, m.Hp, m.Dp, p.rs_kind);
+    case DecodePath::RESIDENT: return find_kernel(kernels::resident, m.Hp, m.Dp, p.cls);
+    case DecodePath::BIG: return find_kernel(kernels::big, m.Hp, m.Dp, p.cls);
+    case DecodePath::WINDOW: return find_kernel(kernels::window, m.Hp, m.Dp, p.cls);
+    case DecodePath::DEEP: return find_kernel(kernels::deep, m.Hp, m.Dp, L > 1 ? 1 : 0);
     default: return nullptr;
   }
 }
 
 // One launch of a cluster-wide decode kernel: a workgroup of 512 threads on every CU of the ncl clusters.
-int launch_cluster_kernel(Launcher& lch, DecodeKernel kern, int n_cu, int ncl, size_t lds, const DevModel& m, const DecodeState& st) {
+int launch_cluster_kernel(Launcher& lch, DecodeKernel kern, int n_cu, int ncl, size_t lds, const DevModel& m, const DecodeState& st,
+                          bool cooperative = true) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, m, st);
+  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, m, st, cooperative);
 }
 
 #if defined(UIS_SELECT_TIMING) || defined(UIS_RESIDENT_PROBE) || defined(UIS_RS_COUNT_PATHS) || defined(UIS_RESIDENT_TIMING)
@@ -1457,12 +1491,11 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
       else if (pipe && m.Dp == 256) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<2>, wgrid, dim3(256), 0, m, xin, gout, n, 0L, (const long*)nullptr);
       else if (pipe && m.Dp == 512) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<4>, wgrid, dim3(256), 0, m, xin, gout, n, 0L, (const long*)nullptr);
       else LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_wide, wgrid, dim3(256), 0, m, xin, gout, n);
-    } else
-      LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj, dense_grid(n, m.G / 16), dim3(256), 0, m, d_x + (size_t)f0 * m.Dp,
-             h->gi0.as<float>() + (size_t)f0 * m.G, n);
-    LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m,
-           d_x + (size_t)f0 * m.Dp, h->mse0.as<float>() + f0, n, 0L, (const long*)nullptr);
-    return UIS_OK;
+      LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, xin, h->mse0.as<float>() + f0, n,
+             0L, (const long*)nullptr);
+      return UIS_OK;
+    }
+    return plain_input_proj(lch, m, d_x + (size_t)f0 * m.Dp, h->gi0.as<float>() + (size_t)f0 * m.G, h->mse0.as<float>() + f0, n);
   };
   // From here on DMA from the caller's (or the pinned staging) memory may be in flight: whichever way
   // this function is left -- an error return inside the chunk loop included -- both streams are
@@ -2228,21 +2261,10 @@ int pm_launch(uis_handle* h) {
   HIPCHK(hipMemsetAsync(ss.d_go, 0, (size_t)UIS_PM_MAX_CLUSTERS * 128, h->stream));
   HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
   Launcher lch{h, h->stream, false};
-  const size_t shmem = std::max<size_t>(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S), 96 * 1024);
-  int rc = UIS_ERR_UNSUPPORTED;
   h->inlaunch_failed = false;
-#define UIS_PERSIST_CASE(HPV, DPV)                                                                                    \
-  if (m.Hp == HPV && m.Dp == DPV) {                                                                                  \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_resident<HPV, DPV, true>),                   \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                             \
-    rc = lch.run_cooperative(UIS_K_GRU, &k_decode_resident<HPV, DPV, true>, h->n_cu, dim3(32 * st.ncl), dim3(512), \
-                             shmem, m, st, true);                                                                    \
-  }
-  UIS_PERSIST_CASE(512, 256)
-  UIS_PERSIST_CASE(512, 512)
-  UIS_PERSIST_CASE(256, 256)
-#undef UIS_PERSIST_CASE
-  if (rc) return rc;
+  if (int rc = launch_cluster_kernel(lch, find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+                                     one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st))
+    return rc;
   ss.pm_running = true;
   ss.pm_launches += 1;
   return UIS_OK;
@@ -2333,14 +2355,9 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   st.max_rows = U * B;
   // a push advances the session with ONE launch of the resident decode kernel where that kernel
   // applies (same conditions as uis_decode); UIS_FLAG_STEPWISE keeps the four kernels per step
-  const int ncl = (h->n_cu >= 32 && h->n_cu % 32 == 0 && h->n_cu / 32 <= UIS_MAX_CLUSTERS) ? h->n_cu / 32 : 0;
-  const int nclq = std::max(ncl, 1);
-  const int rx_stride = (int)(((((long)U + nclq - 1) / nclq) * B + 15) / 16 * 16);
-  const long rows_cap = std::max((long)U * B + 48, (long)nclq * rx_stride);
-  ss.resident = m.depth == 1 && (m.Hp == 256 || m.Hp == 512) && (m.Dp == 128 || m.Dp == 256 || m.Dp == 512) &&
-                select_fast_ok(B, Kmax, S) && ncl >= 1 && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) &&
-                ((double)U * S + 1) * m.Hp * 4.0 < 2.0e9 && (double)rows_cap * m.Hp * 4.0 < 2.0e9 &&
-                (double)U * S * m.Dp * 4.0 < 2.0e9 && resident_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024;
+  const ClusterGeometry geo = cluster_geometry(h->n_cu, U, B, 0, 1);  // (one group, no row slack)
+  // (streams never ran the 128-wide kernel)
+  ss.resident = m.Hp != 128 && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) && resident_fits(m, U, B, Kmax, S, geo);
   if ((opts->flags & UIS_FLAG_RESIDENT) && !ss.resident)
     { ss = uis_handle::Stream{}; return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT: the one-launch decode does not apply to this session's shape"); }
   int rc = UIS_OK;
@@ -2366,18 +2383,18 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   SALLOC(st.beam_slot, 2 * (size_t)U * B * Kmax, false);
   SALLOC(st.beam_blk, 2 * (size_t)U * B * Kmax, false);
   SALLOC(st.bp, (size_t)U * max_frames * B, false);
-  SALLOC(st.rows, rows_cap, true);
+  SALLOC(st.rows, geo.rows_cap, true);
   SALLOC(st.nrows, 2, true);
-  SALLOC(st.gi_up, m.depth > 1 ? (size_t)rows_cap * m.G : (size_t)rows_cap * m.Hp, false);  // depth 1: the resident kernel's h' staging
-  SALLOC(st.a1, (size_t)rows_cap * m.Hp, true);
+  SALLOC(st.gi_up, m.depth > 1 ? (size_t)geo.rows_cap * m.G : (size_t)geo.rows_cap * m.Hp, false);  // depth 1: the resident kernel's h' staging
+  SALLOC(st.a1, (size_t)geo.rows_cap * m.Hp, true);
   SALLOC(st.counters, 96, true);
   ss.ctl_words = (size_t)32 + 3 * UIS_MAX_CLUSTERS * 32;
   SALLOC(ss.d_ctl, ss.ctl_words, true);
   st.cl_abort = ss.d_ctl + 16;
   if (ss.resident) {
-    st.ncl = ncl;
+    st.ncl = geo.ncl;
     st.cl_xcc = ss.d_ctl;
-    st.rx_stride = rx_stride;
+    st.rx_stride = geo.rx_stride;
     st.rx_nrows = reinterpret_cast<int32_t*>(ss.d_ctl) + 32;
     st.rx_bar = ss.d_ctl + 32 + UIS_MAX_CLUSTERS * 32;
     st.rx_flags = ss.d_ctl + 32 + 2 * UIS_MAX_CLUSTERS * 32;
@@ -2386,9 +2403,9 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   if (opts->flags & UIS_FLAG_PERSISTENT) {
     // the launch that stays: needs the one-launch shape with the beam in LDS (at most one utterance
     // per workgroup), unpadded frames, and a mailbox that holds every label of the session
-    const bool shape = (m.Hp == 512 && (m.Dp == 256 || m.Dp == 512)) || (m.Hp == 256 && m.Dp == 256);
+    const bool shape = find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE) != nullptr;
     const double label_bytes = (double)U * (double)max_frames * 4.0;
-    if (!(ss.resident && shape && U <= 32 * ncl && m.D == m.Dp && label_bytes <= 256e6)) {
+    if (!(ss.resident && shape && U <= 32 * geo.ncl && m.D == m.Dp && label_bytes <= 256e6)) {
       stream_free(h);
       return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_PERSISTENT needs the one-launch shape (rnn_depth 1, rnn_hidden_size 512 with "
                                        "observation_dim 256 / 512 or 256 with 256, unpadded), at most one utterance per compute "
@@ -2399,8 +2416,8 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
     // ends between pushes: a row that changed hands from one push to the next would leave a stale
     // dirty line in the previous owner's XCD-private L2, free to be written back over the new
     // owner's data at any time (seen as rare score differences before the ranges were fixed).
-    ss.pm_cluster_rows = std::min<int64_t>(round_up(((U + ncl - 1) / ncl) * 16, 32), (int64_t)UIS_RES_HEAD_TILES * 16 * 6);
-    ss.pm_cap_frames = ss.pm_cluster_rows * ncl;
+    ss.pm_cluster_rows = std::min<int64_t>(round_up(((U + geo.ncl - 1) / geo.ncl) * 16, 32), (int64_t)UIS_RES_HEAD_TILES * 16 * 6);
+    ss.pm_cap_frames = ss.pm_cluster_rows * geo.ncl;
     size_t o = (size_t)UIS_PM_CTL_WORDS * 4;
     auto take = [&](size_t bytes) { o = (o + 127) & ~(size_t)127; const size_t r = o; o += bytes; return r; };
     ss.pm_o_foff = take((size_t)U * 8);
@@ -2418,7 +2435,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
     ss.pm_block = static_cast<unsigned char*>(blk);
     ss.hdr_stride = (((size_t)U * 12) + 127) & ~(size_t)127;
     SALLOC(ss.d_go, (size_t)UIS_PM_MAX_CLUSTERS * 16, true);
-    SALLOC(ss.d_hdr, (size_t)ncl * ss.hdr_stride, true);
+    SALLOC(ss.d_hdr, (size_t)geo.ncl * ss.hdr_stride, true);
     SALLOC(ss.d_pm_args, 1, false);
     // everything a push through the mailbox touches, now: no allocation while the launch is resident
     if ((rc = ss.chunk_x.ensure((size_t)U * 16 + (size_t)ss.pm_cap_frames * m.Dp * 4)) ||
@@ -2581,11 +2598,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   // the chunk's gi0 / mse0: inside the one-launch kernel when the frames need no padding and the
   // chunk's rows fit the kernel's LDS list, else by the two once-per-chunk kernels
   const bool fused = !stepwise && m.D == m.Dp && F <= (int64_t)UIS_RES_HEAD_TILES * 16 * 6;
-  if (!fused) {
-    LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj, dense_grid(F, m.G / 16), dim3(256), 0, m, d_x, ss.chunk_gi0.as<float>(), (long)F);
-    LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((F + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, d_x,
-           ss.chunk_mse0.as<float>(), (long)F, 0L, (const long*)nullptr);
-  }
+  if (!fused && (rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
   HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
   st.push_F = fused ? (int)F : 0;
   bool ran_resident = false;
@@ -2593,7 +2606,6 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     // every step of this push in ONE launch (the kernel runs max over utterances of
     // avail - utt_step steps; utterances without new frames sit them out)
     HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
-    const size_t shmem = std::max<size_t>(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S), 96 * 1024);
     h->inlaunch_failed = false;
     // Every push is a COOPERATIVE launch: the kernel spins on in-launch barriers and needs all its
     // workgroups co-resident, which only that launch path checks against whatever else runs on the
@@ -2602,26 +2614,13 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     // callers that own the device, and used only after the session's first push went through the
     // cooperative path.
     static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
-#define UIS_RESIDENT_CASE(HPV, DPV)                                                                                   \
-  if (m.Hp == HPV && m.Dp == DPV) {                                                                                  \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decode_resident<HPV, DPV>),                         \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                             \
-    rc = lch.run_cooperative(UIS_K_GRU, &k_decode_resident<HPV, DPV>, h->n_cu, dim3(32 * st.ncl), dim3(512), shmem, \
-                             m, st, !(ss.coop_checked && plain_ok));                                                 \
-  }
-    UIS_RESIDENT_CASE(512, 256)
-    UIS_RESIDENT_CASE(512, 512)
-    UIS_RESIDENT_CASE(512, 128)
-    UIS_RESIDENT_CASE(256, 256)
-    UIS_RESIDENT_CASE(256, 128)
-    UIS_RESIDENT_CASE(256, 512)
-#undef UIS_RESIDENT_CASE
+    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+                               one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st,
+                               !(ss.coop_checked && plain_ok));
     if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
       h->resident_off = true; stepwise = true;
       if (fused) {  // ... and they need the chunk's gi0 / mse0
-        LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj, dense_grid(F, m.G / 16), dim3(256), 0, m, d_x, ss.chunk_gi0.as<float>(), (long)F);
-        LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((F + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, d_x,
-               ss.chunk_mse0.as<float>(), (long)F, 0L, (const long*)nullptr);
+        if ((rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
         st.push_F = 0;
       }
     } else if (rc) return rc;
