@@ -397,6 +397,60 @@ void uis_host_free(void* p);
 
 const char* uis_last_error(void);
 
+/*
+ * Training (reference: UISRNN.fit_concatenated's loop, uisrnn/uisrnn.py:254-296, and
+ * uisrnn/loss_func.py).  A trainer handle is separate from uis_handle: it owns the weights
+ * being trained, their gradients, the Adam state and the training sequences on one device.
+ * The host (uisrnn_amd/training.py) prepares the data and draws each iteration's batch.
+ *
+ * Flat parameter order (uis_train_get_params / uis_train_get_grads), float32, row-major:
+ *   for each layer l: gru_weight_ih[l] (3H, D|H), gru_weight_hh[l] (3H, H),
+ *                     gru_bias_ih[l] (3H), gru_bias_hh[l] (3H)
+ *   linear_mean1_weight (H, H), linear_mean1_bias (H),
+ *   linear_mean2_weight (D, H), linear_mean2_bias (D),
+ *   rnn_init_hidden (depth, H), sigma2 (D)
+ * i.e. CoreRNN.parameters() order, then rnn_init_hidden, then sigma2.
+ */
+typedef struct uis_train_opts {
+  double learning_rate;          /* Adam lr (beta 0.9 / 0.999, eps 1e-8, as torch.optim.Adam)   */
+  double regularization_weight;  /* loss3 = weight * sum of the Frobenius norms of CoreRNN's params */
+  double grad_max_norm;          /* clip_grad_norm_ over CoreRNN's params                         */
+  double sigma_alpha;            /* inverse-gamma prior of sigma2                                 */
+  double sigma_beta;
+  double dropout;                /* between GRU layers (depth >= 2); 0 = none                     */
+  uint64_t dropout_key;          /* key of the counter-based dropout stream                       */
+  int32_t estimate_sigma2;       /* 1: Adam also updates sigma2                                   */
+  int32_t reserved[3];
+} uis_train_opts;
+
+typedef struct uis_trainer uis_trainer;
+
+/* A trainer on HIP device `device`, starting from the weights in `desc` with a fresh Adam state.
+ * desc->transition_bias and crp_alpha are not used. */
+int32_t uis_train_create(const uis_model_desc* desc, const uis_train_opts* opts, int32_t device,
+                         uis_trainer** out);
+
+/* Upload the training sub-sequences once.  pool: host, float32, [seq_offsets[n_seqs], D];
+ * sub-sequence s owns rows seq_offsets[s] .. seq_offsets[s+1] (at least one row each). */
+int32_t uis_train_set_data(uis_trainer* th, const float* pool, const int64_t* seq_offsets,
+                           int32_t n_seqs);
+
+/* One iteration on the batch of sub-sequences batch_idx[0 .. batch_size): their row counts must
+ * be non-increasing.  The padded input is gathered on the device (row 0 zeros, then the rows).
+ * out_losses (host, may be NULL): loss, loss1, loss2, loss3 -- with it the call waits for the
+ * device; without it the iteration is only queued. */
+int32_t uis_train_step(uis_trainer* th, const int32_t* batch_idx, int32_t batch_size,
+                       float* out_losses);
+
+/* Number of floats of the flat parameter vector (layout above). */
+int32_t uis_train_param_count(uis_trainer* th, int64_t* count_out);
+
+/* Current weights / the gradients of the last iteration (after clipping), flat layout above. */
+int32_t uis_train_get_params(uis_trainer* th, float* params_out, int64_t count);
+int32_t uis_train_get_grads(uis_trainer* th, float* grads_out, int64_t count);
+
+void uis_train_destroy(uis_trainer* th);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,21 @@ class DecodeOpts(ctypes.Structure):
   ]
 
 
+class TrainOpts(ctypes.Structure):
+  """struct uis_train_opts (include/uisrnn_hip.h)."""
+  _fields_ = [
+      ('learning_rate', ctypes.c_double),
+      ('regularization_weight', ctypes.c_double),
+      ('grad_max_norm', ctypes.c_double),
+      ('sigma_alpha', ctypes.c_double),
+      ('sigma_beta', ctypes.c_double),
+      ('dropout', ctypes.c_double),
+      ('dropout_key', ctypes.c_uint64),
+      ('estimate_sigma2', ctypes.c_int32),
+      ('reserved', ctypes.c_int32 * 3),
+  ]
+
+
 class Stats(ctypes.Structure):
   """struct uis_stats (include/uisrnn_hip.h)."""
   _fields_ = [
@@ -326,6 +341,21 @@ def load_library(path=None):
   lib.uis_host_free.argtypes = [ctypes.c_void_p]
   lib.uis_last_error.restype = ctypes.c_char_p
   lib.uis_last_error.argtypes = []
+  lib.uis_train_create.restype = i32
+  lib.uis_train_create.argtypes = [
+      ctypes.POINTER(ModelDesc), ctypes.POINTER(TrainOpts), i32, ctypes.POINTER(ctypes.c_void_p)]
+  lib.uis_train_set_data.restype = i32
+  lib.uis_train_set_data.argtypes = [ctypes.c_void_p, _fp, i64p, i32]
+  lib.uis_train_step.restype = i32
+  lib.uis_train_step.argtypes = [ctypes.c_void_p, i32p, i32, _fp]
+  lib.uis_train_param_count.restype = i32
+  lib.uis_train_param_count.argtypes = [ctypes.c_void_p, i64p]
+  lib.uis_train_get_params.restype = i32
+  lib.uis_train_get_params.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int64]
+  lib.uis_train_get_grads.restype = i32
+  lib.uis_train_get_grads.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int64]
+  lib.uis_train_destroy.restype = None
+  lib.uis_train_destroy.argtypes = [ctypes.c_void_p]
   _lib = lib
   return lib
 
@@ -336,7 +366,9 @@ EXPORTED_SYMBOLS = (
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
     'uis_stream_labels', 'uis_stream_end', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
-    'uis_eval_last_decode', 'uis_host_alloc', 'uis_host_free', 'uis_last_error')
+    'uis_eval_last_decode', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
+    'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
 
 def last_error(lib):
@@ -664,3 +696,138 @@ class Decoder:
         ctypes.byref(stats))
     rc = self._check(rc, 'uis_decode_device')
     return {'stats': stats.as_dict(), 'status': rc}
+
+
+def flatten_params(params):
+  """The trainer's flat parameter vector (include/uisrnn_hip.h) from a parameter dict."""
+  parts = []
+  for l in range(int(params['rnn_depth'])):
+    for key in ('gru_weight_ih', 'gru_weight_hh', 'gru_bias_ih', 'gru_bias_hh'):
+      parts.append(_f32(params[key][l]).ravel())
+  for key in ('linear_mean1_weight', 'linear_mean1_bias', 'linear_mean2_weight',
+              'linear_mean2_bias', 'rnn_init_hidden', 'sigma2'):
+    parts.append(_f32(params[key]).ravel())
+  return np.concatenate(parts)
+
+
+def unflatten_params(flat, like):
+  """A parameter dict shaped like `like` (uisrnn_amd.weights) holding the values of `flat`."""
+  out = dict(like)
+  pos = 0
+
+  def take(shape):
+    nonlocal pos
+    n = int(np.prod(shape))
+    a = np.array(flat[pos:pos + n], dtype=np.float32).reshape(shape)
+    pos += n
+    return a
+
+  for key in ('gru_weight_ih', 'gru_weight_hh', 'gru_bias_ih', 'gru_bias_hh'):
+    out[key] = list(like[key])
+  for l in range(int(like['rnn_depth'])):
+    for key in ('gru_weight_ih', 'gru_weight_hh', 'gru_bias_ih', 'gru_bias_hh'):
+      out[key][l] = take(np.shape(like[key][l]))
+  for key in ('linear_mean1_weight', 'linear_mean1_bias', 'linear_mean2_weight',
+              'linear_mean2_bias', 'rnn_init_hidden', 'sigma2'):
+    out[key] = take(np.shape(like[key]))
+  assert pos == len(flat), (pos, len(flat))
+  return out
+
+
+class Trainer:
+  """Owns one uis_trainer: the weights being trained, their Adam state and the training data."""
+
+  def __init__(self, params, device=0, learning_rate=1e-3, regularization_weight=1e-5,
+               grad_max_norm=5.0, sigma_alpha=1.0, sigma_beta=1.0, estimate_sigma2=True,
+               dropout=0.0, dropout_key=0):
+    self._lib = load_library()
+    self._handle = None
+    self.params_like = params
+    self.observation_dim = int(params['observation_dim'])
+    p = dict(params)
+    if p.get('transition_bias') is None:
+      p['transition_bias'] = 0.0   # not used by the trainer
+    desc, keep = make_desc(p)
+    opts = TrainOpts()
+    opts.learning_rate = float(learning_rate)
+    opts.regularization_weight = float(regularization_weight)
+    opts.grad_max_norm = float(grad_max_norm)
+    opts.sigma_alpha = float(sigma_alpha)
+    opts.sigma_beta = float(sigma_beta)
+    opts.dropout = float(dropout)
+    opts.dropout_key = int(dropout_key) & 0xffffffffffffffff
+    opts.estimate_sigma2 = 1 if estimate_sigma2 else 0
+    handle = ctypes.c_void_p()
+    rc = self._lib.uis_train_create(ctypes.byref(desc), ctypes.byref(opts), int(device),
+                                    ctypes.byref(handle))
+    del keep
+    if rc != UIS_OK:
+      raise HipLibraryError('uis_train_create failed ({}): {}'.format(rc, last_error(self._lib)))
+    self._handle = handle
+    count = ctypes.c_int64()
+    self._check(self._lib.uis_train_param_count(self._handle, ctypes.byref(count)),
+                'uis_train_param_count')
+    self.n_params = count.value
+    self._lengths = None
+
+  def _check(self, rc, what):
+    if rc == UIS_OK:
+      return
+    msg = last_error(self._lib)
+    if rc == UIS_ERR_DIM_MISMATCH:
+      raise ValueError(msg)
+    err = HipLibraryError('{} failed ({}): {}'.format(what, rc, msg))
+    err.status = rc
+    raise err
+
+  def close(self):
+    if getattr(self, '_handle', None):
+      self._lib.uis_train_destroy(self._handle)
+      self._handle = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # pylint: disable=broad-except
+      pass
+
+  def set_data(self, sub_sequences):
+    """Upload the training sub-sequences (a list of [rows, D] arrays) once."""
+    rows = [len(s) for s in sub_sequences]
+    offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(rows)
+    pool = _f32(np.concatenate([np.asarray(s).reshape(-1, self.observation_dim)
+                                for s in sub_sequences], axis=0))
+    self._check(self._lib.uis_train_set_data(
+        self._handle, _ptr(pool), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+        len(rows)), 'uis_train_set_data')
+    self._lengths = np.asarray(rows)
+
+  def step(self, batch_idx, want_losses=True):
+    """One iteration on the sub-sequences batch_idx (longest first): (loss, loss1, loss2, loss3)."""
+    idx = np.ascontiguousarray(batch_idx, dtype=np.int32)
+    out = np.zeros(4, dtype=np.float32)
+    self._check(self._lib.uis_train_step(
+        self._handle, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
+        _ptr(out) if want_losses else None), 'uis_train_step')
+    return tuple(float(v) for v in out) if want_losses else None
+
+  def flat_params(self):
+    out = np.empty(self.n_params, dtype=np.float32)
+    self._check(self._lib.uis_train_get_params(self._handle, _ptr(out), self.n_params),
+                'uis_train_get_params')
+    return out
+
+  def flat_grads(self):
+    out = np.empty(self.n_params, dtype=np.float32)
+    self._check(self._lib.uis_train_get_grads(self._handle, _ptr(out), self.n_params),
+                'uis_train_get_grads')
+    return out
+
+  def params(self):
+    """The current weights as a parameter dict (the rest of the dict as given at creation)."""
+    return unflatten_params(self.flat_params(), self.params_like)
+
+  def grads(self):
+    """The last iteration's gradients (after clipping), shaped like the parameters."""
+    return unflatten_params(self.flat_grads(), self.params_like)

@@ -12,7 +12,8 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-SOURCES = [os.path.join(_HERE, 'csrc', 'uis_decoder.hip')]
+SOURCES = [os.path.join(_HERE, 'csrc', 'uis_decoder.hip'),
+           os.path.join(_HERE, 'csrc', 'uis_train.hip')]
 DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_kernels.hip'),
     os.path.join(_HERE, 'csrc', 'uis_kernels.h'),

@@ -1846,6 +1846,10 @@ UIS_EXPORT int32_t uis_device_count(void) {
 
 UIS_EXPORT const char* uis_last_error(void) { return g_err.c_str(); }
 
+// For the other translation units of the library (uis_train.hip): their failures land in the
+// same thread-local message uis_last_error() returns.
+int uis_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+
 static void stream_free_on_destroy(uis_handle* h) {
   for (void* p : h->stream_state.allocs) (void)hipFree(p);
   h->stream_state.allocs.clear();

@@ -7,8 +7,9 @@ libuisrnn_hip.so on the MI355X through uisrnn_amd._capi.  There is no CPU
 implementation behind this class: without the HIP library and a gfx950 device
 ``predict`` raises.
 
-Training (``fit``) is outside the scope of this package: train with the
-reference and ``load()`` its checkpoint here.
+``fit`` / ``fit_concatenated`` raise NotImplementedError; ``train`` /
+``train_concatenated`` (uisrnn_amd/training.py, libuisrnn_hip.so's uis_train_*)
+train on the MI355X with the reference's fit semantics.
 """
 
 import threading
@@ -16,6 +17,7 @@ import threading
 import numpy as np
 
 from uisrnn_amd import _capi
+from uisrnn_amd import training
 from uisrnn_amd import weights
 
 _DEFAULT_MAX_CLUSTERS = 16
@@ -91,6 +93,8 @@ class UISRNN:
     self.estimate_transition_bias = args.transition_bias is None
     self.device_index = int(getattr(args, 'device_index', 0))
     self.verbosity = getattr(args, 'verbosity', 3)
+    self.rnn_dropout = float(getattr(args, 'rnn_dropout', 0.0) or 0.0)
+    self.last_train_losses = None  # extension: one {loss, loss1, loss2, loss3} per iteration of train()
     self._decoder = None
     self._extra_decoders = {}
     self.last_stats = None
@@ -164,6 +168,56 @@ class UISRNN:
         'train with google/uis-rnn and load() the checkpoint.')
 
   fit_concatenated = fit
+
+  def _log(self, level, msg):
+    if self.verbosity >= level:
+      print(msg)
+
+  def train_concatenated(self, train_sequence, train_cluster_id, args):
+    """The reference's fit_concatenated (uisrnn/uisrnn.py:172-313), trained on the GPU.
+
+    Same arguments, checks and exceptions.  Draws np.random exactly as the reference does
+    (permutations, then one mini-batch per iteration); dropout between GRU layers uses the
+    trainer's own random stream (uisrnn_amd/training.py).  On return self.params holds the
+    trained weights and last_train_losses one record per iteration.
+    """
+    params, records = training.train_concatenated(
+        self, train_sequence, train_cluster_id, args, self._log)
+    params['transition_bias'] = self.params['transition_bias']
+    params['transition_bias_denominator'] = self.params.get('transition_bias_denominator', 0.0)
+    params['crp_alpha'] = self.params['crp_alpha']
+    self.params = params
+    self._invalidate()
+    self.last_train_losses = records
+
+  def train(self, train_sequences, train_cluster_ids, args):
+    """The reference's fit (uisrnn/uisrnn.py:315-386), trained on the GPU.
+
+    train_sequences is a list of [length, D] float arrays with a list of label sequences, or one
+    concatenated array with its labels.  Estimates (or updates) transition_bias when the model
+    was built with transition_bias None, then concatenates, shuffles and trains.
+    """
+    if isinstance(train_sequences, np.ndarray):
+      if self.estimate_transition_bias:
+        self._log(2, 'Warning: transition_bias cannot be correctly estimated from a '
+                     'concatenated sequence; train_sequences will be treated as a '
+                     'single sequence. This can lead to inaccurate estimation of '
+                     'transition_bias. Please, consider estimating transition_bias '
+                     'before concatenating the sequences and passing it as argument.')
+      train_sequences = [train_sequences]
+      train_cluster_ids = [train_cluster_ids]
+    elif not isinstance(train_sequences, list):
+      raise TypeError('train_sequences must be a list or numpy.ndarray')
+    if self.estimate_transition_bias:
+      bias, denominator = training.estimate_transition_bias(train_cluster_ids)
+      bias, denominator = training.merge_transition_bias(
+          self.params['transition_bias'], self.transition_bias_denominator, bias, denominator)
+      self.params['transition_bias'] = bias
+      self.params['transition_bias_denominator'] = denominator
+      self._invalidate()
+    sequence, labels = training.concatenate_training_data(
+        train_sequences, train_cluster_ids, args.enforce_cluster_id_uniqueness, True)
+    self.train_concatenated(sequence, labels, args)
 
   def _get_decoder(self, device=None):
     if self.params['transition_bias'] is None:
