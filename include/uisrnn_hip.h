@@ -388,6 +388,27 @@ int32_t uis_eval_accuracy_device(uis_handle* h, const int32_t* d_labels_a, const
 int32_t uis_eval_last_decode(uis_handle* h, const int32_t* truth, int32_t n_utt, int64_t* matched_out);
 
 /*
+ * The model's negative log-likelihood of a GIVEN labeling: the neg_likelihood the beam search
+ * minimises (uisrnn/uisrnn.py:388-453) along the fixed trace labels[offsets[u] .. offsets[u+1]) of
+ * every utterance, from an empty BeamState, test_iteration 1.  For labels that a decode with
+ * test_iteration 1 returns (any beam_size / look_ahead), scores_out[u] equals that decode's score
+ * bit for bit: both follow include/uis_numerics.h, the total is ((0 + loss_0) + loss_1) + ... in
+ * float32, frame order.
+ *   frames, offsets : host, packed as for uis_decode (float32, already cast)
+ *   labels  : host, int32 [offsets[n_utt]], in first-appearance form (each label at most one more
+ *             than the largest before it in its utterance).  A larger one makes that utterance +inf
+ *             from that frame on (the reference's invalid trace, uisrnn.py:406-408); a negative one
+ *             is UIS_ERR_INVALID_ARG
+ *   scores_out       : host float32 [n_utt] or NULL; an empty utterance scores 0
+ *   frame_losses_out : host float32 [offsets[n_utt]] or NULL -- each frame's step loss
+ * Refused while a streaming session is open.  Leaves the last decode's results alone
+ * (uis_last_decode_info / _shape, uis_eval_last_decode, uis_debug_scores).  UIS_ERR_OOM: score
+ * the list in parts.
+ */
+int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                         const int32_t* labels, float* scores_out, float* frame_losses_out);
+
+/*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the
  * H2D copy of the frame stream is asynchronous and overlaps the input projection of the chunks
  * already on the device.  Pageable memory works too (staged by the runtime).

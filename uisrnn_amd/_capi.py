@@ -330,6 +330,8 @@ def load_library(path=None):
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
   lib.uis_eval_accuracy_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64p, i32, i64p]
+  lib.uis_score_labels.restype = i32
+  lib.uis_score_labels.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, _fp, _fp]
   lib.uis_eval_last_decode.restype = i32
   lib.uis_eval_last_decode.argtypes = [ctypes.c_void_p, i32p, i32, i64p]
   lib.uis_host_alloc.restype = i32
@@ -363,7 +365,7 @@ EXPORTED_SYMBOLS = (
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
     'uis_stream_labels', 'uis_stream_end', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
-    'uis_eval_last_decode', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
@@ -513,6 +515,36 @@ class Decoder:
     if want_beam_scores:
       out['beam_scores'] = beam_scores
     return out
+
+  def score_labels(self, frames, offsets, labels, want_frame_losses=False):
+    """The model's NLL of given labelings (uis_score_labels).
+
+    Args:
+      frames: float32 [sum N, D]; offsets: int64 [U + 1], packed as for decode().
+      labels: int [sum N] in first-appearance form per utterance.
+    Returns:
+      float32 scores [U], and with want_frame_losses also the float32 per-frame losses [sum N].
+    """
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    n_utt = offsets.shape[0] - 1
+    total = int(offsets[-1])
+    if frames.ndim != 2 or frames.shape[0] != total:
+      raise ValueError('frames must be [offsets[-1], D]')
+    if total and frames.shape[1] != self.observation_dim:
+      raise ValueError('frames do not match observation_dim')
+    if labels.shape != (total,):
+      raise ValueError('labels must be [offsets[-1]]')
+    scores = np.empty(n_utt, dtype=np.float32)
+    losses = np.empty(total, dtype=np.float32) if want_frame_losses else None
+    rc = self._lib.uis_score_labels(
+        self._handle, frames.ctypes.data_as(_fp),
+        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
+        labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scores.ctypes.data_as(_fp),
+        losses.ctypes.data_as(_fp) if want_frame_losses else None)
+    self._check(rc, 'uis_score_labels')
+    return (scores, losses) if want_frame_losses else scores
 
   def last_overflow(self, n_utt=None):
     """Per-utterance flags of the last decode: bit 0 = a survivor hit the cluster cap, bit 1 = an

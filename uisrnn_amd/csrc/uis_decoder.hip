@@ -213,6 +213,7 @@ struct uis_handle {
   int last_U = 0, last_B = 0;
   std::vector<int64_t> io_offsets;  // offsets of the last uis_decode (its labels are still in io_labels)
   DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
+  DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
 };
@@ -1858,7 +1859,9 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
                     &h->counters, &h->beam_scores_out, &h->io_frames, &h->io_labels, &h->io_scores, &h->mse_tab, &h->dbg_scores, &h->utt_nrows, &h->hst, &h->resume, &h->split_tab, &h->scatter_tab, &h->stage,
                     &h->lv_n, &h->lv_K, &h->lv_last, &h->lv_sum, &h->lv_score, &h->lv_origin, &h->lv_path, &h->lv_slot,
                     &h->lv_blk, &h->scratch, &h->bp16, &h->bp_base, &h->cluster_ctl, &h->arena,
-                    &h->ev_a, &h->ev_b, &h->ev_off, &h->ev_out};
+                    &h->ev_a, &h->ev_b, &h->ev_off, &h->ev_out, &h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0,
+                    &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean, &h->sc_gi_up, &h->sc_rows, &h->sc_chains,
+                    &h->sc_utt, &h->sc_out};
   for (DevBuf* b : bufs) b->release();
   for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
@@ -2788,3 +2791,6 @@ UIS_EXPORT int32_t uis_host_alloc(size_t bytes, void** out) {
 UIS_EXPORT void uis_host_free(void* p) {
   if (p) (void)hipHostFree(p);
 }
+
+// ------------------------------------------------------------------ scoring a given labeling
+#include "uis_score.hip"

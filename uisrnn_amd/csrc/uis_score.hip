@@ -1,0 +1,435 @@
+// uis_score.hip -- uis_score_labels: the model's negative log-likelihood of a GIVEN labeling.
+//
+// The neg_likelihood the beam search minimises (uisrnn/uisrnn.py:388-453, _update_beam_state) applied
+// along a fixed trace c_0 .. c_{N-1} from an empty BeamState, test_iteration 1.  Once the labels are
+// known each cluster's GRU chain is independent of the others, so the work is split as
+//   schedule (host)  the chains (utterance, cluster), each frame's position in its chain, the float64
+//                    prior of every frame (the decode's expressions and logblk / logden tables), the
+//                    chains ordered longest first: the chains active at position p are a prefix
+//   frame stream     k_pad_frames, k_dense_input_proj[_wide] (gi0), k_mse0 -- the decode's own kernels
+//   recurrence       a launch per (position, layer): W_hh h + b_hh and the GRU unit for every chain
+//                    still running (k_score_gru), layers >= 1 with their input-side gates first
+//                    (k_score_upper_in); split-K MFMA tiles, the canonical order of uis_numerics.h
+//   heads            linear_mean1 + relu, linear_mean2 over all rows at once (k_score_head, full-K tiles)
+//   losses           the running mean per chain (k_score_mean_scan), the weighted MSE against it and
+//                    the step loss per frame (k_score_loss), the float32 sum per utterance in frame
+//                    order (k_score_sum)
+// A frame-row r is one (chain, position) pair; rows are position-major: row(p, i) = fbase[p] + i for the
+// i-th longest chain.  The GRU of a chain's last row is not run (its state is never read).
+//
+// #included by uis_decoder.hip after the handle, Launcher and the decode kernels.
+
+namespace {
+
+// One launch of the recurrence: position p, layer `layer`.
+struct ScoreStep {
+  int n;                     // chains active at this position (a prefix of the longest-first order)
+  int layer;
+  long row0;                 // row(p, 0)
+  long prev0;                // row(p - 1, 0), or -1 at p = 0 (the state before a cluster's first frame is h1)
+  long Fv;                   // frame-rows: the stride of one layer in `hid`
+  const int32_t* row_frame;  // [Fv] frame of each row in the packed stream
+  const float* gi0;          // [F][G]
+  float* gi_up;              // [n][G] input-side gates of `layer` >= 1
+  float* hid;                // [depth][Fv][Hp]
+};
+
+__device__ __forceinline__ float* score_hid(const DevModel& m, const ScoreStep& a, int layer, long row) {
+  return a.hid + ((size_t)layer * a.Fv + row) * m.Hp;
+}
+
+// gi_up[i] = b_ih + W_ih h'_{layer-1}(row(p, i))   (one 16 x 16 tile per workgroup, split-K)
+__global__ __launch_bounds__(512) void k_score_upper_in(DevModel m, ScoreStep a) {
+  __shared__ __attribute__((aligned(16))) float spart[UIS_KSPLIT * 256];
+  const int nrt = (a.n + 15) >> 4, nft = m.G / 16;
+  int rt, ft;
+  dense_block_map(blockIdx.x, nrt, nft, rt, ft);
+  if (rt >= nrt || ft >= nft) return;
+  const int t = threadIdx.x;
+  int i = rt * 16 + (t & 15);
+  if (i >= a.n) i = a.n - 1;  // (rows past the count stream the last row; not stored)
+  const float* in[1] = {score_hid(m, a, a.layer - 1, a.row0 + i)};
+  splitk_tile<1, 1, 1>(m.wih[a.layer], 0, ft, m.Hp / 16, in, m.bih[a.layer] + ft * 16, 0, spart);
+  if (t >= 256) return;
+  const int er = rt * 16 + (t >> 4);
+  if (er >= a.n) return;
+  a.gi_up[(size_t)er * m.G + ft * 16 + (t & 15)] = splitk_combine<1, 1>(spart, 0, 0, t);
+}
+
+// h'(row(p, i)) = GRU(gi, b_hh + W_hh h(row(p - 1, i)), h(row(p - 1, i)))   (as k_dense_gru<1>)
+__global__ __launch_bounds__(512) void k_score_gru(DevModel m, ScoreStep a) {
+  __shared__ __attribute__((aligned(16))) float spart[UIS_KSPLIT * 3 * 256];
+  const int nrt = (a.n + 15) >> 4, nft = m.Hp / 16;
+  int rt, ft;
+  dense_block_map(blockIdx.x, nrt, nft, rt, ft);
+  if (rt >= nrt || ft >= nft) return;
+  const int t = threadIdx.x;
+  // epilogue operands of thread t < 256 (row t >> 4, unit t & 15), fetched ahead of the chains
+  const int er = rt * 16 + ((t & 255) >> 4), j = ft * 16 + (t & 15);
+  const bool ework = t < 256 && er < a.n;
+  float gir = 0.0f, giz = 0.0f, gin = 0.0f, hprev = 0.0f;
+  if (ework) {
+    const float* gi = a.layer == 0 ? a.gi0 + (size_t)a.row_frame[a.row0 + er] * m.G : a.gi_up + (size_t)er * m.G;
+    const float* hs = a.prev0 >= 0 ? score_hid(m, a, a.layer, a.prev0 + er) : m.h1 + (size_t)a.layer * m.Hp;
+    gir = gi[j]; giz = gi[m.Hp + j]; gin = gi[2 * m.Hp + j]; hprev = hs[j];
+  }
+  int i = rt * 16 + (t & 15);
+  if (i >= a.n) i = a.n - 1;
+  const float* hsrc[1] = {a.prev0 >= 0 ? score_hid(m, a, a.layer, a.prev0 + i) : m.h1 + (size_t)a.layer * m.Hp};
+  splitk_tile<3, 1, 1>(m.whh[a.layer], nft, ft, m.Hp / 16, hsrc, m.bhh[a.layer] + ft * 16, m.Hp, spart);
+  if (!ework) return;
+  const float ghr = splitk_combine<1, 3>(spart, 0, 0, t);
+  const float ghz = splitk_combine<1, 3>(spart, 0, 1, t);
+  const float ghn = splitk_combine<1, 3>(spart, 0, 2, t);
+  const float out = j < m.H_units ? uis_gru_unit(gir, giz, gin, ghr, ghz, ghn, hprev) : 0.0f;
+  score_hid(m, a, a.layer, a.row0 + er)[j] = out;
+}
+
+// out[row] = head(b + W in[row]) for `nrows` rows: a wave owns 2 row tiles x 4 feature tiles and walks
+// the full K (segments combined left to right: the canonical order; k_dense_input_proj_wide's schedule).
+// HEAD 1: relu (linear_mean1, `v > 0 ? v : 0` as the decode), HEAD 2: features past D are 0 (linear_mean2).
+template <int HEAD>
+__global__ __launch_bounds__(256) void k_score_head(DevModel m, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                    int ntiles, int nKb, const float* __restrict__ in,
+                                                    float* __restrict__ out, long nrows) {
+  constexpr int NA = 4, NB = 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4;
+  const int tile0 = (blockIdx.y * 4 + wave) * NA;
+  if (tile0 >= ntiles) return;
+  const long r0 = (long)blockIdx.x * (16 * NB);
+  if (r0 >= nrows) return;
+  const int in_stride = nKb * 16, out_stride = ntiles * 16;
+  long rows[NB];
+  bool valid[NB];
+  const f32x4* bp[NB];
+  const f32x4* wp[NA];
+  int tiles[NA];
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+    rows[r] = r0 + 16 * r + (lane & 15);
+    valid[r] = rows[r] < nrows;
+    if (!valid[r]) rows[r] = nrows - 1;
+    bp[r] = reinterpret_cast<const f32x4*>(in + (size_t)rows[r] * in_stride) + q;
+  }
+#pragma unroll
+  for (int g = 0; g < NA; ++g) {
+    tiles[g] = tile0 + g < ntiles ? tile0 + g : ntiles - 1;
+    wp[g] = reinterpret_cast<const f32x4*>(Wt) + ((size_t)tiles[g] * nKb) * 64 + lane;
+  }
+  const int per = uis_kseg_blocks(nKb);
+  f32x4 total[NB][NA];
+#pragma unroll 1
+  for (int sgm = 0; sgm < UIS_KSPLIT; ++sgm) {
+    const int kb0 = sgm * per;
+    const int kb1 = kb0 + per < nKb ? kb0 + per : nKb;
+    f32x4 acc[NB][NA];
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+#pragma unroll
+      for (int g = 0; g < NA; ++g)
+        acc[r][g] = sgm == 0 ? *reinterpret_cast<const f32x4*>(bias + tiles[g] * 16 + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    if (kb0 < kb1) chain_blocks<NA, NB>(wp, bp, kb0, kb1, acc);
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+#pragma unroll
+      for (int g = 0; g < NA; ++g) {
+        if (sgm == 0) total[r][g] = acc[r][g];
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) total[r][g][e] = total[r][g][e] + acc[r][g][e];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < NB; ++r) {
+#pragma unroll
+    for (int g = 0; g < NA; ++g) {
+      if (!valid[r] || tile0 + g >= ntiles) continue;
+      const int f = (tile0 + g) * 16 + q * 4;
+      f32x4 v = total[r][g];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (HEAD == 1) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
+        else if (f + e >= m.D) v[e] = 0.0f;
+      }
+      *reinterpret_cast<f32x4*>(out + (size_t)rows[r] * out_stride + f) = v;
+    }
+  }
+}
+
+// The running cluster mean along each chain, in place: row(p, i) holds linear_mean2's output m_{p+1} on entry
+// and M_{p+1} on exit, M_1 = m_1, M_q = uis_mean_update(M_{q-1}, m_q, q - 1)  (uisrnn.py:425-429).
+// One thread per (chain, feature); 8 rows fetched ahead of their updates.
+__global__ __launch_bounds__(256) void k_score_mean_scan(DevModel m, const int32_t* __restrict__ len,
+                                                         const int64_t* __restrict__ fbase, float* mean) {
+  const int i = blockIdx.y;
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= m.Dp) return;
+  const int nrow = len[i] - 1;  // rows whose mean a later frame reads
+  constexpr int AHEAD = 8;
+  float M = 0.0f;
+  for (int p0 = 0; p0 < nrow; p0 += AHEAD) {
+    float v[AHEAD];
+    size_t at[AHEAD];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) {
+      const int p = p0 + k < nrow ? p0 + k : nrow - 1;
+      at[k] = (size_t)(fbase[p] + i) * m.Dp + d;
+      v[k] = mean[at[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) {
+      const int p = p0 + k;
+      if (p >= nrow) break;
+      M = p == 0 ? v[k] : uis_mean_update(M, v[k], p);
+      mean[at[k]] = M;
+    }
+  }
+}
+
+// loss[frame] = uis_step_loss(mse, prior[frame]) for every row: mse = mse0[frame] at a chain's first frame,
+// else the weighted MSE against the chain's mean after the previous row (one wave per row).
+__global__ __launch_bounds__(256) void k_score_loss(DevModel m, long Fv, const int32_t* __restrict__ row_frame,
+                                                    const int32_t* __restrict__ row_prev, const float* __restrict__ x,
+                                                    const float* __restrict__ mse0, const float* __restrict__ mean,
+                                                    const double* __restrict__ prior, float* __restrict__ loss) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= Fv) return;
+  const long frame = row_frame[r];
+  const int prev = row_prev[r];
+  float mse;
+  if (prev < 0) mse = mse0[frame];
+  else mse = wave_weighted_mse(mean + (size_t)prev * m.Dp, x + (size_t)frame * m.Dp, m.wgt, m.Dp, m.D, lane);
+  if (lane == 0) loss[frame] = uis_step_loss(mse, prior[frame]);
+}
+
+// scores[u] = ((0 + loss_0) + loss_1) + ... over the utterance's scored frames, in frame order; +inf when a
+// label was past the allowed range (nvalid[u] < its frames: the reference's invalid trace).  One wave each.
+__global__ __launch_bounds__(64) void k_score_sum(const int64_t* __restrict__ off, const int32_t* __restrict__ nvalid,
+                                                  const float* __restrict__ loss, float* __restrict__ scores) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const long f0 = off[u], n = off[u + 1] - f0, nv = nvalid[u];
+  float s = 0.0f;
+  for (long b = 0; b < nv; b += 64) {
+    const float v = b + lane < nv ? loss[f0 + b + lane] : 0.0f;
+    const int cnt = nv - b < 64 ? (int)(nv - b) : 64;
+    for (int k = 0; k < cnt; ++k) s = s + __shfl(v, k, 64);
+  }
+  if (nv < n) s = INFINITY;
+  if (lane == 0) scores[u] = s;
+}
+
+static bool score_timing_env() {  // UIS_SCORE_TIMING=1: one line per call on stderr (schedule / device / total ms)
+  static const bool v = getenv("UIS_SCORE_TIMING") != nullptr && atoi(getenv("UIS_SCORE_TIMING")) != 0;
+  return v;
+}
+
+// The schedule of one call: integer work on the labels and the float64 priors.
+struct ScoreSchedule {
+  std::vector<int32_t> nvalid;     // [U] frames before the first label past the allowed range
+  std::vector<double> prior;       // [F]
+  std::vector<int32_t> len;        // [chains] longest first
+  std::vector<int64_t> fbase;      // [P] row(p, 0)
+  std::vector<int32_t> nfr;        // [P] chains with more than p frames
+  std::vector<int32_t> row_frame;  // [Fv]
+  std::vector<int32_t> row_prev;   // [Fv] row(p - 1, i), -1 at p = 0
+  int64_t Fv = 0;
+};
+
+void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int U, const int32_t* labels, ScoreSchedule& s) {
+  const int64_t F = offsets[U];
+  int64_t maxN = 0;
+  for (int u = 0; u < U; ++u) maxN = std::max<int64_t>(maxN, offsets[u + 1] - offsets[u]);
+  // the decode's tables (uis_decoder.hip, decode_once)
+  std::vector<double> logblk(maxN + 2), logden(maxN + 2);
+  for (int64_t n = 0; n < maxN + 2; ++n) {
+    logblk[n] = n > 0 ? std::log((double)n) : 0.0;
+    logden[n] = std::log((double)n + alpha);
+  }
+  s.nvalid.assign(U, 0);
+  s.prior.assign(F, 0.0);
+  std::vector<int32_t> chain_base(U + 1, 0), chain_len, blk;
+  std::vector<int32_t> frame_chain(F, -1), frame_pos(F, 0);
+  for (int u = 0; u < U; ++u) {
+    int K = 0, last = -1;
+    int64_t sum = 0;
+    blk.clear();
+    int64_t t = offsets[u];
+    for (; t < offsets[u + 1]; ++t) {
+      const int c = labels[t];
+      if (c > K) break;  // invalid trace (uisrnn.py:406-408): +inf from here on
+      double prior;
+      if (c == last) prior = m.lp_stay;
+      else if (c < K) prior = (m.lp_sw + logblk[blk[c]]) - logden[sum];
+      else prior = m.lp_new - logden[sum];
+      s.prior[t] = prior;
+      if (c == K) { blk.push_back(1); ++sum; ++K; chain_len.push_back(0); }
+      else if (c != last) { ++blk[c]; ++sum; }
+      const int ch = chain_base[u] + c;
+      frame_chain[t] = ch;
+      frame_pos[t] = chain_len[ch]++;
+      last = c;
+    }
+    s.nvalid[u] = (int32_t)(t - offsets[u]);
+    chain_base[u + 1] = chain_base[u] + K;
+  }
+  const int nch = chain_base[U];
+  // longest first (counting sort, stable: ties keep (utterance, cluster) order)
+  int P = 0;
+  for (int c = 0; c < nch; ++c) P = std::max(P, chain_len[c]);
+  std::vector<int32_t> cnt(P + 2, 0), rank(nch);
+  for (int c = 0; c < nch; ++c) ++cnt[P - chain_len[c]];
+  for (int k = 1; k <= P + 1; ++k) cnt[k] += cnt[k - 1];
+  for (int c = nch - 1; c >= 0; --c) rank[c] = --cnt[P - chain_len[c]];
+  s.len.assign(nch, 0);
+  for (int c = 0; c < nch; ++c) s.len[rank[c]] = chain_len[c];
+  s.nfr.assign(P, 0);
+  s.fbase.assign(P, 0);
+  for (int i = 0; i < nch; ++i) ++s.nfr[s.len[i] - 1];  // (chains of exactly len[i] frames ...)
+  for (int p = P - 2; p >= 0; --p) s.nfr[p] += s.nfr[p + 1];  // ... summed from the top: chains longer than p
+  int64_t acc = 0;
+  for (int p = 0; p < P; ++p) { s.fbase[p] = acc; acc += s.nfr[p]; }
+  s.Fv = acc;
+  s.row_frame.assign(acc, 0);
+  s.row_prev.assign(acc, -1);
+  for (int64_t t = 0; t < F; ++t) {
+    if (frame_chain[t] < 0) continue;
+    const int i = rank[frame_chain[t]], p = frame_pos[t];
+    const int64_t r = s.fbase[p] + i;
+    s.row_frame[r] = (int32_t)t;
+    s.row_prev[r] = p > 0 ? (int32_t)(s.fbase[p - 1] + i) : -1;
+  }
+}
+
+int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_t U, const int32_t* labels, float* scores_out,
+              float* frame_losses_out) {
+  const DevModel& m = h->m;
+  const int64_t F = offsets[U];
+  const auto t_begin = std::chrono::steady_clock::now();
+  ScoreSchedule s;
+  score_schedule(m, h->alpha, offsets, U, labels, s);
+  const auto t_sched = std::chrono::steady_clock::now();
+  const int64_t Fv = s.Fv;
+  const int P = (int)s.fbase.size(), nch = (int)s.len.size();
+  int maxn = P > 1 ? s.nfr[1] : 0;
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+  auto need = [](int64_t n, size_t each) { return (size_t)std::max<int64_t>(n, 1) * each; };
+  if ((rc = h->sc_x.ensure(need(F, (size_t)m.D * 4))) || (rc = h->sc_gi0.ensure(need(F, (size_t)m.G * 4))) ||
+      (rc = h->sc_mse0.ensure(need(F, 4))) || (rc = h->sc_loss.ensure(need(F, 4))) ||
+      (rc = h->sc_prior.ensure(need(F, 8))) || (rc = h->sc_hid.ensure(need(Fv, (size_t)m.depth * m.Hp * 4))) ||
+      (rc = h->sc_a1.ensure(need(Fv, (size_t)m.Hp * 4))) || (rc = h->sc_mean.ensure(need(Fv, (size_t)m.Dp * 4))) ||
+      (rc = h->sc_gi_up.ensure(need(m.depth > 1 ? maxn : 0, (size_t)m.G * 4))) ||
+      (rc = h->sc_rows.ensure(need(Fv, 8))) || (rc = h->sc_chains.ensure(need(P, 8) + need(nch, 4))) ||
+      (rc = h->sc_utt.ensure(need(U + 1, 8) + need(U, 4))) || (rc = h->sc_out.ensure(need(U, 4))))
+    return rc;
+  if (m.D != m.Dp && (rc = h->sc_xpad.ensure(need(F, (size_t)m.Dp * 4)))) return rc;
+  hipStream_t st = h->stream;
+  int32_t* d_row_frame = h->sc_rows.as<int32_t>();
+  int32_t* d_row_prev = d_row_frame + std::max<int64_t>(Fv, 1);
+  int64_t* d_fbase = h->sc_chains.as<int64_t>();
+  int32_t* d_len = reinterpret_cast<int32_t*>(d_fbase + std::max(P, 1));
+  int64_t* d_off = h->sc_utt.as<int64_t>();
+  int32_t* d_nvalid = reinterpret_cast<int32_t*>(d_off + U + 1);
+  // the tables and the frames travel; everything below runs in order on the handle's stream
+  if (F > 0) {
+    HIPCHK(hipMemcpyAsync(h->sc_x.p, frames, (size_t)F * m.D * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->sc_prior.p, s.prior.data(), (size_t)F * 8, hipMemcpyHostToDevice, st));
+  }
+  if (Fv > 0) {
+    HIPCHK(hipMemcpyAsync(d_row_frame, s.row_frame.data(), (size_t)Fv * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_row_prev, s.row_prev.data(), (size_t)Fv * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_len, s.len.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_fbase, s.fbase.data(), (size_t)P * 8, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_nvalid, s.nvalid.data(), (size_t)U * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(h->ev_begin, st));
+  Launcher lch{h, st, false};
+  const float* d_x = h->sc_x.as<float>();
+  float* gi0 = h->sc_gi0.as<float>();
+  float* mse0 = h->sc_mse0.as<float>();
+  float* loss = h->sc_loss.as<float>();
+  if (F > 0) {
+    // the frame stream: the decode's kernels, unchanged
+    if (m.D != m.Dp) {
+      const long total = (long)F * m.Dp;
+      hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_x, h->sc_xpad.as<float>(),
+                         (long)F, m.D, m.Dp);
+      HIPCHK(hipGetLastError());
+      d_x = h->sc_xpad.as<float>();
+    }
+    if (F >= UIS_PROJ_WIDE_ROWS) {
+      LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_wide, dim3((unsigned)((F + 31) / 32), (unsigned)((m.G / 16 + 15) / 16)), dim3(256), 0,
+             m, d_x, gi0, (long)F);
+      LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((F + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, d_x, mse0, (long)F, 0L,
+             (const long*)nullptr);
+    } else if ((rc = plain_input_proj(lch, m, d_x, gi0, mse0, (long)F))) {
+      return rc;
+    }
+    // frames past an invalid label keep +inf
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(loss), 0x7f800000, (size_t)F, st));
+  }
+  if (Fv > 0) {
+    ScoreStep a{};
+    a.Fv = Fv; a.row_frame = d_row_frame; a.gi0 = gi0; a.gi_up = h->sc_gi_up.as<float>(); a.hid = h->sc_hid.as<float>();
+    // the recurrence: position p's GRU rows are the chains with a frame at p + 1
+    for (int p = 0; p + 1 < P; ++p) {
+      a.n = s.nfr[p + 1];
+      a.row0 = s.fbase[p];
+      a.prev0 = p > 0 ? s.fbase[p - 1] : -1;
+      const int nrt = (a.n + 15) / 16;
+      for (int l = 0; l < m.depth; ++l) {
+        a.layer = l;
+        if (l > 0) LAUNCH(UIS_K_UPPER_IN, k_score_upper_in, dim3((unsigned)dense_grid_blocks(nrt, m.G / 16)), dim3(512), 0, m, a);
+        LAUNCH(UIS_K_GRU, k_score_gru, dim3((unsigned)dense_grid_blocks(nrt, m.Hp / 16)), dim3(512), 0, m, a);
+      }
+    }
+    // the heads of every row at once (a chain's last row included: its mean is computed and never read)
+    const float* htop = a.hid + (size_t)(m.depth - 1) * Fv * m.Hp;
+    float* a1 = h->sc_a1.as<float>();
+    float* mean = h->sc_mean.as<float>();
+    LAUNCH(UIS_K_HEAD1, k_score_head<1>, dim3((unsigned)((Fv + 31) / 32), (unsigned)((m.Hp / 16 + 15) / 16)), dim3(256), 0, m,
+           m.w1, m.b1, m.Hp / 16, m.Hp / 16, htop, a1, (long)Fv);
+    LAUNCH(UIS_K_HEAD2, k_score_head<2>, dim3((unsigned)((Fv + 31) / 32), (unsigned)((m.Dp / 16 + 15) / 16)), dim3(256), 0, m,
+           m.w2, m.b2, m.Dp / 16, m.Hp / 16, a1, mean, (long)Fv);
+    if (P > 1) LAUNCH(UIS_K_HEAD2, k_score_mean_scan, dim3((unsigned)((m.Dp + 255) / 256), (unsigned)nch), dim3(256), 0, m, d_len, d_fbase, mean);
+    LAUNCH(UIS_K_SELECT, k_score_loss, dim3((unsigned)((Fv + 3) / 4)), dim3(256), 0, m, (long)Fv, d_row_frame, d_row_prev, d_x, mse0,
+           mean, h->sc_prior.as<double>(), loss);
+  }
+  LAUNCH(UIS_K_SELECT, k_score_sum, dim3((unsigned)U), dim3(64), 0, d_off, d_nvalid, loss, h->sc_out.as<float>());
+  HIPCHK(hipEventRecord(h->ev_end, st));
+  if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, h->sc_out.p, (size_t)U * 4, hipMemcpyDeviceToHost, st));
+  if (frame_losses_out && F > 0) HIPCHK(hipMemcpyAsync(frame_losses_out, loss, (size_t)F * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (score_timing_env()) {
+    float dev_ms = 0.0f;
+    (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
+    const auto t_end = std::chrono::steady_clock::now();
+    fprintf(stderr, "uis_score_labels: frames %lld chains %d longest %d schedule_ms %.3f device_ms %.3f total_ms %.3f\n",
+            (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
+            std::chrono::duration<double, std::milli>(t_end - t_begin).count());
+  }
+  return UIS_OK;
+}
+
+}  // namespace
+
+UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                                    const int32_t* labels, float* scores_out, float* frame_losses_out) {
+  if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
+  if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
+  if (n_utt == 0) return UIS_OK;
+  if (offsets[0] != 0) return fail(UIS_ERR_INVALID_ARG, "offsets[0] must be 0");
+  for (int u = 0; u < n_utt; ++u)
+    if (offsets[u + 1] < offsets[u]) return fail(UIS_ERR_INVALID_ARG, "offsets must be non-decreasing");
+  const int64_t F = offsets[n_utt];
+  if (F > 0 && (!frames || !labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels is null");
+  if (F > 0x7fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "more than 2^31 - 1 frames in one call");
+  for (int64_t t = 0; t < F; ++t)
+    if (labels[t] < 0) return fail(UIS_ERR_INVALID_ARG, "label " + std::to_string(labels[t]) + " at frame " + std::to_string(t) + " is negative");
+  return score_run(h, frames, offsets, n_utt, labels, scores_out, frame_losses_out);
+}

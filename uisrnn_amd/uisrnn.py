@@ -489,6 +489,72 @@ class UISRNN:
       return self._decode_batch(test_sequences, args)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
+  def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
+    """The model's negative log-likelihood of given labelings (extension).
+
+    The neg_likelihood predict's beam search minimises (uisrnn.py:388-453), applied along the
+    given trace from an empty beam state, test_iteration 1: for labels that predict returns with
+    test_iteration 1, the score of that decode, bit for bit.  Ids may be of any hashable kind;
+    they are renamed by order of first appearance, so the result does not depend on the names.
+
+    Args:
+      test_sequences: a [N, D] float array or a list of them (as predict).
+      test_cluster_ids: N ids for an array, or a list of such sequences for a list.
+      per_frame: also return each frame's float32 loss (their float32 running sum is the score).
+    Returns:
+      a float (array) or a list of floats (list); with per_frame, a pair (scores, losses) where
+      losses is a float32 array per sequence.
+    """
+    single = isinstance(test_sequences, np.ndarray)
+    if single:
+      seqs, ids = [test_sequences], [test_cluster_ids]
+    elif isinstance(test_sequences, list):
+      seqs = test_sequences
+      if not isinstance(test_cluster_ids, (list, tuple)) or len(test_cluster_ids) != len(seqs):
+        raise ValueError('test_cluster_ids must be a list with one id sequence per test sequence.')
+      ids = list(test_cluster_ids)
+    else:
+      raise TypeError('test_sequences should be either a list or numpy array.')
+    for seq in seqs:
+      self._check_sequence(seq)
+    labels = []
+    for seq, seq_ids in zip(seqs, ids):
+      seq_ids = list(np.asarray(seq_ids).tolist()) if isinstance(seq_ids, np.ndarray) else list(seq_ids)
+      if len(seq_ids) != seq.shape[0]:
+        raise ValueError('test_cluster_ids has {} ids for a sequence of {} frames.'.format(
+            len(seq_ids), seq.shape[0]))
+      names = {}
+      labels.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
+    decoder = self._get_decoder()
+    lens = [s.shape[0] for s in seqs]
+    out_scores, out_losses = [None] * len(seqs), [None] * len(seqs)
+
+    def run(members):
+      sub_off = np.zeros(len(members) + 1, dtype=np.int64)
+      sub_off[1:] = np.cumsum([lens[u] for u in members])
+      frames = np.empty((int(sub_off[-1]), self.observation_dim), dtype=np.float32)
+      for u, start in zip(members, sub_off[:-1]):
+        frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
+      sub_labels = (np.concatenate([labels[u] for u in members]) if members else
+                    np.zeros(0, dtype=np.int32))
+      try:
+        scores, losses = decoder.score_labels(frames, sub_off, sub_labels, want_frame_losses=True)
+      except _capi.HipLibraryError as err:
+        if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
+          run(members[0::2])  # (as _decode_batch: alternating members, each half may halve again)
+          run(members[1::2])
+          return
+        raise
+      for k, u in enumerate(members):
+        out_scores[u] = float(scores[k])
+        out_losses[u] = losses[sub_off[k]:sub_off[k + 1]].copy()
+
+    if seqs:
+      run(list(range(len(seqs))))
+    if single:
+      return (out_scores[0], out_losses[0]) if per_frame else out_scores[0]
+    return (out_scores, out_losses) if per_frame else out_scores
+
 
 class OnlineSession:
   """Online (streaming) diarization of a fixed set of utterances.
