@@ -148,6 +148,7 @@ class Stats(ctypes.Structure):
         'n_overflow': self.n_overflow,
         'n_streams': self.n_streams,
         'decode_kernel': decode_kernel_name(self.decode_kernel),
+        'decode_kernel_code': int(self.decode_kernel),   # the raw word: bits 16..23 = k_decode_rs's kind (1 generic, 2 the fixed-shape class)
     }
 
 

@@ -194,6 +194,7 @@ struct uis_handle {
   DevBuf gi_up, a1, counters, beam_scores_out, io_frames, io_labels, io_scores, mse_tab, dbg_scores, utt_nrows, hst;
   size_t dbg_floats = 0;  // what the last decode left in dbg_scores (UIS_FLAG_DEBUG_SCORES)
   DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
+  DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   // uis_decode_f64: the caller's float64 utterances (set for the duration of that call) and the
   // pinned float32 staging buffer they are cast into, chunk by chunk, ahead of each H2D copy
@@ -334,8 +335,9 @@ struct Launcher {
   // `cooperative` = false: a plain launch of the same grid after the occupancy check (same
   // residency, 15-19 us less host time per launch: MI355X_MICROARCH.md "coop-launch"); used by the
   // streaming pushes after the session's first push went through the cooperative path.
-  int run_cooperative(int cls, void (*kernel)(DevModel, DecodeState), int n_cu, dim3 grid, dim3 block, size_t shmem,
-                      DevModel m, DecodeState st, bool cooperative = true) {
+  template <typename... KArgs>
+  int run_cooperative(int cls, void (*kernel)(KArgs...), int n_cu, dim3 grid, dim3 block, size_t shmem, bool cooperative,
+                      KArgs... args) {
     int per_cu = 0;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), (int)block.x, shmem));
     if ((long)per_cu * n_cu < (long)grid.x) {
@@ -349,12 +351,12 @@ struct Launcher {
       if (rc) return rc;
       HIPCHK(hipEventRecord(a, stream));
     }
-    void* argv[2] = {&m, &st};
+    void* argv[] = {static_cast<void*>(&args)...};
     hipError_t e;
     if (cooperative) {
       e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, (unsigned)shmem, stream);
     } else {
-      hipLaunchKernelGGL(kernel, grid, block, shmem, stream, m, st);
+      hipLaunchKernelGGL(kernel, grid, block, shmem, stream, args...);
       e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -695,6 +697,7 @@ struct DecodeKnobs {
   double max_state_bytes = 200e9, split_min_bytes = 0.0;
   bool split_min_set = false, split_frames_set = false, no_split = false, no_arena = false, no_ctl_tune = false;
   bool ctl_offset_set = false, agent_flags = false;
+  bool no_rs = false;  // (not from the environment: decode_once sets it when k_decode_rs's workspace stretch would pass 4 GB)
   std::vector<long> split_frames;
   size_t arena_shift = 0, ctl_offset = 0;
 };
@@ -843,10 +846,16 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
   if (resident) {
     const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0;
     const int per_xcd = (U + p.ncl - 1) / p.ncl;
-    const bool frames32 = s.F < 0x7fffffffLL;  // (k_decode_rs keeps frame numbers in 32 bits)
+    // (k_decode_rs keeps frame numbers in 32 bits and reads the frame stream through 4 GB descriptors with 32-bit byte
+    // offsets: a row of gi0 is 3 Hp floats, a row of x Dp)
+    const bool frames32 = s.F < 0x7fffffffLL && (double)s.F * std::max(3 * m.Hp, m.Dp) * 4.0 < 4.0e9;
+    // (... and everything else its step loop addresses through ONE descriptor over the workspace from pool_mean to mse_tab
+    // -- RsArgs, uis_kernels.h.  decode_once sums that stretch from the workspace list itself and plans again with
+    // k.no_rs set should it ever pass 4 GB: the next kernel then decodes, as for any other term below)
+    const bool rs_block = !k.no_rs;
     // the REPLICATED select (k_decode_rs, uis_select_rs.hip): every workgroup of an XCD decides all of the cluster's
     // utterances, one wave each; the default where it applies (UIS_FLAG_OWNER_SELECT keeps k_decode_resident)
-    if (!owner && m.Dp <= 256 && rs_select_ok(B, Kmax, S, (long)s.maxT) && frames32 && per_xcd <= UIS_RS_UTT &&
+    if (!owner && m.Dp <= 256 && rs_select_ok(B, Kmax, S, (long)s.maxT) && frames32 && rs_block && per_xcd <= UIS_RS_UTT &&
         resident_rs_lds_bytes(m.Hp, m.Dp, B, Kmax, S) <= 160 * 1024)
       p.rs_kind = c1 ? RS_C1 : RS_BASE;
     // more utterances than workgroups: k_decode_big, whose dense stages give a wave a whole row tile (+6 % at 288
@@ -955,11 +964,13 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
 }
 
 typedef void (*DecodeKernel)(DevModel, DecodeState);
-struct KernelEntry { int Hp, Dp, variant; DecodeKernel fn; };
+typedef void (*RsKernel)(RsArgs);  // k_decode_rs takes its own compact argument block (uis_kernels.h)
+template <typename Fn> struct KernelEntryOf { int Hp, Dp, variant; Fn fn; };
+typedef KernelEntryOf<DecodeKernel> KernelEntry;
 
-template <size_t N>
-DecodeKernel find_kernel(const KernelEntry (&table)[N], int Hp, int Dp, int variant) {
-  for (const KernelEntry& e : table)
+template <typename Fn, size_t N>
+Fn find_kernel(const KernelEntryOf<Fn> (&table)[N], int Hp, int Dp, int variant) {
+  for (const KernelEntryOf<Fn>& e : table)
     if (e.Hp == Hp && e.Dp == Dp && e.variant == variant) return e.fn;
   return nullptr;
 }
@@ -973,7 +984,7 @@ const KernelEntry big_ws[] = {
     {512, 256, CLS_NONE, &k_decode_big<512, 256, true>}, {512, 128, CLS_NONE, &k_decode_big<512, 128, true>},
     {256, 256, CLS_NONE, &k_decode_big<256, 256, true>}, {256, 128, CLS_NONE, &k_decode_big<256, 128, true>},
     {128, 256, CLS_NONE, &k_decode_big<128, 256, true>}, {128, 128, CLS_NONE, &k_decode_big<128, 128, true>}};
-const KernelEntry rs[] = {
+const KernelEntryOf<RsKernel> rs[] = {
     {512, 256, RS_BASE, &k_decode_rs<512, 256>}, {512, 128, RS_BASE, &k_decode_rs<512, 128>},
     {256, 256, RS_BASE, &k_decode_rs<256, 256>}, {256, 128, RS_BASE, &k_decode_rs<256, 128>},
     {128, 256, RS_BASE, &k_decode_rs<128, 256>}, {128, 128, RS_BASE, &k_decode_rs<128, 128>},
@@ -1012,7 +1023,6 @@ const KernelEntry persist[] = {
 DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L) {
   switch (p.path) {
     case DecodePath::BIG_WS: return find_kernel(kernels::big_ws, m.Hp, m.Dp, p.cls);
-    case DecodePath::RS: return find_kernel(kernels::rs, m.Hp, m.Dp, p.rs_kind);
     case DecodePath::RESIDENT: return find_kernel(kernels::resident, m.Hp, m.Dp, p.cls);
     case DecodePath::BIG: return find_kernel(kernels::big, m.Hp, m.Dp, p.cls);
     case DecodePath::WINDOW: return find_kernel(kernels::window, m.Hp, m.Dp, p.cls);
@@ -1025,7 +1035,54 @@ DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L) {
 int launch_cluster_kernel(Launcher& lch, DecodeKernel kern, int n_cu, int ncl, size_t lds, const DevModel& m, const DecodeState& st,
                           bool cooperative = true) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, m, st, cooperative);
+  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, cooperative, m, st);
+}
+
+// k_decode_rs's argument block from the decode's model and state.  Everything its step loop addresses in the workspace
+// -- the pools, the row tiles, the MSE tables, the control words, what it leaves for k_backtrace -- is named by a 32-bit
+// offset from pool_mean, the first of them in the arena (plan_decode keeps that stretch below 4 GB; checked again here).
+int rs_make_args(const DevModel& m, const DecodeState& st, size_t bp_bytes, RsArgs* out) {
+  RsArgs a{};
+  a.U = st.U; a.B = st.B; a.Kmax = st.Kmax; a.S = st.S; a.D = m.D; a.H_units = m.H_units; a.tau = st.tau;
+  a.ncl = st.ncl; a.rx_stride = st.rx_stride; a.step0 = st.step0; a.step1 = st.step1; a.flags = st.flags;
+  a.lp_stay = m.lp_stay; a.lp_sw = m.lp_sw; a.lp_new = m.lp_new;
+  a.whh = m.whh[0]; a.w1 = m.w1; a.w2 = m.w2; a.bhh = m.bhh[0]; a.b1 = m.b1; a.b2 = m.b2; a.wgt = m.wgt;
+  a.off = st.off; a.resume = st.resume;
+  a.logblk = st.logblk; a.logden = st.logden;
+  a.x = st.x; a.gi0 = st.gi0; a.mse0 = st.mse0;
+  a.overflow = st.overflow; a.dbg_scores = st.dbg_scores; a.counters = st.counters;
+  a.blk = reinterpret_cast<unsigned char*>(st.pool_mean);
+  bool ok = true;
+  auto at = [&](const void* p, size_t bytes) -> uint32_t {
+    const unsigned char* q = static_cast<const unsigned char*>(p);
+    if (q < a.blk || (size_t)(q - a.blk) + bytes >= ((size_t)1 << 32)) { ok = false; return 0u; }
+    return (uint32_t)(q - a.blk);
+  };
+  const size_t rows = (size_t)st.ncl * st.rx_stride, US = (size_t)st.U * st.S;
+  a.o_mean = at(st.pool_mean, US * m.Dp * 4);
+  a.o_hid = at(st.pool_hid, (US + 1) * m.Hp * 4);
+  a.o_h1 = a.o_hid + (uint32_t)(US * m.Hp * 4);
+  a.o_hst = at(st.gi_up, rows * m.Hp * 4);
+  a.o_a1 = at(st.a1, rows * m.Hp * 4);
+  a.o_tab = at(st.mse_tab, 2 * US * 4);
+  a.o_part = at(st.mse_part, rows * rs_part_stride(m.Dp) * 4);
+  a.o_ctl = at(st.cl_xcc, 0);
+  a.o_flag_word = (uint32_t)(st.rx_flags - st.cl_xcc);
+  ok = ok && st.cl_abort == st.cl_xcc + 16 && st.rx_flags > st.cl_xcc;
+  (void)at(st.rx_flags, (size_t)st.ncl * 128);
+  a.o_beam_n = at(st.beam_n, (size_t)2 * st.U * 4);
+  a.o_beam_score = at(st.beam_score, (size_t)2 * st.U * st.B * 4);
+  a.o_bp = at(st.bp, bp_bytes);
+  if (!ok) return fail(UIS_ERR_HIP, "k_decode_rs: its workspace is not one stretch below 4 GB");
+  *out = a;
+  return UIS_OK;
+}
+
+int launch_rs_kernel(Launcher& lch, RsKernel kern, int n_cu, int ncl, size_t lds, const DevModel& m, const DecodeState& st, size_t bp_bytes) {
+  RsArgs a;
+  if (int rc = rs_make_args(m, st, bp_bytes, &a)) return rc;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return lch.run_cooperative(UIS_K_GRU, kern, n_cu, dim3(32 * ncl), dim3(512), lds, true, a);
 }
 
 #if defined(UIS_SELECT_TIMING) || defined(UIS_RESIDENT_PROBE) || defined(UIS_RS_COUNT_PATHS) || defined(UIS_RESIDENT_TIMING)
@@ -1247,7 +1304,11 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // ---- the plan: which kernels decode this list
   const DecodeShape shape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, h_frames != nullptr,
                           wnd, (size_t)lds.total, wsl.total};
-  const DecodePlan plan = plan_decode(m, shape, opts->flags, knobs, h->n_cu, h->resident_off);
+  bool no_rs = false;
+replan:  // (taken once at most, from below the workspace list: k_decode_rs's stretch of it must stay below 4 GB)
+  DecodeKnobs plan_knobs = knobs;
+  plan_knobs.no_rs = no_rs;
+  const DecodePlan plan = plan_decode(m, shape, opts->flags, plan_knobs, h->n_cu, h->resident_off);
   if ((opts->flags & UIS_FLAG_RESIDENT) && !plan.one_launch())
     return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT needs (look_ahead 1:) one stream, beam_size * (max_clusters + 1) <= 256, no "
                                      "per-step path flag and either a small model (rnn_hidden_size up to about 64, any rnn_depth) "
@@ -1340,6 +1401,18 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     ENSURE(bp_base, (size_t)(U + 1) * 8);
   }
 #undef ENSURE
+  // k_decode_rs names everything from pool_mean to the end of mse_tab by 32-bit offsets from pool_mean (RsArgs): that
+  // stretch of THIS list must stay below 4 GB -- it does unless the back-pointers of a very long list push it there,
+  // and then the planner's next kernel decodes
+  size_t rs_first = 0, rs_last = 0, rs_stretch = 0;
+  if (rs) {
+    for (size_t i = 0; i < want.size(); ++i) {
+      if (want[i].first == &h->pool_mean) rs_first = i;
+      if (want[i].first == &h->mse_tab) rs_last = i;
+    }
+    for (size_t i = rs_first; i <= rs_last; ++i) rs_stretch += (want[i].second + 4095) & ~(size_t)4095;
+    if (rs_stretch >= ((size_t)1 << 32)) { no_rs = true; goto replan; }
+  }
   {
     size_t total = 0;
     for (auto& w : want) total += (w.second + 4095) & ~(size_t)4095;
@@ -1357,8 +1430,21 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
         o += (w.second + 4095) & ~(size_t)4095;
       }
     } else {
-      for (auto& w : want)
-        if ((rc = w.first->ensure(w.second))) return rc;
+      // (no arena: an allocation per buffer -- but k_decode_rs's stretch stays ONE, laid out as the arena would)
+      if (rs && (rc = h->rs_block.ensure(rs_stretch))) return rc;
+      size_t o = 0;
+      for (size_t i = 0; i < want.size(); ++i) {
+        auto& w = want[i];
+        if (rs && i >= rs_first && i <= rs_last) {
+          if (w.first->p && !w.first->borrowed) (void)hipFree(w.first->p);
+          w.first->p = static_cast<char*>(h->rs_block.p) + o;
+          w.first->cap = w.second;
+          w.first->borrowed = true;
+          o += (w.second + 4095) & ~(size_t)4095;
+        } else if ((rc = w.first->ensure(w.second))) {
+          return rc;
+        }
+      }
     }
   }
 
@@ -1657,8 +1743,9 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   }
 
   // ---- the decode of every group on its own stream
-  const DecodeKernel cluster_kern = plan.clustered() ? cluster_kernel(plan, m, L) : nullptr;
-  if (plan.clustered() && !cluster_kern) return fail(UIS_ERR_HIP, "no one-launch kernel instantiated for this shape");
+  const DecodeKernel cluster_kern = plan.clustered() && !rs ? cluster_kernel(plan, m, L) : nullptr;
+  const RsKernel rs_kern = rs ? find_kernel(kernels::rs, m.Hp, m.Dp, plan.rs_kind) : nullptr;
+  if (plan.clustered() && !cluster_kern && !rs_kern) return fail(UIS_ERR_HIP, "no one-launch kernel instantiated for this shape");
   for (int g = 0; g < G; ++g) {
     GroupPlan& gp = groups[g];
     hipStream_t sg = h->gstreams[g];
@@ -1688,7 +1775,8 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
           gp.st.step0 = k ? (int)cuts[k - 1] - 1 : 0;
           gp.st.step1 = k < cuts.size() ? (int)cuts[k] - 1 : 0;
         }
-        if ((rc = launch_cluster_kernel(gl, cluster_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st))) return rc;
+        if ((rc = rs ? launch_rs_kernel(gl, rs_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st, h->bp.cap)
+                     : launch_cluster_kernel(gl, cluster_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st))) return rc;
       }
     } else if (plan.path == DecodePath::SMALL) {
       DecodeKernel kern = L == 1 ? &k_decode_small<false> : &k_decode_small<true>;
@@ -1858,7 +1946,7 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
                     &h->beam_score, &h->beam_slot, &h->beam_blk, &h->bp, &h->rows, &h->nrows, &h->gi_up, &h->a1,
                     &h->counters, &h->beam_scores_out, &h->io_frames, &h->io_labels, &h->io_scores, &h->mse_tab, &h->dbg_scores, &h->utt_nrows, &h->hst, &h->resume, &h->split_tab, &h->scatter_tab, &h->stage,
                     &h->lv_n, &h->lv_K, &h->lv_last, &h->lv_sum, &h->lv_score, &h->lv_origin, &h->lv_path, &h->lv_slot,
-                    &h->lv_blk, &h->scratch, &h->bp16, &h->bp_base, &h->cluster_ctl, &h->arena,
+                    &h->lv_blk, &h->scratch, &h->bp16, &h->bp_base, &h->cluster_ctl, &h->rs_block, &h->arena,
                     &h->ev_a, &h->ev_b, &h->ev_off, &h->ev_out, &h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0,
                     &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean, &h->sc_gi_up, &h->sc_rows, &h->sc_chains,
                     &h->sc_utt, &h->sc_out};

@@ -59,6 +59,37 @@ struct DevModel {
   double lp_new;  // lp_sw + l_alpha, added once on the host (the same IEEE sum the kernels formed per candidate)
 };
 
+// The argument block of k_decode_rs: what that kernel reads and nothing else.  Its step loop is bound by scalar
+// registers, so everything it addresses while it steps sits in ONE stretch of the workspace
+// arena -- `blk`, from pool_mean up to the end of mse_tab, below 4 GB: the planner checks -- and is named by a 32-bit
+// byte offset into it (one buffer descriptor, offsets in the instructions' scalar-offset field); the frame stream
+// (x / gi0 / mse0, each below 4 GB) through three more.  The other kernels of the same decode (k_init_state,
+// k_backtrace, ...) see ordinary pointers into the same memory.  Built on the host by rs_make_args (uis_decoder.hip).
+struct RsArgs {
+  int U, B, Kmax, S, D, H_units, tau, ncl, rx_stride, step0, step1;
+  uint32_t flags;
+  double lp_stay, lp_sw, lp_new;
+  // read once per launch: the rank's weight and bias slices, 1 / (2 sigma^2), the utterances' offsets, the hand-over
+  // block of a decode in several launches
+  const float* whh;  const float* w1;  const float* w2;
+  const float* bhh;  const float* b1;  const float* b2;
+  const float* wgt;
+  const int64_t* off;
+  unsigned char* resume;
+  // the loop's
+  const double* logblk;  const double* logden;     // (counts beyond the LDS copies only)
+  const float* x;  const float* gi0;  const float* mse0;
+  unsigned char* blk;
+  uint32_t o_mean, o_hid, o_h1, o_hst, o_a1;       // pool_mean, pool_hid, its h1 slot, the h' staging tiles, a1
+  uint32_t o_tab, o_part;                          // mse_tab, mse_part
+  uint32_t o_ctl;                                  // the control words: [0, 16) XCC ids, [16] abort, phase words from word o_flag_word
+  uint32_t o_flag_word;
+  uint32_t o_beam_n, o_beam_score, o_bp;           // what an utterance's owner rank leaves for k_backtrace
+  int32_t* overflow;
+  float* dbg_scores;
+  unsigned long long* counters;
+};
+
 // Persistent streaming launch (UIS_FLAG_PERSISTENT sessions): k_decode_resident stays on the device
 // between pushes and takes its commands from a block of host-coherent pinned memory.  `ctl` and
 // the other pointers below name HOST memory mapped into the device's address space, except go / hdr.

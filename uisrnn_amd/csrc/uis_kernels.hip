@@ -796,8 +796,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // 16 bytes with sc1: bypasses this CU's L1, served by the XCD's L2 (where the sibling
 // workgroups' plain stores land)
-__device__ __forceinline__ f32x4 load_sc1(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 16 /* sc1 */));
+// (soff: a wave-uniform byte offset that rides in the instruction's scalar-offset field -- no per-lane add)
+__device__ __forceinline__ f32x4 load_sc1(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off, uint32_t soff = 0u) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, soff, 16 /* sc1 */));
 }
 
 // mse0[frame] = weighted MSE(m0, x[frame])   (fresh-cluster score term; one wave per frame)
@@ -1898,11 +1899,18 @@ __device__ __forceinline__ float load_f32_sc1(const float* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // one float through a buffer descriptor with a 32-bit byte offset (no 64-bit address arithmetic per lane)
-__device__ __forceinline__ float rs_buf_load_f32_sc1(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, 0, 16 /* sc1 */));
+__device__ __forceinline__ float rs_buf_load_f32_sc1(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off, uint32_t soff = 0u) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, soff, 16 /* sc1 */));
 }
-__device__ __forceinline__ void rs_buf_store_f32(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, byte_off, 0, 0);
+__device__ __forceinline__ void rs_buf_store_f32(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off, float v, uint32_t soff = 0u) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, byte_off, soff, 0);
+}
+// ... and what the cached global loads of the frame stream become (no sc1: the stream is read-only while a decode runs)
+__device__ __forceinline__ float rs_buf_load_f32(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, 0, 0));
+}
+__device__ __forceinline__ f32x4 rs_buf_load_f32x4(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0));
 }
 __device__ __forceinline__ void rs_buf_store_f32x4(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off, f32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, byte_off, 0, 0);
@@ -3963,8 +3971,8 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
       win.keep = 0; win.C = 0; win.nlead = 0; win.a = 0u; win.b = 0u; win.c = 0u; win.score = 0.0f;
       if (act_w) {
         const RsDims dm{st.B, st.Kmax, S, m.D};
-        const RsPrep prep = rs_prep<true>(m, st, RL, dm, s, pers_w, scr_w, ws_lblk, ws_lden, []() {});
-        win = rs_front<DP, true>(m, st, RL, dm, u_w, s, frame_w, pers_w, scr_w, rs_mean /* unused: FULL */, 0u, prep, nullptr, ws_swgt);
+        const RsPrep prep = rs_prep<true>(RsBigView{m, st}, RL, dm, s, pers_w, scr_w, ws_lblk, ws_lden, []() {});
+        win = rs_front<DP, true>(RsBigView{m, st}, RL, dm, u_w, s, frame_w, pers_w, scr_w, 0u, prep, nullptr, ws_swgt);
         int row_base = 0;
         if (lane == 0 && win.nlead > 0) row_base = atomicAdd(sink.count, win.nlead);
         row_base = __shfl(row_base, 0, 64);
@@ -3976,7 +3984,7 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
       RSTAMP(0 + (WIN ? 8 * (s & 1) : 0));
       xcd_arrive(st, cluster, s_ctl);
       if (act_w) {
-        rs_back(m, st, RL, RsDims{st.B, st.Kmax, S, m.D}, u_w, s, off0_w, pers_w, true, win, []() {});
+        rs_back(RsBigView{m, st}, RL, RsDims{st.B, st.Kmax, S, m.D}, u_w, s, off0_w, pers_w, true, win, []() {});
         fpos_w = fpos_w + 1 == N_w ? 0 : fpos_w + 1;
       }
       if (rs_xcd_wait(st, cluster, 32u * ++bar, s_ctl)) return;

@@ -116,7 +116,9 @@ __host__ __device__ inline size_t rs_spart_bytes() { return (size_t)UIS_KSPLIT *
 
 // LDS of k_decode_rs: 1 / (2 sigma^2) | log tables | the utterance slots' persistent blocks | split-K
 // partial tiles (the slots' select scratch lives in the same bytes) | control words | the rank's
-// linear_mean1 / linear_mean2 weight tiles | this step's row descriptors (built locally) | frames
+// linear_mean1 / linear_mean2 weight tiles | this step's row descriptors (built locally) | frames | the rank's
+// bias slices (b_hh 3 x 16, b1 16, b2 16 floats)
+#define UIS_RS_BIAS_FLOATS 80
 __host__ __device__ inline size_t resident_rs_lds_bytes(int Hp, int Dp, int B, int Kmax, int S) {
   const RsLds L = rs_lds_layout(B, Kmax, S);
   const int slots = UIS_RS_UTT;
@@ -124,7 +126,7 @@ __host__ __device__ inline size_t resident_rs_lds_bytes(int Hp, int Dp, int B, i
   const size_t scratch = (size_t)slots * L.scratch_stride;
   return (size_t)Dp * 4 + (size_t)2 * UIS_RS_LOGTAB * 8 + (size_t)slots * L.persist_stride +
          (spart > scratch ? spart : scratch) + 128 + (size_t)2 * (Hp / 16) * 64 * 16 + (size_t)rs_head_tiles(B) * 16 * 16 +
-         (size_t)2 * slots * 8;
+         (size_t)2 * slots * 8 + (size_t)UIS_RS_BIAS_FLOATS * 4;
 }
 
 // ceil(2^20 / d) for 1 <= d < 4096 without the integer-division sequence: the float quotient of
@@ -190,11 +192,11 @@ __device__ __forceinline__ float rs_mse16_regs(int D, const f32x4 (&mv)[4 * ((DP
 }
 template <int DP>
 __device__ __forceinline__ void rs_load_mean16(__amdgpu_buffer_rsrc_t rs_mean, size_t slot_index, int p,
-                                               f32x4 (&mv)[4 * ((DP + 255) / 256)]) {
+                                               f32x4 (&mv)[4 * ((DP + 255) / 256)], uint32_t soff = 0u) {
 #pragma unroll
   for (int k = 0; k < 4 * ((DP + 255) / 256); ++k) {
     const int d = 256 * (k >> 2) + 4 * (p + 16 * (k & 3));
-    mv[k] = d < DP ? load_sc1(rs_mean, (uint32_t)((slot_index * DP + d) * 4)) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    mv[k] = d < DP ? load_sc1(rs_mean, (uint32_t)((slot_index * DP + d) * 4), soff) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   }
 }
 template <int DP>
@@ -205,6 +207,103 @@ __device__ __forceinline__ void rs_load_frame16(const float* xrow, int p, f32x4 
     xv[k] = d < DP ? *reinterpret_cast<const f32x4*>(xrow + d) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   }
 }
+// ... through the frame stream's descriptor (row_off = the row's byte offset: the planner keeps the stream below 4 GB)
+template <int DP>
+__device__ __forceinline__ void rs_load_frame16(__amdgpu_buffer_rsrc_t rs_x, uint32_t row_off, int p, f32x4 (&xv)[4 * ((DP + 255) / 256)]) {
+#pragma unroll
+  for (int k = 0; k < 4 * ((DP + 255) / 256); ++k) {
+    const int d = 256 * (k >> 2) + 4 * (p + 16 * (k & 3));
+    xv[k] = d < DP ? rs_buf_load_f32x4(rs_x, row_off + (uint32_t)(d * 4)) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+}
+
+// What the select's parts (rs_prep / rs_front / rs_back) read and write of the decode, behind one interface with two
+// implementations, so that each kernel pays only for what it names:
+//   RsBigView   k_decode_big<WS>: the kernel's DevModel / DecodeState as they are (plain pointers);
+//   RsView      k_decode_rs: its compact argument block (RsArgs, uis_kernels.h) -- one buffer descriptor for the state,
+//               32-bit offsets, nothing live across the step loop that the loop does not read.
+struct RsBigView {
+  const DevModel& m;
+  const DecodeState& st;
+  __device__ __forceinline__ double lp_stay() const { return m.lp_stay; }
+  __device__ __forceinline__ double lp_sw() const { return m.lp_sw; }
+  __device__ __forceinline__ double lp_new() const { return m.lp_new; }
+  __device__ __forceinline__ const double* logblk() const { return st.logblk; }
+  __device__ __forceinline__ const double* logden() const { return st.logden; }
+  __device__ __forceinline__ int U() const { return st.U; }
+  __device__ __forceinline__ int tau() const { return st.tau; }
+  __device__ __forceinline__ uint32_t flags() const { return st.flags; }
+  __device__ __forceinline__ float mse_fresh(long frame) const { return st.mse0[frame]; }
+  __device__ __forceinline__ float* dbg_scores() const { return st.dbg_scores; }
+  __device__ __forceinline__ unsigned long long* counters() const { return st.counters; }
+  __device__ __forceinline__ void put_overflow(int u) const { st.overflow[u] = 1; }
+  struct Blk {};
+  __device__ __forceinline__ Blk blk() const { return Blk{}; }
+  __device__ __forceinline__ void put_beam_score(Blk, size_t i, float v) const { st.beam_score[i] = v; }
+  __device__ __forceinline__ void put_bp(Blk, size_t i, unsigned v) const { st.bp[i] = v; }
+  __device__ __forceinline__ void put_beam_n(Blk, size_t i, int v) const { st.beam_n[i] = v; }
+};
+// A kernel argument in scalar registers OF ITS OWN.  The argument block arrives through 16-dword scalar loads, and the
+// register allocator treats what such a load returns as one value: while any field of it is live across the step loop
+// all sixteen registers are, and a spill reloads all sixteen to read one.  A move the compiler cannot see through
+// (an empty asm with a tied operand is folded back into the tuple) gives each field its own one or two registers and
+// its own live range; the wide tuples end with the prologue.
+__device__ __forceinline__ void rs_own_sgprs(uint32_t& v) { uint32_t o; asm volatile("s_mov_b32 %0, %1" : "=s"(o) : "s"(v)); v = o; }
+__device__ __forceinline__ void rs_own_sgprs(int& v) { int o; asm volatile("s_mov_b32 %0, %1" : "=s"(o) : "s"(v)); v = o; }
+__device__ __forceinline__ unsigned long long rs_own_sgprs64(unsigned long long q) {
+  unsigned long long o;
+  asm volatile("s_mov_b64 %0, %1" : "=s"(o) : "s"(q));
+  return o;
+}
+__device__ __forceinline__ void rs_own_sgprs(double& v) { v = __builtin_bit_cast(double, rs_own_sgprs64(__builtin_bit_cast(unsigned long long, v))); }
+template <typename T> __device__ __forceinline__ void rs_own_sgprs(T*& v) { v = (T*)rs_own_sgprs64((unsigned long long)v); }
+__device__ __forceinline__ RsArgs rs_own_args(RsArgs a) {
+  static_assert(sizeof(RsArgs) == 264, "a field was added to RsArgs: give it registers of its own below (tests/test_rs_loop_static.py counts the spills)");
+  rs_own_sgprs(a.U); rs_own_sgprs(a.B); rs_own_sgprs(a.Kmax); rs_own_sgprs(a.S); rs_own_sgprs(a.D); rs_own_sgprs(a.H_units);
+  rs_own_sgprs(a.tau); rs_own_sgprs(a.ncl); rs_own_sgprs(a.rx_stride); rs_own_sgprs(a.step0); rs_own_sgprs(a.step1);
+  rs_own_sgprs(a.flags);
+  rs_own_sgprs(a.lp_stay); rs_own_sgprs(a.lp_sw); rs_own_sgprs(a.lp_new);
+  rs_own_sgprs(a.whh); rs_own_sgprs(a.w1); rs_own_sgprs(a.w2); rs_own_sgprs(a.bhh); rs_own_sgprs(a.b1); rs_own_sgprs(a.b2);
+  rs_own_sgprs(a.wgt); rs_own_sgprs(a.off); rs_own_sgprs(a.resume);
+  rs_own_sgprs(a.logblk); rs_own_sgprs(a.logden);
+  rs_own_sgprs(a.x); rs_own_sgprs(a.gi0); rs_own_sgprs(a.mse0); rs_own_sgprs(a.blk);
+  rs_own_sgprs(a.o_mean); rs_own_sgprs(a.o_hid); rs_own_sgprs(a.o_h1); rs_own_sgprs(a.o_hst); rs_own_sgprs(a.o_a1);
+  rs_own_sgprs(a.o_tab); rs_own_sgprs(a.o_part); rs_own_sgprs(a.o_ctl); rs_own_sgprs(a.o_flag_word);
+  rs_own_sgprs(a.o_beam_n); rs_own_sgprs(a.o_beam_score); rs_own_sgprs(a.o_bp);
+  rs_own_sgprs(a.overflow); rs_own_sgprs(a.dbg_scores); rs_own_sgprs(a.counters);
+  return a;
+}
+
+// A 4 GB descriptor over p, built WHERE IT IS USED: a descriptor is four scalar registers of which two are constants, and
+// one that is live across the step loop is spilled and reloaded as four -- so the loop keeps the pointer (two) and every
+// stage forms its own (the empty asm keeps the optimiser from hoisting the four words back out of the loop).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rs_desc(const void* p) {
+  unsigned long long q = (unsigned long long)p;
+  asm volatile("" : "+s"(q));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)q, (short)0, 0xffffffff, 0x00020000);
+}
+struct RsView {
+  const RsArgs& a;
+  typedef __amdgpu_buffer_rsrc_t Blk;
+  __device__ __forceinline__ Blk blk() const { return rs_desc(a.blk); }
+  __device__ __forceinline__ Blk x() const { return rs_desc(a.x); }
+  __device__ __forceinline__ Blk gi0() const { return rs_desc(a.gi0); }
+  __device__ __forceinline__ double lp_stay() const { return a.lp_stay; }
+  __device__ __forceinline__ double lp_sw() const { return a.lp_sw; }
+  __device__ __forceinline__ double lp_new() const { return a.lp_new; }
+  __device__ __forceinline__ const double* logblk() const { return a.logblk; }
+  __device__ __forceinline__ const double* logden() const { return a.logden; }
+  __device__ __forceinline__ int U() const { return a.U; }
+  __device__ __forceinline__ int tau() const { return a.tau; }
+  __device__ __forceinline__ uint32_t flags() const { return a.flags; }
+  __device__ __forceinline__ float mse_fresh(long frame) const { return rs_buf_load_f32(rs_desc(a.mse0), (uint32_t)frame * 4u); }
+  __device__ __forceinline__ float* dbg_scores() const { return a.dbg_scores; }
+  __device__ __forceinline__ unsigned long long* counters() const { return a.counters; }
+  __device__ __forceinline__ void put_overflow(int u) const { a.overflow[u] = 1; }
+  __device__ __forceinline__ void put_beam_score(Blk blk, size_t i, float v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, v, a.o_beam_score); }
+  __device__ __forceinline__ void put_bp(Blk blk, size_t i, unsigned v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, __builtin_bit_cast(float, v), a.o_bp); }
+  __device__ __forceinline__ void put_beam_n(Blk blk, size_t i, int v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, __builtin_bit_cast(float, v), a.o_beam_n); }
+};
 
 // What the front part of a wave's select leaves in registers: lane r = winner r (four packed
 // words per lane, so that they can stay live across the GRU stage's MFMA chain).
@@ -241,8 +340,8 @@ struct RsPrep {
   float bs[3];
 };
 
-template <bool FULL = false, typename Mid>
-__device__ __forceinline__ RsPrep rs_prep(const DevModel& m, const DecodeState& st, const RsLds& L, const RsDims dm, int step,
+template <bool FULL = false, typename View, typename Mid>
+__device__ __forceinline__ RsPrep rs_prep(const View& a, const RsLds& L, const RsDims dm, int step,
                                           const unsigned char* pers, unsigned char* scr, const double* s_lblk,
                                           const double* s_lden, Mid mid) {
   int lane_ = threadIdx.x & 63;
@@ -300,21 +399,21 @@ __device__ __forceinline__ RsPrep rs_prep(const DevModel& m, const DecodeState& 
       if (c <= Kb) {
         const int sum = (int)h[2];
         double ld = s_lden[sum < UIS_RS_LOGTAB ? sum : 0];  // (no pointer select between LDS and global: two loads)
-        if (sum >= UIS_RS_LOGTAB) ld = st.logden[sum];
+        if (sum >= UIS_RS_LOGTAB) ld = a.logden()[sum];
         base = __builtin_bit_cast(float, (uint32_t)h[3]);
         if (c < Kb) {
           const uint32_t en = sent[b * Kmax + c];
           cslot = (int)(en & 0xffffu);
-          if (c == (int)h[1]) { prior = m.lp_stay; P.stay |= 1 << k; }
+          if (c == (int)h[1]) { prior = a.lp_stay(); P.stay |= 1 << k; }
           else {
             const int blk = (int)(en >> 16);
             double lb = s_lblk[blk < UIS_RS_LOGTAB ? blk : 0];
-            if (blk >= UIS_RS_LOGTAB) lb = st.logblk[blk];
-            prior = (m.lp_sw + lb) - ld;
+            if (blk >= UIS_RS_LOGTAB) lb = a.logblk()[blk];
+            prior = (a.lp_sw() + lb) - ld;
           }
         } else {
           cslot = -1;
-          prior = m.lp_new - ld;
+          prior = a.lp_new() - ld;
         }
       }
     }
@@ -382,14 +481,16 @@ __device__ __forceinline__ void rs_full_mse(const DecodeState& st, const RsLds& 
 // FRONT: the MSEs, scores, prune, winners, rows -- what the step's dense stages wait for.  One wave
 // (all 64 lanes), utterance u, decode step `step` whose frame is row `frame` of the stream.  pers =
 // the utterance's persistent block, scr = its scratch (rs_prep left the free slots there).
-// rs_part + part_off = where the partial sums of the rows this utterance emitted in the previous step
+// part_off = where (in the view's block) the partial sums of the rows this utterance emitted in the previous step
 // start (the i-th slot of its new-slot list was written by its i-th row).
 // FULL: the wave computes the MSE of the frame against EVERY live cluster mean itself (no published
 // values, no partial sums: k_decode_big, where a wave owns its utterance alone); P.old* then lists all
 // live slots and `swgt_full` is 1 / (2 sigma^2) in LDS.
-template <int DP, bool FULL = false>
-__device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& st, const RsLds& L, const RsDims dm, int u, int step,
-                                          long frame, unsigned char* pers, unsigned char* scr, __amdgpu_buffer_rsrc_t rs_part,
+// (not FULL: the view is an RsView; part_off = the byte offset IN ITS BLOCK of the partial sums of the rows this
+// utterance emitted in the previous step)
+template <int DP, bool FULL = false, typename View>
+__device__ __forceinline__ RsWin rs_front(const View& a, const RsLds& L, const RsDims dm, int u, int step,
+                                          long frame, unsigned char* pers, unsigned char* scr,
                                           uint32_t part_off, const RsPrep& P, unsigned long long* ph,
                                           const float* swgt_full = nullptr) {
   // (opaque to the optimiser: nothing lane-derived is hoisted out of the kernel's step loop, where
@@ -403,7 +504,7 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
 #else
 #define PSTAMP(k) do {} while (0)
 #endif
-  const int B = dm.B, Kmax = dm.Kmax, S = dm.S, U = st.U;
+  const int B = dm.B, Kmax = dm.Kmax, S = dm.S, U = a.U();
   const int par = step & 1;
   const unsigned char* const set_cur = pers + par * L.set_stride;
   const u32x4* shyp = reinterpret_cast<const u32x4*>(set_cur + L.off_hyp);
@@ -415,23 +516,24 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
 
   const int Kcur = P.Kcur, kmagic = P.kmagic, nch = P.nch, C = P.C, nn = P.nn;
   const unsigned long long old[4] = {P.old0, P.old1, P.old2, P.old3};
-  const float mse_new = st.mse0[frame];
-  if (FULL) {
+  const float mse_new = a.mse_fresh(frame);
+  if constexpr (FULL) {
     // ---- every live cluster's MSE from its mean (P.old*: the slots whose MSE is still to be computed -- all live
     // ones, unless the caller ran rs_full_mse on some of them earlier)
-    rs_full_mse<DP>(st, L, dm, u, frame, scr, old, swgt_full);
+    rs_full_mse<DP>(a.st, L, dm, u, frame, scr, old, swgt_full);
   } else {
   // ---- ONE round trip: the fresh-cluster MSE, the published MSEs of the clusters the previous
   // step left alone, and for the ones it rewrote the tile sums its linear_mean2 epilogue emitted
   // (one float per 16-feature tile + the squared first difference per cluster: lane i takes new cluster i)
   constexpr int PSTR = rs_part_stride(DP), PV = DP <= 256 ? 4 : 8;
+  const __amdgpu_buffer_rsrc_t blk = a.blk();
   float vold[4];
   {
-    const float* tab = st.mse_tab + ((size_t)par * U + u) * S;
+    const uint32_t tab = (uint32_t)((par * U + u) * S) * 4u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       vold[k] = 0.0f;
-      if ((old[k] >> lane) & 1ull) vold[k] = load_f32_sc1(tab + lane + 64 * k);
+      if ((old[k] >> lane) & 1ull) vold[k] = rs_buf_load_f32_sc1(blk, tab + (uint32_t)((lane + 64 * k) * 4), a.a.o_tab);
     }
   }
   f32x4 pv[PV];
@@ -440,8 +542,8 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
   if (lane < nn) {
     nsl = snewlist[1 + lane];
 #pragma unroll
-    for (int k = 0; k < PV; ++k) pv[k] = load_sc1(rs_part, part_off + (uint32_t)(lane * PSTR * 4 + 16 * k));
-    pfirst = rs_buf_load_f32_sc1(rs_part, part_off + (uint32_t)((lane * PSTR + rs_part_first(DP)) * 4));
+    for (int k = 0; k < PV; ++k) pv[k] = load_sc1(blk, (uint32_t)(lane * PSTR * 4 + 16 * k), part_off);
+    pfirst = rs_buf_load_f32_sc1(blk, (uint32_t)((lane * PSTR + rs_part_first(DP)) * 4), part_off);
   }
   PSTAMP(0);
   // ---- the MSEs: the published values first (they arrive first), then the rewritten clusters
@@ -477,13 +579,13 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
       if (uis_isfinite(sc[k])) key[k] = uis_score_key(sc[k]);
     }
   }
-  if (st.dbg_scores) {  // UIS_FLAG_DEBUG_SCORES: the step's _calculate_score arrays
+  if (a.dbg_scores()) {  // UIS_FLAG_DEBUG_SCORES: the step's _calculate_score arrays
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       if ((k == 0 || nch > k) && P.cslot[k] != -2) {
         const int e = lane + 64 * k;
         const int b = (int)(((unsigned)e * (unsigned)kmagic) >> 20), c = e - b * Kcur;
-        st.dbg_scores[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc[k];
+        a.dbg_scores()[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc[k];
       }
     }
   }
@@ -524,7 +626,7 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
   }
   const int nsv = nbefore[3];
 #if defined(UIS_RS_COUNT_PATHS)  // diagnostic: how long the short lists are (workgroup 0's copies; uis_decoder.hip prints them)
-  if (!FULL && blockIdx.x == 0 && lane == 0) atomicAdd(&st.counters[88 + (nsv <= 16 ? 0 : nsv <= 32 ? 1 : nsv <= 64 ? 2 : 3)], 1ull);
+  if (!FULL && blockIdx.x == 0 && lane == 0) atomicAdd(&a.counters()[88 + (nsv <= 16 ? 0 : nsv <= 32 ? 1 : nsv <= 64 ? 2 : 3)], 1ull);
 #endif
   if (nsv <= 64) {
     uint32_t* sck = reinterpret_cast<uint32_t*>(scr + L.sc_ckey);
@@ -593,7 +695,7 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
   RsWin out;
   out.keep = keep;
   out.C = C;
-  const bool nodedup = (st.flags & 1u) != 0;
+  const bool nodedup = (a.flags() & 1u) != 0;
   const int r = lane;
   const bool isw = r < keep;
   int wb = 0, wc = 0, src = -2, Kb = 0;
@@ -636,13 +738,13 @@ __device__ __forceinline__ RsWin rs_front(const DevModel& m, const DecodeState& 
 
 // BACK: the next step's tables, masks and counts, the back-pointers -- nothing anybody waits for.
 // `owner`: this workgroup writes what outlives the step to memory.
-template <typename Mid>
-__device__ __forceinline__ void rs_back(const DevModel& m, const DecodeState& st, const RsLds& L, const RsDims dm, int u, int step,
+template <typename View, typename Mid>
+__device__ __forceinline__ void rs_back(const View& a, const RsLds& L, const RsDims dm, int u, int step,
                                         long off0, unsigned char* pers, bool owner, const RsWin& w, Mid mid) {
   int lane_ = threadIdx.x & 63;
   asm volatile("" : "+v"(lane_));
   const int lane = lane_;
-  const int B = dm.B, Kmax = dm.Kmax, S = dm.S, U = st.U;
+  const int B = dm.B, Kmax = dm.Kmax, S = dm.S, U = a.U();
   const int par = step & 1, nxt = par ^ 1;
   const unsigned char* const set_cur = pers + par * L.set_stride;
   unsigned char* const set_nxt = pers + nxt * L.set_stride;
@@ -657,6 +759,7 @@ __device__ __forceinline__ void rs_back(const DevModel& m, const DecodeState& st
   unsigned long long* snew = reinterpret_cast<unsigned long long*>(pers + L.off_new);
   int* snewlist = reinterpret_cast<int*>(pers + L.off_newlist);
 
+  const typename View::Blk blk = a.blk();
   const int r = lane;
   const bool isw = r < w.keep;
   int Knew_w = 0;
@@ -668,13 +771,13 @@ __device__ __forceinline__ void rs_back(const DevModel& m, const DecodeState& st
     const int lastb = (int)h[1];
     Knew_w = Kb + (is_new ? 1 : 0);
     const int blk_new = is_new ? 1 : (int)(sent[wb * Kmax + (is_new ? 0 : wc)] >> 16) + (wc != lastb ? 1 : 0);
-    if (Knew_w > Kmax) { Knew_w = Kmax; if (owner) st.overflow[u] = 1; }
+    if (Knew_w > Kmax) { Knew_w = Kmax; if (owner) a.put_overflow(u); }
     const int sum_new = (int)h[2] + ((is_new || wc != lastb) ? 1 : 0);
     nhyp[r] = u32x4{(uint32_t)Knew_w, (uint32_t)wc, (uint32_t)sum_new, __builtin_bit_cast(uint32_t, w.score)};
     info_b = ((unsigned)w.dst() & 0xffffu) | ((unsigned)blk_new << 16);
     if (owner) {
-      st.beam_score[((size_t)nxt * U + u) * B + r] = w.score;  // (the final beam's scores are read back by k_backtrace)
-      st.bp[((size_t)st.tau * off0 + step) * B + r] = ((unsigned)wb << 16) | (unsigned)wc;
+      a.put_beam_score(blk, ((size_t)nxt * U + u) * B + r, w.score);  // (the final beam's scores are read back by k_backtrace)
+      a.put_bp(blk, ((size_t)a.tau() * off0 + step) * B + r, ((unsigned)wb << 16) | (unsigned)wc);
     }
   }
   // which slots the next beam references: byte flags (plain stores; LDS atomics on four mask words
@@ -728,7 +831,7 @@ __device__ __forceinline__ void rs_back(const DevModel& m, const DecodeState& st
     acc[1] += (unsigned long long)w.keep;
     acc[2] += (unsigned long long)w.C;
     if ((unsigned long long)Kmaxseen > acc[3]) acc[3] = (unsigned long long)Kmaxseen;
-    if (owner) st.beam_n[(size_t)nxt * U + u] = w.keep;
+    if (owner) a.put_beam_n(blk, (size_t)nxt * U + u, w.keep);
   }
 }
 
@@ -739,13 +842,13 @@ __device__ __forceinline__ void rs_back(const DevModel& m, const DecodeState& st
 // handful, in one round trip, between the arrival at the barrier behind the GRU stage and the wait
 // (it needs nobody else's data of this step: those means were final a step ago).
 template <int DP, typename Mid>
-__device__ __forceinline__ void rs_early_mse(const DevModel& m, const DecodeState& st, const RsLds& L, const RsDims dm, int u, int step,
+__device__ __forceinline__ void rs_early_mse(const RsView& a, const RsLds& L, const RsDims dm, int u, int step,
                                              long frame_next, const unsigned char* pers, const float* swgt,
                                              int rank, int w, Mid mid) {
   int lane_ = threadIdx.x & 63;
   asm volatile("" : "+v"(lane_));
   const int lane = lane_;
-  const int S = dm.S, U = st.U;
+  const int S = dm.S, U = a.U();
   const unsigned long long* slive = reinterpret_cast<const unsigned long long*>(pers + L.off_live);
   const unsigned long long* snew = reinterpret_cast<const unsigned long long*>(pers + L.off_new);
   // (the list lives in rs_back's byte-flag area, free between two steps' table updates -- NOT in the
@@ -770,19 +873,18 @@ __device__ __forceinline__ void rs_early_mse(const DevModel& m, const DecodeStat
   if (n == 0) return;
   rs_lds_fence();
   constexpr int NV = 4 * ((DP + 255) / 256);
-  const __amdgpu_buffer_rsrc_t rs_mean =
-      __builtin_amdgcn_make_buffer_rsrc((void*)st.pool_mean, (short)0, 0x7fffffff, 0x00020000);
   const int grp = lane >> 4, p = lane & 15;
   f32x4 xv[NV];
-  rs_load_frame16<DP>(st.x + (size_t)frame_next * DP, p, xv);
-  float* tab = st.mse_tab + ((size_t)((step + 1) & 1) * U + u) * S;
+  const __amdgpu_buffer_rsrc_t blk = a.blk();
+  rs_load_frame16<DP>(a.x(), (uint32_t)frame_next * (uint32_t)(DP * 4), p, xv);
+  const uint32_t tab = (uint32_t)((((step + 1) & 1) * U + u) * S) * 4u;
   for (int i0 = 0; i0 < n; i0 += 4) {
     const int i = i0 + grp;
     const int sl = (int)s_list[i < n ? i : 0];
     f32x4 mv[NV];
-    rs_load_mean16<DP>(rs_mean, (size_t)u * S + sl, p, mv);
+    rs_load_mean16<DP>(blk, (size_t)(u * S + sl), p, mv, a.a.o_mean);
     const float v = rs_mse16_regs<DP>(dm.D, mv, xv, swgt, p);
-    if (p == 0 && i < n) tab[sl] = v;
+    if (p == 0 && i < n) rs_buf_store_f32(blk, tab + (uint32_t)(sl * 4), v, a.a.o_tab);
   }
 }
 
@@ -790,10 +892,10 @@ __device__ __forceinline__ void rs_early_mse(const DevModel& m, const DecodeStat
 // put work that needs no other wave's partial tiles in front of it).
 template <int NG, int PER, int RC, int NV, int KBS, typename After>
 __device__ __forceinline__ void rs_tile_nv(const f32x4 (&wr)[NG][PER], const float* __restrict__ bias, int gate_stride,
-                                           __amdgpu_buffer_rsrc_t rsrc, const uint32_t (&boff)[RC], float* spart,
+                                           __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, const uint32_t (&boff)[RC], float* spart,
                                            After after_issue) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, q = lane >> 4;
-  f32x4 bv[NG];  // oldest in the vmcnt queue: the chain's first operand
+  f32x4 bv[NG];  // the chain's first operand (k_decode_rs: from the LDS copy of the rank's bias slices)
 #pragma unroll
   for (int g = 0; g < NG; ++g)
     bv[g] = w == 0 ? *reinterpret_cast<const f32x4*>(bias + (size_t)g * gate_stride + 4 * q) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -801,7 +903,7 @@ __device__ __forceinline__ void rs_tile_nv(const f32x4 (&wr)[NG][PER], const flo
 #pragma unroll
   for (int kb = 0; kb < PER; ++kb)
 #pragma unroll
-    for (int r = 0; r < NV; ++r) b[r][kb] = load_sc1(rsrc, boff[r] + (uint32_t)((w * PER + kb) * KBS + q * 16));
+    for (int r = 0; r < NV; ++r) b[r][kb] = load_sc1(rsrc, boff[r] + (uint32_t)((w * PER + kb) * KBS + q * 16), soff);
   after_issue();
   f32x4 acc[NV][NG];
 #pragma unroll
@@ -825,12 +927,12 @@ __device__ __forceinline__ void rs_tile_nv(const f32x4 (&wr)[NG][PER], const flo
 }
 template <int NG, int PER, int RC, int KBS, typename After>
 __device__ __forceinline__ void rs_tile(const f32x4 (&wr)[NG][PER], const float* __restrict__ bias, int gate_stride,
-                                        __amdgpu_buffer_rsrc_t rsrc, const uint32_t (&boff)[RC], int nvalid, float* spart,
-                                        After after_issue) {
+                                        __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, const uint32_t (&boff)[RC], int nvalid,
+                                        float* spart, After after_issue) {
   static_assert(RC == 3, "dispatch below");
-  if (nvalid >= 3) rs_tile_nv<NG, PER, RC, 3, KBS>(wr, bias, gate_stride, rsrc, boff, spart, after_issue);
-  else if (nvalid == 2) rs_tile_nv<NG, PER, RC, 2, KBS>(wr, bias, gate_stride, rsrc, boff, spart, after_issue);
-  else rs_tile_nv<NG, PER, RC, 1, KBS>(wr, bias, gate_stride, rsrc, boff, spart, after_issue);
+  if (nvalid >= 3) rs_tile_nv<NG, PER, RC, 3, KBS>(wr, bias, gate_stride, rsrc, soff, boff, spart, after_issue);
+  else if (nvalid == 2) rs_tile_nv<NG, PER, RC, 2, KBS>(wr, bias, gate_stride, rsrc, soff, boff, spart, after_issue);
+  else rs_tile_nv<NG, PER, RC, 1, KBS>(wr, bias, gate_stride, rsrc, soff, boff, spart, after_issue);
 }
 
 // The wait half of the in-launch barrier for a workgroup that has ARRIVED already (xcd_arrive: its
@@ -861,6 +963,64 @@ __device__ __forceinline__ bool rs_xcd_wait(const DecodeState& st, int cluster, 
   return *s_abort != 0;
 }
 
+// The hand-offs' phase words, the abort word and the XCC ids of k_decode_rs through its block descriptor (rs_flag_publish /
+// rs_flag_peek* / rs_flag_wait* of uis_kernels.hip with the same scopes: a plain store = workgroup scope, sc1 = agent
+// scope).  fl = the byte offset in the block of the cluster's line of phase words, ab = of the abort word.
+__device__ __forceinline__ uint32_t rs_blk_load_agent(__amdgpu_buffer_rsrc_t blk, uint32_t voff, uint32_t soff) {
+  return __builtin_amdgcn_raw_buffer_load_b32(blk, voff, soff, 16 /* sc1 */);
+}
+__device__ __forceinline__ void rs_blk_store_agent(__amdgpu_buffer_rsrc_t blk, uint32_t voff, uint32_t soff, uint32_t v) {
+  __builtin_amdgcn_raw_buffer_store_b32(v, blk, voff, soff, 16 /* sc1 */);
+}
+__device__ __forceinline__ void rs_blk_publish(__amdgpu_buffer_rsrc_t blk, uint32_t fl, int rank, uint32_t phase, bool agent_scope) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have reached L2
+  __syncthreads();
+#if defined(UIS_RS_FLAG_AGENT)
+  agent_scope = true;
+#endif
+  if (threadIdx.x == 0) {  // (the scope of the store: see rs_flag_publish)
+    if (agent_scope) rs_blk_store_agent(blk, (uint32_t)rank * 4u, fl, phase);
+    else __builtin_amdgcn_raw_buffer_store_b32(phase, blk, (uint32_t)rank * 4u, fl, 0);
+  }
+}
+__device__ __forceinline__ u32x4 rs_blk_peek4(__amdgpu_buffer_rsrc_t blk, uint32_t fl, uint32_t byte_off) {
+  return __builtin_bit_cast(u32x4, load_sc1(blk, byte_off, fl));
+}
+__device__ __forceinline__ uint32_t rs_blk_peek_all(__amdgpu_buffer_rsrc_t blk, uint32_t fl) {
+  const int lane = threadIdx.x & 63;
+  return rs_blk_load_agent(blk, (uint32_t)(lane & 31) * 4u, fl);
+}
+// true: gave up (a producer never published, or somebody else gave up)
+__device__ __forceinline__ bool rs_blk_wait(__amdgpu_buffer_rsrc_t blk, uint32_t fl, uint32_t ab, uint32_t byte_off, uint32_t phase) {
+  unsigned spins = 0;
+  for (;;) {
+    const u32x4 f = __builtin_bit_cast(u32x4, load_sc1(blk, byte_off, fl));
+    asm volatile("" ::: "memory");  // (a fresh load every round)
+    if (rs_flag_ready4(f, phase)) return false;
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > (1u << 21)) {  // ~1 s: give up instead of hanging the device
+      rs_blk_store_agent(blk, 0u, ab, 1u);
+      return true;
+    }
+    if ((spins & 255u) == 0 && __builtin_amdgcn_readfirstlane((int)rs_blk_load_agent(blk, 0u, ab))) return true;
+  }
+}
+__device__ __forceinline__ bool rs_blk_wait_all(__amdgpu_buffer_rsrc_t blk, uint32_t fl, uint32_t ab, uint32_t phase) {
+  const int lane = threadIdx.x & 63;
+  unsigned spins = 0;
+  for (;;) {
+    const uint32_t f = lane < 32 ? rs_blk_load_agent(blk, (uint32_t)lane * 4u, fl) : phase;
+    asm volatile("" ::: "memory");
+    if (__ballot(f < phase) == 0ull) return false;
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > (1u << 21)) {
+      rs_blk_store_agent(blk, 0u, ab, 1u);
+      return true;
+    }
+    if ((spins & 255u) == 0 && __builtin_amdgcn_readfirstlane((int)rs_blk_load_agent(blk, 0u, ab))) return true;
+  }
+}
+
 // The one-launch decode with the replicated select (see the top of this file).  Same grid, same
 // weight residency, same dense stages and arithmetic as k_decode_resident; three in-launch
 // hand-offs per step instead of four barriers, no row reservation, no descriptor staging.
@@ -869,7 +1029,8 @@ __device__ __forceinline__ bool rs_xcd_wait(const DecodeState& st, int cluster, 
 //   CB, CK  beam_size and max_clusters as compile-time constants (0: run-time values) -- the instantiation
 //           of a shape whose LDS layout then folds into the instruction stream (LABNOTES.md 4.0a)
 template <int HP, int DP, int CB = 0, int CK = 0>
-__global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
+__global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
+  const RsArgs a = rs_own_args(args);
   constexpr int NKB = HP / 16, PER = NKB / UIS_KSPLIT, RC = UIS_RES_RC;
   constexpr int NFT1 = HP / 16, SH1 = 32 / NFT1;
   constexpr int NFT2 = DP / 16, SH2 = 32 / NFT2;
@@ -880,12 +1041,13 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);  // the wave's number, known to be uniform (scalar addresses)
-  const int ncl = st.ncl;
+  const int ncl = a.ncl;
   const int cluster = blockIdx.x % ncl, rank = blockIdx.x / ncl;
-  const int U = st.U;
+  const int U = a.U;
+  const RsView av{a};
   // (the fixed-shape classes are dispatched for unpadded models only: observation_dim = DP, rnn_hidden_size = HP)
-  const RsDims dm{CB ? CB : st.B, CB ? CK : st.Kmax, CB ? CB * CK + CB : st.S, CB ? DP : m.D};
-  const int Hreal = CB ? HP : m.H_units;
+  const RsDims dm{CB ? CB : a.B, CB ? CK : a.Kmax, CB ? CB * CK + CB : a.S, CB ? DP : a.D};
+  const int Hreal = CB ? HP : a.H_units;
   const int S = dm.S, B = dm.B;
   const RsLds L = rs_lds_layout(dm.B, dm.Kmax, dm.S);
   float* swgt = reinterpret_cast<float*>(smem_raw);
@@ -903,16 +1065,26 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   u32x4* s_head = reinterpret_cast<u32x4*>(s_w2 + NKB * 64);
   long* s_wframe = reinterpret_cast<long*>(s_head + head_tiles * 16);  // [SLOTS] this step's frame of every slot's utterance
   long* s_wnext = s_wframe + SLOTS;                                    // [SLOTS] ... and the next step's
+  float* s_bias = reinterpret_cast<float*>(s_wnext + SLOTS);           // b_hh r | z | n, b1, b2: this rank's 16 features of each
+  const int ft1 = rank / SH1, tpar1 = rank % SH1;
+  const int ft2 = rank / SH2, tpar2 = rank % SH2;
+  // where this cluster's words and rows are in the block (scalar: they ride in the buffer instructions' offset field)
+  const uint32_t ab_off = a.o_ctl + 16u * 4u;
+  const uint32_t fl_off = a.o_ctl + (a.o_flag_word + (uint32_t)cluster * 32u) * 4u;
+  const uint32_t xcc_off = a.o_ctl + (uint32_t)cluster * 4u;
 
   uint32_t xcc = 0;
   if (t == 0) {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     xcc &= 0xfu;
-    if (rank == 0) __hip_atomic_store(st.cl_xcc + cluster, xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (rank == 0) rs_blk_store_agent(av.blk(), 0u, xcc_off, xcc);
     for (int k = 0; k < 32; ++k) s_ctl[k] = 0;
   }
-  for (int i = t; i < DP; i += 512) swgt[i] = m.wgt[i];
-  for (int i = t; i < UIS_RS_LOGTAB; i += 512) { s_lblk[i] = st.logblk[i]; s_lden[i] = st.logden[i]; }
+  for (int i = t; i < DP; i += 512) swgt[i] = a.wgt[i];
+  for (int i = t; i < UIS_RS_LOGTAB; i += 512) { s_lblk[i] = a.logblk[i]; s_lden[i] = a.logden[i]; }
+  if (t < 48) s_bias[t] = a.bhh[(t >> 4) * HP + ft1 * 16 + (t & 15)];
+  else if (t < 64) s_bias[t] = a.b1[ft1 * 16 + (t & 15)];
+  else if (t < UIS_RS_BIAS_FLOATS) s_bias[t] = a.b2[ft2 * 16 + (t & 15)];
   for (int i = t; i < head_tiles * 16; i += 512) s_head[i] = u32x4{0u, 0u, 0u, 0u};
   if (t < SLOTS) { s_wframe[t] = 0; s_wnext[t] = 0; }
   // ---- this wave's utterance: slot w of the cluster
@@ -923,8 +1095,8 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   // (32-bit: the one-launch path decodes fewer than 2^31 frames -- the host checks -- and fewer than 65535 steps)
   int off0_w = 0, N_w = 0, fpos_w = 0;
   int prev_base = 0;  // first row of the slot's utterance in the previous step's row list
-  if (has_u) { off0_w = (int)st.off[u_w]; N_w = (int)st.off[u_w + 1] - off0_w; }
-  const int T_w = st.tau * N_w;
+  if (has_u) { off0_w = (int)a.off[u_w]; N_w = (int)a.off[u_w + 1] - off0_w; }
+  const int T_w = a.tau * N_w;
   // beam_set = [BeamState()] (uisrnn.py:528): one empty hypothesis, nothing live
   for (int i = lane; i < L.persist_stride / 4; i += 64) reinterpret_cast<int*>(pers_w)[i] = 0;
   __syncthreads();
@@ -938,16 +1110,16 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   const int nsteps = s_ctl[1];
   // (round 5) this launch runs steps [step0, s_end) of the decode: a launch that starts late picks up what the
   // previous one left in st.resume -- per utterance its persistent block, then the rows its last step emitted
-  const int step0 = st.step0;
-  const int s_end = (st.step1 > 0 && st.step1 < nsteps) ? st.step1 : nsteps;
+  const int step0 = a.step0;
+  const int s_end = (a.step1 > 0 && a.step1 < nsteps) ? a.step1 : nsteps;
   if (step0 > 0) {
     for (int k = 0; k < SLOTS; ++k) {
       const int u = cluster + ncl * k;
       if (u >= U) break;
-      const int* src = reinterpret_cast<const int*>(st.resume + (size_t)u * L.persist_stride);
+      const int* src = reinterpret_cast<const int*>(a.resume + (size_t)u * L.persist_stride);
       int* dst = reinterpret_cast<int*>(s_pers + (size_t)k * L.persist_stride);
       for (int i = t; i < L.persist_stride / 4; i += 512) dst[i] = src[i];
-      if (t == 0) s_ctl[8 + k] = reinterpret_cast<const int*>(st.resume + (size_t)U * L.persist_stride)[u];
+      if (t == 0) s_ctl[8 + k] = reinterpret_cast<const int*>(a.resume + (size_t)U * L.persist_stride)[u];
     }
     __syncthreads();
     fpos_w = N_w > 0 ? step0 % N_w : 0;
@@ -955,35 +1127,22 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   }
 
   f32x4 wg[3][PER];
-  const int ft1 = rank / SH1, tpar1 = rank % SH1;
-  const int ft2 = rank / SH2, tpar2 = rank % SH2;
 #pragma unroll
   for (int kb = 0; kb < PER; ++kb) {
 #pragma unroll
     for (int g = 0; g < 3; ++g)
-      wg[g][kb] = reinterpret_cast<const f32x4*>(m.whh[0])[((size_t)(g * NFT1 + ft1) * NKB + w * PER + kb) * 64 + lane];
-    s_w1[(w * PER + kb) * 64 + lane] = reinterpret_cast<const f32x4*>(m.w1)[((size_t)ft1 * NKB + w * PER + kb) * 64 + lane];
-    s_w2[(w * PER + kb) * 64 + lane] = reinterpret_cast<const f32x4*>(m.w2)[((size_t)ft2 * NKB + w * PER + kb) * 64 + lane];
+      wg[g][kb] = reinterpret_cast<const f32x4*>(a.whh)[((size_t)(g * NFT1 + ft1) * NKB + w * PER + kb) * 64 + lane];
+    s_w1[(w * PER + kb) * 64 + lane] = reinterpret_cast<const f32x4*>(a.w1)[((size_t)ft1 * NKB + w * PER + kb) * 64 + lane];
+    s_w2[(w * PER + kb) * 64 + lane] = reinterpret_cast<const f32x4*>(a.w2)[((size_t)ft2 * NKB + w * PER + kb) * 64 + lane];
   }
-  const __amdgpu_buffer_rsrc_t rs_hid =
-      __builtin_amdgcn_make_buffer_rsrc((void*)st.pool_hid, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_a1 =
-      __builtin_amdgcn_make_buffer_rsrc((void*)st.a1, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_hst =
-      __builtin_amdgcn_make_buffer_rsrc((void*)st.gi_up, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_mean =
-      __builtin_amdgcn_make_buffer_rsrc((void*)st.pool_mean, (short)0, 0x7fffffff, 0x00020000);
-  // per-producer phase words of this cluster (one 128-byte line of the control block)
-  uint32_t* const flags_c = st.rx_flags + cluster * 32;
-  const __amdgpu_buffer_rsrc_t rs_flags =
-      __builtin_amdgcn_make_buffer_rsrc((void*)flags_c, (short)0, 128, 0x00020000);
   // UIS_FLAG_TEST_STALL: one workgroup publishes phases below 8 only (it goes silent after two steps)
-  const uint32_t live_mask = ((st.flags & 0x4000u) != 0u && cluster == 0 && rank == 5) ? 7u : 0xffffffffu;
-  const int tile0 = (cluster * st.rx_stride) >> 4;
-  const uint32_t h1_off = (uint32_t)((size_t)U * S * HP * 4);
-  // this cluster's rows of partial sums
-  const __amdgpu_buffer_rsrc_t rs_part = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(st.mse_part + (size_t)cluster * st.rx_stride * PSTR), (short)0, 0x7fffffff, 0x00020000);
+  const uint32_t live_mask = ((a.flags & 0x4000u) != 0u && cluster == 0 && rank == 5) ? 7u : 0xffffffffu;
+  const bool agent_flags = (a.flags & UIS_FLAG_AGENT_FLAGS) != 0u;
+  // this cluster's row tiles of the h' staging buffer and of a1, its rows of partial sums; the slot that holds h1
+  const uint32_t tile0_bytes = (uint32_t)(((cluster * a.rx_stride) >> 4) * NFT1) * 1024u;
+  const uint32_t hst_off = a.o_hst + tile0_bytes, a1_off = a.o_a1 + tile0_bytes;
+  const uint32_t part_off = a.o_part + (uint32_t)(cluster * a.rx_stride * PSTR) * 4u;
+  const uint32_t h1_rel = a.o_h1 - a.o_hid;
   __syncthreads();
 #if defined(UIS_RESIDENT_TIMING)
   unsigned long long rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -992,7 +1151,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   unsigned long long ft_acc[4] = {0, 0, 0, 0}, rt_prev2 = rt_prev;
 #endif
 
-  RsPrep prep = rs_prep<false>(m, st, L, dm, step0, pers_w, scr_w, s_lblk, s_lden, []() {});  // (later steps: prepared inside the previous step's last hand-off)
+  RsPrep prep = rs_prep<false>(av, L, dm, step0, pers_w, scr_w, s_lblk, s_lden, []() {});  // (later steps: prepared inside the previous step's last hand-off)
   for (int s = step0; s < s_end; ++s) {
     // ---- select, replicated: wave w decides utterance slot w; every workgroup gets the same rows
     RsWin win;
@@ -1001,10 +1160,10 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     const long frame_w = (long)(off0_w + fpos_w);
     if (act_w) {
 #if defined(UIS_RESIDENT_TIMING)
-      win = rs_front<DP>(m, st, L, dm, u_w, s, frame_w, pers_w, scr_w, rs_part, (uint32_t)(prev_base * PSTR * 4), prep,
+      win = rs_front<DP>(av, L, dm, u_w, s, frame_w, pers_w, scr_w, part_off + (uint32_t)__builtin_amdgcn_readfirstlane(prev_base * PSTR * 4), prep,
                          (blockIdx.x == 0 && w == 0) ? ph_acc : nullptr);
 #else
-      win = rs_front<DP>(m, st, L, dm, u_w, s, frame_w, pers_w, scr_w, rs_part, (uint32_t)(prev_base * PSTR * 4), prep, nullptr);
+      win = rs_front<DP>(av, L, dm, u_w, s, frame_w, pers_w, scr_w, part_off + (uint32_t)__builtin_amdgcn_readfirstlane(prev_base * PSTR * 4), prep, nullptr);
 #endif
     }
     if (lane == 0) {
@@ -1036,6 +1195,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
 
     // ---- GRU: h' = gru(gi0[frame], W_hh h_src + b_hh) -> dst slot
     {
+      const __amdgpu_buffer_rsrc_t blk = av.blk(), rs_gi0 = av.gi0();
       const int my1 = nrt > tpar1 ? (nrt - tpar1 + SH1 - 1) / SH1 : 0;
       for (int i0 = 0; i0 < my1; i0 += RC) {
         uint32_t boff[RC];
@@ -1043,7 +1203,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
         for (int r = 0; r < RC; ++r) {
           const int tile = tpar1 + SH1 * (i0 + r < my1 ? i0 + r : i0);
           const RowHead rh = lds_row_head(s_head, 16 * tile + (t & 15));
-          boff[r] = rh.src >= 0 ? (uint32_t)((((size_t)rh.utt * S + rh.src) * HP) * 4) : h1_off;
+          boff[r] = rh.src >= 0 ? (uint32_t)(((rh.utt * S + rh.src) * HP) * 4) : h1_rel;
         }
         const int j = ft1 * 16 + (t & 15);
         RowHead re[EPT];
@@ -1059,15 +1219,15 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
             // EVERYTHING in flight -- these gi0 rows, first touched here, come from HBM -- before
             // the stage's first MFMA; a thread without a row fetches row 0's operands instead)
             re[k] = lds_row_head(s_head, ework[k] ? lrow : 0);
-            const long frame = s_wframe[((unsigned)re[k].nprev >> 16) & (unsigned)(SLOTS - 1)];
+            const uint32_t frame = (uint32_t)s_wframe[((unsigned)re[k].nprev >> 16) & (unsigned)(SLOTS - 1)];
             re[k].nprev &= 0xffff;
-            const float* gi = st.gi0 + (size_t)frame * (3 * HP);  // (m.G)
-            gir[k] = gi[j]; giz[k] = gi[HP + j]; gin[k] = gi[2 * HP + j];
-            hprev[k] = rs_buf_load_f32_sc1(rs_hid, (uint32_t)(((re[k].src >= 0 ? re[k].utt * S + re[k].src : U * S) * HP + j) * 4));
+            const uint32_t gi = frame * (uint32_t)(3 * HP * 4) + (uint32_t)(j * 4);  // (m.G; below 4 GB: the planner's frames32)
+            gir[k] = rs_buf_load_f32(rs_gi0, gi); giz[k] = rs_buf_load_f32(rs_gi0, gi + HP * 4); gin[k] = rs_buf_load_f32(rs_gi0, gi + 2 * HP * 4);
+            hprev[k] = rs_buf_load_f32_sc1(blk, (uint32_t)(((re[k].src >= 0 ? re[k].utt * S + re[k].src : U * S) * HP + j) * 4), a.o_hid);
           }
         };
         FSTAMP(0);
-        rs_tile<3, PER, RC, 64>(wg, m.bhh[0] + ft1 * 16, HP, rs_hid, boff, my1 - i0 < RC ? my1 - i0 : RC, spart, epilogue_operands);
+        rs_tile<3, PER, RC, 64>(wg, s_bias, 16, blk, a.o_hid, boff, my1 - i0 < RC ? my1 - i0 : RC, spart, epilogue_operands);
         __syncthreads();
         FSTAMP(1);
 #pragma unroll
@@ -1078,8 +1238,8 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
           const float ghz = splitk_combine<RC, 3>(spart, r, 1, e);
           const float ghn = splitk_combine<RC, 3>(spart, r, 2, e);
           const float out = j < Hreal ? uis_gru_unit(gir[k], giz[k], gin[k], ghr, ghz, ghn, hprev[k]) : 0.0f;
-          rs_buf_store_f32(rs_hid, (uint32_t)(((re[k].utt * S + re[k].dst) * HP + j) * 4), out);
-          rs_buf_store_f32(rs_hst, (uint32_t)(((tile0 + tpar1 + SH1 * (i0 + r)) * NFT1 + ft1) * 256 + e) * 4u, out);
+          rs_buf_store_f32(blk, (uint32_t)(((re[k].utt * S + re[k].dst) * HP + j) * 4), out, a.o_hid);
+          rs_buf_store_f32(blk, (uint32_t)(((tpar1 + SH1 * (i0 + r)) * NFT1 + ft1) * 256 + e) * 4u, out, hst_off);
         }
         FSTAMP(2);
         __syncthreads();
@@ -1091,44 +1251,47 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // for); the first look at the producers' words is requested from inside it, so that its round
     // trip is over when the wave gets there; then wait
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 1u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
+      const __amdgpu_buffer_rsrc_t blk = av.blk();
+      rs_blk_publish(blk, fl_off, rank, (3u * (uint32_t)s + 1u) & live_mask, agent_flags);
       u32x4 pk = u32x4{0u, 0u, 0u, 0u};
-      auto peek = [&]() { pk = rs_flag_peek4(rs_flags, (uint32_t)(16 * w)); };
+      auto peek = [&]() { pk = rs_blk_peek4(blk, fl_off, (uint32_t)(16 * w)); };
       if (act_w) {
         // (the owner of utterance slot r is rank r: it alone writes that utterance's lasting outputs)
-        rs_back(m, st, L, dm, u_w, s, off0_w, pers_w, rank == w, win, peek);
+        // (the utterance's first frame as a scalar: the back-pointers' base is then scalar arithmetic, not a lane value kept across the loop)
+        rs_back(av, L, dm, u_w, s, __builtin_amdgcn_readfirstlane(off0_w), pers_w, rank == w, win, peek);
         fpos_w = fpos_w + 1 == N_w ? 0 : fpos_w + 1;
       } else {
         peek();
       }
       if (nrt > tpar1 && !rs_flag_ready4(pk, 3u * (uint32_t)s + 1u) &&
-          rs_flag_wait(st, rs_flags, (uint32_t)(16 * w), 3u * (uint32_t)s + 1u))
+          rs_blk_wait(blk, fl_off, ab_off, (uint32_t)(16 * w), 3u * (uint32_t)s + 1u))
         s_ctl[0] = 1;
     }
-    if (s == step0 && t == 0 && rank == 1 && (st.flags & 0x100u)) xcc ^= 1u;  // UIS_FLAG_TEST_MISPLACED: pretend
-    if (s == step0 && t == 0 && __hip_atomic_load(st.cl_xcc + cluster, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != xcc)
-      __hip_atomic_store(st.cl_abort, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // not on one XCD
+    if (s == step0 && t == 0 && rank == 1 && (a.flags & 0x100u)) xcc ^= 1u;  // UIS_FLAG_TEST_MISPLACED: pretend
+    if (s == step0 && t == 0 && rs_blk_load_agent(av.blk(), 0u, xcc_off) != xcc)
+      rs_blk_store_agent(av.blk(), 0u, ab_off, 2u);  // not on one XCD
     RSTAMP(3);
 
     // ---- linear_mean1 + relu -> a1
     {
+      const __amdgpu_buffer_rsrc_t blk = av.blk();
       const int my1h = nrt > tpar1 ? (nrt - tpar1 + SH1 - 1) / SH1 : 0;
       for (int i0 = 0; i0 < my1h; i0 += RC) {
         uint32_t boff[RC];
 #pragma unroll
         for (int r = 0; r < RC; ++r) {
           const int tile = tpar1 + SH1 * (i0 + r < my1h ? i0 + r : i0);
-          boff[r] = (uint32_t)((((tile0 + tile) * NFT1) * 256 + (t & 15) * 16) * 4);
+          boff[r] = hst_off + (uint32_t)(((tile * NFT1) * 256 + (t & 15) * 16) * 4);
         }
         f32x4 w1r[1][PER];
 #pragma unroll
         for (int kb = 0; kb < PER; ++kb) w1r[0][kb] = s_w1[(w * PER + kb) * 64 + lane];
-        resident_tile<1, PER, RC, 1024>(w1r, m.b1 + ft1 * 16, 0, rs_hst, boff, my1h - i0 < RC ? my1h - i0 : RC, spart, []() {});
+        resident_tile<1, PER, RC, 1024>(w1r, s_bias + 48, 0, blk, boff, my1h - i0 < RC ? my1h - i0 : RC, spart, []() {});
         for (int e = t; e < RC * 256; e += 512) {
           const int r = e >> 8, tile = tpar1 + SH1 * (i0 + r), lrow = 16 * tile + ((e & 255) >> 4);
           if (i0 + r < my1h && lrow < nrows) {
             const float v = splitk_combine<RC, 1>(spart, r, 0, e & 255);
-            rs_buf_store_f32(rs_a1, (uint32_t)(((tile0 + tile) * NFT1 + ft1) * 256 + (e & 255)) * 4u, v > 0.0f ? v : 0.0f);
+            rs_buf_store_f32(blk, (uint32_t)((tile * NFT1 + ft1) * 256 + (e & 255)) * 4u, v > 0.0f ? v : 0.0f, a1_off);
           }
         }
         __syncthreads();
@@ -1138,28 +1301,30 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // publish; then the next step's MSEs of the clusters this step did not rewrite (every workgroup
     // its share of every utterance's; visible to all behind the step's last hand-off); then wait
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 2u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
+      const __amdgpu_buffer_rsrc_t blk = av.blk();
+      rs_blk_publish(blk, fl_off, rank, (3u * (uint32_t)s + 2u) & live_mask, agent_flags);
       u32x4 pk = u32x4{0u, 0u, 0u, 0u};
-      auto peek = [&]() { pk = rs_flag_peek4(rs_flags, (uint32_t)(16 * w)); };
+      auto peek = [&]() { pk = rs_blk_peek4(blk, fl_off, (uint32_t)(16 * w)); };
       if (has_u && s + 1 < T_w)
-        rs_early_mse<DP>(m, st, L, dm, u_w, s, (long)(off0_w + fpos_w), pers_w, swgt, rank, w, peek);
+        rs_early_mse<DP>(av, L, dm, u_w, s, (long)(off0_w + fpos_w), pers_w, swgt, rank, w, peek);
       else
         peek();
       if (nrt > tpar2 && !rs_flag_ready4(pk, 3u * (uint32_t)s + 2u) &&
-          rs_flag_wait(st, rs_flags, (uint32_t)(16 * w), 3u * (uint32_t)s + 2u))
+          rs_blk_wait(blk, fl_off, ab_off, (uint32_t)(16 * w), 3u * (uint32_t)s + 2u))
         s_ctl[0] = 1;
     }
     RSTAMP(5);
 
     // ---- linear_mean2 + running mean -> dst slot
     {
+      const __amdgpu_buffer_rsrc_t blk = av.blk(), rs_x = av.x();
       const int my_tiles = nrt > tpar2 ? (nrt - tpar2 + SH2 - 1) / SH2 : 0;
       for (int i0 = 0; i0 < my_tiles; i0 += RC) {
         uint32_t boff[RC];
 #pragma unroll
         for (int r = 0; r < RC; ++r) {
           const int tile = tpar2 + SH2 * (i0 + r < my_tiles ? i0 + r : i0);
-          boff[r] = (uint32_t)((((tile0 + tile) * NFT1) * 256 + (t & 15) * 16) * 4);
+          boff[r] = a1_off + (uint32_t)(((tile * NFT1) * 256 + (t & 15) * 16) * 4);
         }
         const int f = ft2 * 16 + (t & 15);
         RowHead re[EPT];
@@ -1172,15 +1337,15 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
             const int lrow = 16 * (tpar2 + SH2 * (i0 + r)) + ((t & 255) >> 4);
             ework[k] = r < RC && i0 + r < my_tiles && lrow < nrows;
             re[k] = lds_row_head(s_head, ework[k] ? lrow : 0);  // (no branch around the load: see the GRU stage)
-            xn[k] = st.x[(size_t)s_wnext[((unsigned)re[k].nprev >> 16) & (unsigned)(SLOTS - 1)] * DP + f];  // the NEXT frame of the row's utterance
+            xn[k] = rs_buf_load_f32(rs_x, (uint32_t)s_wnext[((unsigned)re[k].nprev >> 16) & (unsigned)(SLOTS - 1)] * (uint32_t)(DP * 4) + (uint32_t)(f * 4));  // the NEXT frame of the row's utterance
             re[k].nprev &= 0xffff;
-            old[k] = rs_buf_load_f32_sc1(rs_mean, (uint32_t)(((re[k].utt * S + (re[k].src >= 0 ? re[k].src : 0)) * DP + f) * 4));
+            old[k] = rs_buf_load_f32_sc1(blk, (uint32_t)(((re[k].utt * S + (re[k].src >= 0 ? re[k].src : 0)) * DP + f) * 4), a.o_mean);
           }
         };
         f32x4 w2r[1][PER];
 #pragma unroll
         for (int kb = 0; kb < PER; ++kb) w2r[0][kb] = s_w2[(w * PER + kb) * 64 + lane];
-        resident_tile<1, PER, RC, 1024>(w2r, m.b2 + ft2 * 16, 0, rs_a1, boff, my_tiles - i0 < RC ? my_tiles - i0 : RC, spart,
+        resident_tile<1, PER, RC, 1024>(w2r, s_bias + 64, 0, blk, boff, my_tiles - i0 < RC ? my_tiles - i0 : RC, spart,
                                         epilogue_operands);
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
@@ -1189,7 +1354,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
           float v = splitk_combine<RC, 1>(spart, r, 0, t & 255);
           if (re[k].src >= 0) v = uis_mean_update(old[k], v, re[k].nprev);
           if (f >= dm.D) v = 0.0f;
-          rs_buf_store_f32(rs_mean, (uint32_t)(((re[k].utt * S + re[k].dst) * DP + f) * 4), v);
+          rs_buf_store_f32(blk, (uint32_t)(((re[k].utt * S + re[k].dst) * DP + f) * 4), v, a.o_mean);
           // this tile's share of the next step's weighted MSE against the mean just written
           // (uis_numerics.h: the row's 16 features of the tile sit in 16 adjacent lanes -- quad sums
           // left to right, then (q0 + q1) + (q2 + q3)); the select adds the tiles' sums
@@ -1198,8 +1363,8 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
           q = q + dpp_perm<0x141>(q);  // row_half_mirror: the neighbouring quad's sum
           q = q + dpp_perm<0x140>(q);  // row_mirror: the other half's
           const int lrow = 16 * (tpar2 + SH2 * (i0 + r)) + ((t & 255) >> 4);
-          if ((t & 15) == 0) rs_buf_store_f32(rs_part, (uint32_t)((lrow * PSTR + ft2) * 4), q);
-          if (f == 0) { const float d0 = v - xn[k]; rs_buf_store_f32(rs_part, (uint32_t)((lrow * PSTR + rs_part_first(DP)) * 4), d0 * d0); }
+          if ((t & 15) == 0) rs_buf_store_f32(blk, (uint32_t)((lrow * PSTR + ft2) * 4), q, part_off);
+          if (f == 0) { const float d0 = v - xn[k]; rs_buf_store_f32(blk, (uint32_t)((lrow * PSTR + rs_part_first(DP)) * 4), d0 * d0, part_off); }
         }
         __syncthreads();
       }
@@ -1208,22 +1373,23 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
     // publish; then the next step's candidate grid (this wave's own tables: nobody else's data); then
     // wait -- every wave, every step, for all 32 producers (rs_flag_wait_all)
     {
-      rs_flag_publish(flags_c, rank, (3u * (uint32_t)s + 3u) & live_mask, (st.flags & UIS_FLAG_AGENT_FLAGS) != 0u);
+      const __amdgpu_buffer_rsrc_t blk = av.blk();
+      rs_blk_publish(blk, fl_off, rank, (3u * (uint32_t)s + 3u) & live_mask, agent_flags);
       uint32_t pk = 0u;
-      auto peek = [&]() { pk = rs_flag_peek_all(flags_c); };
+      auto peek = [&]() { pk = rs_blk_peek_all(blk, fl_off); };
       if (has_u && s + 1 < T_w)
-        prep = rs_prep<false>(m, st, L, dm, s + 1, pers_w, scr_w, s_lblk, s_lden, peek);
+        prep = rs_prep<false>(av, L, dm, s + 1, pers_w, scr_w, s_lblk, s_lden, peek);
       else
         peek();
-      if (!rs_flag_ready_all(pk, 3u * (uint32_t)s + 3u) && rs_flag_wait_all(st, flags_c, 3u * (uint32_t)s + 3u)) s_ctl[0] = 1;
+      if (!rs_flag_ready_all(pk, 3u * (uint32_t)s + 3u) && rs_blk_wait_all(blk, fl_off, ab_off, 3u * (uint32_t)s + 3u)) s_ctl[0] = 1;
     }
     RSTAMP(7);
   }
 #if defined(UIS_RESIDENT_TIMING)
   if (t == 0 && (blockIdx.x == 0 || blockIdx.x == 31 * ncl))
-    for (int k = 0; k < 8; ++k) st.counters[(blockIdx.x == 0 ? 48 : 64) + k] = rt_acc[k];
-  if (t == 0 && blockIdx.x == 0) for (int k = 0; k < 8; ++k) st.counters[80 + k] = ph_acc[k];
-  if (t == 0 && blockIdx.x == 31 * ncl) for (int k = 0; k < 4; ++k) st.counters[72 + k] = ft_acc[k];
+    for (int k = 0; k < 8; ++k) a.counters[(blockIdx.x == 0 ? 48 : 64) + k] = rt_acc[k];
+  if (t == 0 && blockIdx.x == 0) for (int k = 0; k < 8; ++k) a.counters[80 + k] = ph_acc[k];
+  if (t == 0 && blockIdx.x == 31 * ncl) for (int k = 0; k < 4; ++k) a.counters[72 + k] = ft_acc[k];
 #endif
   if (s_end < nsteps) {  // more steps to come in another launch: rank 0's copy of the cluster's tables goes to st.resume
     __syncthreads();
@@ -1233,9 +1399,9 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
         const int u = cluster + ncl * k;
         if (u >= U) break;
         const int* src = reinterpret_cast<const int*>(s_pers + (size_t)k * L.persist_stride);
-        int* dst = reinterpret_cast<int*>(st.resume + (size_t)u * L.persist_stride);
+        int* dst = reinterpret_cast<int*>(a.resume + (size_t)u * L.persist_stride);
         for (int i = t; i < L.persist_stride / 4; i += 512) dst[i] = src[i];
-        if (t == 0) reinterpret_cast<int*>(st.resume + (size_t)U * L.persist_stride)[u] = s_ctl[8 + k];
+        if (t == 0) reinterpret_cast<int*>(a.resume + (size_t)U * L.persist_stride)[u] = s_ctl[8 + k];
       }
     }
     return;
@@ -1243,9 +1409,9 @@ __global__ __launch_bounds__(512) void k_decode_rs(DevModel m, DecodeState st) {
   if (rank < SLOTS && cluster + ncl * rank < U && t == 0) {  // this utterance's statistics, by its owner rank
     const unsigned long long* acc =
         reinterpret_cast<const unsigned long long*>(s_pers + (size_t)rank * L.persist_stride + L.off_stats);
-    atomicAdd(&st.counters[0], acc[0]);
-    atomicAdd(&st.counters[1], acc[1]);
-    atomicAdd(&st.counters[2], acc[2]);
-    atomicMax(&st.counters[3], acc[3]);
+    atomicAdd(&a.counters[0], acc[0]);
+    atomicAdd(&a.counters[1], acc[1]);
+    atomicAdd(&a.counters[2], acc[2]);
+    atomicMax(&a.counters[3], acc[3]);
   }
 }
