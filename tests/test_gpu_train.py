@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 import test_train_host as host
+from train_ref import dropout_scales
+from train_ref import torch_gradients as _torch_gradients
 from tools import train_behaviour
 import uisrnn_amd
 from uisrnn_amd import _capi
@@ -156,73 +158,6 @@ def test_four_clusters_depth2_with_dropout(tmp_path):
   training_args.train_iteration = 2
   loaded.train(train_seqs[:1], [['A', 'B'] * 50], training_args)
   assert loaded.transition_bias != bias
-
-
-M64 = (1 << 64) - 1
-
-
-def _mix64(x):
-  """uis_train.hip's mix64 on a uint64 array."""
-  with np.errstate(over='ignore'):
-    x = x + np.uint64(0x9e3779b97f4a7c15)
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    return x ^ (x >> np.uint64(31))
-
-
-def dropout_scales(key, iteration, layer, n, p):
-  """The trainer's dropout multipliers for the n outputs of layer-1 feeding `layer` (include/uisrnn_hip.h)."""
-  salt = _mix64(np.array([(iteration * 0x100000001b3 + layer) & M64], dtype=np.uint64))[0]
-  h = _mix64(np.uint64(key) ^ salt ^ _mix64(np.arange(n, dtype=np.uint64)))
-  u = (h >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-  return np.where(u >= np.float32(p), np.float32(1.0) / (np.float32(1.0) - np.float32(p)), np.float32(0.0))
-
-
-def _torch_gradients(params, padded, lengths, masks, reg=1e-5, alpha=1.0, beta=1.0):
-  """Iteration-0 gradients of the reference's loss in float64 torch (CPU), the given dropout masks
-  between layers, no clipping; flat order of the trainer."""
-  import torch  # pylint: disable=import-outside-toplevel
-  from torch import nn  # pylint: disable=import-outside-toplevel
-  t64 = lambda a: torch.tensor(np.asarray(a, np.float64))  # noqa: E731
-  depth, hid, dim = params['rnn_depth'], params['rnn_hidden_size'], params['observation_dim']
-  grus = []
-  for l in range(depth):
-    gru = nn.GRU(dim if l == 0 else hid, hid, 1).double()
-    with torch.no_grad():
-      gru.weight_ih_l0.copy_(t64(params['gru_weight_ih'][l]))
-      gru.weight_hh_l0.copy_(t64(params['gru_weight_hh'][l]))
-      gru.bias_ih_l0.copy_(t64(params['gru_bias_ih'][l]))
-      gru.bias_hh_l0.copy_(t64(params['gru_bias_hh'][l]))
-    grus.append(gru)
-  lin1, lin2 = nn.Linear(hid, hid).double(), nn.Linear(hid, dim).double()
-  with torch.no_grad():
-    lin1.weight.copy_(t64(params['linear_mean1_weight']))
-    lin1.bias.copy_(t64(params['linear_mean1_bias']))
-    lin2.weight.copy_(t64(params['linear_mean2_weight']))
-    lin2.bias.copy_(t64(params['linear_mean2_bias']))
-  h0 = nn.Parameter(t64(params['rnn_init_hidden']).view(depth, 1, hid))
-  sigma2 = nn.Parameter(t64(params['sigma2']))
-  x = t64(padded)
-  seq = x
-  for l, gru in enumerate(grus):
-    if l > 0:
-      seq = seq * t64(masks[l]).view(seq.shape)
-    packed = nn.utils.rnn.pack_padded_sequence(seq, lengths)
-    out, _ = gru(packed, h0[l:l + 1].repeat(1, x.shape[1], 1))
-    seq, _ = nn.utils.rnn.pad_packed_sequence(out, total_length=x.shape[0])
-  mean = lin2(torch.relu(lin1(seq)))
-  mean = torch.cumsum(mean, dim=0) / torch.arange(1, mean.shape[0] + 1).double().view(-1, 1, 1)
-  truth = x[1:]
-  sq = (((truth != 0).double() * mean[:-1] - truth) ** 2).view(-1, dim)
-  n_d = (sq != 0).double().sum(dim=0)
-  loss1 = (sq / (2 * sigma2)).sum() / (sq[:, 0] != 0).double().sum()
-  loss2 = ((2 * alpha + n_d + 2) / (2 * n_d) * torch.log(sigma2)).sum() + (beta / (sigma2 * n_d)).sum()
-  rnn_params = [p for g in grus for p in g.parameters()] + list(lin1.parameters()) + list(lin2.parameters())
-  loss3 = reg * sum(torch.norm(p) for p in rnn_params)
-  (loss1 + loss2 + loss3).backward()
-  grads = [p.grad.numpy().ravel() for p in rnn_params] + [h0.grad.numpy().ravel(), sigma2.grad.numpy().ravel()]
-  losses = [loss1 + loss2 + loss3, loss1, loss2, loss3]
-  return np.concatenate(grads), [float(v.detach()) for v in losses]
 
 
 @pytest.mark.parametrize('p', [0.0, 0.4])
