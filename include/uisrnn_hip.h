@@ -409,6 +409,39 @@ int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offs
                          const int32_t* labels, float* scores_out, float* frame_losses_out);
 
 /*
+ * N-best readout: the labels of EVERY hypothesis of the final beam, not only of rank 0.  A decode
+ * leaves the back-pointers of all beam_size ranks and the final beam's scores on the device; these
+ * calls only read them (no decode kernel is involved).
+ *   n_best     : hypotheses wanted per utterance, in [1, beam_size of that decode / session]
+ *   labels_out : host int32.  Utterance u with N_u frames owns
+ *                labels_out[n_best * off[u] .. n_best * off[u+1]), off = the last decode's offsets
+ *                (a session: prefix sums of the frames received); hypothesis k is the row at
+ *                + k * N_u, trace[-N_u:] in the form of uis_decode's labels_out.  Row 0 equals what
+ *                the decode / uis_stream_labels returned; rows k >= counts_out[u] hold -1
+ *   capacity   : int32 slots at labels_out (n_best * off[n_utt] needed)
+ *   scores_out : host float32 [n_utt * n_best] or NULL: the final beam's scores, ascending, +inf padded
+ *   counts_out : host int32 [n_utt] or NULL: min(n_best, live hypotheses); 0 for an empty utterance, an
+ *                emptied beam and an utterance flagged in the overflow word
+ * uis_last_decode_nbest: after a uis_decode / uis_decode_f64 / uis_decode_device that returned UIS_OK or
+ * UIS_ERR_CLUSTER_CAP, whichever kernels decoded; any number of times, also after uis_score_labels and
+ * uis_eval_*; it leaves uis_last_decode_info / _shape and uis_eval_last_decode alone.
+ * UIS_ERR_INVALID_ARG: no such decode, a session is open, n_best or capacity out of range -- and after a
+ * session that called uis_stream_labels: that call makes the session what uis_last_decode_info / _shape
+ * describe, so the earlier decode's hypotheses are given up with it (the three always answer for one decode).
+ * uis_stream_nbest: in an open session, for everything received so far.
+ *   stable_out : host int64 [n_utt] or NULL: the number of leading frames on which all live hypotheses
+ *                share one ancestor.  Every later beam descends from the current one, so
+ *                uis_stream_labels' first stable_out[u] labels never change again (a guarantee, not a
+ *                latency promise: a wide beam can keep an early alternative alive for long)
+ * In a UIS_FLAG_PERSISTENT session the resident launch leaves the device for this call and the next
+ * push starts a new one.  Returns UIS_ERR_CLUSTER_CAP (everything still written) if a cap was hit.
+ */
+int32_t uis_last_decode_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int64_t capacity,
+                              float* scores_out, int32_t* counts_out);
+int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int64_t capacity,
+                         float* scores_out, int32_t* counts_out, int64_t* stable_out);
+
+/*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the
  * H2D copy of the frame stream is asynchronous and overlaps the input projection of the chunks
  * already on the device.  Pageable memory works too (staged by the runtime).

@@ -327,6 +327,10 @@ def load_library(path=None):
   lib.uis_stream_labels.argtypes = [ctypes.c_void_p, i32p, _fp, i32p]
   lib.uis_stream_end.restype = i32
   lib.uis_stream_end.argtypes = [ctypes.c_void_p]
+  lib.uis_last_decode_nbest.restype = i32
+  lib.uis_last_decode_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p]
+  lib.uis_stream_nbest.restype = i32
+  lib.uis_stream_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p, i64p]
   lib.uis_eval_accuracy.restype = i32
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
@@ -365,7 +369,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -393,6 +397,7 @@ class Decoder:
           rc, last_error(self._lib)))
     self._handle = handle
     self.device = int(device)
+    self._last_offsets = None  # offsets of the last decode through this object: last_nbest() sizes its buffers from them
 
   def close(self):
     if getattr(self, '_handle', None):
@@ -466,6 +471,7 @@ class Decoder:
         ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
         scores.ctypes.data_as(_fp), ctypes.byref(stats))
     rc = self._check(rc, 'uis_decode')
+    self._last_offsets = offsets.copy()
     out = {'labels': labels, 'scores': scores, 'stats': stats.as_dict(),
            'status': rc}
     overflow = np.zeros(n_utt, dtype=np.int32)
@@ -504,6 +510,7 @@ class Decoder:
         ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
         scores.ctypes.data_as(_fp), ctypes.byref(stats))
     rc = self._check(rc, 'uis_decode_f64')
+    self._last_offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     out = {'labels': labels, 'scores': scores, 'stats': stats.as_dict(), 'status': rc}
     overflow = np.zeros(n_utt, dtype=np.int32)
     beam_scores = (np.empty((n_utt, int(beam_size)), dtype=np.float32)
@@ -652,6 +659,64 @@ class Decoder:
   def stream_end(self):
     self._check(self._lib.uis_stream_end(self._handle), 'uis_stream_end')
 
+  # ---- n-best readout (uis_last_decode_nbest / uis_stream_nbest)
+  @staticmethod
+  def _nbest_split(labels, scores, counts, offsets, n_best):
+    per_utt = []
+    for u in range(offsets.shape[0] - 1):
+      n = int(offsets[u + 1] - offsets[u])
+      per_utt.append(labels[n_best * int(offsets[u]):n_best * int(offsets[u + 1])].reshape(n_best, n).copy())
+    return {'labels': per_utt, 'scores': scores.reshape(offsets.shape[0] - 1, n_best), 'counts': counts}
+
+  def last_nbest(self, n_best):
+    """Every hypothesis of the last decode's final beam (uis_last_decode_nbest).
+
+    Returns a dict: labels -- per utterance an int32 [n_best, N_u] array, row k = hypothesis k in the
+    form of decode()'s labels, rows >= counts[u] filled with -1; scores float32 [U, n_best], ascending,
+    +inf padded; counts int32 [U] = min(n_best, live hypotheses), 0 for an utterance that hit the
+    cluster cap."""
+    offsets = self._last_offsets
+    if offsets is None:
+      offsets = np.zeros(1, dtype=np.int64)  # (no decode yet: the library refuses below)
+    n_best = int(n_best)
+    n_utt = offsets.shape[0] - 1
+    n_lib = ctypes.c_int32(0)
+    self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), None), 'uis_last_decode_shape')
+    if int(n_lib.value) != n_utt:  # (a decode that did not go through this object's wrappers: its layout is not known here)
+      raise HipLibraryError('last_nbest: the library\'s last decode had {} utterances, this object remembers {}'.format(
+          int(n_lib.value), n_utt))
+    total = max(n_best, 0) * int(offsets[-1])
+    labels = np.empty(max(total, 1), dtype=np.int32)
+    scores = np.empty(max(n_utt * max(n_best, 0), 1), dtype=np.float32)
+    counts = np.zeros(max(n_utt, 1), dtype=np.int32)
+    rc = self._lib.uis_last_decode_nbest(
+        self._handle, n_best, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
+        scores.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    self._check(rc, 'uis_last_decode_nbest')
+    return self._nbest_split(labels, scores[:n_utt * n_best], counts[:n_utt], offsets, n_best)
+
+  def stream_nbest(self, n_best):
+    """Every hypothesis of the open session's beam for everything received so far (uis_stream_nbest).
+
+    The dict of last_nbest() plus stable (int64 [U]: leading frames whose labels are final) and status."""
+    n_best = int(n_best)
+    offsets = np.concatenate([[0], np.cumsum(self._stream_have)]).astype(np.int64)
+    n_utt = self._stream_n
+    total = max(n_best, 0) * int(offsets[-1])
+    labels = np.empty(max(total, 1), dtype=np.int32)
+    scores = np.empty(max(n_utt * max(n_best, 0), 1), dtype=np.float32)
+    counts = np.zeros(n_utt, dtype=np.int32)
+    stable = np.zeros(n_utt, dtype=np.int64)
+    rc = self._lib.uis_stream_nbest(
+        self._handle, n_best, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
+        scores.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+        stable.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+    rc = self._check(rc, 'uis_stream_nbest')
+    out = self._nbest_split(labels, scores[:n_utt * n_best], counts, offsets, n_best)
+    out['stable'] = stable
+    out['status'] = rc
+    return out
+
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
                   labels_ptr, scores_ptr, max_clusters=0, flags=0):
     """uis_decode on raw HOST pointers (e.g. pinned buffers from uis_host_alloc or torch)."""
@@ -667,6 +732,7 @@ class Decoder:
         ctypes.cast(ctypes.c_void_p(int(scores_ptr)), _fp) if scores_ptr else None,
         ctypes.byref(stats))
     rc = self._check(rc, 'uis_decode')
+    self._last_offsets = offsets.copy()
     return {'stats': stats.as_dict(), 'status': rc}
 
   # ---- evaluation on the device (uis_eval_*)
@@ -725,6 +791,7 @@ class Decoder:
         ctypes.c_void_p(int(d_scores_ptr) if d_scores_ptr else None),
         ctypes.byref(stats))
     rc = self._check(rc, 'uis_decode_device')
+    self._last_offsets = offsets.copy()
     return {'stats': stats.as_dict(), 'status': rc}
 
 

@@ -217,6 +217,15 @@ struct uis_handle {
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
+  // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
+  // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
+  // offsets, the record format -- and the readout's own buffers
+  struct NbestGroup { DecodeState st; int u0; };
+  bool nb_valid = false, nb_wnd = false;
+  int nb_B = 0;
+  std::vector<NbestGroup> nb_groups;
+  std::vector<int64_t> nb_offsets;
+  DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;
 };
 
 namespace {
@@ -1202,6 +1211,7 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // (whatever refuses this decode below: uis_last_decode_info must not hand out the PREVIOUS decode's arrays)
   h->last_U = 0; h->last_B = 0;
   h->last_overflow.clear(); h->last_beam_scores.clear();
+  h->nb_valid = false;  // (... nor uis_last_decode_nbest its hypotheses)
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
   const DevModel& m = h->m;
   const int B = opts->beam_size, L = opts->look_ahead, tau = opts->test_iteration;
@@ -1229,7 +1239,10 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   h->last_U = n_utt; h->last_B = B;
   h->last_overflow.assign(n_utt, 0);
   h->last_beam_scores.assign((size_t)n_utt * B, INFINITY);
-  if (n_utt == 0) return UIS_OK;
+  if (n_utt == 0) {
+    h->nb_groups.clear(); h->nb_offsets.assign(1, 0); h->nb_B = B; h->nb_wnd = false; h->nb_valid = true;
+    return UIS_OK;
+  }
   if (F > 0 && (!d_frames || !d_labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels_out is null");
   const int64_t maxT = (int64_t)tau * maxN;
   if (maxT > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "test_iteration * N too large");
@@ -1880,6 +1893,11 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
                 std::to_string(n_level) + " utterance(s) had more than " + std::to_string((long long)NC) +
                     " live assignment prefixes inside a look-ahead window (beam_size * clusters ^ (look_ahead - 1)); "
                     "a larger max_clusters cannot help: lower look_ahead or beam_size");
+  // the back-pointers and the final beam of every group stay where they are until the next decode: uis_last_decode_nbest
+  h->nb_groups.clear();
+  for (int g = 0; g < G; ++g) h->nb_groups.push_back(uis_handle::NbestGroup{groups[g].st, groups[g].u0});
+  h->nb_offsets.assign(offsets, offsets + U + 1);
+  h->nb_B = B; h->nb_wnd = wnd; h->nb_valid = true;
   if (n_over)
     return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
                                          std::to_string(Kmax) + " clusters per hypothesis");
@@ -1949,7 +1967,7 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
                     &h->lv_blk, &h->scratch, &h->bp16, &h->bp_base, &h->cluster_ctl, &h->rs_block, &h->arena,
                     &h->ev_a, &h->ev_b, &h->ev_off, &h->ev_out, &h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0,
                     &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean, &h->sc_gi_up, &h->sc_rows, &h->sc_chains,
-                    &h->sc_utt, &h->sc_out};
+                    &h->sc_utt, &h->sc_out, &h->nb_labels, &h->nb_scores, &h->nb_counts, &h->nb_stable, &h->nb_off};
   for (DevBuf* b : bufs) b->release();
   for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
@@ -2073,6 +2091,7 @@ UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                               const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
+  h->nb_valid = false;  // (a decode refused below leaves nothing for uis_last_decode_nbest either)
   const int64_t F = n_utt ? offsets[n_utt] : 0;
   if (F < 0) return fail(UIS_ERR_INVALID_ARG, "offsets must be non-decreasing");
   if (F > 0 && (!frames || !labels_out)) return fail(UIS_ERR_INVALID_ARG, "frames/labels_out is null");
@@ -2104,10 +2123,16 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
       sc_dst = reinterpret_cast<float*>(static_cast<char*>(h->h_out) + (size_t)std::max<int64_t>(F, 1) * 4);
     }
   }
+  // (a copy that fails below fails the decode: then there is nothing for uis_last_decode_nbest either)
+  struct NbestGuard {
+    uis_handle* h; bool ok = false;
+    ~NbestGuard() { if (!ok) h->nb_valid = false; }
+  } nbest_guard{h};
   if (F > 0) HIPCHK(hipMemcpyAsync(lab_dst, h->io_labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
   if (scores_out && n_utt > 0)
     HIPCHK(hipMemcpyAsync(sc_dst, h->io_scores.p, (size_t)n_utt * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  nbest_guard.ok = true;
   if (lab_dst != labels_out) {
     if (F > 0) memcpy(labels_out, lab_dst, (size_t)F * 4);
     if (scores_out && n_utt > 0) memcpy(scores_out, sc_dst, (size_t)n_utt * 4);
@@ -2119,6 +2144,7 @@ UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances
                                   const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
   if (!h || n_utt < 0 || (n_utt > 0 && (!utterances || !n_frames)))
     return fail(UIS_ERR_INVALID_ARG, "null handle/utterances/n_frames or negative n_utt");
+  h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)
   std::vector<int64_t> offsets((size_t)n_utt + 1, 0);
   for (int u = 0; u < n_utt; ++u) {
     if (n_frames[u] < 0 || (n_frames[u] > 0 && !utterances[u])) return fail(UIS_ERR_INVALID_ARG, "negative n_frames or null utterance");
@@ -2733,7 +2759,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
     if (rc == UIS_OK) {
       if (F > 0) memcpy(labels_out, ss.pm_block + ss.pm_o_labels, (size_t)F * 4);
       if (scores_out) memcpy(scores_out, ss.pm_block + ss.pm_o_scores, (size_t)U * 4);
-      h->last_U = U; h->last_B = ss.B;
+      h->last_U = U; h->last_B = ss.B; h->nb_valid = false;
       h->last_overflow.assign(reinterpret_cast<const int32_t*>(ss.pm_block + ss.pm_o_overflow),
                               reinterpret_cast<const int32_t*>(ss.pm_block + ss.pm_o_overflow) + U);
       h->last_beam_scores.assign(reinterpret_cast<const float*>(ss.pm_block + ss.pm_o_bscores),
@@ -2764,6 +2790,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
   if (F > 0) HIPCHK(hipMemcpyAsync(labels_out, ss.labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
   if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, ss.scores.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
   h->last_U = U; h->last_B = ss.B;
+  h->nb_valid = false;  // (the "last decode" of uis_last_decode_info / _shape is this session from here on: the readout follows)
   h->last_overflow.assign(U, 0);
   h->last_beam_scores.assign((size_t)U * ss.B, INFINITY);
   HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
@@ -2882,3 +2909,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ scoring a given labeling
 #include "uis_score.hip"
+
+// ------------------------------------------------------------------ n-best readout
+#include "uis_nbest.hip"

@@ -242,11 +242,14 @@ class UISRNN:
       raise ValueError('test_sequence does not match the dimension specified '
                        'by args.observation_dim.')
 
-  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0):
+  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
     `device`; parallel_predict passes one per worker thread.
+
+    n_best > 0 (predict_nbest): an utterance's result is the pair (labelings, scores) of its final
+    beam instead of the label list, read right after the decode call whose labels are accepted for it.
     """
     decoder = decoder or self._get_decoder(device)
     # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
@@ -275,7 +278,7 @@ class UISRNN:
           level_full, first_err = [], None
           for part in (pending[0::2], pending[1::2]):
             try:
-              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap)
+              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best)
             except LookAheadWindowError as inner:
               # (a half whose look-ahead window overflowed: its indices and results are numbered inside
               # the half -- hand them up in the caller's numbering, and still decode the other half)
@@ -321,7 +324,7 @@ class UISRNN:
           if not members:
             continue
           try:
-            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level)
+            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best)
           except LookAheadWindowError as inner:
             # (indices and results are numbered inside `members`: hand them up in the caller's numbering)
             partial = inner.results
@@ -336,7 +339,7 @@ class UISRNN:
             partial = []
             for u in members:
               try:
-                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level)
+                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best)
                 one_err = inner if len(members) == 1 else None
               except LookAheadWindowError as e1:
                 one, one_err = [None], e1
@@ -361,6 +364,8 @@ class UISRNN:
       if stats is None:
         stats = out['stats']
       still = []
+      # (the hypotheses of THIS decode call, before a retry of the flagged utterances replaces its state)
+      hyps = decoder.last_nbest(n_best) if n_best else None
       for k, u in enumerate(pending):
         if out['overflow'][k]:
           still.append(u)
@@ -374,6 +379,12 @@ class UISRNN:
                                  'index out of range in the reference): non-finite scores in '
                                  'utterance {}'.format(u))
           results[u] = labels.tolist()
+          if hyps is not None and labels.size:
+            live = int(hyps['counts'][k])
+            results[u] = ([row.tolist() for row in hyps['labels'][k][:live]],
+                          [float(x) for x in hyps['scores'][k][:live]])
+          elif hyps is not None:  # no frames: the one empty labeling, as predict answers, at score 0
+            results[u] = ([[]], [0.0])
       pending = still
       if pending:
         # a surviving hypothesis opened more clusters than the device tables
@@ -489,6 +500,37 @@ class UISRNN:
       return self._decode_batch(test_sequences, args)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
+  def predict_nbest(self, test_sequences, args, n_best=None):
+    """predict, returning every hypothesis of the final beam instead of the best one (extension).
+
+    Args:
+      test_sequences, args: as predict.
+      n_best: the most hypotheses wanted per sequence, in [1, args.beam_size] (default: beam_size).
+    Returns:
+      for an array the pair (labelings, scores): at most n_best label lists -- fewer when the final
+      beam holds fewer -- best first, and their scores as floats, ascending; labelings[0] is predict's
+      answer.  For a list, a list of such pairs.
+
+    Raises:
+      what predict raises; ValueError for n_best outside [1, args.beam_size].
+    """
+    if n_best is None:
+      n_best = args.beam_size
+    if isinstance(n_best, bool) or not isinstance(n_best, (int, np.integer)):
+      raise ValueError('n_best must be an integer in [1, args.beam_size].')
+    if not 1 <= int(n_best) <= int(args.beam_size):
+      raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(args.beam_size))
+    if isinstance(test_sequences, np.ndarray):
+      self._check_sequence(test_sequences)
+      return self._decode_batch([test_sequences], args, n_best=int(n_best))[0]
+    if isinstance(test_sequences, list):
+      for test_sequence in test_sequences:
+        self._check_sequence(test_sequence)
+      if not test_sequences:
+        return []
+      return self._decode_batch(test_sequences, args, n_best=int(n_best))
+    raise TypeError('test_sequences should be either a list or numpy array.')
+
   def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
     """The model's negative log-likelihood of given labelings (extension).
 
@@ -570,6 +612,8 @@ class OnlineSession:
       session.push([chunk_a, None])        # [n, D] float arrays; None = nothing new
       session.push([chunk_a2, chunk_b])
       labels = session.labels()            # list of lists of ints, one per utterance
+      hyps = session.nbest(3)              # per utterance (labelings, scores) of the three best hypotheses
+      final = session.stable_frames()      # per utterance: labels()[u][:final[u]] can no longer change
 
   persistent=True (UIS_FLAG_PERSISTENT): the decode kernel stays on the GPU between pushes and is
   fed through a mailbox in pinned host memory -- the lowest push latency (no launch, no copy
@@ -580,6 +624,7 @@ class OnlineSession:
 
   def __init__(self, model, num_utterances, args, max_frames, persistent=False):
     self._model = model
+    self._beam_size = int(args.beam_size)
     self._decoder = _capi.Decoder(model.params, model.device_index)  # own handle: one session per handle
     cap = _initial_cluster_cap(args)
     self.persistent = False
@@ -630,6 +675,42 @@ class OnlineSession:
                          'open the session with a larger args.max_clusters'.format(
                              np.flatnonzero(overflow).tolist()))
     return [x.tolist() for x in per_utt]
+
+  def _nbest(self, n_best):
+    if n_best is None:
+      n_best = self._beam_size
+    if isinstance(n_best, bool) or not isinstance(n_best, (int, np.integer)):
+      raise ValueError('n_best must be an integer in [1, args.beam_size].')
+    if not 1 <= int(n_best) <= self._beam_size:
+      raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(self._beam_size))
+    out = self._decoder.stream_nbest(int(n_best))
+    if out['status'] == _capi.UIS_ERR_CLUSTER_CAP:
+      self.labels()  # (raises, naming the utterances)
+    return out
+
+  def nbest(self, n_best=None):
+    """Every hypothesis of the current beam for everything received: per utterance the pair
+    (labelings, scores) of UISRNN.predict_nbest; labelings[0] is what labels() returns.  An utterance
+    that has received nothing yet has no hypothesis: ([], []).
+
+    Cost: a back-trace of every requested rank and a download of n_best labels per frame received.
+    In a persistent session the resident launch has to leave the device for it and the next push
+    starts a new one (a launch plus the kernel's weight load): read every few pushes, not after each,
+    or the session loses most of what persistent=True buys."""
+    out = self._nbest(n_best)
+    return [([row.tolist() for row in out['labels'][u][:int(out['counts'][u])]],
+             [float(x) for x in out['scores'][u][:int(out['counts'][u])]])
+            for u in range(len(out['labels']))]
+
+  def stable_frames(self):
+    """Per utterance, the number of leading frames whose labels are final: all hypotheses of the
+    beam share them, and every later beam descends from this one.  A guarantee, not a latency
+    promise -- a wide beam can keep an early alternative alive for a long time.
+
+    Cost: that of nbest(1) -- the readout runs and the best hypothesis' labels are downloaded -- and,
+    like nbest, it makes a persistent session's resident launch leave the device.  Not for polling
+    after every push of a persistent session."""
+    return [int(x) for x in self._nbest(1)['stable']]
 
   def close(self):
     if self._open:
