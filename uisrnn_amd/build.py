@@ -17,6 +17,7 @@ SOURCES = [os.path.join(_HERE, 'csrc', 'uis_decoder.hip'),
 DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_kernels.hip'),
     os.path.join(_HERE, 'csrc', 'uis_kernels.h'),
+    os.path.join(_HERE, 'csrc', 'uis_poison.h'),
     os.path.join(_HERE, 'csrc', 'uis_select_rs.hip'),
     os.path.join(_HERE, 'csrc', 'uis_eval.hip'),
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),

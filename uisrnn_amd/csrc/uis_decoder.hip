@@ -29,6 +29,7 @@
 #include <emmintrin.h>
 #endif
 
+#include "uis_poison.h"
 #include "uis_kernels.hip"
 #include "uis_eval.hip"
 #include "uisrnn_hip.h"
@@ -187,6 +188,7 @@ struct uis_handle {
     PersistArgs* d_pm_args = nullptr;
     size_t hdr_stride = 0;
     int64_t pm_launches = 0, pm_commands = 0;
+    UisPoison poison;                 // UIS_POISON_WORKSPACE as uis_stream_begin / the running uis_stream_push read it
   } stream_state;
   // workspace (grow only)
   DevBuf off, utt_step, overflow, xpad, gi0, mse0, logblk, logden, pool_mean, pool_hid, pool_cnt;
@@ -196,6 +198,7 @@ struct uis_handle {
   DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
   DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
+  UisPoison poison;  // UIS_POISON_WORKSPACE as the running uis_decode* call read it at its entry (one getenv per call)
   // uis_decode_f64: the caller's float64 utterances (set for the duration of that call) and the
   // pinned float32 staging buffer they are cast into, chunk by chunk, ahead of each H2D copy
   const double* const* src64 = nullptr;
@@ -702,6 +705,9 @@ struct CastPool {
 //   UIS_NO_SPLIT          one launch (A/B switch, bit-identical)
 //   UIS_NO_ARENA, UIS_ARENA_SHIFT, UIS_NO_CTL_TUNE, UIS_CTL_OFFSET   buffer placement (tools/experiments/bimodal.py)
 //   UIS_AGENT_FLAGS       (read once per process) UIS_FLAG_AGENT_FLAGS on every decode
+//   UIS_POISON_WORKSPACE  a 32-bit hex word: every call fills the working memory it is about to use with it before its first
+//                         write (uis_poison.h; also read, once per call, by the sessions, the readouts, uis_score_labels,
+//                         uis_eval_* and uis_train_step).  A test switch: no output may depend on stale memory
 struct DecodeKnobs {
   double max_state_bytes = 200e9, split_min_bytes = 0.0;
   bool split_min_set = false, split_frames_set = false, no_split = false, no_arena = false, no_ctl_tune = false;
@@ -1459,6 +1465,17 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
         }
       }
     }
+    // UIS_POISON_WORKSPACE: the whole placed arena (or every buffer of the list and k_decode_rs's stretch), on the
+    // handle's stream ahead of ev_begin -- every other stream of this decode waits for that event (uis_poison.h)
+    if (h->poison.on) {
+      if (!knobs.no_arena) {
+        HIPCHK(h->poison.device(h->arena.p, total + knobs.arena_shift, h->stream));
+      } else {
+        if (rs) HIPCHK(h->poison.device(h->rs_block.p, h->rs_block.cap, h->stream));
+        for (auto& w : want)
+          if (!w.first->borrowed) HIPCHK(h->poison.device(w.first->p, w.first->cap, h->stream));
+      }
+    }
   }
 
   // ---- placement of the control words for this decode (uis_handle::CtlTune)
@@ -2085,6 +2102,7 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
 UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
                                      const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out,
                                      uis_stats* stats) {
+  if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
 }
 
@@ -2100,6 +2118,13 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
   if ((rc = h->io_frames.ensure((size_t)std::max<int64_t>(F, 1) * h->m.D * 4))) return rc;
   if ((rc = h->io_labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
   if ((rc = h->io_scores.ensure((size_t)std::max(n_utt, 1) * 4))) return rc;
+  if (!h->src64) h->poison = UisPoison::from_env();  // (uis_decode_f64 has read it)
+  const UisPoison poison = h->poison;
+  if (poison.on) {  // (the frames travel on the copy stream, behind ev_begin: uis_poison.h)
+    HIPCHK(poison.device(h->io_frames.p, h->io_frames.cap, h->stream));
+    HIPCHK(poison.device(h->io_labels.p, h->io_labels.cap, h->stream));
+    HIPCHK(poison.device(h->io_scores.p, h->io_scores.cap, h->stream));
+  }
   h->io_offsets.clear();
   rc = decode_impl(h, h->io_frames.as<float>(), offsets, n_utt, opts, h->io_labels.as<int32_t>(),
                    h->io_scores.as<float>(), stats, frames);
@@ -2118,6 +2143,7 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
       if (hipHostMalloc(&p, need, hipHostMallocDefault) == hipSuccess) { h->h_out = p; h->h_out_cap = need; }
       else (void)hipGetLastError();  // (no pinned memory to be had: straight into the caller's arrays)
     }
+    poison.host(h->h_out, h->h_out_cap);  // (before the copies that land in it are enqueued)
     if (h->h_out) {
       lab_dst = static_cast<int32_t*>(h->h_out);
       sc_dst = reinterpret_cast<float*>(static_cast<char*>(h->h_out) + (size_t)std::max<int64_t>(F, 1) * 4);
@@ -2161,6 +2187,8 @@ UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances
     h->h_cast = static_cast<float*>(p);
     h->h_cast_cap = need;
   }
+  h->poison = UisPoison::from_env();
+  h->poison.host(h->h_cast, h->h_cast_cap);  // (before the cast team is posted)
   h->src64 = utterances;
   const int rc = uis_decode(h, h->h_cast, offsets.data(), n_utt, opts, labels_out, scores_out, stats);
   h->src64 = nullptr;
@@ -2272,6 +2300,7 @@ int stream_alloc(uis_handle* h, T** out, size_t count, bool zero = false) {
   hipError_t e = hipMalloc(&p, bytes);
   if (e != hipSuccess) return fail(UIS_ERR_OOM, "hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
   h->stream_state.allocs.push_back(p);
+  HIPCHK(h->stream_state.poison.device(p, bytes, h->stream));  // (UIS_POISON_WORKSPACE: ahead of the block's defining writes)
   if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, h->stream));
   *out = static_cast<T*>(p);
   return UIS_OK;
@@ -2451,6 +2480,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   if (bytes > 200e9) return fail(UIS_ERR_OOM, "streaming state would need " + std::to_string((long long)(bytes / 1e9)) + " GB");
   HIPCHK(hipSetDevice(h->device));
   ss = uis_handle::Stream{};
+  ss.poison = UisPoison::from_env();
   ss.U = U; ss.B = B; ss.Kmax = Kmax; ss.S = S; ss.cap = max_frames;
   ss.have.assign(U, 0);
   DecodeState& st = ss.st;
@@ -2534,6 +2564,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
     void* blk = nullptr;
     hipError_t e = hipHostMalloc(&blk, o, hipHostMallocMapped | hipHostMallocCoherent);
     if (e != hipSuccess) { stream_free(h); return fail(UIS_ERR_OOM, std::string("hipHostMalloc (mailbox): ") + hipGetErrorString(e)); }
+    ss.poison.host(blk, o);  // (... and then the mailbox's initial state)
     memset(blk, 0, o);
     ss.pm_block = static_cast<unsigned char*>(blk);
     ss.hdr_stride = (((size_t)U * 12) + 127) & ~(size_t)127;
@@ -2546,6 +2577,9 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
       stream_free(h);
       return rc;
     }
+    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
     ss.persist = true;
   }
 #undef SALLOC
@@ -2661,6 +2695,15 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if ((rc = ss.chunk_x.ensure(need))) return rc;
   if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
   if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
+  // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
+  // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
+  ss.poison = UisPoison::from_env();
+  if (ss.poison.on) {
+    ss.poison.host(ss.h_stage, ss.h_stage_cap);
+    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
+  }
   int64_t* h_foff = static_cast<int64_t*>(ss.h_stage);
   int32_t* h_avail = reinterpret_cast<int32_t*>(static_cast<char*>(ss.h_stage) + (size_t)U * 8);
   {
@@ -2680,6 +2723,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   const float* d_x = reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr);
   if (m.D != m.Dp) {
     if ((rc = ss.chunk_pad.ensure((size_t)F * m.Dp * 4))) return rc;
+    HIPCHK(ss.poison.device(ss.chunk_pad.p, ss.chunk_pad.cap, h->stream));
     const long total = (long)F * m.Dp;
     hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_x,
                        ss.chunk_pad.as<float>(), (long)F, m.D, m.Dp);
@@ -2778,6 +2822,11 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
   }
   if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
   if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
+  {
+    const UisPoison poison = UisPoison::from_env();
+    HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
+    HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
+  }
   HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
   // frames received = steps run, from the host's own count: the `avail` table of the last push may
   // live in a chunk buffer this path did not fill (pushes taken by the persistent launch)
@@ -2826,7 +2875,7 @@ UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
 namespace {
 
 int eval_run(uis_handle* h, const int32_t* d_a, const int32_t* d_b, const int64_t* offsets, int32_t n_utt,
-             int64_t* matched_out) {
+             int64_t* matched_out, const UisPoison& poison) {
   if (n_utt == 0) return UIS_OK;
   if (offsets[0] != 0) return fail(UIS_ERR_INVALID_ARG, "offsets[0] must be 0");
   for (int u = 0; u < n_utt; ++u)
@@ -2834,6 +2883,8 @@ int eval_run(uis_handle* h, const int32_t* d_a, const int32_t* d_b, const int64_
   int rc;
   if ((rc = h->ev_off.ensure((size_t)(n_utt + 1) * 8))) return rc;
   if ((rc = h->ev_out.ensure((size_t)n_utt * 12))) return rc;
+  HIPCHK(poison.device(h->ev_off.p, h->ev_off.cap, h->stream));  // (UIS_POISON_WORKSPACE, as the entry point read it)
+  HIPCHK(poison.device(h->ev_out.p, h->ev_out.cap, h->stream));
   long long* d_matched = h->ev_out.as<long long>();
   int32_t* d_status = reinterpret_cast<int32_t*>(d_matched + n_utt);
   HIPCHK(hipMemcpyAsync(h->ev_off.p, offsets, (size_t)(n_utt + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -2861,7 +2912,7 @@ UIS_EXPORT int32_t uis_eval_accuracy_device(uis_handle* h, const int32_t* d_labe
   if (!h || !offsets || n_utt < 0 || (n_utt > 0 && !matched_out)) return fail(UIS_ERR_INVALID_ARG, "null argument or negative n_utt");
   if (n_utt > 0 && offsets[n_utt] > 0 && (!d_labels_a || !d_labels_b)) return fail(UIS_ERR_INVALID_ARG, "label pointer is null");
   HIPCHK(hipSetDevice(h->device));
-  return eval_run(h, d_labels_a, d_labels_b, offsets, n_utt, matched_out);
+  return eval_run(h, d_labels_a, d_labels_b, offsets, n_utt, matched_out, UisPoison::from_env());
 }
 
 UIS_EXPORT int32_t uis_eval_accuracy(uis_handle* h, const int32_t* labels_a, const int32_t* labels_b,
@@ -2873,11 +2924,14 @@ UIS_EXPORT int32_t uis_eval_accuracy(uis_handle* h, const int32_t* labels_a, con
   int rc;
   if ((rc = h->ev_a.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
   if ((rc = h->ev_b.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
+  const UisPoison poison = UisPoison::from_env();
+  HIPCHK(poison.device(h->ev_a.p, h->ev_a.cap, h->stream));
+  HIPCHK(poison.device(h->ev_b.p, h->ev_b.cap, h->stream));
   if (F > 0) {
     HIPCHK(hipMemcpyAsync(h->ev_a.p, labels_a, (size_t)F * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->ev_b.p, labels_b, (size_t)F * 4, hipMemcpyHostToDevice, h->stream));
   }
-  return eval_run(h, h->ev_a.as<int32_t>(), h->ev_b.as<int32_t>(), offsets, n_utt, matched_out);
+  return eval_run(h, h->ev_a.as<int32_t>(), h->ev_b.as<int32_t>(), offsets, n_utt, matched_out, poison);
 }
 
 UIS_EXPORT int32_t uis_eval_last_decode(uis_handle* h, const int32_t* truth, int32_t n_utt, int64_t* matched_out) {
@@ -2889,9 +2943,11 @@ UIS_EXPORT int32_t uis_eval_last_decode(uis_handle* h, const int32_t* truth, int
   HIPCHK(hipSetDevice(h->device));
   int rc;
   if ((rc = h->ev_b.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
+  const UisPoison poison = UisPoison::from_env();
+  HIPCHK(poison.device(h->ev_b.p, h->ev_b.cap, h->stream));  // (io_labels: the last decode's, carried)
   if (F > 0) HIPCHK(hipMemcpyAsync(h->ev_b.p, truth, (size_t)F * 4, hipMemcpyHostToDevice, h->stream));
   // the predicted labels of the last uis_decode never left HBM for this
-  return eval_run(h, h->io_labels.as<int32_t>(), h->ev_b.as<int32_t>(), h->io_offsets.data(), n_utt, matched_out);
+  return eval_run(h, h->io_labels.as<int32_t>(), h->ev_b.as<int32_t>(), h->io_offsets.data(), n_utt, matched_out, poison);
 }
 
 // ------------------------------------------------------------------ pinned host memory

@@ -204,6 +204,11 @@ int nbest_run(uis_handle* h, const std::vector<uis_handle::NbestGroup>& groups, 
   if ((rc = h->nb_counts.ensure((size_t)U * 4))) return rc;
   if ((rc = h->nb_stable.ensure((size_t)U * 8))) return rc;
   if ((rc = h->nb_off.ensure((size_t)U * 8))) return rc;
+  {  // UIS_POISON_WORKSPACE: the readout's own buffers (what the decode or the session left behind is its input)
+    const UisPoison poison = UisPoison::from_env();
+    for (DevBuf* b : {&h->nb_labels, &h->nb_scores, &h->nb_counts, &h->nb_stable, &h->nb_off})
+      HIPCHK(poison.device(b->p, b->cap, h->stream));
+  }
   std::vector<int64_t> out_off(U);
   for (int u = 0; u < U; ++u) out_off[u] = (int64_t)n_best * off[u];
   HIPCHK(hipMemcpyAsync(h->nb_off.p, out_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));

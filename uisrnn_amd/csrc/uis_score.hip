@@ -328,6 +328,12 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     return rc;
   if (m.D != m.Dp && (rc = h->sc_xpad.ensure(need(F, (size_t)m.Dp * 4)))) return rc;
   hipStream_t st = h->stream;
+  {  // UIS_POISON_WORKSPACE: every sc_* buffer, ahead of the tables and the frames on the same stream
+    const UisPoison poison = UisPoison::from_env();
+    for (DevBuf* b : {&h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0, &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean,
+                      &h->sc_gi_up, &h->sc_rows, &h->sc_chains, &h->sc_utt, &h->sc_out})
+      HIPCHK(poison.device(b->p, b->cap, st));
+  }
   int32_t* d_row_frame = h->sc_rows.as<int32_t>();
   int32_t* d_row_prev = d_row_frame + std::max<int64_t>(Fv, 1);
   int64_t* d_fbase = h->sc_chains.as<int64_t>();

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "uis_poison.h"
 #include "uisrnn_hip.h"
 
 #define UIS_EXPORT extern "C" __attribute__((visibility("default")))
@@ -748,6 +749,11 @@ UIS_EXPORT int32_t uis_train_step(uis_trainer* th, const int32_t* batch_idx, int
     const int64_t cap = std::max<int64_t>(TB, (int64_t)T * th->cap_B);
     TCHK(hipMalloc(&th->ws, sizeof(float) * (size_t)ws_floats(th, cap, th->cap_B, nullptr, nullptr)));
     th->cap_TB = cap;
+  }
+  {  // UIS_POISON_WORKSPACE: the whole workspace, on the trainer's stream ahead of the step's first kernel
+    const UisPoison poison = UisPoison::from_env();
+    if (poison.on)
+      TCHK(poison.device(th->ws, sizeof(float) * (size_t)ws_floats(th, th->cap_TB, th->cap_B, nullptr, nullptr), st));
   }
   Ws w;
   const int64_t wsn = ws_floats(th, TB, B, &w, th->ws);
