@@ -114,23 +114,48 @@ def test_config5_and_config3_shapes(oracle_lib):
   assert np.array_equal(ref['beam_scores'].view(np.uint32), out['beam_scores'].view(np.uint32))
 
 
+def _use_every_owner_of_memory(dec, seqs, truth):
+  """One call of everything on a handle that keeps device or pinned memory of its own: the decode workspace (both
+  machineries), the float64 staging blocks, the scoring, n-best and evaluation buffers, a session that is closed and a
+  persistent one that is NOT -- the handle's destruction has to end its launch and free what it holds."""
+  _decode(dec, seqs, 10, 1, 2)
+  out, off = _decode(dec, seqs, 5, 2, 1)
+  frames = np.concatenate(seqs).astype(np.float32)
+  assert np.isfinite(dec.score_labels(frames, off, out['labels'])).all()
+  f64 = dec.decode_f64(seqs, 10, 1, 1, want_beam_scores=True)
+  assert f64['status'] == 0
+  nbest = dec.last_nbest(3)
+  for u in range(len(seqs)):
+    assert np.array_equal(nbest['labels'][u][0], f64['labels'][off[u]:off[u + 1]])
+  matched = dec.eval_last_decode(np.concatenate(truth), len(seqs))
+  assert (matched >= 0).all() and (matched <= 40).all()
+  chunks = np.stack(seqs).astype(np.float32)   # [8, 40, 256]
+  dec.stream_begin(len(seqs), 10, 40)
+  dec.stream_push(chunks[:, :4])
+  dec.stream_push(chunks[:, 4:12])
+  labels, _, _, status = dec.stream_labels()
+  assert status == 0 and all(len(l) == 12 for l in labels)
+  dec.stream_end()
+  dec.stream_begin(len(seqs), 10, 40, flags=_capi.UIS_FLAG_PERSISTENT)
+  dec.stream_push(chunks[:, :4])   # (the launch is on the device from here; the session stays open)
+
+
 def test_handles_release_their_memory():
-  """create / decode / destroy in a loop leaves the device memory where it was."""
+  """create / decode, score, read out, evaluate, stream / destroy in a loop leaves the device memory where it was."""
   import gc
   import torch
   params = synth.tracker_params(256, 512, 1, seed=0)
-  seqs, _ = synth.make_utterances(60_000, 8, 40, 256)
+  seqs, truth = synth.make_utterances(60_000, 8, 40, 256)
   torch.cuda.init()
   dec = _capi.Decoder(params)
-  _decode(dec, seqs, 10, 1, 2)
+  _use_every_owner_of_memory(dec, seqs, truth)
   dec.close()
   gc.collect()
   torch.cuda.synchronize()
   free0, _ = torch.cuda.mem_get_info()
   for _ in range(20):
     dec = _capi.Decoder(params)
-    _decode(dec, seqs, 10, 1, 2)
-    _decode(dec, seqs, 5, 2, 1)
+    _use_every_owner_of_memory(dec, seqs, truth)
     dec.close()
   gc.collect()
   torch.cuda.synchronize()

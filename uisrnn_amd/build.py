@@ -22,6 +22,8 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_eval.hip'),
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),
     os.path.join(_HERE, 'csrc', 'uis_nbest.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_stream.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_workspace.hip'),
     os.path.join(_ROOT, 'include', 'uis_numerics.h'),
     os.path.join(_ROOT, 'include', 'uisrnn_hip.h'),
 ]

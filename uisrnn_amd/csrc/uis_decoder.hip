@@ -55,24 +55,54 @@ int fail(int code, const std::string& msg) {
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// Device memory that frees itself (move-only).  ensure() grows it and never shrinks it; alloc() is one allocation of
+// exactly `bytes`; view() makes it a window into someone else's allocation (`borrowed`: never freed from here).
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
   bool borrowed = false;  // a view into the handle's workspace arena, not an allocation of its own
-  int ensure(size_t bytes) {
-    if (borrowed) { p = nullptr; cap = 0; borrowed = false; }
-    if (bytes <= cap) return UIS_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&p, want);
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }  // (o's destructor frees what this one held)
+  ~DevBuf() { release(); }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(borrowed, o.borrowed); }
+  int alloc(size_t bytes) {
+    release();
+    hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
       p = nullptr;
-      return fail(UIS_ERR_OOM, "hipMalloc of " + std::to_string(want) + " bytes failed: " + hipGetErrorString(e));
+      return fail(UIS_ERR_OOM, "hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
     }
-    cap = want;
+    cap = bytes;
     return UIS_OK;
   }
+  int ensure(size_t bytes) {
+    if (borrowed) release();
+    return bytes <= cap ? UIS_OK : alloc(bytes + bytes / 8 + 256);
+  }
+  void view(void* at, size_t bytes) { release(); p = at; cap = bytes; borrowed = true; }
   void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }
+  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// The same for pinned host memory.  ensure() allocates exactly `bytes` when the block is smaller (the caller adds its
+// own head-room where a block grows often) and leaves the HIP error to the caller: some can do without the block.
+struct HostBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(HostBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+  HostBuf& operator=(HostBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~HostBuf() { release(); }
+  hipError_t ensure(size_t bytes, unsigned flags) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipHostMalloc(&p, bytes, flags);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    cap = bytes;
+    return hipSuccess;
+  }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -123,9 +153,35 @@ struct ProfileEvents {
   size_t used = 0;
 };
 
+// What a streaming session owns: one move-assignment of a fresh one frees it all.
+struct StreamMem {
+  std::vector<DevBuf> allocs;  // the session's state, one allocation per table (uis_stream_begin)
+  DevBuf chunk_x, chunk_pad, chunk_gi0, chunk_mse0, labels, scores;
+  // one push = one H2D copy: [foff U x int64][avail U x int32, padded][frames] staged in pinned
+  // host memory (h_stage) and mirrored in chunk_x
+  HostBuf h_stage;
+  HostBuf pm_block;  // the persistent launch's mailbox (host-coherent)
+};
+
+// Every device and pinned buffer of a handle outside its session, likewise.
+struct HandleMem {
+  // workspace (grow only)
+  DevBuf off, utt_step, overflow, xpad, gi0, mse0, logblk, logden, pool_mean, pool_hid, pool_cnt;
+  DevBuf beam_n, beam_K, beam_last, beam_sum, beam_score, beam_slot, beam_blk, bp, rows, nrows;
+  DevBuf gi_up, a1, counters, beam_scores_out, io_frames, io_labels, io_scores, mse_tab, dbg_scores, utt_nrows, hst;
+  DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
+  DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
+  DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
+  HostBuf h_cast;  // uis_decode_f64: the pinned float32 staging buffer the utterances are cast into, chunk by chunk, ahead of each H2D copy
+  HostBuf h_out;   // pinned landing block of uis_decode_f64's labels and scores
+  DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
+  DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
+  DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
+};
+
 }  // namespace
 
-struct uis_handle {
+struct uis_handle : HandleMem {
   int device = 0;
   hipStream_t stream = nullptr, copy_stream = nullptr;
   std::vector<hipEvent_t> h2d_done;
@@ -149,17 +205,11 @@ struct uis_handle {
     float ms[4] = {0, 0, 0, 0};
   } ctl_tune;
   // streaming session (uis_stream_*): owns its device memory
-  struct Stream {
+  struct Stream : StreamMem {
     bool active = false;
     int U = 0, B = 0, Kmax = 0, S = 0;
     int64_t cap = 0;                  // frames per utterance the session can hold
     std::vector<int32_t> have;        // frames received per utterance
-    std::vector<void*> allocs;
-    DevBuf chunk_x, chunk_pad, chunk_gi0, chunk_mse0, labels, scores;
-    // one push = one H2D copy: [foff U x int64][avail U x int32, padded][frames] staged in pinned
-    // host memory (h_stage) and mirrored in chunk_x
-    void* h_stage = nullptr;
-    size_t h_stage_cap = 0;
     DecodeState st{};
     int32_t* d_avail = nullptr;
     int32_t* d_have = nullptr;        // frames received per utterance, refreshed for every back-trace
@@ -176,7 +226,6 @@ struct uis_handle {
     // pushes; commands, tables, frames and labels travel through pm_block (host-coherent pinned memory)
     bool persist = false;             // the session asked for it and its shape allows it
     bool pm_running = false;          // the launch is on the device
-    unsigned char* pm_block = nullptr;
     uint32_t pm_seq = 0;              // commands issued to the running launch
     int64_t pm_cap_frames = 0;        // rows of the mailbox's frame area = ncl * pm_cluster_rows
     int64_t pm_cluster_rows = 0;      // each cluster's FIXED share of the chunk buffers (rows), see uis_stream_begin
@@ -190,23 +239,10 @@ struct uis_handle {
     int64_t pm_launches = 0, pm_commands = 0;
     UisPoison poison;                 // UIS_POISON_WORKSPACE as uis_stream_begin / the running uis_stream_push read it
   } stream_state;
-  // workspace (grow only)
-  DevBuf off, utt_step, overflow, xpad, gi0, mse0, logblk, logden, pool_mean, pool_hid, pool_cnt;
-  DevBuf beam_n, beam_K, beam_last, beam_sum, beam_score, beam_slot, beam_blk, bp, rows, nrows;
-  DevBuf gi_up, a1, counters, beam_scores_out, io_frames, io_labels, io_scores, mse_tab, dbg_scores, utt_nrows, hst;
   size_t dbg_floats = 0;  // what the last decode left in dbg_scores (UIS_FLAG_DEBUG_SCORES)
-  DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
-  DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
-  DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   UisPoison poison;  // UIS_POISON_WORKSPACE as the running uis_decode* call read it at its entry (one getenv per call)
-  // uis_decode_f64: the caller's float64 utterances (set for the duration of that call) and the
-  // pinned float32 staging buffer they are cast into, chunk by chunk, ahead of each H2D copy
-  const double* const* src64 = nullptr;
-  float* h_cast = nullptr;
-  size_t h_cast_cap = 0;
+  const double* const* src64 = nullptr;  // uis_decode_f64: the caller's float64 utterances (set for the duration of that call)
   void* cast_pool = nullptr;  // CastPool: the threads that cast (created by the first uis_decode_f64)
-  void* h_out = nullptr;      // pinned landing block of uis_decode_f64's labels and scores
-  size_t h_out_cap = 0;
   ProfileEvents prof;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_pre = nullptr;
   // utterance groups: one stream + one cached step graph each
@@ -216,24 +252,21 @@ struct uis_handle {
   // info of the last decode
   int last_U = 0, last_B = 0;
   std::vector<int64_t> io_offsets;  // offsets of the last uis_decode (its labels are still in io_labels)
-  DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
-  DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
-  // offsets, the record format -- and the readout's own buffers
+  // offsets, the record format
   struct NbestGroup { DecodeState st; int u0; };
   bool nb_valid = false, nb_wnd = false;
   int nb_B = 0;
   std::vector<NbestGroup> nb_groups;
   std::vector<int64_t> nb_offsets;
-  DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;
 };
 
 namespace {
 
-inline volatile uint32_t* pm_ctl(uis_handle::Stream& ss) { return reinterpret_cast<volatile uint32_t*>(ss.pm_block); }
+inline volatile uint32_t* pm_ctl(uis_handle::Stream& ss) { return ss.pm_block.as<volatile uint32_t>(); }
 
 // every cluster's doorbell: command words first, then the sequence numbers
 void pm_ring(uis_handle::Stream& ss, uint32_t seq, uint32_t type, uint32_t frames, const uint32_t* row0 = nullptr,
@@ -305,6 +338,16 @@ inline dim3 dense_grid_xcd(long rows, int tiles) {
   return dim3((unsigned)dense_grid_blocks((int)((rows + 15) / 16), tiles), 1, 1);
 }
 
+// Events of a vector that only grows (one per copy piece, group, profiled launch): create until there are n.
+int grow_events(std::vector<hipEvent_t>& ev, size_t n, unsigned flags = hipEventDisableTiming) {
+  while (ev.size() < n) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreateWithFlags(&e, flags));
+    ev.push_back(e);
+  }
+  return UIS_OK;
+}
+
 // Launches go through here.  With UIS_FLAG_PROFILE every kernel is launched with
 // hipExtLaunchKernelGGL's start/stop events, which carry the dispatch's own begin/end
 // timestamps (what rocprofv3 --kernel-trace reports), not host-side bracket times.
@@ -314,13 +357,7 @@ struct Launcher {
   bool profile;
   int events(hipEvent_t* a, hipEvent_t* b, int cls) {
     ProfileEvents& p = h->prof;
-    if (p.used + 2 > p.ev.size()) {
-      for (int i = 0; i < 2; ++i) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        p.ev.push_back(e);
-      }
-    }
+    if (int rc = grow_events(p.ev, p.used + 2, hipEventDefault)) return rc;
     p.cls.push_back(cls);
     *a = p.ev[p.used];
     *b = p.ev[p.used + 1];
@@ -623,12 +660,7 @@ struct CastTeam {
       r = e;
     }
   }
-  void wait_rows(int64_t f1) {  // rows [0, f1) are cast when this returns
-    const int64_t b1 = (f1 + kBlockRows - 1) / kBlockRows;
-    for (int64_t b = 0; b < b1; ++b)
-      while (!done[(size_t)b].load(std::memory_order_acquire))
-        if (!take()) std::this_thread::yield();
-  }
+  void wait_rows(int64_t f1) { wait_blocks((f1 + kBlockRows - 1) / kBlockRows); }  // rows [0, f1) are cast when this returns
 };
 
 // The threads that cast: created once per handle (a decode used to spawn and join up to sixteen
@@ -712,7 +744,7 @@ struct DecodeKnobs {
   double max_state_bytes = 200e9, split_min_bytes = 0.0;
   bool split_min_set = false, split_frames_set = false, no_split = false, no_arena = false, no_ctl_tune = false;
   bool ctl_offset_set = false, agent_flags = false;
-  bool no_rs = false;  // (not from the environment: decode_once sets it when k_decode_rs's workspace stretch would pass 4 GB)
+  bool no_rs = false;  // (not from the environment: plan_and_place sets it when k_decode_rs's workspace stretch would pass 4 GB)
   std::vector<long> split_frames;
   size_t arena_shift = 0, ctl_offset = 0;
 };
@@ -865,8 +897,8 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
     // offsets: a row of gi0 is 3 Hp floats, a row of x Dp)
     const bool frames32 = s.F < 0x7fffffffLL && (double)s.F * std::max(3 * m.Hp, m.Dp) * 4.0 < 4.0e9;
     // (... and everything else its step loop addresses through ONE descriptor over the workspace from pool_mean to mse_tab
-    // -- RsArgs, uis_kernels.h.  decode_once sums that stretch from the workspace list itself and plans again with
-    // k.no_rs set should it ever pass 4 GB: the next kernel then decodes, as for any other term below)
+    // -- RsArgs, uis_kernels.h.  place_workspace sums that stretch from the workspace list itself and plan_and_place plans
+    // again with k.no_rs set should it ever pass 4 GB: the next kernel then decodes, as for any other term below)
     const bool rs_block = !k.no_rs;
     // the REPLICATED select (k_decode_rs, uis_select_rs.hip): every workgroup of an XCD decides all of the cluster's
     // utterances, one wave each; the default where it applies (UIS_FLAG_OWNER_SELECT keeps k_decode_resident)
@@ -1209,11 +1241,64 @@ int report_diagnostics(uis_handle* h, const DecodePlan& plan, int U, int64_t max
 }
 #endif
 
-int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
-                const uis_decode_opts* opts, int32_t* d_labels, float* d_scores, uis_stats* stats,
-                const float* h_frames = nullptr) {
-  if (!h || !offsets || !opts || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets/opts or negative n_utt");
-  const DecodeKnobs knobs = read_knobs();
+// ---- decode_once(): one uis_decode* call as a sequence of steps.  What the steps hand to each other:
+struct DecodeCall {
+  // the call as it came in
+  uis_handle* h; const float* d_frames; const int64_t* offsets; int32_t n_utt; const uis_decode_opts* opts;
+  int32_t* d_labels; float* d_scores; uis_stats* stats; const float* h_frames;
+  DecodeKnobs knobs;
+  // derive_shape
+  DecodeShape shape{};
+  int tau = 1;
+  bool profile = false, dbg = false;
+  WindowScratch wsl{};
+  std::vector<GroupPlan> groups;
+  std::vector<int64_t> bp_base;  // back-pointer records per utterance (the window machinery's): windows x B
+  // plan_and_place
+  DecodePlan plan;
+  bool rs = false;
+  size_t dbg_floats = 0;
+  int64_t n_log = 0;
+  size_t mse_tab_bytes = 0, mse_part_bytes = 0;
+  DecodeKernel cluster_kern = nullptr;
+  RsKernel rs_kern = nullptr;
+  // ctl_choose
+  bool ctl_tune = false;
+  uint32_t* ctl = nullptr;
+  // upload_tables
+  const float* d_x = nullptr;    // the frames as the kernels read them: padded where D is no multiple of 16
+  std::vector<double> log_host;  // (the source of asynchronous copies: lives until the call's streams are drained)
+};
+
+}  // namespace
+
+#include "uis_workspace.hip"
+
+namespace {
+
+// How many utterances hit the cluster cap (their flags to overflow_out, if given), and the status every entry point
+// that reads labels returns for that count.
+int count_cluster_cap(const std::vector<int32_t>& overflow, int32_t* overflow_out = nullptr) {
+  int n_over = 0;
+  for (size_t u = 0; u < overflow.size(); ++u) {
+    if (overflow_out) overflow_out[u] = overflow[u];
+    n_over += overflow[u] != 0;
+  }
+  return n_over;
+}
+int cluster_cap_status(int n_over, int Kmax) {
+  if (!n_over) return UIS_OK;
+  return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
+                                       std::to_string(Kmax) + " clusters per hypothesis");
+}
+
+// Step 1: the arguments checked, the DecodeShape and the utterance groups.  shape.U == 0 with UIS_OK: an empty list,
+// nothing left to do.
+int derive_shape(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const int64_t* offsets = c.offsets;
+  const uis_decode_opts* opts = c.opts;
+  const int32_t n_utt = c.n_utt;
   // (whatever refuses this decode below: uis_last_decode_info must not hand out the PREVIOUS decode's arrays)
   h->last_U = 0; h->last_B = 0;
   h->last_overflow.clear(); h->last_beam_scores.clear();
@@ -1241,7 +1326,7 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   const int64_t F = n_utt ? offsets[n_utt] : 0;
   bool ragged_list = false;  // (utterances of different lengths)
   for (int u = 1; u < n_utt; ++u) ragged_list = ragged_list || offsets[u + 1] - offsets[u] != offsets[1] - offsets[0];
-  if (stats) memset(stats, 0, sizeof(*stats));
+  if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
   h->last_U = n_utt; h->last_B = B;
   h->last_overflow.assign(n_utt, 0);
   h->last_beam_scores.assign((size_t)n_utt * B, INFINITY);
@@ -1249,7 +1334,7 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     h->nb_groups.clear(); h->nb_offsets.assign(1, 0); h->nb_B = B; h->nb_wnd = false; h->nb_valid = true;
     return UIS_OK;
   }
-  if (F > 0 && (!d_frames || !d_labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels_out is null");
+  if (F > 0 && (!c.d_frames || !c.d_labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels_out is null");
   const int64_t maxT = (int64_t)tau * maxN;
   if (maxT > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "test_iteration * N too large");
   HIPCHK(hipSetDevice(h->device));
@@ -1270,8 +1355,9 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   }
   if (S64 > 0x3fffffff) return fail(UIS_ERR_UNSUPPORTED, "beam_size * max_clusters ^ look_ahead too large");
   const int S = (int)S64;
-  const bool profile = (opts->flags & UIS_FLAG_PROFILE) != 0;
-  Launcher lch{h, h->stream, profile};
+  c.profile = (opts->flags & UIS_FLAG_PROFILE) != 0;
+  c.dbg = (opts->flags & UIS_FLAG_DEBUG_SCORES) != 0;
+  c.tau = tau;
   h->prof.used = 0; h->prof.cls.clear();
 
   // wnd: the window machinery decodes -- look_ahead >= 2, and look_ahead 1 where the select kernels do not apply
@@ -1289,11 +1375,11 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
     return fail(UIS_ERR_UNSUPPORTED, "level capacity * max_clusters beyond the kernels' 32-bit indices");
   if ((int64_t)U * std::max<int64_t>(NC, B) > 0x3fffffff)
     return fail(UIS_ERR_OOM, "utterances * level capacity beyond the kernels' 32-bit indices");
-  const WindowScratch wsl = window_scratch_layout(S, (int)NC, Kmax, B);
+  c.wsl = window_scratch_layout(S, (int)NC, Kmax, B);
   {  // refuse configurations whose state would not fit the device instead of failing in hipMalloc
     const double bytes = (double)U * S * (m.Dp + (double)m.depth * m.Hp) * 4.0 +
-                         (wnd ? (double)U * (wsl.total + 2.0 * NC * (Kmax * 8.0 + 32.0) + NC * (m.Hp + m.G) * 4.0) : 0.0);
-    if (bytes > knobs.max_state_bytes)
+                         (wnd ? (double)U * (c.wsl.total + 2.0 * NC * (Kmax * 8.0 + 32.0) + NC * (m.Hp + m.G) * 4.0) : 0.0);
+    if (bytes > c.knobs.max_state_bytes)
       return fail(UIS_ERR_OOM, "decode state would need " + std::to_string((long long)(bytes / 1e9)) + " GB");
   }
 
@@ -1301,209 +1387,150 @@ int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, in
   // MI355X: the device overlaps at most ~2 of these small kernels, so more
   // groups mean more launches, not more throughput -- the default is one group.
   int G = opts->n_streams > 0 ? opts->n_streams : 1;
-  if (profile || (opts->flags & UIS_FLAG_DEBUG_SCORES)) G = 1;
+  if (c.profile || c.dbg) G = 1;
   G = std::max(1, std::min(std::min(G, UIS_MAX_GROUPS), U));
   while ((int)h->gstreams.size() < G) {
     hipStream_t sgrp;
     HIPCHK(hipStreamCreateWithFlags(&sgrp, hipStreamNonBlocking));
     h->gstreams.push_back(sgrp);
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h->gdone.push_back(e);
-    h->gcache.emplace_back();
   }
-  std::vector<GroupPlan> groups(G);
+  if (int rc = grow_events(h->gdone, (size_t)G)) return rc;
+  if ((int)h->gcache.size() < G) h->gcache.resize(G);
+  c.groups.assign(G, GroupPlan{});
   for (int g = 0; g < G; ++g) {
-    groups[g].u0 = (int)((int64_t)U * g / G);
-    groups[g].U = (int)((int64_t)U * (g + 1) / G) - groups[g].u0;
-    for (int u = groups[g].u0; u < groups[g].u0 + groups[g].U; ++u)
-      groups[g].maxT = std::max<int64_t>(groups[g].maxT, (int64_t)tau * (offsets[u + 1] - offsets[u]));
+    GroupPlan& gp = c.groups[g];
+    gp.u0 = (int)((int64_t)U * g / G);
+    gp.U = (int)((int64_t)U * (g + 1) / G) - gp.u0;
+    for (int u = gp.u0; u < gp.u0 + gp.U; ++u) gp.maxT = std::max<int64_t>(gp.maxT, (int64_t)tau * (offsets[u + 1] - offsets[u]));
   }
-
-  // ---- the plan: which kernels decode this list
-  const DecodeShape shape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, h_frames != nullptr,
-                          wnd, (size_t)lds.total, wsl.total};
-  bool no_rs = false;
-replan:  // (taken once at most, from below the workspace list: k_decode_rs's stretch of it must stay below 4 GB)
-  DecodeKnobs plan_knobs = knobs;
-  plan_knobs.no_rs = no_rs;
-  const DecodePlan plan = plan_decode(m, shape, opts->flags, plan_knobs, h->n_cu, h->resident_off);
-  if ((opts->flags & UIS_FLAG_RESIDENT) && !plan.one_launch())
-    return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT needs (look_ahead 1:) one stream, beam_size * (max_clusters + 1) <= 256, no "
-                                     "per-step path flag and either a small model (rnn_hidden_size up to about 64, any rnn_depth) "
-                                     "or rnn_depth 1 with rnn_hidden_size 128, 256 or 512 (padded), observation_dim 128, "
-                                     "256 or 512 (padded) and a device whose CU count is a multiple of 32");
-  const bool rs = plan.path == DecodePath::RS, split = plan.split;
-  const std::vector<int64_t>& cuts = plan.cuts;
-  const long rows_cap = plan.rows_cap;
-  const bool dbg = (opts->flags & UIS_FLAG_DEBUG_SCORES) != 0;
-  // one array per window: [windows][U][B][Kmax + 1] ^ look_ahead
-  double dbg_want = dbg ? (double)((maxT + L - 1) / L) * U * B : 0.0;
-  for (int k = 0; k < L; ++k) dbg_want *= (double)(Kmax + 1);
-  if (dbg_want > 1e9) return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_DEBUG_SCORES: more than 1e9 candidate scores (a test hook for small decodes)");
-  const size_t dbg_floats = (size_t)dbg_want;
-  h->dbg_floats = 0;
-
-  // back-pointer records per utterance (look_ahead >= 2): windows x B
-  std::vector<int64_t> bp_base(U + 1, 0);
+  c.bp_base.assign(U + 1, 0);
   if (wnd)
     for (int u = 0; u < U; ++u)
-      bp_base[u + 1] = bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
+      c.bp_base[u + 1] = c.bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
+  c.shape = DecodeShape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, c.h_frames != nullptr,
+                        wnd, (size_t)lds.total, c.wsl.total};
+  return UIS_OK;
+}
 
-  // ---- workspace: every buffer is a 4 KB-aligned view into ONE allocation (h->arena), laid out in the order of the
-  // ENSUREs below -- which is part of the measured speed: keep the order and the sizes
-  int rc;
-  std::vector<std::pair<DevBuf*, size_t>> want;
-#define ENSURE(buf, bytes) want.emplace_back(&h->buf, (size_t)(bytes))
-  ENSURE(off, (size_t)(U + 1) * 8);
-  ENSURE(utt_step, (size_t)U * 4);
-  ENSURE(overflow, (size_t)U * 4);
-  if (m.D != m.Dp) ENSURE(xpad, (size_t)std::max<int64_t>(F, 1) * m.Dp * 4);
-  ENSURE(gi0, (size_t)std::max<int64_t>(F, 1) * m.G * 4);
-  ENSURE(mse0, (size_t)std::max<int64_t>(F, 1) * 4);
-  // (k_decode_rs / k_decode_big<WS> copy the first UIS_RS_LOGTAB entries into LDS whatever the decode's length)
-  const int64_t n_log = std::max<int64_t>(maxT + 2, UIS_RS_LOGTAB);
-  ENSURE(logblk, (size_t)n_log * 8);
-  ENSURE(logden, (size_t)n_log * 8);
-  ENSURE(pool_mean, (size_t)U * S * m.Dp * 4);
-  ENSURE(pool_hid, ((size_t)U * S + 1) * m.depth * m.Hp * 4);  // + the slot k_decode_resident keeps h1 in
-  ENSURE(pool_cnt, (size_t)U * S * 4);
-  ENSURE(beam_n, (size_t)2 * U * 4);
-  ENSURE(beam_K, (size_t)2 * U * B * 4);
-  ENSURE(beam_last, (size_t)2 * U * B * 4);
-  ENSURE(beam_sum, (size_t)2 * U * B * 4);
-  ENSURE(beam_score, (size_t)2 * U * B * 4);
-  ENSURE(beam_slot, (size_t)2 * U * B * Kmax * 4);
-  ENSURE(beam_blk, (size_t)2 * U * B * Kmax * 4);
-  ENSURE(bp, !wnd ? (size_t)std::max<int64_t>(tau * F, 1) * B * 4 : 16);
-  ENSURE(rows, (size_t)rows_cap * sizeof(RnnRow));
-  ENSURE(nrows, (size_t)UIS_MAX_GROUPS * 2 * 4);
-  // depth 1: k_decode_resident's h' staging buffer
-  ENSURE(gi_up, m.depth > 1 ? (size_t)rows_cap * m.G * 4 : (size_t)rows_cap * m.Hp * 4);
-  ENSURE(a1, (size_t)rows_cap * m.Hp * 4);
-  // rnn_depth >= 2 in one launch (k_decode_deep): the two hand-off buffers a layer's h' goes through
-  if (plan.hst) ENSURE(hst, (size_t)2 * rows_cap * m.Hp * 4);
-#if defined(UIS_RESIDENT_TIMING)
-  ENSURE(counters, (size_t)UIS_MAX_GROUPS * 4 * 8 + (96 + 1024) * 8);
-#else
-  ENSURE(counters, (size_t)UIS_MAX_GROUPS * 4 * 8 + 96 * 8);
-#endif
-  ENSURE(beam_scores_out, (size_t)U * B * 4);
-  ENSURE(utt_nrows, (size_t)U * 2 * 4);
-  // (a decode in several launches: DecodeState::resume -- only lists given in host memory can split, and never through
-  // the window machinery: wide beams, large caps and look-ahead decodes do not pay for it)
-  ENSURE(resume, (h_frames && !wnd) ? (size_t)U * (rs_lds_layout(B, Kmax, S).persist_stride + 4) + 16 : (size_t)16);
-  ENSURE(split_tab, (size_t)8 * U * 2 * sizeof(long));                                     // (... of a ragged list: batch tables of up to 8 slices)
-  ENSURE(scatter_tab, (size_t)64 * U * 3 * sizeof(long));                                  // (... and of its copy units: the scatter's tables)
-  if (plan.stage) ENSURE(stage, (size_t)F * m.D * 4);                                      // (... the device's copy of the time-major staging block)
-  // control words: [0, 16) XCC id per cluster, [16] abort, [32, 32 + 32 ncl) row counters,
-  // then 32 ncl barrier counters, then 32 ncl phase words (one 128-byte line per cluster each)
-  const size_t ctl_words = (size_t)32 + 3 * UIS_MAX_CLUSTERS * 32;
-  static const size_t ctl_place[4] = {0, 8192, (size_t)1 << 20, ((size_t)1 << 20) + 8192};
-  ENSURE(cluster_ctl, ctl_place[3] + ((ctl_words * 4 + 4095) & ~(size_t)4095));
-  const size_t mse_tab_bytes = ((size_t)2 * U * S * 4 + 255) & ~(size_t)255;
-  const size_t mse_part_bytes = (size_t)plan.nclq * plan.rx_stride * rs_part_stride(m.Dp) * 4;
-  if (rs) ENSURE(mse_tab, mse_tab_bytes + mse_part_bytes);
-  if (dbg) ENSURE(dbg_scores, std::max<size_t>(dbg_floats, 1) * 4);
-  if (wnd) {
-    ENSURE(lv_n, (size_t)2 * U * 4);
-    ENSURE(lv_K, (size_t)2 * U * NC * 4);
-    ENSURE(lv_last, (size_t)2 * U * NC * 4);
-    ENSURE(lv_sum, (size_t)2 * U * NC * 4);
-    ENSURE(lv_score, (size_t)2 * U * NC * 4);
-    ENSURE(lv_origin, (size_t)2 * U * NC * 4);
-    ENSURE(lv_path, (size_t)2 * U * NC * L * 2);
-    ENSURE(lv_slot, (size_t)2 * U * NC * Kmax * 4);
-    ENSURE(lv_blk, (size_t)2 * U * NC * Kmax * 4);
-    ENSURE(scratch, (size_t)U * wsl.total);
-    ENSURE(bp16, (size_t)std::max<int64_t>(bp_base[U], 1) * (L + 1) * 2);
-    ENSURE(bp_base, (size_t)(U + 1) * 8);
+// Step 2: which kernels decode this list, and its workspace placed.  Planned a second time, without k_decode_rs, should
+// that kernel's stretch of the workspace pass 4 GB (place_workspace).
+int plan_and_place(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const DevModel& m = h->m;
+  const DecodeShape& s = c.shape;
+  DecodeKnobs plan_knobs = c.knobs;
+  for (;;) {
+    c.plan = plan_decode(m, s, c.opts->flags, plan_knobs, h->n_cu, h->resident_off);
+    if ((c.opts->flags & UIS_FLAG_RESIDENT) && !c.plan.one_launch())
+      return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT needs (look_ahead 1:) one stream, beam_size * (max_clusters + 1) <= 256, no "
+                                       "per-step path flag and either a small model (rnn_hidden_size up to about 64, any rnn_depth) "
+                                       "or rnn_depth 1 with rnn_hidden_size 128, 256 or 512 (padded), observation_dim 128, "
+                                       "256 or 512 (padded) and a device whose CU count is a multiple of 32");
+    c.rs = c.plan.path == DecodePath::RS;
+    // one array per window: [windows][U][B][Kmax + 1] ^ look_ahead
+    double dbg_want = c.dbg ? (double)((s.maxT + s.L - 1) / s.L) * s.U * s.B : 0.0;
+    for (int k = 0; k < s.L; ++k) dbg_want *= (double)(s.Kmax + 1);
+    if (dbg_want > 1e9) return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_DEBUG_SCORES: more than 1e9 candidate scores (a test hook for small decodes)");
+    c.dbg_floats = (size_t)dbg_want;
+    h->dbg_floats = 0;
+    const int rc = place_workspace(h, c.knobs, c.rs, workspace_list(c));
+    if (rc == UIS_OK) break;
+    if (rc != WS_REPLAN) return rc;
+    plan_knobs.no_rs = true;
   }
-#undef ENSURE
-  // k_decode_rs names everything from pool_mean to the end of mse_tab by 32-bit offsets from pool_mean (RsArgs): that
-  // stretch of THIS list must stay below 4 GB -- it does unless the back-pointers of a very long list push it there,
-  // and then the planner's next kernel decodes
-  size_t rs_first = 0, rs_last = 0, rs_stretch = 0;
-  if (rs) {
-    for (size_t i = 0; i < want.size(); ++i) {
-      if (want[i].first == &h->pool_mean) rs_first = i;
-      if (want[i].first == &h->mse_tab) rs_last = i;
-    }
-    for (size_t i = rs_first; i <= rs_last; ++i) rs_stretch += (want[i].second + 4095) & ~(size_t)4095;
-    if (rs_stretch >= ((size_t)1 << 32)) { no_rs = true; goto replan; }
-  }
-  {
-    size_t total = 0;
-    for (auto& w : want) total += (w.second + 4095) & ~(size_t)4095;
-    if (!knobs.no_arena) {
-      // (UIS_ARENA_SHIFT, tools/experiments/bimodal.py: the one-launch decode runs in one of two modes
-      // 4 % apart depending on where its buffers land)
-      const size_t shift = knobs.arena_shift;
-      if ((rc = h->arena.ensure(total + shift))) return rc;
-      size_t o = shift;
-      for (auto& w : want) {
-        if (w.first->p && !w.first->borrowed) (void)hipFree(w.first->p);
-        w.first->p = static_cast<char*>(h->arena.p) + o;
-        w.first->cap = w.second;
-        w.first->borrowed = true;
-        o += (w.second + 4095) & ~(size_t)4095;
-      }
-    } else {
-      // (no arena: an allocation per buffer -- but k_decode_rs's stretch stays ONE, laid out as the arena would)
-      if (rs && (rc = h->rs_block.ensure(rs_stretch))) return rc;
-      size_t o = 0;
-      for (size_t i = 0; i < want.size(); ++i) {
-        auto& w = want[i];
-        if (rs && i >= rs_first && i <= rs_last) {
-          if (w.first->p && !w.first->borrowed) (void)hipFree(w.first->p);
-          w.first->p = static_cast<char*>(h->rs_block.p) + o;
-          w.first->cap = w.second;
-          w.first->borrowed = true;
-          o += (w.second + 4095) & ~(size_t)4095;
-        } else if ((rc = w.first->ensure(w.second))) {
-          return rc;
-        }
-      }
-    }
-    // UIS_POISON_WORKSPACE: the whole placed arena (or every buffer of the list and k_decode_rs's stretch), on the
-    // handle's stream ahead of ev_begin -- every other stream of this decode waits for that event (uis_poison.h)
-    if (h->poison.on) {
-      if (!knobs.no_arena) {
-        HIPCHK(h->poison.device(h->arena.p, total + knobs.arena_shift, h->stream));
-      } else {
-        if (rs) HIPCHK(h->poison.device(h->rs_block.p, h->rs_block.cap, h->stream));
-        for (auto& w : want)
-          if (!w.first->borrowed) HIPCHK(h->poison.device(w.first->p, w.first->cap, h->stream));
-      }
-    }
-  }
+  c.cluster_kern = c.plan.clustered() && !c.rs ? cluster_kernel(c.plan, m, s.L) : nullptr;
+  c.rs_kern = c.rs ? find_kernel(kernels::rs, m.Hp, m.Dp, c.plan.rs_kind) : nullptr;
+  return UIS_OK;
+}
 
-  // ---- placement of the control words for this decode (uis_handle::CtlTune)
+// Step 3: where this decode's control words sit inside cluster_ctl (uis_handle::CtlTune) -- ctl_choose before the
+// decode, ctl_record after it with the device time the placement got.
+void ctl_choose(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const DecodeShape& s = c.shape;
   uis_handle::CtlTune& tn = h->ctl_tune;
   int ctl_cand = 0;
   // (not for k_decode_rs: its row descriptors and row counters live in LDS, only the barrier
   // counters are polled in memory, and what is left of the placement effect is 1 % --
   // profiles/r03_bimodal.txt -- against 5 % for the kernels that keep them in global memory)
-  const bool ctl_tune = plan.resident() && !rs && !knobs.no_ctl_tune;
-  if (ctl_tune) {
-    const uint64_t sig = ((uint64_t)U << 44) ^ ((uint64_t)F << 16) ^ ((uint64_t)maxT << 6) ^ ((uint64_t)B << 1) ^ ((uint64_t)Kmax << 54);
+  c.ctl_tune = c.plan.resident() && !c.rs && !c.knobs.no_ctl_tune;
+  if (c.ctl_tune) {
+    const uint64_t sig = ((uint64_t)s.U << 44) ^ ((uint64_t)s.F << 16) ^ ((uint64_t)s.maxT << 6) ^ ((uint64_t)s.B << 1) ^ ((uint64_t)s.Kmax << 54);
     if (tn.sig != sig) { tn = uis_handle::CtlTune{}; tn.sig = sig; }
     ctl_cand = (tn.phase >= 1 && tn.phase <= 4) ? tn.phase - 1 : tn.best;
   }
-  size_t ctl_off = ctl_place[ctl_cand];
-  if (knobs.ctl_offset_set) ctl_off = std::min<size_t>(knobs.ctl_offset, ctl_place[3]);  // experiments
-  uint32_t* const ctl = reinterpret_cast<uint32_t*>(h->cluster_ctl.as<char>() + ctl_off);
+  size_t ctl_off = kCtlPlace[ctl_cand];
+  if (c.knobs.ctl_offset_set) ctl_off = std::min<size_t>(c.knobs.ctl_offset, kCtlPlace[3]);  // experiments
+  c.ctl = reinterpret_cast<uint32_t*>(h->cluster_ctl.as<char>() + ctl_off);
+}
 
-  // ---- ingestion: the frames onto the device, the input projection and the fresh-cluster MSEs
-  const bool uniform = !ragged_list;
-  const int64_t uniN = maxN;  // the longest utterance: slice boundaries are frame indices inside an utterance
-  const int64_t T1 = split ? cuts[0] : 0;
+int ctl_record(DecodeCall& c) {
+  uis_handle::CtlTune& tn = c.h->ctl_tune;
+  if (!(c.ctl_tune && tn.sig != 0 && tn.phase <= 4)) return UIS_OK;
+  float ms = 0.0f;
+  HIPCHK(hipEventElapsedTime(&ms, c.h->ev_begin, c.h->ev_end));
+  if (tn.phase >= 1) tn.ms[tn.phase - 1] = ms;
+  if (++tn.phase == 5) {
+    tn.best = 0;
+    for (int k = 1; k < 4; ++k)
+      if (tn.ms[k] < 0.995f * tn.ms[tn.best]) tn.best = k;  // (another placement has to win by 0.5 %: repeats agree to 0.1 %)
+  }
+  return UIS_OK;
+}
+
+// Step 4a: the per-decode tables onto the device, ev_begin, and the memory that must start out defined.
+int upload_tables(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const DevModel& m = h->m;
+  const DecodeShape& s = c.shape;
+  HIPCHK(hipMemcpyAsync(h->off.p, c.offsets, (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  if (int rc = upload_log_tables(h->alpha, c.n_log, c.log_host, h->logblk.p, h->logden.p, h->stream)) return rc;
+  if (s.wnd)
+    HIPCHK(hipMemcpyAsync(h->bp_base.p, c.bp_base.data(), (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
+
+  HIPCHK(hipEventRecord(h->ev_begin, h->stream));
+  // never-written row descriptors must still name valid slots (step_tile in uis_kernels.hip)
+  HIPCHK(hipMemsetAsync(h->rows.p, 0, (size_t)c.plan.rows_cap * sizeof(RnnRow), h->stream));
+  HIPCHK(hipMemsetAsync(c.ctl, 0, kCtlWords * 4, h->stream));
+  if (c.dbg && c.dbg_floats) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->dbg_scores.p), 0x7f800000, c.dbg_floats, h->stream));
+  if (c.rs)  // tiles a model does not have stay +0 in every row's partial sums
+    HIPCHK(hipMemsetAsync(h->mse_tab.as<char>() + c.mse_tab_bytes, 0, c.mse_part_bytes, h->stream));
+  c.d_x = (m.D != m.Dp && s.F > 0) ? h->xpad.as<float>() : c.d_frames;
+  return UIS_OK;
+}
+
+// gi0 = W_ih0 x + b_ih0 and mse0 of n rows in each of `batches` batches (grid.z) with the 32-row x 16-tile workgroups:
+// batch z starts z * stride rows behind the first, or -- `tab` -- at row tab[2 z] with tab[2 z + 1] rows.  `pipe`: the
+// pipelined walk, instantiated for Dp 128 / 256 / 512 (every shape the planner splits a decode at is one of them).
+int wide_input_proj(Launcher& lch, const DevModel& m, const float* x, float* gi0, float* mse0, long n, int batches, long stride,
+                    const long* tab, bool pipe) {
+  const dim3 wgrid((unsigned)((n + 31) / 32), (unsigned)((m.G / 16 + 15) / 16), (unsigned)batches);
+  if (pipe && m.Dp == 128) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<1>, wgrid, dim3(256), 0, m, x, gi0, n, stride, tab);
+  else if (pipe && m.Dp == 256) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<2>, wgrid, dim3(256), 0, m, x, gi0, n, stride, tab);
+  else if (pipe && m.Dp == 512) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<4>, wgrid, dim3(256), 0, m, x, gi0, n, stride, tab);
+  else LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_wide, wgrid, dim3(256), 0, m, x, gi0, n);
+  LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4), 1, (unsigned)batches), dim3(256), (size_t)5 * m.Dp * 4, m, x, mse0, n, stride, tab);
+  return UIS_OK;
+}
+
+// Step 4: ingestion -- the frames onto the device, the input projection and the fresh-cluster MSEs.  Owns the cast
+// team of a float64 list, the copy units and tables of a decode in several launches, and the way out: whichever way
+// decode_once is left once begin() has run, both streams are drained first (the caller never gets its buffers back
+// while the copy engine still reads them, and the tables below outlive their copies), and nobody is still inside the
+// cast team when it goes away.
+//   start()  the copy units; a float64 list's cast starts, in the order the frames are needed
+//   begin()  everything a decode needs before its first launch: the whole list, or (split) its first slice
+//   slice()  slice k of every utterance behind launch k - 1
+struct Ingest {
+  DecodeCall& c;
+  uis_handle* const h;
+  const DevModel& m;
+  const bool uniform;    // utterances of equal length
+  const int64_t uniN;    // the longest utterance: slice boundaries are frame indices inside an utterance
+  const size_t pitch;    // (split, equal lengths: bytes between utterances, in the staging block and on the device)
   std::unique_ptr<CastTeam> team;
-  struct TeamGuard {  // nobody may still be inside the team when it goes out of scope
-    CastPool* pool = nullptr;
-    ~TeamGuard() { if (pool) pool->finish(); }
-  } team_guard;
-  int64_t cast_blocks_a = 0;
+  CastPool* pool = nullptr;
+  bool drain = false;
   // (split) what travels as ONE strided copy: a slice, or -- float64 lists, whose cast feeds the copies -- a piece of a
   // slice, so that a piece is on its way while the next one is cast; slice k = units [unit_first[k], unit_first[k + 1])
   struct CopyUnit { int64_t t0, t1; };
@@ -1512,16 +1539,36 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
   std::vector<int64_t> cast_blocks_upto;  // blocks of the cast's order that end unit i
   std::vector<int64_t> unit_row0;         // (ragged) first row of unit i in the staging block (one more: the end)
   std::vector<long> scatter_tab_host;     // (ragged) k_scatter_rows' tables, unit after unit, {block row, stream row, rows} per utterance
-  if (split) {
-    for (size_t k = 0; k <= cuts.size(); ++k) {
-      const int64_t t0 = k ? cuts[k - 1] : 0, t1 = k < cuts.size() ? cuts[k] : uniN;
+  std::vector<long> split_tab_host;       // (ragged) the slices' batch tables
+
+  explicit Ingest(DecodeCall& c_)
+      : c(c_), h(c_.h), m(c_.h->m), uniform(!c_.shape.ragged), uniN(c_.shape.maxN), pitch((size_t)c_.shape.maxN * c_.h->m.D * 4) {}
+  Ingest(const Ingest&) = delete;
+  ~Ingest() {
+    if (drain) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(h->stream); }
+    if (pool) pool->finish();
+  }
+  const std::vector<int64_t>& cuts() const { return c.plan.cuts; }
+  int64_t slice_begin(size_t k) const { return k ? cuts()[k - 1] : 0; }
+  int64_t slice_end(size_t k) const { return k < cuts().size() ? cuts()[k] : uniN; }
+
+  void post(std::vector<std::pair<int64_t, int64_t>> order = {}, std::vector<int64_t> dst_rows = {}) {
+    if (!h->cast_pool) h->cast_pool = new CastPool();
+    team.reset(new CastTeam(h->src64, c.offsets, c.n_utt, m.D, c.shape.F, h->h_cast.as<float>(), std::move(order), std::move(dst_rows)));
+    pool = static_cast<CastPool*>(h->cast_pool);
+    pool->post(team.get());
+  }
+
+  void start() {
+    if (!c.plan.split) return;
+    for (size_t k = 0; k <= cuts().size(); ++k) {
+      const int64_t t0 = slice_begin(k), t1 = slice_end(k);
       const int np = (k > 0 && h->src64) ? (int)std::max<int64_t>(1, std::min<int64_t>(8, (t1 - t0) / 64)) : 1;
       unit_first.push_back(units.size());
       for (int q = 0; q < np; ++q) units.push_back(CopyUnit{t0 + (t1 - t0) * q / np, t0 + (t1 - t0) * (q + 1) / np});
     }
     unit_first.push_back(units.size());
-  }
-  if (split && h->src64) {
+    if (!h->src64) return;
     // the cast starts NOW, in the order the frames are needed (every utterance's first slice, then the next ...), while
     // this thread is still busy with the decode's tables and memsets
     std::vector<std::pair<int64_t, int64_t>> order;
@@ -1529,9 +1576,9 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
     int64_t cursor = 0;  // (ragged) next free row of the staging block
     for (size_t un = 0; un < units.size(); ++un) {
       unit_row0.push_back(cursor);
-      for (int u = 0; u < n_utt; ++u) {
-        const int64_t nu = offsets[u + 1] - offsets[u];
-        const int64_t r0 = offsets[u] + std::min(units[un].t0, nu), r1 = offsets[u] + std::min(units[un].t1, nu);
+      for (int u = 0; u < c.n_utt; ++u) {
+        const int64_t nu = c.offsets[u + 1] - c.offsets[u];
+        const int64_t r0 = c.offsets[u] + std::min(units[un].t0, nu), r1 = c.offsets[u] + std::min(units[un].t1, nu);
         if (!uniform) {  // the scatter's table: {row in the block, row in the stream, rows}
           scatter_tab_host.push_back((long)cursor); scatter_tab_host.push_back((long)r0); scatter_tab_host.push_back((long)(r1 - r0));
         }
@@ -1544,180 +1591,138 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
       cast_blocks_upto.push_back((int64_t)order.size());
     }
     unit_row0.push_back(cursor);
-    cast_blocks_a = cast_blocks_upto[0];
-    if (!h->cast_pool) h->cast_pool = new CastPool();
-    team.reset(new CastTeam(h->src64, offsets, n_utt, m.D, F, h->h_cast, std::move(order), std::move(dst_rows)));
-    team_guard.pool = static_cast<CastPool*>(h->cast_pool);
-    team_guard.pool->post(team.get());
+    post(std::move(order), std::move(dst_rows));
   }
-  // ---- per-decode tables
-  std::vector<double> logblk(n_log), logden(n_log);
-  for (int64_t n = 0; n < n_log; ++n) {
-    logblk[n] = n > 0 ? std::log((double)n) : 0.0;      // np.log(block_counts[cluster]), uisrnn.py:418-419
-    logden[n] = std::log((double)n + h->alpha);          // np.log(sum(block_counts) + crp_alpha)
-  }
-  HIPCHK(hipMemcpyAsync(h->off.p, offsets, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->logblk.p, logblk.data(), logblk.size() * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->logden.p, logden.data(), logden.size() * 8, hipMemcpyHostToDevice, h->stream));
-  if (wnd)
-    HIPCHK(hipMemcpyAsync(h->bp_base.p, bp_base.data(), (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream));
 
-  HIPCHK(hipEventRecord(h->ev_begin, h->stream));
-  // never-written row descriptors must still name valid slots (step_tile in uis_kernels.hip)
-  HIPCHK(hipMemsetAsync(h->rows.p, 0, (size_t)rows_cap * sizeof(RnnRow), h->stream));
-  HIPCHK(hipMemsetAsync(ctl, 0, ctl_words * 4, h->stream));
-  if (dbg && dbg_floats) HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->dbg_scores.p), 0x7f800000, dbg_floats, h->stream));
-  if (rs)  // tiles a model does not have stay +0 in every row's partial sums
-    HIPCHK(hipMemsetAsync(h->mse_tab.as<char>() + mse_tab_bytes, 0, mse_part_bytes, h->stream));
-  // once per decode: pad (only when D is not a multiple of 16), gi0 = W_ih0 x + b_ih0, mse0.
-  // Host frames (uis_decode) arrive in chunks on the copy stream; chunk i's kernels overlap the
-  // H2D of chunk i+1 (true overlap needs pinned host memory, uis_host_alloc).
-  const float* d_x = (m.D != m.Dp && F > 0) ? h->xpad.as<float>() : d_frames;
-  auto pre_chunk = [&](int64_t f0, int64_t f1) -> int {
+  // once per decode: pad (only when D is not a multiple of 16), gi0 = W_ih0 x + b_ih0, mse0 of frames [f0, f1)
+  int pre_chunk(Launcher& lch, int64_t f0, int64_t f1) {
     const long n = (long)(f1 - f0);
     if (m.D != m.Dp) {
       const long total = n * m.Dp;
       hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
-                         d_frames + (size_t)f0 * m.D, h->xpad.as<float>() + (size_t)f0 * m.Dp, n, m.D, m.Dp);
+                         c.d_frames + (size_t)f0 * m.D, h->xpad.as<float>() + (size_t)f0 * m.Dp, n, m.D, m.Dp);
       HIPCHK(hipGetLastError());
     }
-    if (n >= UIS_PROJ_WIDE_ROWS) {  // enough rows to fill the device with 32-row x 16-tile workgroups
-      const dim3 wgrid((unsigned)((n + 31) / 32), (unsigned)((m.G / 16 + 15) / 16));
-      const float* xin = d_x + (size_t)f0 * m.Dp;
-      float* gout = h->gi0.as<float>() + (size_t)f0 * m.G;
-      const bool pipe = !(opts->flags & UIS_FLAG_SMALL_TILES);  // (the flag keeps the plain walk for A/B runs)
-      if (pipe && m.Dp == 128) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<1>, wgrid, dim3(256), 0, m, xin, gout, n, 0L, (const long*)nullptr);
-      else if (pipe && m.Dp == 256) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<2>, wgrid, dim3(256), 0, m, xin, gout, n, 0L, (const long*)nullptr);
-      else if (pipe && m.Dp == 512) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<4>, wgrid, dim3(256), 0, m, xin, gout, n, 0L, (const long*)nullptr);
-      else LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_wide, wgrid, dim3(256), 0, m, xin, gout, n);
-      LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4)), dim3(256), (size_t)5 * m.Dp * 4, m, xin, h->mse0.as<float>() + f0, n,
-             0L, (const long*)nullptr);
-      return UIS_OK;
-    }
-    return plain_input_proj(lch, m, d_x + (size_t)f0 * m.Dp, h->gi0.as<float>() + (size_t)f0 * m.G, h->mse0.as<float>() + f0, n);
-  };
-  // From here on DMA from the caller's (or the pinned staging) memory may be in flight: whichever way
-  // this function is left -- an error return inside the chunk loop included -- both streams are
-  // drained first, so the caller never gets its buffers back while the copy engine still reads them.
-  std::vector<long> split_tab_host;  // (the source of an asynchronous copy: declared BEFORE the drain, so that it outlives the stream sync on every way out)
-  struct Drain {
-    uis_handle* h;
-    ~Drain() { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamSynchronize(h->stream); }
-  } drain_on_exit{h};
-  // a time slice [t0, t1) of every utterance (equal lengths): input projection and fresh-cluster MSE, the
-  // utterances as batches along grid.z
-  const size_t pitch = (size_t)uniN * m.D * 4;  // (split, equal lengths: bytes between utterances, in the staging block and on the device)
-  auto pre_rows = [&](Launcher& lch, size_t k, int64_t t0, int64_t t1) -> int {
-    const long n = (long)(t1 - t0);
-    const dim3 wgrid((unsigned)((n + 31) / 32), (unsigned)((m.G / 16 + 15) / 16), (unsigned)U);
-    // (uniform: batch z starts z * uniN rows behind the first; ragged: the slice's table of {first row, rows} per utterance)
-    const long* tab = uniform ? nullptr : h->split_tab.as<long>() + k * (size_t)U * 2;
-    const float* xin = uniform ? d_x + (size_t)t0 * m.Dp : d_x;
-    float* gout = uniform ? h->gi0.as<float>() + (size_t)t0 * m.G : h->gi0.as<float>();
-    float* mout = uniform ? h->mse0.as<float>() + t0 : h->mse0.as<float>();
-    if (m.Dp == 128) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<1>, wgrid, dim3(256), 0, m, xin, gout, n, (long)uniN, tab);
-    else if (m.Dp == 256) LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<2>, wgrid, dim3(256), 0, m, xin, gout, n, (long)uniN, tab);
-    else LAUNCH(UIS_K_INPUT_PROJ, k_dense_input_proj_pipe<4>, wgrid, dim3(256), 0, m, xin, gout, n, (long)uniN, tab);
-    LAUNCH(UIS_K_INPUT_PROJ, k_mse0, dim3((unsigned)((n + 3) / 4), 1, (unsigned)U), dim3(256), (size_t)5 * m.Dp * 4, m, xin, mout, n,
-           (long)uniN, tab);
-    return UIS_OK;
-  };
-  // rows [t0, t1) of every utterance, host -> device
-  auto copy_rows = [&](size_t un) -> int {
+    const float* xin = c.d_x + (size_t)f0 * m.Dp;
+    float* gout = h->gi0.as<float>() + (size_t)f0 * m.G;
+    if (n >= UIS_PROJ_WIDE_ROWS)  // enough rows to fill the device with 32-row x 16-tile workgroups
+      return wide_input_proj(lch, m, xin, gout, h->mse0.as<float>() + f0, n, 1, 0L, nullptr,
+                             !(c.opts->flags & UIS_FLAG_SMALL_TILES));  // (the flag keeps the plain walk for A/B runs)
+    return plain_input_proj(lch, m, xin, gout, h->mse0.as<float>() + f0, n);
+  }
+  // slice k = rows [t0, t1) of every utterance: input projection and fresh-cluster MSE, the utterances as batches
+  // (uniform: batch z starts z * uniN rows behind the first; ragged: the slice's table of {first row, rows} per utterance)
+  int pre_rows(Launcher& lch, size_t k) {
+    const int64_t t0 = slice_begin(k);
+    if (uniform)
+      return wide_input_proj(lch, m, c.d_x + (size_t)t0 * m.Dp, h->gi0.as<float>() + (size_t)t0 * m.G, h->mse0.as<float>() + t0,
+                             (long)(slice_end(k) - t0), c.shape.U, (long)uniN, nullptr, true);
+    return wide_input_proj(lch, m, c.d_x, h->gi0.as<float>(), h->mse0.as<float>(), (long)(slice_end(k) - t0), c.shape.U, (long)uniN,
+                           h->split_tab.as<long>() + k * (size_t)c.shape.U * 2, true);
+  }
+  // copy unit `un` of every utterance, host -> device
+  int copy_rows(size_t un) {
+    if (team) team->wait_blocks(cast_blocks_upto[un]);
     if (uniform) {
       const int64_t t0 = units[un].t0, t1 = units[un].t1;
-      HIPCHK(hipMemcpy2DAsync(const_cast<float*>(d_frames) + (size_t)t0 * m.D, pitch, h_frames + (size_t)t0 * m.D, pitch,
-                              (size_t)(t1 - t0) * m.D * 4, (size_t)U, hipMemcpyHostToDevice, h->copy_stream));
+      HIPCHK(hipMemcpy2DAsync(const_cast<float*>(c.d_frames) + (size_t)t0 * m.D, pitch, c.h_frames + (size_t)t0 * m.D, pitch,
+                              (size_t)(t1 - t0) * m.D * 4, (size_t)c.shape.U, hipMemcpyHostToDevice, h->copy_stream));
       return UIS_OK;
     }
     // ragged (float64 lists only): the unit is one block of the staging buffer -> the same rows of the device's block,
     // then every utterance's part to its place in the frame stream (on the copy stream too: ordered behind the copy)
     const int64_t r0 = unit_row0[un], r1 = unit_row0[un + 1];
     if (r1 > r0) {
-      HIPCHK(hipMemcpyAsync(h->stage.as<float>() + (size_t)r0 * m.D, h_frames + (size_t)r0 * m.D, (size_t)(r1 - r0) * m.D * 4,
+      HIPCHK(hipMemcpyAsync(h->stage.as<float>() + (size_t)r0 * m.D, c.h_frames + (size_t)r0 * m.D, (size_t)(r1 - r0) * m.D * 4,
                             hipMemcpyHostToDevice, h->copy_stream));
       const long max_rows = (long)(units[un].t1 - units[un].t0);
-      hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)std::min<long>(64, (max_rows * (m.D / 4) + 255) / 256), (unsigned)U), dim3(256), 0,
-                         h->copy_stream, h->stage.as<float>(), const_cast<float*>(d_frames), h->scatter_tab.as<long>() + un * (size_t)U * 3, m.D);
+      hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)std::min<long>(64, (max_rows * (m.D / 4) + 255) / 256), (unsigned)c.shape.U), dim3(256), 0,
+                         h->copy_stream, h->stage.as<float>(), const_cast<float*>(c.d_frames), h->scatter_tab.as<long>() + un * (size_t)c.shape.U * 3, m.D);
       HIPCHK(hipGetLastError());
     }
     return UIS_OK;
-  };
-  if (split) {
-    while (h->h2d_done.size() < cuts.size() + 1) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->h2d_done.push_back(e);
-    }
-    HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_begin, 0));
-    if (!uniform) {  // the slices' batch tables: {first row, rows} per utterance and slice
-      split_tab_host.assign((cuts.size() + 1) * (size_t)U * 2, 0L);
-      std::vector<long>& tab = split_tab_host;
-      for (size_t k = 0; k <= cuts.size(); ++k) {
-        const int64_t t0 = k ? cuts[k - 1] : 0, t1 = k < cuts.size() ? cuts[k] : uniN;
-        for (int u = 0; u < n_utt; ++u) {
-          const int64_t nu = offsets[u + 1] - offsets[u], a = std::min(t0, nu);
-          tab[(k * U + u) * 2] = (long)(offsets[u] + a);
-          tab[(k * U + u) * 2 + 1] = (long)(std::min(t1, nu) - a);
-        }
-      }
-      HIPCHK(hipMemcpyAsync(h->split_tab.p, tab.data(), tab.size() * sizeof(long), hipMemcpyHostToDevice, h->stream));
-      // (the scatter runs on the copy stream: its tables go up on that stream, ahead of the first block)
-      HIPCHK(hipMemcpyAsync(h->scatter_tab.p, scatter_tab_host.data(), scatter_tab_host.size() * sizeof(long), hipMemcpyHostToDevice,
-                            h->copy_stream));
-    }
-    if (team) team->wait_blocks(cast_blocks_a);
-    if ((rc = copy_rows(0))) return rc;
-    HIPCHK(hipEventRecord(h->h2d_done[0], h->copy_stream));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->h2d_done[0], 0));
-    if ((rc = pre_rows(lch, 0, 0, T1))) return rc;
-  } else if (F > 0 && h_frames) {
-    const int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(UIS_H2D_CHUNKS, F / UIS_H2D_MIN_FRAMES));
-    while ((int)h->h2d_done.size() < n_chunks) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->h2d_done.push_back(e);
-    }
-    HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_begin, 0));
-    // float64 utterances: cast into the pinned staging buffer by the handle's pool (and this thread),
-    // piece p + 1 while piece p copies / projects.  A projection chunk then travels in several pieces,
-    // so that the first copy starts after an eighth of the cast, not half of it.
-    if (h->src64) {
-      if (!h->cast_pool) h->cast_pool = new CastPool();
-      team.reset(new CastTeam(h->src64, offsets, n_utt, m.D, F, h->h_cast));
-      team_guard.pool = static_cast<CastPool*>(h->cast_pool);
-      team_guard.pool->post(team.get());
-    }
-    const int pieces = team ? (int)std::max<int64_t>(1, std::min<int64_t>(UIS_F64_PIECES, (F / n_chunks) / 1024)) : 1;
-    for (int c = 0; c < n_chunks; ++c) {
-      const int64_t f0 = F * c / n_chunks, f1 = F * (c + 1) / n_chunks;
-      for (int pc = 0; pc < pieces; ++pc) {
-        const int64_t g0 = f0 + (f1 - f0) * pc / pieces, g1 = f0 + (f1 - f0) * (pc + 1) / pieces;
-        if (team) team->wait_rows(g1);
-        HIPCHK(hipMemcpyAsync(const_cast<float*>(d_frames) + (size_t)g0 * m.D, h_frames + (size_t)g0 * m.D,
-                              (size_t)(g1 - g0) * m.D * 4, hipMemcpyHostToDevice, h->copy_stream));
-      }
-      HIPCHK(hipEventRecord(h->h2d_done[c], h->copy_stream));
-      HIPCHK(hipStreamWaitEvent(h->stream, h->h2d_done[c], 0));
-      if ((rc = pre_chunk(f0, f1))) return rc;
-    }
-  } else if (F > 0) {
-    if ((rc = pre_chunk(0, F))) return rc;
   }
-  HIPCHK(hipEventRecord(h->ev_pre, h->stream));
+  // the copy units of slice k, then its projection on lch's stream once they have landed
+  int slice(Launcher& lch, size_t k) {
+    int rc;
+    for (size_t un = unit_first[k]; un < unit_first[k + 1]; ++un)
+      if ((rc = copy_rows(un))) return rc;
+    HIPCHK(hipEventRecord(h->h2d_done[k], h->copy_stream));
+    HIPCHK(hipStreamWaitEvent(lch.stream, h->h2d_done[k], 0));
+    return pre_rows(lch, k);
+  }
 
-  // ---- group views of the shared buffers
-  const size_t rows_per_utt = (size_t)(L == 1 ? B : NC);
-  for (int g = 0; g < G; ++g) {
-    GroupPlan& gp = groups[g];
+  int begin(Launcher& lch) {
+    const int64_t F = c.shape.F;
+    const int U = c.shape.U;
+    int rc;
+    drain = true;  // from here on DMA from the caller's (or the pinned staging) memory may be in flight
+    if (c.plan.split) {
+      if ((rc = grow_events(h->h2d_done, cuts().size() + 1))) return rc;
+      HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_begin, 0));
+      if (!uniform) {  // the slices' batch tables: {first row, rows} per utterance and slice
+        std::vector<long>& tab = split_tab_host;
+        tab.assign((cuts().size() + 1) * (size_t)U * 2, 0L);
+        for (size_t k = 0; k <= cuts().size(); ++k) {
+          for (int u = 0; u < U; ++u) {
+            const int64_t nu = c.offsets[u + 1] - c.offsets[u], a = std::min(slice_begin(k), nu);
+            tab[(k * U + u) * 2] = (long)(c.offsets[u] + a);
+            tab[(k * U + u) * 2 + 1] = (long)(std::min(slice_end(k), nu) - a);
+          }
+        }
+        HIPCHK(hipMemcpyAsync(h->split_tab.p, tab.data(), tab.size() * sizeof(long), hipMemcpyHostToDevice, h->stream));
+        // (the scatter runs on the copy stream: its tables go up on that stream, ahead of the first block)
+        HIPCHK(hipMemcpyAsync(h->scatter_tab.p, scatter_tab_host.data(), scatter_tab_host.size() * sizeof(long), hipMemcpyHostToDevice,
+                              h->copy_stream));
+      }
+      return slice(lch, 0);
+    }
+    if (F > 0 && c.h_frames) {
+      // Host frames (uis_decode) arrive in chunks on the copy stream; chunk i's kernels overlap the
+      // H2D of chunk i+1 (true overlap needs pinned host memory, uis_host_alloc).
+      const int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(UIS_H2D_CHUNKS, F / UIS_H2D_MIN_FRAMES));
+      if ((rc = grow_events(h->h2d_done, (size_t)n_chunks))) return rc;
+      HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_begin, 0));
+      // float64 utterances: cast into the pinned staging buffer by the handle's pool (and this thread),
+      // piece p + 1 while piece p copies / projects.  A projection chunk then travels in several pieces,
+      // so that the first copy starts after an eighth of the cast, not half of it.
+      if (h->src64) post();
+      const int pieces = team ? (int)std::max<int64_t>(1, std::min<int64_t>(UIS_F64_PIECES, (F / n_chunks) / 1024)) : 1;
+      for (int ch = 0; ch < n_chunks; ++ch) {
+        const int64_t f0 = F * ch / n_chunks, f1 = F * (ch + 1) / n_chunks;
+        for (int pc = 0; pc < pieces; ++pc) {
+          const int64_t g0 = f0 + (f1 - f0) * pc / pieces, g1 = f0 + (f1 - f0) * (pc + 1) / pieces;
+          if (team) team->wait_rows(g1);
+          HIPCHK(hipMemcpyAsync(const_cast<float*>(c.d_frames) + (size_t)g0 * m.D, c.h_frames + (size_t)g0 * m.D,
+                                (size_t)(g1 - g0) * m.D * 4, hipMemcpyHostToDevice, h->copy_stream));
+        }
+        HIPCHK(hipEventRecord(h->h2d_done[ch], h->copy_stream));
+        HIPCHK(hipStreamWaitEvent(h->stream, h->h2d_done[ch], 0));
+        if ((rc = pre_chunk(lch, f0, f1))) return rc;
+      }
+      return UIS_OK;
+    }
+    return F > 0 ? pre_chunk(lch, 0, F) : UIS_OK;
+  }
+};
+
+// Step 5: every group's view of the shared buffers (pointers offset to the group's first utterance).
+void build_group_states(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const DevModel& m = h->m;
+  const DecodeShape& s = c.shape;
+  const int B = s.B, Kmax = s.Kmax, S = s.S, L = s.L;
+  const size_t NC = (size_t)s.NC, rows_per_utt = (size_t)(L == 1 ? B : s.NC);
+  for (int g = 0; g < s.G; ++g) {
+    GroupPlan& gp = c.groups[g];
     DecodeState& st = gp.st;
     const size_t u0 = (size_t)gp.u0;
-    st.U = gp.U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = L; st.tau = tau; st.flags = opts->flags | (knobs.agent_flags ? UIS_FLAG_AGENT_FLAGS : 0u); st.wnd = wnd ? 1 : 0;
+    st.U = gp.U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = L; st.tau = c.tau; st.flags = c.opts->flags | (c.knobs.agent_flags ? UIS_FLAG_AGENT_FLAGS : 0u); st.wnd = s.wnd ? 1 : 0;
     st.max_rows = (int)((size_t)gp.U * rows_per_utt);
     st.off = h->off.as<int64_t>() + u0;
     st.utt_step = h->utt_step.as<int32_t>() + u0;
     st.overflow = h->overflow.as<int32_t>() + u0;
-    st.x = d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
+    st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
     st.pool_hid = h->pool_hid.as<float>() + u0 * S * m.depth * m.Hp;
@@ -1736,25 +1741,17 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
     st.gi_up = h->gi_up.as<float>() + (m.depth > 1 ? (u0 * rows_per_utt + 48 * (size_t)g) * m.G : 0);
     st.a1 = h->a1.as<float>() + (u0 * rows_per_utt + 48 * (size_t)g) * m.Hp;
     st.counters = h->counters.as<unsigned long long>() + 4 * g;
-    st.cl_abort = ctl + 16;
     st.utt_nrows = h->utt_nrows.as<int32_t>() + 2 * u0;
-    st.hst = plan.hst ? h->hst.as<float>() : nullptr;
+    st.hst = c.plan.hst ? h->hst.as<float>() : nullptr;
     st.step0 = 0; st.step1 = 0; st.resume = h->resume.as<unsigned char>(); st.resume_stride = 0;
-    st.hst_elems = (size_t)rows_cap * m.Hp;
-    st.dbg_scores = dbg ? h->dbg_scores.as<float>() + 0 : nullptr;  // (one group: groups would need their own utterance offset)
-    if (plan.clustered()) {
-      st.ncl = plan.ncl;
-      st.cl_xcc = ctl;
-      st.rx_stride = plan.rx_stride;
-      st.rx_nrows = reinterpret_cast<int32_t*>(ctl) + 32;
-      st.rx_bar = ctl + 32 + UIS_MAX_CLUSTERS * 32;
-      st.rx_flags = ctl + 32 + 2 * UIS_MAX_CLUSTERS * 32;
-      if (rs) {  // (one group)
-        st.mse_tab = h->mse_tab.as<float>();
-        st.mse_part = reinterpret_cast<float*>(h->mse_tab.as<char>() + mse_tab_bytes);
-      }
+    st.hst_elems = (size_t)c.plan.rows_cap * m.Hp;
+    st.dbg_scores = c.dbg ? h->dbg_scores.as<float>() + 0 : nullptr;  // (one group: groups would need their own utterance offset)
+    wire_cluster_ctl(st, c.ctl, c.plan.clustered() ? &c.plan : nullptr);
+    if (c.rs) {  // (one group)
+      st.mse_tab = h->mse_tab.as<float>();
+      st.mse_part = reinterpret_cast<float*>(h->mse_tab.as<char>() + c.mse_tab_bytes);
     }
-    if (wnd) {  // level buffers: groups back to back, each [2][U_g][NC]...
+    if (s.wnd) {  // level buffers: groups back to back, each [2][U_g][NC]...
       st.NC = (int)NC;
       st.lv_n = h->lv_n.as<int32_t>() + 2 * u0;
       st.lv_K = h->lv_K.as<int32_t>() + 2 * u0 * NC;
@@ -1765,124 +1762,121 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
       st.lv_path = h->lv_path.as<int16_t>() + 2 * u0 * NC * L;
       st.lv_slot = h->lv_slot.as<int32_t>() + 2 * u0 * NC * Kmax;
       st.lv_blk = h->lv_blk.as<int32_t>() + 2 * u0 * NC * Kmax;
-      st.scratch = h->scratch.as<unsigned char>() + u0 * wsl.total;
-      st.scratch_stride = wsl.total;
+      st.scratch = h->scratch.as<unsigned char>() + u0 * c.wsl.total;
+      st.scratch_stride = c.wsl.total;
       st.bp16 = h->bp16.as<uint16_t>();
       st.bp_base = h->bp_base.as<int64_t>() + u0;
     }
   }
+}
 
-  // ---- the decode of every group on its own stream
-  const DecodeKernel cluster_kern = plan.clustered() && !rs ? cluster_kernel(plan, m, L) : nullptr;
-  const RsKernel rs_kern = rs ? find_kernel(kernels::rs, m.Hp, m.Dp, plan.rs_kind) : nullptr;
-  if (plan.clustered() && !cluster_kern && !rs_kern) return fail(UIS_ERR_HIP, "no one-launch kernel instantiated for this shape");
-  for (int g = 0; g < G; ++g) {
-    GroupPlan& gp = groups[g];
-    hipStream_t sg = h->gstreams[g];
-    Launcher gl{h, sg, profile};
-    Launcher& lch = gl;  // LAUNCH() below targets this group's stream
-    HIPCHK(hipStreamWaitEvent(sg, h->ev_pre, 0));
-    LAUNCH(-1, k_init_state, dim3((gp.U + 255) / 256), dim3(256), 0, gp.st);
-    if (plan.clustered()) {
-      // h1 (of every layer) into the extra slot, then ONE launch for every step of every utterance -- or (split) one
-      // per slice of the frames, the next slice arriving behind it
-      HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)U * S * m.depth * m.Hp, m.h1, (size_t)m.depth * m.Hp * 4, hipMemcpyDeviceToDevice, sg));
-      for (size_t k = 0; k <= cuts.size(); ++k) {
-        if (k > 0) {
-          // slice k of every utterance: cast (float64 lists), one strided copy, projection -- behind launch k - 1
-          const int64_t t0 = cuts[k - 1], t1 = k < cuts.size() ? cuts[k] : uniN;
-          for (size_t un = unit_first[k]; un < unit_first[k + 1]; ++un) {
-            if (team) team->wait_blocks(cast_blocks_upto[un]);
-            if ((rc = copy_rows(un))) return rc;
-          }
-          HIPCHK(hipEventRecord(h->h2d_done[k], h->copy_stream));
-          HIPCHK(hipStreamWaitEvent(sg, h->h2d_done[k], 0));
-          if ((rc = pre_rows(gl, k, t0, t1))) return rc;
-          // (k_decode_big<WS> counts its barriers and rows from zero in every launch; the abort word and the XCC ids stay)
-          if (!rs) HIPCHK(hipMemsetAsync(ctl + 32, 0, (ctl_words - 32) * 4, sg));
-        }
-        if (split) {
-          gp.st.step0 = k ? (int)cuts[k - 1] - 1 : 0;
-          gp.st.step1 = k < cuts.size() ? (int)cuts[k] - 1 : 0;
-        }
-        if ((rc = rs ? launch_rs_kernel(gl, rs_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st, h->bp.cap)
-                     : launch_cluster_kernel(gl, cluster_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st))) return rc;
-      }
-    } else if (plan.path == DecodePath::SMALL) {
-      DecodeKernel kern = L == 1 ? &k_decode_small<false> : &k_decode_small<true>;
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-      LAUNCH(UIS_K_GRU, kern, dim3(gp.U), dim3(512), plan.lds, m, gp.st);
-    } else if (plan.path == DecodePath::GRAPH && gp.maxT >= UIS_GRAPH_STEPS) {
-      GraphCache& gc = h->gcache[g];
-      const bool same = gc.exec && gc.lds == plan.lds && memcmp(&gc.st, &gp.st, sizeof(DecodeState)) == 0;
-      if (!same) {
-        if (gc.exec) { (void)hipGraphExecDestroy(gc.exec); gc.exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        HIPCHK(hipStreamBeginCapture(sg, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_steps(h, gl, gp.st, plan.lds, UIS_GRAPH_STEPS);
-        hipError_t ce = hipStreamEndCapture(sg, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        ce = hipGraphInstantiate(&gc.exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ce != hipSuccess) { gc.exec = nullptr; return fail(UIS_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ce)); }
-        gc.st = gp.st; gc.lds = plan.lds;
-      }
-      const int64_t nlaunch = (gp.maxT + UIS_GRAPH_STEPS - 1) / UIS_GRAPH_STEPS;  // the tail steps are no-ops
-      for (int64_t i = 0; i < nlaunch; ++i) HIPCHK(hipGraphLaunch(gc.exec, sg));
-    } else {
-      const int64_t nsteps = gp.maxT + (gp.maxT & 1);
-      for (int64_t s0 = 0; s0 < nsteps; s0 += 2)
-        if ((rc = enqueue_steps(h, gl, gp.st, plan.lds, 2))) return rc;
-    }
-    if (!wnd)
-      LAUNCH(UIS_K_BACKTRACE, k_backtrace, dim3(gp.U), dim3(64), (size_t)64 * B, gp.st, d_labels,
-             d_scores ? d_scores + gp.u0 : nullptr, h->beam_scores_out.as<float>() + (size_t)gp.u0 * B);
-    else
-      LAUNCH(UIS_K_BACKTRACE, k_backtrace_window, dim3((gp.U + 63) / 64), dim3(64), 0, gp.st, d_labels,
-             d_scores ? d_scores + gp.u0 : nullptr, h->beam_scores_out.as<float>() + (size_t)gp.u0 * B);
-    HIPCHK(hipEventRecord(h->gdone[g], sg));
+// The step kernels of a group as a captured graph of UIS_GRAPH_STEPS steps, launched as often as the group needs
+// (the graph is kept while the group's state and LDS size stay what they were).
+int launch_graph(DecodeCall& c, int g, Launcher& gl) {
+  uis_handle* h = c.h;
+  const GroupPlan& gp = c.groups[g];
+  GraphCache& gc = h->gcache[g];
+  const bool same = gc.exec && gc.lds == c.plan.lds && memcmp(&gc.st, &gp.st, sizeof(DecodeState)) == 0;
+  if (!same) {
+    if (gc.exec) { (void)hipGraphExecDestroy(gc.exec); gc.exec = nullptr; }
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(gl.stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue_steps(h, gl, gp.st, c.plan.lds, UIS_GRAPH_STEPS);
+    hipError_t ce = hipStreamEndCapture(gl.stream, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    ce = hipGraphInstantiate(&gc.exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ce != hipSuccess) { gc.exec = nullptr; return fail(UIS_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ce)); }
+    gc.st = gp.st; gc.lds = c.plan.lds;
   }
-  for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(h->stream, h->gdone[g], 0));
-  HIPCHK(hipEventRecord(h->ev_end, h->stream));
+  const int64_t nlaunch = (gp.maxT + UIS_GRAPH_STEPS - 1) / UIS_GRAPH_STEPS;  // the tail steps are no-ops
+  for (int64_t i = 0; i < nlaunch; ++i) HIPCHK(hipGraphLaunch(gc.exec, gl.stream));
+  return UIS_OK;
+}
 
-  // ---- stats
+// Step 6: the decode of group g on its own stream, by the plan's path, and its back-trace.
+int launch_group(DecodeCall& c, Ingest& ing, int g) {
+  uis_handle* h = c.h;
+  const DevModel& m = h->m;
+  const DecodeShape& s = c.shape;
+  const DecodePlan& plan = c.plan;
+  GroupPlan& gp = c.groups[g];
+  hipStream_t sg = h->gstreams[g];
+  Launcher lch{h, sg, c.profile};  // LAUNCH() below targets this group's stream
+  int rc;
+  HIPCHK(hipStreamWaitEvent(sg, h->ev_pre, 0));
+  LAUNCH(-1, k_init_state, dim3((gp.U + 255) / 256), dim3(256), 0, gp.st);
+  if (plan.clustered()) {
+    // h1 (of every layer) into the extra slot, then ONE launch for every step of every utterance -- or (split) one
+    // per slice of the frames, the next slice arriving behind it
+    HIPCHK(hipMemcpyAsync(gp.st.pool_hid + (size_t)s.U * s.S * m.depth * m.Hp, m.h1, (size_t)m.depth * m.Hp * 4, hipMemcpyDeviceToDevice, sg));
+    const std::vector<int64_t>& cuts = plan.cuts;
+    for (size_t k = 0; k <= cuts.size(); ++k) {
+      if (k > 0) {
+        // slice k of every utterance: cast (float64 lists), one strided copy, projection -- behind launch k - 1
+        if ((rc = ing.slice(lch, k))) return rc;
+        // (k_decode_big<WS> counts its barriers and rows from zero in every launch; the abort word and the XCC ids stay)
+        if (!c.rs) HIPCHK(hipMemsetAsync(c.ctl + 32, 0, (kCtlWords - 32) * 4, sg));
+      }
+      if (plan.split) {
+        gp.st.step0 = k ? (int)cuts[k - 1] - 1 : 0;
+        gp.st.step1 = k < cuts.size() ? (int)cuts[k] - 1 : 0;
+      }
+      if ((rc = c.rs ? launch_rs_kernel(lch, c.rs_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st, h->bp.cap)
+                     : launch_cluster_kernel(lch, c.cluster_kern, h->n_cu, plan.ncl, plan.lds, m, gp.st))) return rc;
+    }
+  } else if (plan.path == DecodePath::SMALL) {
+    DecodeKernel kern = s.L == 1 ? &k_decode_small<false> : &k_decode_small<true>;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    LAUNCH(UIS_K_GRU, kern, dim3(gp.U), dim3(512), plan.lds, m, gp.st);
+  } else if (plan.path == DecodePath::GRAPH && gp.maxT >= UIS_GRAPH_STEPS) {
+    if ((rc = launch_graph(c, g, lch))) return rc;
+  } else {
+    const int64_t nsteps = gp.maxT + (gp.maxT & 1);
+    for (int64_t s0 = 0; s0 < nsteps; s0 += 2)
+      if ((rc = enqueue_steps(h, lch, gp.st, plan.lds, 2))) return rc;
+  }
+  float* const scores = c.d_scores ? c.d_scores + gp.u0 : nullptr;
+  float* const beam_scores = h->beam_scores_out.as<float>() + (size_t)gp.u0 * s.B;
+  if (!s.wnd) LAUNCH(UIS_K_BACKTRACE, k_backtrace, dim3(gp.U), dim3(64), (size_t)64 * s.B, gp.st, c.d_labels, scores, beam_scores);
+  else LAUNCH(UIS_K_BACKTRACE, k_backtrace_window, dim3((gp.U + 63) / 64), dim3(64), 0, gp.st, c.d_labels, scores, beam_scores);
+  HIPCHK(hipEventRecord(h->gdone[g], sg));
+  return UIS_OK;
+}
+
+// Step 7: what the decode left behind -- its counters, flags and final beam to the host, uis_stats, and the state
+// uis_last_decode_nbest reads.
+int collect_results(DecodeCall& c) {
+  uis_handle* h = c.h;
+  const DecodeShape& s = c.shape;
+  const int U = s.U, G = s.G;
   std::vector<unsigned long long> counters((size_t)UIS_MAX_GROUPS * 4, 0ull);
   HIPCHK(hipMemcpyAsync(counters.data(), h->counters.p, (size_t)G * 4 * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(h->last_overflow.data(), h->overflow.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), h->beam_scores_out.p, (size_t)U * B * 4, hipMemcpyDeviceToHost,
+  HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), h->beam_scores_out.p, (size_t)U * s.B * 4, hipMemcpyDeviceToHost,
                         h->stream));
   uint32_t abort_word = 0;
-  HIPCHK(hipMemcpyAsync(&abort_word, ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&abort_word, c.ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (dbg) h->dbg_floats = dbg_floats;
+  if (c.dbg) h->dbg_floats = c.dbg_floats;
   if (abort_word) {
     h->inlaunch_failed = true;
     return fail(UIS_ERR_HIP, abort_word == 2 ? "workgroup cluster not placed on one XCD (in-launch barrier path)"
                                              : "in-launch barrier timed out");
   }
+  int rc;
 #if defined(UIS_SELECT_TIMING) || defined(UIS_RESIDENT_PROBE) || defined(UIS_RS_COUNT_PATHS) || defined(UIS_RESIDENT_TIMING)
-  if ((rc = report_diagnostics(h, plan, U, maxT, L))) return rc;
+  if ((rc = report_diagnostics(h, c.plan, U, s.maxT, s.L))) return rc;
 #endif
-  if (ctl_tune && tn.sig != 0 && tn.phase <= 4) {  // the decode's device time goes to the placement it ran with
+  if ((rc = ctl_record(c))) return rc;
+  const int n_over = count_cluster_cap(h->last_overflow);
+  int n_level = 0;
+  for (int u = 0; u < U; ++u) n_level += (h->last_overflow[u] & 2) != 0;  // look_ahead >= 2: an intermediate level was full
+  if (uis_stats* stats = c.stats) {
     float ms = 0.0f;
     HIPCHK(hipEventElapsedTime(&ms, h->ev_begin, h->ev_end));
-    if (tn.phase >= 1) tn.ms[tn.phase - 1] = ms;
-    if (++tn.phase == 5) {
-      tn.best = 0;
-      for (int k = 1; k < 4; ++k)
-        if (tn.ms[k] < 0.995f * tn.ms[tn.best]) tn.best = k;  // (another placement has to win by 0.5 %: repeats agree to 0.1 %)
-    }
-  }
-  int n_over = 0, n_level = 0;
-  for (int u = 0; u < U; ++u) {
-    n_level += (h->last_overflow[u] & 2) != 0;  // look_ahead >= 2: an intermediate level was full
-    n_over += h->last_overflow[u] != 0;
-  }
-  if (stats) {
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev_begin, h->ev_end));
-    stats->n_steps = (int32_t)maxT;
+    stats->n_steps = (int32_t)s.maxT;
     stats->decode_ms = ms;
     for (int g = 0; g < G; ++g) {
       stats->rnn_rows += (int64_t)counters[4 * g + 0];
@@ -1892,33 +1886,54 @@ replan:  // (taken once at most, from below the workspace list: k_decode_rs's st
     }
     stats->n_overflow = n_over;
     stats->n_streams = G;
-    stats->decode_kernel = plan.decode_kernel;
-    stats->decode_launches = plan.one_launch() ? (int)cuts.size() + 1 : 0;
-    if (profile) {
+    stats->decode_kernel = c.plan.decode_kernel;
+    stats->decode_launches = c.plan.one_launch() ? (int)c.plan.cuts.size() + 1 : 0;
+    if (c.profile) {
       for (size_t i = 0; i + 1 < h->prof.used; i += 2) {
         float t = 0.0f;
         HIPCHK(hipEventElapsedTime(&t, h->prof.ev[i], h->prof.ev[i + 1]));
-        const int c = h->prof.cls[i / 2];
-        if (c < 0) continue;
-        stats->kernel_ms[c] += t;
-        stats->kernel_launches[c] += 1;
+        const int cl = h->prof.cls[i / 2];
+        if (cl < 0) continue;
+        stats->kernel_ms[cl] += t;
+        stats->kernel_launches[cl] += 1;
       }
     }
   }
   if (n_level)
     return fail(UIS_ERR_UNSUPPORTED,
-                std::to_string(n_level) + " utterance(s) had more than " + std::to_string((long long)NC) +
+                std::to_string(n_level) + " utterance(s) had more than " + std::to_string((long long)s.NC) +
                     " live assignment prefixes inside a look-ahead window (beam_size * clusters ^ (look_ahead - 1)); "
                     "a larger max_clusters cannot help: lower look_ahead or beam_size");
   // the back-pointers and the final beam of every group stay where they are until the next decode: uis_last_decode_nbest
   h->nb_groups.clear();
-  for (int g = 0; g < G; ++g) h->nb_groups.push_back(uis_handle::NbestGroup{groups[g].st, groups[g].u0});
-  h->nb_offsets.assign(offsets, offsets + U + 1);
-  h->nb_B = B; h->nb_wnd = wnd; h->nb_valid = true;
-  if (n_over)
-    return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
-                                         std::to_string(Kmax) + " clusters per hypothesis");
-  return UIS_OK;
+  for (int g = 0; g < G; ++g) h->nb_groups.push_back(uis_handle::NbestGroup{c.groups[g].st, c.groups[g].u0});
+  h->nb_offsets.assign(c.offsets, c.offsets + U + 1);
+  h->nb_B = s.B; h->nb_wnd = s.wnd; h->nb_valid = true;
+  return cluster_cap_status(n_over, s.Kmax);
+}
+
+int decode_once(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
+                const uis_decode_opts* opts, int32_t* d_labels, float* d_scores, uis_stats* stats,
+                const float* h_frames = nullptr) {
+  if (!h || !offsets || !opts || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets/opts or negative n_utt");
+  DecodeCall c{h, d_frames, offsets, n_utt, opts, d_labels, d_scores, stats, h_frames, read_knobs()};
+  int rc;
+  if ((rc = derive_shape(c)) || c.shape.U == 0) return rc;
+  if ((rc = plan_and_place(c))) return rc;
+  ctl_choose(c);
+  Launcher lch{h, h->stream, c.profile};
+  Ingest ing(c);  // (declared after `c`: its way out drains the streams while c's tables are still there)
+  ing.start();
+  if ((rc = upload_tables(c))) return rc;
+  if ((rc = ing.begin(lch))) return rc;
+  HIPCHK(hipEventRecord(h->ev_pre, h->stream));
+  build_group_states(c);
+  if (c.plan.clustered() && !c.cluster_kern && !c.rs_kern) return fail(UIS_ERR_HIP, "no one-launch kernel instantiated for this shape");
+  for (int g = 0; g < c.shape.G; ++g)
+    if ((rc = launch_group(c, ing, g))) return rc;
+  for (int g = 0; g < c.shape.G; ++g) HIPCHK(hipStreamWaitEvent(h->stream, h->gdone[g], 0));
+  HIPCHK(hipEventRecord(h->ev_end, h->stream));
+  return collect_results(c);
 }
 
 // One decode; if the one-launch path was chosen automatically and its placement / barrier checks
@@ -1956,14 +1971,14 @@ UIS_EXPORT const char* uis_last_error(void) { return g_err.c_str(); }
 // same thread-local message uis_last_error() returns.
 int uis_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
 
-static void stream_free_on_destroy(uis_handle* h) {
-  for (void* p : h->stream_state.allocs) (void)hipFree(p);
-  h->stream_state.allocs.clear();
-  DevBuf* bufs[] = {&h->stream_state.chunk_x, &h->stream_state.chunk_pad, &h->stream_state.chunk_gi0,
-                    &h->stream_state.chunk_mse0, &h->stream_state.labels, &h->stream_state.scores};
-  for (DevBuf* b : bufs) b->release();
-  if (h->stream_state.h_stage) { (void)hipHostFree(h->stream_state.h_stage); h->stream_state.h_stage = nullptr; }
-  if (h->stream_state.pm_block) { (void)hipHostFree(h->stream_state.pm_block); h->stream_state.pm_block = nullptr; }
+// A session's memory back to the device and the host, and the session closed (uis_stream_end, a uis_stream_begin that
+// fails half-way, uis_destroy).
+static void stream_free(uis_handle* h) {
+  uis_handle::Stream& ss = h->stream_state;
+  static_cast<StreamMem&>(ss) = StreamMem{};
+  ss.persist = false; ss.pm_running = false;
+  ss.active = false;
+  ss.have.clear();
 }
 
 UIS_EXPORT void uis_destroy(uis_handle* h) {
@@ -1974,18 +1989,9 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
     h->stream_state.pm_running = false;
   }
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  stream_free_on_destroy(h);
+  stream_free(h);
   for (void* p : h->model_allocs) (void)hipFree(p);
-  DevBuf* bufs[] = {&h->off, &h->utt_step, &h->overflow, &h->xpad, &h->gi0, &h->mse0, &h->logblk, &h->logden,
-                    &h->pool_mean, &h->pool_hid, &h->pool_cnt, &h->beam_n, &h->beam_K, &h->beam_last, &h->beam_sum,
-                    &h->beam_score, &h->beam_slot, &h->beam_blk, &h->bp, &h->rows, &h->nrows, &h->gi_up, &h->a1,
-                    &h->counters, &h->beam_scores_out, &h->io_frames, &h->io_labels, &h->io_scores, &h->mse_tab, &h->dbg_scores, &h->utt_nrows, &h->hst, &h->resume, &h->split_tab, &h->scatter_tab, &h->stage,
-                    &h->lv_n, &h->lv_K, &h->lv_last, &h->lv_sum, &h->lv_score, &h->lv_origin, &h->lv_path, &h->lv_slot,
-                    &h->lv_blk, &h->scratch, &h->bp16, &h->bp_base, &h->cluster_ctl, &h->rs_block, &h->arena,
-                    &h->ev_a, &h->ev_b, &h->ev_off, &h->ev_out, &h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0,
-                    &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean, &h->sc_gi_up, &h->sc_rows, &h->sc_chains,
-                    &h->sc_utt, &h->sc_out, &h->nb_labels, &h->nb_scores, &h->nb_counts, &h->nb_stable, &h->nb_off};
-  for (DevBuf* b : bufs) b->release();
+  static_cast<HandleMem&>(*h) = HandleMem{};  // (every buffer, before the streams they were used on go)
   for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
@@ -1995,8 +2001,6 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
   for (hipStream_t sg : h->gstreams) { (void)hipStreamSynchronize(sg); (void)hipStreamDestroy(sg); }
   for (hipEvent_t e : h->h2d_done) (void)hipEventDestroy(e);
   if (h->cast_pool) { delete static_cast<CastPool*>(h->cast_pool); h->cast_pool = nullptr; }
-  if (h->h_cast) (void)hipHostFree(h->h_cast);
-  if (h->h_out) (void)hipHostFree(h->h_out);
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -2137,16 +2141,11 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
   float* sc_dst = scores_out;
   if (h->src64) {
     const size_t need = (size_t)std::max<int64_t>(F, 1) * 4 + (size_t)std::max(n_utt, 1) * 4;
-    if (need > h->h_out_cap) {
-      if (h->h_out) { (void)hipHostFree(h->h_out); h->h_out = nullptr; h->h_out_cap = 0; }
-      void* p = nullptr;
-      if (hipHostMalloc(&p, need, hipHostMallocDefault) == hipSuccess) { h->h_out = p; h->h_out_cap = need; }
-      else (void)hipGetLastError();  // (no pinned memory to be had: straight into the caller's arrays)
-    }
-    poison.host(h->h_out, h->h_out_cap);  // (before the copies that land in it are enqueued)
-    if (h->h_out) {
-      lab_dst = static_cast<int32_t*>(h->h_out);
-      sc_dst = reinterpret_cast<float*>(static_cast<char*>(h->h_out) + (size_t)std::max<int64_t>(F, 1) * 4);
+    if (h->h_out.ensure(need, hipHostMallocDefault) != hipSuccess) (void)hipGetLastError();  // (no pinned memory to be had: straight into the caller's arrays)
+    poison.host(h->h_out.p, h->h_out.cap);  // (before the copies that land in it are enqueued)
+    if (h->h_out.p) {
+      lab_dst = h->h_out.as<int32_t>();
+      sc_dst = reinterpret_cast<float*>(h->h_out.as<char>() + (size_t)std::max<int64_t>(F, 1) * 4);
     }
   }
   // (a copy that fails below fails the decode: then there is nothing for uis_last_decode_nbest either)
@@ -2179,18 +2178,12 @@ UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances
   const int64_t F = offsets[n_utt];
   const size_t need = (size_t)std::max<int64_t>(F, 1) * h->m.D * 4;
   HIPCHK(hipSetDevice(h->device));
-  if (need > h->h_cast_cap) {  // grow only, like the device workspace
-    if (h->h_cast) { (void)hipHostFree(h->h_cast); h->h_cast = nullptr; h->h_cast_cap = 0; }
-    void* p = nullptr;
-    hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc (float32 staging): ") + hipGetErrorString(e));
-    h->h_cast = static_cast<float*>(p);
-    h->h_cast_cap = need;
-  }
+  const hipError_t e = h->h_cast.ensure(need, hipHostMallocDefault);  // grow only, like the device workspace
+  if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc (float32 staging): ") + hipGetErrorString(e));
   h->poison = UisPoison::from_env();
-  h->poison.host(h->h_cast, h->h_cast_cap);  // (before the cast team is posted)
+  h->poison.host(h->h_cast.p, h->h_cast.cap);  // (before the cast team is posted)
   h->src64 = utterances;
-  const int rc = uis_decode(h, h->h_cast, offsets.data(), n_utt, opts, labels_out, scores_out, stats);
+  const int rc = uis_decode(h, h->h_cast.as<float>(), offsets.data(), n_utt, opts, labels_out, scores_out, stats);
   h->src64 = nullptr;
   return rc;
 }
@@ -2265,606 +2258,8 @@ UIS_EXPORT int32_t uis_debug_scores(uis_handle* h, float* scores_out, int64_t ca
   return UIS_OK;
 }
 
-
-// ------------------------------------------------------------------ streaming
-//
-// Online decoding (the caller side of the path -- UIS-RNN is an online model, the
-// reference only offers offline predict()).  A session keeps the beam, the cluster-state pool
-// and the back-pointers of n_utt utterances on the device; uis_stream_push() appends frames (any
-// number per utterance, also none) and advances every utterance by the frames it received;
-// uis_stream_labels() reads the best hypothesis' labels for everything received so far.
-// Semantics = predict_single with test_iteration 1 (uisrnn.py:479-562): pushing an utterance
-// in any chunking gives bit for bit the labels / scores of one uis_decode over the whole of it
-// (tests/test_gpu_stream.py).  look_ahead 1.  A push of four or more steps runs as ONE launch of
-// k_decode_resident where that kernel applies, shorter pushes on the launch-per-step kernels.
-
-namespace {
-
-void stream_free(uis_handle* h) {
-  uis_handle::Stream& ss = h->stream_state;
-  for (void* p : ss.allocs) (void)hipFree(p);
-  ss.allocs.clear();
-  DevBuf* bufs[] = {&ss.chunk_x, &ss.chunk_pad, &ss.chunk_gi0, &ss.chunk_mse0, &ss.labels, &ss.scores};
-  for (DevBuf* b : bufs) b->release();
-  if (ss.h_stage) { (void)hipHostFree(ss.h_stage); ss.h_stage = nullptr; ss.h_stage_cap = 0; }
-  if (ss.pm_block) { (void)hipHostFree(ss.pm_block); ss.pm_block = nullptr; }
-  ss.persist = false; ss.pm_running = false;
-  ss.active = false;
-  ss.have.clear();
-}
-
-template <typename T>
-int stream_alloc(uis_handle* h, T** out, size_t count, bool zero = false) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) return fail(UIS_ERR_OOM, "hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
-  h->stream_state.allocs.push_back(p);
-  HIPCHK(h->stream_state.poison.device(p, bytes, h->stream));  // (UIS_POISON_WORKSPACE: ahead of the block's defining writes)
-  if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, h->stream));
-  *out = static_cast<T*>(p);
-  return UIS_OK;
-}
-
-// ---- the persistent launch of a UIS_FLAG_PERSISTENT session
-//
-// Mailbox protocol (pm_block, host-coherent pinned memory; uint32 view, one 64-byte line per item,
-// uis_kernels.h UIS_PM_*_WORD): a doorbell line per cluster {sequence number, command | frames << 8,
-// first row | rows << 16} whose sequence number the host writes LAST (release) and rank 0 of the
-// cluster polls with one 16-byte read; the sequence number of the last command each cluster
-// completed; a word per cluster that turns non-zero when the cluster has left the kernel.
-// While the launch is on the device the host makes NO HIP call that could wait for the device:
-// everything a command needs was allocated by uis_stream_begin.
-
-double pm_now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-unsigned long long pm_idle_ticks() {
-  double ms = 50.0;  // without a command for this long the launch ends by itself (the next push starts a new one)
-  if (const char* e = getenv("UIS_PERSIST_IDLE_MS")) ms = atof(e);
-  ms = std::min(std::max(ms, 0.05), 2000.0);
-  return (unsigned long long)(ms * 1e5);  // s_memrealtime ticks of 10 ns
-}
-
-// After the launch has ended (every cluster left, or an in-launch barrier gave up): look at the abort word.
-int pm_reap(uis_handle* h) {
-  uis_handle::Stream& ss = h->stream_state;
-  // (a launch that is really stuck must not take the caller with it: poll with a deadline instead
-  // of an unbounded hipStreamSynchronize; the kernel's own barrier time-out is ~1 s)
-  {
-    const double t0 = pm_now_s();
-    hipError_t q;
-    while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) {
-      if (pm_now_s() - t0 > 15.0) {
-        ss.persist = false;
-        h->resident_off = true;
-        return fail(UIS_ERR_HIP, "the persistent streaming launch does not leave the device (15 s); the handle's "
-                                 "stream is unusable -- destroy the handle");
-      }
-      __builtin_ia32_pause();
-    }
-    if (q != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-  }
-  ss.pm_running = false;
-  uint32_t abort_word = 0;
-  HIPCHK(hipMemcpy(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost));
-  if (abort_word) {
-    ss.persist = false;
-    h->resident_off = true;
-    return fail(UIS_ERR_HIP, "in-launch barrier failed inside the persistent streaming launch; close the session "
-                             "(uis_stream_end) and reopen it with UIS_FLAG_STEPWISE");
-  }
-  return UIS_OK;
-}
-
-int pm_launch(uis_handle* h) {
-  uis_handle::Stream& ss = h->stream_state;
-  const DevModel& m = h->m;
-  DecodeState st = ss.st;
-  // the mailbox as the device sees it (the same address under unified addressing; asked for anyway)
-  void* blk_dev = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&blk_dev, ss.pm_block, 0));
-  unsigned char* blk = static_cast<unsigned char*>(blk_dev);
-  st.x = reinterpret_cast<const float*>(ss.chunk_x.as<char>());
-  st.gi0 = ss.chunk_gi0.as<float>();
-  st.mse0 = ss.chunk_mse0.as<float>();
-  st.push_F = 0;
-  PersistArgs& pa = ss.pm_args;
-  pa.ctl = reinterpret_cast<uint32_t*>(blk);
-  pa.foff = reinterpret_cast<const int64_t*>(blk + ss.pm_o_foff);
-  pa.avail = reinterpret_cast<const int32_t*>(blk + ss.pm_o_avail);
-  pa.lab_off = reinterpret_cast<const int64_t*>(blk + ss.pm_o_laboff);
-  pa.frames = reinterpret_cast<const float*>(blk + ss.pm_o_frames);
-  pa.labels = reinterpret_cast<int32_t*>(blk + ss.pm_o_labels);
-  pa.scores = reinterpret_cast<float*>(blk + ss.pm_o_scores);
-  pa.beam_scores = reinterpret_cast<float*>(blk + ss.pm_o_bscores);
-  pa.overflow = reinterpret_cast<int32_t*>(blk + ss.pm_o_overflow);
-  pa.go = ss.d_go;
-  pa.hdr = ss.d_hdr;
-  pa.hdr_stride = ss.hdr_stride;
-  pa.idle_ticks = pm_idle_ticks();
-  HIPCHK(hipMemcpyAsync(ss.d_pm_args, &pa, sizeof(pa), hipMemcpyHostToDevice, h->stream));
-  st.pm = ss.d_pm_args;
-  // avail / foff only have to be non-null here (the kernel points them at its cluster's copies)
-  st.avail = reinterpret_cast<const int32_t*>(ss.d_hdr);
-  st.foff = reinterpret_cast<const int64_t*>(ss.d_hdr);
-  HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
-  HIPCHK(hipMemsetAsync(ss.d_go, 0, (size_t)UIS_PM_MAX_CLUSTERS * 128, h->stream));
-  HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
-  Launcher lch{h, h->stream, false};
-  h->inlaunch_failed = false;
-  if (int rc = launch_cluster_kernel(lch, find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
-                                     one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st))
-    return rc;
-  ss.pm_running = true;
-  ss.pm_launches += 1;
-  return UIS_OK;
-}
-
-// Issue one command and wait until every cluster has completed it.  A launch that is not on the
-// device (never started, or left because it was idle) is started first when `may_launch`; a
-// launch that left while the command was on its way is reaped and the command issued again to a
-// new one -- harmless: a cluster that did take a push has nothing left to do for it.
-// Returns UIS_OK, an error, or 1 = not running and may_launch was false.
-int pm_command(uis_handle* h, uint32_t type, uint32_t frames, bool may_launch, const uint32_t* row0 = nullptr,
-               const uint32_t* nrow = nullptr) {
-  uis_handle::Stream& ss = h->stream_state;
-  volatile uint32_t* ctl = pm_ctl(ss);
-  const int ncl = ss.st.ncl;
-  for (int attempt = 0; attempt < 3; ++attempt) {
-    int rc;
-    if (!ss.pm_running) {
-      if (!may_launch) return 1;
-      for (int i = 0; i < UIS_PM_CTL_WORDS; ++i) ctl[i] = 0;
-      ss.pm_seq = 1;
-      pm_ring(ss, 1, type, frames, row0, nrow);
-      if ((rc = pm_launch(h))) return rc;
-    } else {
-      ss.pm_seq += 1;
-      pm_ring(ss, ss.pm_seq, type, frames, row0, nrow);
-    }
-    ss.pm_commands += 1;
-    const double t0 = pm_now_s();
-    bool left = false;
-    unsigned spins = 0;
-    for (;;) {
-      bool all = true;
-      for (int c = 0; c < ncl; ++c) all = all && ctl[UIS_PM_DONE_WORD + 16 * c] == ss.pm_seq;
-      if (all) return UIS_OK;
-      for (int c = 0; c < ncl; ++c) left = left || ctl[UIS_PM_LEFT_WORD + 16 * c] != 0;
-      if (left) break;
-      if ((++spins & 4095u) == 0) {
-        if (pm_now_s() - t0 > 10.0) break;
-        // (a launch that ended without saying so -- an in-launch barrier gave up -- is noticed here)
-        if ((spins & 0xffffu) == 0 && hipStreamQuery(h->stream) == hipSuccess) { left = true; break; }
-      }
-      __builtin_ia32_pause();
-    }
-    // a cluster left before (or instead of) completing the command: tell the others to leave too
-    // (they complete this command first if they had not seen it yet), then look at what happened
-    ss.pm_seq += 1;
-    pm_ring(ss, ss.pm_seq, UIS_PM_QUIT, 0);
-    if ((rc = pm_reap(h))) return rc;
-    if (!left) return fail(UIS_ERR_HIP, "the persistent streaming launch did not answer within 10 s");
-  }
-  return fail(UIS_ERR_HIP, "the persistent streaming launch kept leaving before it took the command");
-}
-
-int pm_quit(uis_handle* h) {
-  uis_handle::Stream& ss = h->stream_state;
-  if (!ss.pm_running) return UIS_OK;
-  ss.pm_seq += 1;
-  pm_ring(ss, ss.pm_seq, UIS_PM_QUIT, 0);
-  return pm_reap(h);
-}
-
-}  // namespace
-
-UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
-  if (!h || !opts || n_utt < 1 || max_frames < 1) return fail(UIS_ERR_INVALID_ARG, "null handle/opts, n_utt < 1 or max_frames < 1");
-  uis_handle::Stream& ss = h->stream_state;
-  if (ss.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is already open on this handle");
-  const DevModel& m = h->m;
-  const int B = opts->beam_size;
-  const int Kmax = opts->max_clusters > 0 ? opts->max_clusters : 16;
-  if (B < 1 || B > 256) return fail(UIS_ERR_UNSUPPORTED, "beam_size must be in [1, 256]");
-  if (opts->look_ahead != 1) return fail(UIS_ERR_UNSUPPORTED, "streaming needs look_ahead 1");
-  if (opts->test_iteration != 1) return fail(UIS_ERR_UNSUPPORTED, "streaming is online decoding: test_iteration must be 1");
-  if (Kmax > 4096) return fail(UIS_ERR_UNSUPPORTED, "max_clusters must be <= 4096");
-  if (max_frames > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "max_frames too large");
-  const int U = n_utt, S = B * Kmax + B;
-  const SelectLds lds = select_lds_layout(m.Dp, B, Kmax, S);
-  if (lds.total > 160 * 1024) return fail(UIS_ERR_UNSUPPORTED, "beam_size * max_clusters too large for the select kernel's LDS budget");
-  const double bytes = (double)U * S * (m.Dp + (double)m.depth * m.Hp) * 4.0 + (double)U * max_frames * B * 4.0;
-  if (bytes > 200e9) return fail(UIS_ERR_OOM, "streaming state would need " + std::to_string((long long)(bytes / 1e9)) + " GB");
-  HIPCHK(hipSetDevice(h->device));
-  ss = uis_handle::Stream{};
-  ss.poison = UisPoison::from_env();
-  ss.U = U; ss.B = B; ss.Kmax = Kmax; ss.S = S; ss.cap = max_frames;
-  ss.have.assign(U, 0);
-  DecodeState& st = ss.st;
-  st.U = U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = 1; st.tau = 1; st.flags = opts->flags | (agent_flags_env() ? UIS_FLAG_AGENT_FLAGS : 0u);
-  st.max_rows = U * B;
-  // a push advances the session with ONE launch of the resident decode kernel where that kernel
-  // applies (same conditions as uis_decode); UIS_FLAG_STEPWISE keeps the four kernels per step
-  const ClusterGeometry geo = cluster_geometry(h->n_cu, U, B, 0, 1);  // (one group, no row slack)
-  // (streams never ran the 128-wide kernel)
-  ss.resident = m.Hp != 128 && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) && resident_fits(m, U, B, Kmax, S, geo);
-  if ((opts->flags & UIS_FLAG_RESIDENT) && !ss.resident)
-    { ss = uis_handle::Stream{}; return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT: the one-launch decode does not apply to this session's shape"); }
-  int rc = UIS_OK;
-  int64_t* d_off = nullptr; double *d_logblk = nullptr, *d_logden = nullptr;
-#define SALLOC(ptr, count, zero) if ((rc = stream_alloc(h, &(ptr), (size_t)(count), zero))) { stream_free(h); return rc; }
-  SALLOC(d_off, U + 1, false);
-  SALLOC(st.utt_step, U, false);
-  SALLOC(st.overflow, U, false);
-  SALLOC(ss.d_avail, U, true);
-  SALLOC(ss.d_have, U, true);
-  SALLOC(ss.d_foff, U, true);
-  SALLOC(ss.d_lab_off, U, true);
-  SALLOC(d_logblk, max_frames + 2, false);
-  SALLOC(d_logden, max_frames + 2, false);
-  SALLOC(st.pool_mean, (size_t)U * S * m.Dp, false);
-  SALLOC(st.pool_hid, ((size_t)U * S + 1) * m.depth * m.Hp, false);
-  SALLOC(st.pool_cnt, (size_t)U * S, false);
-  SALLOC(st.beam_n, 2 * (size_t)U, false);
-  SALLOC(st.beam_K, 2 * (size_t)U * B, false);
-  SALLOC(st.beam_last, 2 * (size_t)U * B, false);
-  SALLOC(st.beam_sum, 2 * (size_t)U * B, false);
-  SALLOC(st.beam_score, 2 * (size_t)U * B, false);
-  SALLOC(st.beam_slot, 2 * (size_t)U * B * Kmax, false);
-  SALLOC(st.beam_blk, 2 * (size_t)U * B * Kmax, false);
-  SALLOC(st.bp, (size_t)U * max_frames * B, false);
-  SALLOC(st.rows, geo.rows_cap, true);
-  SALLOC(st.nrows, 2, true);
-  SALLOC(st.gi_up, m.depth > 1 ? (size_t)geo.rows_cap * m.G : (size_t)geo.rows_cap * m.Hp, false);  // depth 1: the resident kernel's h' staging
-  SALLOC(st.a1, (size_t)geo.rows_cap * m.Hp, true);
-  SALLOC(st.counters, 96, true);
-  ss.ctl_words = (size_t)32 + 3 * UIS_MAX_CLUSTERS * 32;
-  SALLOC(ss.d_ctl, ss.ctl_words, true);
-  st.cl_abort = ss.d_ctl + 16;
-  if (ss.resident) {
-    st.ncl = geo.ncl;
-    st.cl_xcc = ss.d_ctl;
-    st.rx_stride = geo.rx_stride;
-    st.rx_nrows = reinterpret_cast<int32_t*>(ss.d_ctl) + 32;
-    st.rx_bar = ss.d_ctl + 32 + UIS_MAX_CLUSTERS * 32;
-    st.rx_flags = ss.d_ctl + 32 + 2 * UIS_MAX_CLUSTERS * 32;
-  }
-  SALLOC(ss.d_beam_scores, (size_t)U * B, false);
-  if (opts->flags & UIS_FLAG_PERSISTENT) {
-    // the launch that stays: needs the one-launch shape with the beam in LDS (at most one utterance
-    // per workgroup), unpadded frames, and a mailbox that holds every label of the session
-    const bool shape = find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE) != nullptr;
-    const double label_bytes = (double)U * (double)max_frames * 4.0;
-    if (!(ss.resident && shape && U <= 32 * geo.ncl && m.D == m.Dp && label_bytes <= 256e6)) {
-      stream_free(h);
-      return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_PERSISTENT needs the one-launch shape (rnn_depth 1, rnn_hidden_size 512 with "
-                                       "observation_dim 256 / 512 or 256 with 256, unpadded), at most one utterance per compute "
-                                       "unit and n_utt * max_frames <= 64 M labels");
-    }
-    // Every cluster gets a FIXED row range of the chunk buffers (x, gi0, mse0) and of the mailbox's
-    // frame area: room for 16 frames of each of its utterances.  Fixed, because the launch never
-    // ends between pushes: a row that changed hands from one push to the next would leave a stale
-    // dirty line in the previous owner's XCD-private L2, free to be written back over the new
-    // owner's data at any time (seen as rare score differences before the ranges were fixed).
-    ss.pm_cluster_rows = std::min<int64_t>(round_up(((U + geo.ncl - 1) / geo.ncl) * 16, 32), (int64_t)UIS_RES_HEAD_TILES * 16 * 6);
-    ss.pm_cap_frames = ss.pm_cluster_rows * geo.ncl;
-    size_t o = (size_t)UIS_PM_CTL_WORDS * 4;
-    auto take = [&](size_t bytes) { o = (o + 127) & ~(size_t)127; const size_t r = o; o += bytes; return r; };
-    ss.pm_o_foff = take((size_t)U * 8);
-    ss.pm_o_avail = take((size_t)U * 4);
-    ss.pm_o_laboff = take((size_t)U * 8);
-    ss.pm_o_scores = take((size_t)U * 4);
-    ss.pm_o_bscores = take((size_t)U * B * 4);
-    ss.pm_o_overflow = take((size_t)U * 4);
-    ss.pm_o_frames = take((size_t)ss.pm_cap_frames * m.D * 4);
-    ss.pm_o_labels = take((size_t)U * (size_t)max_frames * 4);
-    void* blk = nullptr;
-    hipError_t e = hipHostMalloc(&blk, o, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) { stream_free(h); return fail(UIS_ERR_OOM, std::string("hipHostMalloc (mailbox): ") + hipGetErrorString(e)); }
-    ss.poison.host(blk, o);  // (... and then the mailbox's initial state)
-    memset(blk, 0, o);
-    ss.pm_block = static_cast<unsigned char*>(blk);
-    ss.hdr_stride = (((size_t)U * 12) + 127) & ~(size_t)127;
-    SALLOC(ss.d_go, (size_t)UIS_PM_MAX_CLUSTERS * 16, true);
-    SALLOC(ss.d_hdr, (size_t)geo.ncl * ss.hdr_stride, true);
-    SALLOC(ss.d_pm_args, 1, false);
-    // everything a push through the mailbox touches, now: no allocation while the launch is resident
-    if ((rc = ss.chunk_x.ensure((size_t)U * 16 + (size_t)ss.pm_cap_frames * m.Dp * 4)) ||
-        (rc = ss.chunk_gi0.ensure((size_t)ss.pm_cap_frames * m.G * 4)) || (rc = ss.chunk_mse0.ensure((size_t)ss.pm_cap_frames * 4))) {
-      stream_free(h);
-      return rc;
-    }
-    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
-    ss.persist = true;
-  }
-#undef SALLOC
-  if (ss.resident)  // the extra slot every GRU source row of a fresh cluster reads
-    HIPCHK(hipMemcpyAsync(st.pool_hid + (size_t)U * S * m.Hp, m.h1, (size_t)m.Hp * 4, hipMemcpyDeviceToDevice, h->stream));
-  std::vector<int64_t> off(U + 1);
-  for (int u = 0; u <= U; ++u) off[u] = (int64_t)u * max_frames;  // capacity offsets: they address the back-pointers
-  std::vector<double> logblk(max_frames + 2), logden(max_frames + 2);
-  for (int64_t n = 0; n < max_frames + 2; ++n) {
-    logblk[n] = n > 0 ? std::log((double)n) : 0.0;
-    logden[n] = std::log((double)n + h->alpha);
-  }
-  HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d_logblk, logblk.data(), logblk.size() * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(d_logden, logden.data(), logden.size() * 8, hipMemcpyHostToDevice, h->stream));
-  st.off = d_off; st.logblk = d_logblk; st.logden = d_logden;
-  st.avail = ss.d_avail; st.foff = ss.d_foff; st.lab_off = ss.d_lab_off;
-  hipLaunchKernelGGL(k_init_state, dim3((U + 255) / 256), dim3(256), 0, h->stream, st);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
-  ss.active = true;
-  return UIS_OK;
-}
-
-UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
-  if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
-  uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
-  const DevModel& m = h->m;
-  const int U = ss.U;
-  int64_t F = 0, max_new = 0;
-  for (int u = 0; u < U; ++u) {
-    if (counts[u] < 0) return fail(UIS_ERR_INVALID_ARG, "negative frame count");
-    if ((int64_t)ss.have[u] + counts[u] > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames");
-    F += counts[u];
-    max_new = std::max<int64_t>(max_new, counts[u]);
-  }
-  if (F == 0) return UIS_OK;
-  if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
-#if defined(UIS_PM_TIMING)
-  const double t_enter = pm_now_s();
-#endif
-  bool pm_fits = ss.persist && !h->resident_off;
-  if (pm_fits) {  // every cluster's new frames must fit its fixed row range
-    const int ncl = ss.st.ncl;
-    for (int c = 0; c < ncl && pm_fits; ++c) {
-      int64_t rows = 0;
-      for (int u = c; u < U; u += ncl) rows += counts[u];
-      pm_fits = rows <= ss.pm_cluster_rows;
-    }
-  }
-  if (pm_fits) {
-    // ---- the launch that stays on the device: tables and frames into the mailbox, ring, wait
-    int64_t* p_foff = reinterpret_cast<int64_t*>(ss.pm_block + ss.pm_o_foff);
-    int32_t* p_avail = reinterpret_cast<int32_t*>(ss.pm_block + ss.pm_o_avail);
-    // frames cluster by cluster (cluster c owns utterances c, c + ncl, ...): each cluster's rank 0
-    // fetches ONE contiguous row range
-    const int ncl = ss.st.ncl;
-    uint32_t row0[UIS_PM_MAX_CLUSTERS + 1];
-    std::vector<int64_t> src(U + 1, 0);  // where utterance u's frames start in the caller's buffer
-    for (int u = 0; u < U; ++u) src[u + 1] = src[u] + counts[u];
-    uint32_t nrow[UIS_PM_MAX_CLUSTERS];
-    float* dst = reinterpret_cast<float*>(ss.pm_block + ss.pm_o_frames);
-    for (int c = 0; c < ncl; ++c) {
-      int64_t pos = (int64_t)c * ss.pm_cluster_rows;  // the cluster's fixed range
-      row0[c] = (uint32_t)pos;
-      for (int u = c; u < U; u += ncl) {
-        p_foff[u] = pos - ss.have[u];
-        p_avail[u] = ss.have[u] + counts[u];
-        if (counts[u]) memcpy(dst + (size_t)pos * m.D, frames + (size_t)src[u] * m.D, (size_t)counts[u] * m.D * 4);
-        pos += counts[u];
-      }
-      nrow[c] = (uint32_t)(pos - (int64_t)c * ss.pm_cluster_rows);
-    }
-    h->inlaunch_failed = false;
-#if defined(UIS_PM_TIMING)
-    static double fill_s = 0.0, wait_s = 0.0; static long n_push = 0;
-    const double t_mid = pm_now_s();
-    fill_s += t_mid - t_enter;
-#endif
-    rc = pm_command(h, UIS_PM_PUSH, (uint32_t)std::min<int64_t>(F, 4095), true, row0, nrow);
-#if defined(UIS_PM_TIMING)
-    wait_s += pm_now_s() - t_mid;
-    if (++n_push % 100 == 0) {
-      const volatile unsigned long long* k = reinterpret_cast<const volatile unsigned long long*>(pm_ctl(ss) + UIS_PM_TIMING_WORD);
-      const unsigned long long k5 = k[5]; const double n = (double)(k5 ? k5 : 1);
-      fprintf(stderr, "[pm timing] host per push: fill %.1f us, ring + wait %.1f us; kernel (workgroup 0) per push: fetch %.1f, pass on %.1f, "
-              "count + chunk projection %.1f, steps %.1f us\n", 1e6 * fill_s / n_push, 1e6 * wait_s / n_push, k[0] * 0.01 / n, k[1] * 0.01 / n,
-              k[2] * 0.01 / n, k[3] * 0.01 / n);
-    }
-#endif
-    if (rc == UIS_OK) {
-      for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
-      ss.steps_run += max_new;
-      return UIS_OK;
-    }
-    if (!h->inlaunch_failed) return rc;
-    ss.persist = false;  // the cooperative launch was refused: ordinary launches from here on
-  }
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
-  // ---- one staging block, one H2D: [foff][avail][frames]
-  const size_t hdr = (size_t)U * 8 + (((size_t)U * 4 + 15) & ~(size_t)15);
-  const size_t need = hdr + (size_t)F * m.D * 4;
-  if (need > ss.h_stage_cap) {
-    if (ss.h_stage) { (void)hipHostFree(ss.h_stage); ss.h_stage = nullptr; ss.h_stage_cap = 0; }
-    const size_t want = need + need / 4 + 4096;
-    hipError_t e = hipHostMalloc(&ss.h_stage, want, hipHostMallocDefault);
-    if (e != hipSuccess) { ss.h_stage = nullptr; return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
-    ss.h_stage_cap = want;
-  }
-  if ((rc = ss.chunk_x.ensure(need))) return rc;
-  if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
-  if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
-  // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
-  // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
-  ss.poison = UisPoison::from_env();
-  if (ss.poison.on) {
-    ss.poison.host(ss.h_stage, ss.h_stage_cap);
-    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
-  }
-  int64_t* h_foff = static_cast<int64_t*>(ss.h_stage);
-  int32_t* h_avail = reinterpret_cast<int32_t*>(static_cast<char*>(ss.h_stage) + (size_t)U * 8);
-  {
-    int64_t pos = 0;
-    for (int u = 0; u < U; ++u) {
-      h_foff[u] = pos - ss.have[u];  // row of step s's frame in this chunk = foff + s
-      pos += counts[u];
-      h_avail[u] = ss.have[u] + counts[u];
-    }
-  }
-  memcpy(static_cast<char*>(ss.h_stage) + hdr, frames, (size_t)F * m.D * 4);
-  HIPCHK(hipMemcpyAsync(ss.chunk_x.p, ss.h_stage, need, hipMemcpyHostToDevice, h->stream));
-  ss.d_foff = ss.chunk_x.as<int64_t>();
-  ss.d_avail = reinterpret_cast<int32_t*>(ss.chunk_x.as<char>() + (size_t)U * 8);
-  ss.st.foff = ss.d_foff;
-  ss.st.avail = ss.d_avail;
-  const float* d_x = reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr);
-  if (m.D != m.Dp) {
-    if ((rc = ss.chunk_pad.ensure((size_t)F * m.Dp * 4))) return rc;
-    HIPCHK(ss.poison.device(ss.chunk_pad.p, ss.chunk_pad.cap, h->stream));
-    const long total = (long)F * m.Dp;
-    hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_x,
-                       ss.chunk_pad.as<float>(), (long)F, m.D, m.Dp);
-    HIPCHK(hipGetLastError());
-    d_x = ss.chunk_pad.as<float>();
-  }
-  Launcher lch{h, h->stream, false};
-  DecodeState st = ss.st;
-  st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
-  const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
-  // One-launch path: the chunk's projection fused into the kernel and plain launches after the
-  // session's first push make a push one H2D, one memset and ONE kernel.  Measured
-  // (tools/stream_latency.py, profiles/): that kernel re-reads its weights into registers / LDS at
-  // every launch (~10 us), so for 1-3 steps per push the four small kernels per step are still
-  // quicker (79 vs 96 us for one frame of 64 utterances); from 4 steps on the single launch wins
-  // (16 frames: 690 vs 880 us).  UIS_FLAG_RESIDENT forces it, UIS_FLAG_STEPWISE forbids it.
-  bool stepwise = !ss.resident || h->resident_off ||
-                  (max_new < UIS_STREAM_RESIDENT_MIN_STEPS && !(ss.st.flags & UIS_FLAG_RESIDENT));
-  // the chunk's gi0 / mse0: inside the one-launch kernel when the frames need no padding and the
-  // chunk's rows fit the kernel's LDS list, else by the two once-per-chunk kernels
-  const bool fused = !stepwise && m.D == m.Dp && F <= (int64_t)UIS_RES_HEAD_TILES * 16 * 6;
-  if (!fused && (rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
-  HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
-  st.push_F = fused ? (int)F : 0;
-  bool ran_resident = false;
-  if (!stepwise) {
-    // every step of this push in ONE launch (the kernel runs max over utterances of
-    // avail - utt_step steps; utterances without new frames sit them out)
-    HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
-    h->inlaunch_failed = false;
-    // Every push is a COOPERATIVE launch: the kernel spins on in-launch barriers and needs all its
-    // workgroups co-resident, which only that launch path checks against whatever else runs on the
-    // device at that moment (another handle's decode, a second session).  A plain launch of the
-    // same grid saves 15-19 us of host time per push; it is opt-in (UIS_STREAM_PLAIN_LAUNCH=1) for
-    // callers that own the device, and used only after the session's first push went through the
-    // cooperative path.
-    static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
-    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
-                               one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st,
-                               !(ss.coop_checked && plain_ok));
-    if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
-      h->resident_off = true; stepwise = true;
-      if (fused) {  // ... and they need the chunk's gi0 / mse0
-        if ((rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
-        st.push_F = 0;
-      }
-    } else if (rc) return rc;
-    else { ran_resident = true; ss.coop_checked = true; }
-  }
-  if (stepwise && (rc = enqueue_steps(h, lch, st, lds.total, (int)max_new))) return rc;
-  uint32_t abort_word = 0;
-  if (ran_resident) HIPCHK(hipMemcpyAsync(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // the staging block and the caller's frames may be reused
-  if (abort_word)  // an in-launch barrier gave up mid-push: the session's state is not trustworthy any more
-    return fail(UIS_ERR_HIP, "in-launch barrier failed during uis_stream_push; close the session (uis_stream_end) and reopen it "
-                             "with UIS_FLAG_STEPWISE");
-  for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
-  ss.steps_run += max_new;
-  return UIS_OK;
-}
-
-UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
-  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
-  const int U = ss.U;
-  std::vector<int64_t> lab_off(U);
-  int64_t F = 0;
-  for (int u = 0; u < U; ++u) { lab_off[u] = F; F += ss.have[u]; }
-  if (F > 0 && !labels_out) return fail(UIS_ERR_INVALID_ARG, "labels_out is null");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
-  if (ss.persist && ss.pm_running) {
-    // the resident launch back-traces every utterance and writes into the mailbox
-    memcpy(ss.pm_block + ss.pm_o_laboff, lab_off.data(), (size_t)U * 8);
-    rc = pm_command(h, UIS_PM_LABELS, 0, false);
-    if (rc == UIS_OK) {
-      if (F > 0) memcpy(labels_out, ss.pm_block + ss.pm_o_labels, (size_t)F * 4);
-      if (scores_out) memcpy(scores_out, ss.pm_block + ss.pm_o_scores, (size_t)U * 4);
-      h->last_U = U; h->last_B = ss.B; h->nb_valid = false;
-      h->last_overflow.assign(reinterpret_cast<const int32_t*>(ss.pm_block + ss.pm_o_overflow),
-                              reinterpret_cast<const int32_t*>(ss.pm_block + ss.pm_o_overflow) + U);
-      h->last_beam_scores.assign(reinterpret_cast<const float*>(ss.pm_block + ss.pm_o_bscores),
-                                 reinterpret_cast<const float*>(ss.pm_block + ss.pm_o_bscores) + (size_t)U * ss.B);
-      int n_over = 0;
-      for (int u = 0; u < U; ++u) {
-        if (overflow_out) overflow_out[u] = h->last_overflow[u];
-        n_over += h->last_overflow[u] != 0;
-      }
-      if (n_over)
-        return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
-                                             std::to_string(ss.Kmax) + " clusters per hypothesis");
-      return UIS_OK;
-    }
-    if (rc != 1) return rc;  // (1: the launch had left -- its tables are back in global memory)
-  }
-  if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
-  if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
-  {
-    const UisPoison poison = UisPoison::from_env();
-    HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
-    HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
-  }
-  HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
-  // frames received = steps run, from the host's own count: the `avail` table of the last push may
-  // live in a chunk buffer this path did not fill (pushes taken by the persistent launch)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, h->stream));
-  DecodeState stl = ss.st;
-  stl.avail = ss.d_have;
-  hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, h->stream, stl, ss.labels.as<int32_t>(),
-                     ss.scores.as<float>(), ss.d_beam_scores);
-  HIPCHK(hipGetLastError());
-  if (F > 0) HIPCHK(hipMemcpyAsync(labels_out, ss.labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-  if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, ss.scores.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  h->last_U = U; h->last_B = ss.B;
-  h->nb_valid = false;  // (the "last decode" of uis_last_decode_info / _shape is this session from here on: the readout follows)
-  h->last_overflow.assign(U, 0);
-  h->last_beam_scores.assign((size_t)U * ss.B, INFINITY);
-  HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, (size_t)U * ss.B * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  int n_over = 0;
-  for (int u = 0; u < U; ++u) {
-    if (overflow_out) overflow_out[u] = h->last_overflow[u];
-    n_over += h->last_overflow[u] != 0;
-  }
-  if (n_over)
-    return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
-                                         std::to_string(ss.Kmax) + " clusters per hypothesis");
-  return UIS_OK;
-}
-
-UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
-  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  if (!h->stream_state.active) return UIS_OK;
-  HIPCHK(hipSetDevice(h->device));
-  const int rc_quit = pm_quit(h);
-  HIPCHK(hipStreamSynchronize(h->stream));
-  stream_free(h);
-  return rc_quit;
-}
+// ------------------------------------------------------------------ streaming sessions
+#include "uis_stream.hip"
 
 
 // ------------------------------------------------------------------ evaluation

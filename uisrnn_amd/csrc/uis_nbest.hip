@@ -282,10 +282,5 @@ UIS_EXPORT int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labe
   std::vector<int32_t> overflow;
   if ((rc = nbest_run(h, groups, false, ss.B, off, n_best, labels_out, capacity, scores_out, counts_out, stable_out, &overflow)))
     return rc;
-  int n_over = 0;
-  for (int u = 0; u < U; ++u) n_over += overflow[u] != 0;
-  if (n_over)
-    return fail(UIS_ERR_CLUSTER_CAP, std::to_string(n_over) + " utterance(s) needed more than max_clusters=" +
-                                         std::to_string(ss.Kmax) + " clusters per hypothesis");
-  return UIS_OK;
+  return cluster_cap_status(count_cluster_cap(overflow), ss.Kmax);
 }

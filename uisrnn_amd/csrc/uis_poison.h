@@ -3,7 +3,9 @@
 // unset, the knob costs the one getenv of from_env() per call and nothing else.
 //
 // What is filled is what a call may read without having written it in a correct program only by accident: the
-// workspace arena, the staging buffers, the readouts' and the trainer's scratch.  What a call defines as input
+// workspace arena (place_workspace() in uis_workspace.hip fills what it has just placed: the arena, or every buffer
+// of workspace_list() and k_decode_rs's stretch), a session's tables (stream_alloc, block by block), the staging
+// buffers, the readouts' and the trainer's scratch.  What a call defines as input
 // carried over from an earlier call (the last decode's tables for the readouts, `resume` between the launches of a
 // split decode, a session's state between pushes, the labels uis_eval_last_decode reads, the trainer's parameters
 // and moments) is never filled.

@@ -243,7 +243,7 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
   const int64_t F = offsets[U];
   int64_t maxN = 0;
   for (int u = 0; u < U; ++u) maxN = std::max<int64_t>(maxN, offsets[u + 1] - offsets[u]);
-  // the decode's tables (uis_decoder.hip, decode_once)
+  // the decode's tables (upload_log_tables, uis_workspace.hip)
   std::vector<double> logblk(maxN + 2), logden(maxN + 2);
   for (int64_t n = 0; n < maxN + 2; ++n) {
     logblk[n] = n > 0 ? std::log((double)n) : 0.0;

@@ -1,0 +1,556 @@
+// uis_stream.hip -- the streaming sessions of the C ABI (uis_stream_*), included by uis_decoder.hip.
+//
+// Online decoding (the caller side of the path -- UIS-RNN is an online model, the
+// reference only offers offline predict()).  A session keeps the beam, the cluster-state pool
+// and the back-pointers of n_utt utterances on the device; uis_stream_push() appends frames (any
+// number per utterance, also none) and advances every utterance by the frames it received;
+// uis_stream_labels() reads the best hypothesis' labels for everything received so far.
+// Semantics = predict_single with test_iteration 1 (uisrnn.py:479-562): pushing an utterance
+// in any chunking gives bit for bit the labels / scores of one uis_decode over the whole of it
+// (tests/test_gpu_stream.py).  look_ahead 1.  A push of four or more steps runs as ONE launch of
+// k_decode_resident where that kernel applies, shorter pushes on the launch-per-step kernels.
+
+namespace {
+
+// One table of the session's state: an allocation of its own (the persistent launch's fixed row ranges and the L2
+// note in uis_stream_begin are why a session's addresses are left alone: no arena here).
+template <typename T>
+int stream_alloc(uis_handle* h, T** out, size_t count, bool zero = false) {
+  DevBuf b;
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  if (int rc = b.alloc(bytes)) return rc;
+  *out = b.as<T>();
+  h->stream_state.allocs.push_back(std::move(b));
+  HIPCHK(h->stream_state.poison.device(*out, bytes, h->stream));  // (UIS_POISON_WORKSPACE: ahead of the block's defining writes)
+  if (zero) HIPCHK(hipMemsetAsync(*out, 0, bytes, h->stream));
+  return UIS_OK;
+}
+
+// ---- the persistent launch of a UIS_FLAG_PERSISTENT session
+//
+// Mailbox protocol (pm_block, host-coherent pinned memory; uint32 view, one 64-byte line per item,
+// uis_kernels.h UIS_PM_*_WORD): a doorbell line per cluster {sequence number, command | frames << 8,
+// first row | rows << 16} whose sequence number the host writes LAST (release) and rank 0 of the
+// cluster polls with one 16-byte read; the sequence number of the last command each cluster
+// completed; a word per cluster that turns non-zero when the cluster has left the kernel.
+// While the launch is on the device the host makes NO HIP call that could wait for the device:
+// everything a command needs was allocated by uis_stream_begin.
+
+double pm_now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+unsigned long long pm_idle_ticks() {
+  double ms = 50.0;  // without a command for this long the launch ends by itself (the next push starts a new one)
+  if (const char* e = getenv("UIS_PERSIST_IDLE_MS")) ms = atof(e);
+  ms = std::min(std::max(ms, 0.05), 2000.0);
+  return (unsigned long long)(ms * 1e5);  // s_memrealtime ticks of 10 ns
+}
+
+// After the launch has ended (every cluster left, or an in-launch barrier gave up): look at the abort word.
+int pm_reap(uis_handle* h) {
+  uis_handle::Stream& ss = h->stream_state;
+  // (a launch that is really stuck must not take the caller with it: poll with a deadline instead
+  // of an unbounded hipStreamSynchronize; the kernel's own barrier time-out is ~1 s)
+  {
+    const double t0 = pm_now_s();
+    hipError_t q;
+    while ((q = hipStreamQuery(h->stream)) == hipErrorNotReady) {
+      if (pm_now_s() - t0 > 15.0) {
+        ss.persist = false;
+        h->resident_off = true;
+        return fail(UIS_ERR_HIP, "the persistent streaming launch does not leave the device (15 s); the handle's "
+                                 "stream is unusable -- destroy the handle");
+      }
+      __builtin_ia32_pause();
+    }
+    if (q != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
+  }
+  ss.pm_running = false;
+  uint32_t abort_word = 0;
+  HIPCHK(hipMemcpy(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost));
+  if (abort_word) {
+    ss.persist = false;
+    h->resident_off = true;
+    return fail(UIS_ERR_HIP, "in-launch barrier failed inside the persistent streaming launch; close the session "
+                             "(uis_stream_end) and reopen it with UIS_FLAG_STEPWISE");
+  }
+  return UIS_OK;
+}
+
+int pm_launch(uis_handle* h) {
+  uis_handle::Stream& ss = h->stream_state;
+  const DevModel& m = h->m;
+  DecodeState st = ss.st;
+  // the mailbox as the device sees it (the same address under unified addressing; asked for anyway)
+  void* blk_dev = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&blk_dev, ss.pm_block.p, 0));
+  unsigned char* blk = static_cast<unsigned char*>(blk_dev);
+  st.x = reinterpret_cast<const float*>(ss.chunk_x.as<char>());
+  st.gi0 = ss.chunk_gi0.as<float>();
+  st.mse0 = ss.chunk_mse0.as<float>();
+  st.push_F = 0;
+  PersistArgs& pa = ss.pm_args;
+  pa.ctl = reinterpret_cast<uint32_t*>(blk);
+  pa.foff = reinterpret_cast<const int64_t*>(blk + ss.pm_o_foff);
+  pa.avail = reinterpret_cast<const int32_t*>(blk + ss.pm_o_avail);
+  pa.lab_off = reinterpret_cast<const int64_t*>(blk + ss.pm_o_laboff);
+  pa.frames = reinterpret_cast<const float*>(blk + ss.pm_o_frames);
+  pa.labels = reinterpret_cast<int32_t*>(blk + ss.pm_o_labels);
+  pa.scores = reinterpret_cast<float*>(blk + ss.pm_o_scores);
+  pa.beam_scores = reinterpret_cast<float*>(blk + ss.pm_o_bscores);
+  pa.overflow = reinterpret_cast<int32_t*>(blk + ss.pm_o_overflow);
+  pa.go = ss.d_go;
+  pa.hdr = ss.d_hdr;
+  pa.hdr_stride = ss.hdr_stride;
+  pa.idle_ticks = pm_idle_ticks();
+  HIPCHK(hipMemcpyAsync(ss.d_pm_args, &pa, sizeof(pa), hipMemcpyHostToDevice, h->stream));
+  st.pm = ss.d_pm_args;
+  // avail / foff only have to be non-null here (the kernel points them at its cluster's copies)
+  st.avail = reinterpret_cast<const int32_t*>(ss.d_hdr);
+  st.foff = reinterpret_cast<const int64_t*>(ss.d_hdr);
+  HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
+  HIPCHK(hipMemsetAsync(ss.d_go, 0, (size_t)UIS_PM_MAX_CLUSTERS * 128, h->stream));
+  HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
+  Launcher lch{h, h->stream, false};
+  h->inlaunch_failed = false;
+  if (int rc = launch_cluster_kernel(lch, find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+                                     one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st))
+    return rc;
+  ss.pm_running = true;
+  ss.pm_launches += 1;
+  return UIS_OK;
+}
+
+// Issue one command and wait until every cluster has completed it.  A launch that is not on the
+// device (never started, or left because it was idle) is started first when `may_launch`; a
+// launch that left while the command was on its way is reaped and the command issued again to a
+// new one -- harmless: a cluster that did take a push has nothing left to do for it.
+// Returns UIS_OK, an error, or 1 = not running and may_launch was false.
+int pm_command(uis_handle* h, uint32_t type, uint32_t frames, bool may_launch, const uint32_t* row0 = nullptr,
+               const uint32_t* nrow = nullptr) {
+  uis_handle::Stream& ss = h->stream_state;
+  volatile uint32_t* ctl = pm_ctl(ss);
+  const int ncl = ss.st.ncl;
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    int rc;
+    if (!ss.pm_running) {
+      if (!may_launch) return 1;
+      for (int i = 0; i < UIS_PM_CTL_WORDS; ++i) ctl[i] = 0;
+      ss.pm_seq = 1;
+      pm_ring(ss, 1, type, frames, row0, nrow);
+      if ((rc = pm_launch(h))) return rc;
+    } else {
+      ss.pm_seq += 1;
+      pm_ring(ss, ss.pm_seq, type, frames, row0, nrow);
+    }
+    ss.pm_commands += 1;
+    const double t0 = pm_now_s();
+    bool left = false;
+    unsigned spins = 0;
+    for (;;) {
+      bool all = true;
+      for (int c = 0; c < ncl; ++c) all = all && ctl[UIS_PM_DONE_WORD + 16 * c] == ss.pm_seq;
+      if (all) return UIS_OK;
+      for (int c = 0; c < ncl; ++c) left = left || ctl[UIS_PM_LEFT_WORD + 16 * c] != 0;
+      if (left) break;
+      if ((++spins & 4095u) == 0) {
+        if (pm_now_s() - t0 > 10.0) break;
+        // (a launch that ended without saying so -- an in-launch barrier gave up -- is noticed here)
+        if ((spins & 0xffffu) == 0 && hipStreamQuery(h->stream) == hipSuccess) { left = true; break; }
+      }
+      __builtin_ia32_pause();
+    }
+    // a cluster left before (or instead of) completing the command: tell the others to leave too
+    // (they complete this command first if they had not seen it yet), then look at what happened
+    ss.pm_seq += 1;
+    pm_ring(ss, ss.pm_seq, UIS_PM_QUIT, 0);
+    if ((rc = pm_reap(h))) return rc;
+    if (!left) return fail(UIS_ERR_HIP, "the persistent streaming launch did not answer within 10 s");
+  }
+  return fail(UIS_ERR_HIP, "the persistent streaming launch kept leaving before it took the command");
+}
+
+int pm_quit(uis_handle* h) {
+  uis_handle::Stream& ss = h->stream_state;
+  if (!ss.pm_running) return UIS_OK;
+  ss.pm_seq += 1;
+  pm_ring(ss, ss.pm_seq, UIS_PM_QUIT, 0);
+  return pm_reap(h);
+}
+
+}  // namespace
+
+UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
+  if (!h || !opts || n_utt < 1 || max_frames < 1) return fail(UIS_ERR_INVALID_ARG, "null handle/opts, n_utt < 1 or max_frames < 1");
+  uis_handle::Stream& ss = h->stream_state;
+  if (ss.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is already open on this handle");
+  const DevModel& m = h->m;
+  const int B = opts->beam_size;
+  const int Kmax = opts->max_clusters > 0 ? opts->max_clusters : 16;
+  if (B < 1 || B > 256) return fail(UIS_ERR_UNSUPPORTED, "beam_size must be in [1, 256]");
+  if (opts->look_ahead != 1) return fail(UIS_ERR_UNSUPPORTED, "streaming needs look_ahead 1");
+  if (opts->test_iteration != 1) return fail(UIS_ERR_UNSUPPORTED, "streaming is online decoding: test_iteration must be 1");
+  if (Kmax > 4096) return fail(UIS_ERR_UNSUPPORTED, "max_clusters must be <= 4096");
+  if (max_frames > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "max_frames too large");
+  const int U = n_utt, S = B * Kmax + B;
+  const SelectLds lds = select_lds_layout(m.Dp, B, Kmax, S);
+  if (lds.total > 160 * 1024) return fail(UIS_ERR_UNSUPPORTED, "beam_size * max_clusters too large for the select kernel's LDS budget");
+  const double bytes = (double)U * S * (m.Dp + (double)m.depth * m.Hp) * 4.0 + (double)U * max_frames * B * 4.0;
+  if (bytes > 200e9) return fail(UIS_ERR_OOM, "streaming state would need " + std::to_string((long long)(bytes / 1e9)) + " GB");
+  HIPCHK(hipSetDevice(h->device));
+  ss = uis_handle::Stream{};
+  ss.poison = UisPoison::from_env();
+  ss.U = U; ss.B = B; ss.Kmax = Kmax; ss.S = S; ss.cap = max_frames;
+  ss.have.assign(U, 0);
+  DecodeState& st = ss.st;
+  st.U = U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = 1; st.tau = 1; st.flags = opts->flags | (agent_flags_env() ? UIS_FLAG_AGENT_FLAGS : 0u);
+  st.max_rows = U * B;
+  // a push advances the session with ONE launch of the resident decode kernel where that kernel
+  // applies (same conditions as uis_decode); UIS_FLAG_STEPWISE keeps the four kernels per step
+  const ClusterGeometry geo = cluster_geometry(h->n_cu, U, B, 0, 1);  // (one group, no row slack)
+  // (streams never ran the 128-wide kernel)
+  ss.resident = m.Hp != 128 && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) && resident_fits(m, U, B, Kmax, S, geo);
+  if ((opts->flags & UIS_FLAG_RESIDENT) && !ss.resident)
+    { ss = uis_handle::Stream{}; return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT: the one-launch decode does not apply to this session's shape"); }
+  int rc = UIS_OK;
+  int64_t* d_off = nullptr; double *d_logblk = nullptr, *d_logden = nullptr;
+#define SALLOC(ptr, count, zero) if ((rc = stream_alloc(h, &(ptr), (size_t)(count), zero))) { stream_free(h); return rc; }
+  const StateCounts n = state_counts(m, U, B, Kmax, S, geo.rows_cap, 1);  // (one group)
+  SALLOC(d_off, U + 1, false);
+  SALLOC(st.utt_step, U, false);
+  SALLOC(st.overflow, U, false);
+  SALLOC(ss.d_avail, U, true);
+  SALLOC(ss.d_have, U, true);
+  SALLOC(ss.d_foff, U, true);
+  SALLOC(ss.d_lab_off, U, true);
+  SALLOC(d_logblk, max_frames + 2, false);
+  SALLOC(d_logden, max_frames + 2, false);
+  SALLOC(st.pool_mean, n.pool_mean, false);
+  SALLOC(st.pool_hid, n.pool_hid, false);
+  SALLOC(st.pool_cnt, n.pool_cnt, false);
+  SALLOC(st.beam_n, n.beam_n, false);
+  SALLOC(st.beam_K, n.beam, false);
+  SALLOC(st.beam_last, n.beam, false);
+  SALLOC(st.beam_sum, n.beam, false);
+  SALLOC(st.beam_score, n.beam, false);
+  SALLOC(st.beam_slot, n.beam_lists, false);
+  SALLOC(st.beam_blk, n.beam_lists, false);
+  SALLOC(st.bp, (size_t)U * max_frames * B, false);  // (a record per frame of the session's capacity; a decode's: per step of the frames given)
+  SALLOC(st.rows, n.rows, true);
+  SALLOC(st.nrows, n.nrows, true);
+  SALLOC(st.gi_up, n.gi_up, false);
+  SALLOC(st.a1, n.a1, true);
+  SALLOC(st.counters, 96, true);  // (one group's statistics words and room to spare; a decode's: every group's plus the diagnostic builds' clocks)
+  ss.ctl_words = n.ctl_words;
+  SALLOC(ss.d_ctl, ss.ctl_words, true);
+  wire_cluster_ctl(st, ss.d_ctl, ss.resident ? &geo : nullptr);
+  SALLOC(ss.d_beam_scores, (size_t)U * B, false);
+  if (opts->flags & UIS_FLAG_PERSISTENT) {
+    // the launch that stays: needs the one-launch shape with the beam in LDS (at most one utterance
+    // per workgroup), unpadded frames, and a mailbox that holds every label of the session
+    const bool shape = find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE) != nullptr;
+    const double label_bytes = (double)U * (double)max_frames * 4.0;
+    if (!(ss.resident && shape && U <= 32 * geo.ncl && m.D == m.Dp && label_bytes <= 256e6)) {
+      stream_free(h);
+      return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_PERSISTENT needs the one-launch shape (rnn_depth 1, rnn_hidden_size 512 with "
+                                       "observation_dim 256 / 512 or 256 with 256, unpadded), at most one utterance per compute "
+                                       "unit and n_utt * max_frames <= 64 M labels");
+    }
+    // Every cluster gets a FIXED row range of the chunk buffers (x, gi0, mse0) and of the mailbox's
+    // frame area: room for 16 frames of each of its utterances.  Fixed, because the launch never
+    // ends between pushes: a row that changed hands from one push to the next would leave a stale
+    // dirty line in the previous owner's XCD-private L2, free to be written back over the new
+    // owner's data at any time (seen as rare score differences before the ranges were fixed).
+    ss.pm_cluster_rows = std::min<int64_t>(round_up(((U + geo.ncl - 1) / geo.ncl) * 16, 32), (int64_t)UIS_RES_HEAD_TILES * 16 * 6);
+    ss.pm_cap_frames = ss.pm_cluster_rows * geo.ncl;
+    size_t o = (size_t)UIS_PM_CTL_WORDS * 4;
+    auto take = [&](size_t bytes) { o = (o + 127) & ~(size_t)127; const size_t r = o; o += bytes; return r; };
+    ss.pm_o_foff = take((size_t)U * 8);
+    ss.pm_o_avail = take((size_t)U * 4);
+    ss.pm_o_laboff = take((size_t)U * 8);
+    ss.pm_o_scores = take((size_t)U * 4);
+    ss.pm_o_bscores = take((size_t)U * B * 4);
+    ss.pm_o_overflow = take((size_t)U * 4);
+    ss.pm_o_frames = take((size_t)ss.pm_cap_frames * m.D * 4);
+    ss.pm_o_labels = take((size_t)U * (size_t)max_frames * 4);
+    hipError_t e = ss.pm_block.ensure(o, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) { stream_free(h); return fail(UIS_ERR_OOM, std::string("hipHostMalloc (mailbox): ") + hipGetErrorString(e)); }
+    ss.poison.host(ss.pm_block.p, o);  // (... and then the mailbox's initial state)
+    memset(ss.pm_block.p, 0, o);
+    ss.hdr_stride = (((size_t)U * 12) + 127) & ~(size_t)127;
+    SALLOC(ss.d_go, (size_t)UIS_PM_MAX_CLUSTERS * 16, true);
+    SALLOC(ss.d_hdr, (size_t)geo.ncl * ss.hdr_stride, true);
+    SALLOC(ss.d_pm_args, 1, false);
+    // everything a push through the mailbox touches, now: no allocation while the launch is resident
+    if ((rc = ss.chunk_x.ensure((size_t)U * 16 + (size_t)ss.pm_cap_frames * m.Dp * 4)) ||
+        (rc = ss.chunk_gi0.ensure((size_t)ss.pm_cap_frames * m.G * 4)) || (rc = ss.chunk_mse0.ensure((size_t)ss.pm_cap_frames * 4))) {
+      stream_free(h);
+      return rc;
+    }
+    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
+    ss.persist = true;
+  }
+#undef SALLOC
+  if (ss.resident)  // the extra slot every GRU source row of a fresh cluster reads
+    HIPCHK(hipMemcpyAsync(st.pool_hid + (size_t)U * S * m.Hp, m.h1, (size_t)m.Hp * 4, hipMemcpyDeviceToDevice, h->stream));
+  std::vector<int64_t> off(U + 1);
+  for (int u = 0; u <= U; ++u) off[u] = (int64_t)u * max_frames;  // capacity offsets: they address the back-pointers
+  std::vector<double> log_host;
+  HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
+  if ((rc = upload_log_tables(h->alpha, max_frames + 2, log_host, d_logblk, d_logden, h->stream))) return rc;
+  st.off = d_off; st.logblk = d_logblk; st.logden = d_logden;
+  st.avail = ss.d_avail; st.foff = ss.d_foff; st.lab_off = ss.d_lab_off;
+  hipLaunchKernelGGL(k_init_state, dim3((U + 255) / 256), dim3(256), 0, h->stream, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
+  ss.active = true;
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
+  if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
+  uis_handle::Stream& ss = h->stream_state;
+  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
+  const DevModel& m = h->m;
+  const int U = ss.U;
+  int64_t F = 0, max_new = 0;
+  for (int u = 0; u < U; ++u) {
+    if (counts[u] < 0) return fail(UIS_ERR_INVALID_ARG, "negative frame count");
+    if ((int64_t)ss.have[u] + counts[u] > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames");
+    F += counts[u];
+    max_new = std::max<int64_t>(max_new, counts[u]);
+  }
+  if (F == 0) return UIS_OK;
+  if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+#if defined(UIS_PM_TIMING)
+  const double t_enter = pm_now_s();
+#endif
+  bool pm_fits = ss.persist && !h->resident_off;
+  if (pm_fits) {  // every cluster's new frames must fit its fixed row range
+    const int ncl = ss.st.ncl;
+    for (int c = 0; c < ncl && pm_fits; ++c) {
+      int64_t rows = 0;
+      for (int u = c; u < U; u += ncl) rows += counts[u];
+      pm_fits = rows <= ss.pm_cluster_rows;
+    }
+  }
+  if (pm_fits) {
+    // ---- the launch that stays on the device: tables and frames into the mailbox, ring, wait
+    unsigned char* const pm = ss.pm_block.as<unsigned char>();
+    int64_t* p_foff = reinterpret_cast<int64_t*>(pm + ss.pm_o_foff);
+    int32_t* p_avail = reinterpret_cast<int32_t*>(pm + ss.pm_o_avail);
+    // frames cluster by cluster (cluster c owns utterances c, c + ncl, ...): each cluster's rank 0
+    // fetches ONE contiguous row range
+    const int ncl = ss.st.ncl;
+    uint32_t row0[UIS_PM_MAX_CLUSTERS + 1];
+    std::vector<int64_t> src(U + 1, 0);  // where utterance u's frames start in the caller's buffer
+    for (int u = 0; u < U; ++u) src[u + 1] = src[u] + counts[u];
+    uint32_t nrow[UIS_PM_MAX_CLUSTERS];
+    float* dst = reinterpret_cast<float*>(pm + ss.pm_o_frames);
+    for (int c = 0; c < ncl; ++c) {
+      int64_t pos = (int64_t)c * ss.pm_cluster_rows;  // the cluster's fixed range
+      row0[c] = (uint32_t)pos;
+      for (int u = c; u < U; u += ncl) {
+        p_foff[u] = pos - ss.have[u];
+        p_avail[u] = ss.have[u] + counts[u];
+        if (counts[u]) memcpy(dst + (size_t)pos * m.D, frames + (size_t)src[u] * m.D, (size_t)counts[u] * m.D * 4);
+        pos += counts[u];
+      }
+      nrow[c] = (uint32_t)(pos - (int64_t)c * ss.pm_cluster_rows);
+    }
+    h->inlaunch_failed = false;
+#if defined(UIS_PM_TIMING)
+    static double fill_s = 0.0, wait_s = 0.0; static long n_push = 0;
+    const double t_mid = pm_now_s();
+    fill_s += t_mid - t_enter;
+#endif
+    rc = pm_command(h, UIS_PM_PUSH, (uint32_t)std::min<int64_t>(F, 4095), true, row0, nrow);
+#if defined(UIS_PM_TIMING)
+    wait_s += pm_now_s() - t_mid;
+    if (++n_push % 100 == 0) {
+      const volatile unsigned long long* k = reinterpret_cast<const volatile unsigned long long*>(pm_ctl(ss) + UIS_PM_TIMING_WORD);
+      const unsigned long long k5 = k[5]; const double n = (double)(k5 ? k5 : 1);
+      fprintf(stderr, "[pm timing] host per push: fill %.1f us, ring + wait %.1f us; kernel (workgroup 0) per push: fetch %.1f, pass on %.1f, "
+              "count + chunk projection %.1f, steps %.1f us\n", 1e6 * fill_s / n_push, 1e6 * wait_s / n_push, k[0] * 0.01 / n, k[1] * 0.01 / n,
+              k[2] * 0.01 / n, k[3] * 0.01 / n);
+    }
+#endif
+    if (rc == UIS_OK) {
+      for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
+      ss.steps_run += max_new;
+      return UIS_OK;
+    }
+    if (!h->inlaunch_failed) return rc;
+    ss.persist = false;  // the cooperative launch was refused: ordinary launches from here on
+  }
+  if (ss.pm_running && (rc = pm_quit(h))) return rc;
+  // ---- one staging block, one H2D: [foff][avail][frames]
+  const size_t hdr = (size_t)U * 8 + (((size_t)U * 4 + 15) & ~(size_t)15);
+  const size_t need = hdr + (size_t)F * m.D * 4;
+  if (need > ss.h_stage.cap) {  // (with head-room: pushes of a session vary in size)
+    hipError_t e = ss.h_stage.ensure(need + need / 4 + 4096, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  }
+  if ((rc = ss.chunk_x.ensure(need))) return rc;
+  if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
+  if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
+  // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
+  // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
+  ss.poison = UisPoison::from_env();
+  if (ss.poison.on) {
+    ss.poison.host(ss.h_stage.p, ss.h_stage.cap);
+    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
+  }
+  int64_t* h_foff = ss.h_stage.as<int64_t>();
+  int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + (size_t)U * 8);
+  {
+    int64_t pos = 0;
+    for (int u = 0; u < U; ++u) {
+      h_foff[u] = pos - ss.have[u];  // row of step s's frame in this chunk = foff + s
+      pos += counts[u];
+      h_avail[u] = ss.have[u] + counts[u];
+    }
+  }
+  memcpy(ss.h_stage.as<char>() + hdr, frames, (size_t)F * m.D * 4);
+  HIPCHK(hipMemcpyAsync(ss.chunk_x.p, ss.h_stage.p, need, hipMemcpyHostToDevice, h->stream));
+  ss.d_foff = ss.chunk_x.as<int64_t>();
+  ss.d_avail = reinterpret_cast<int32_t*>(ss.chunk_x.as<char>() + (size_t)U * 8);
+  ss.st.foff = ss.d_foff;
+  ss.st.avail = ss.d_avail;
+  const float* d_x = reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr);
+  if (m.D != m.Dp) {
+    if ((rc = ss.chunk_pad.ensure((size_t)F * m.Dp * 4))) return rc;
+    HIPCHK(ss.poison.device(ss.chunk_pad.p, ss.chunk_pad.cap, h->stream));
+    const long total = (long)F * m.Dp;
+    hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_x,
+                       ss.chunk_pad.as<float>(), (long)F, m.D, m.Dp);
+    HIPCHK(hipGetLastError());
+    d_x = ss.chunk_pad.as<float>();
+  }
+  Launcher lch{h, h->stream, false};
+  DecodeState st = ss.st;
+  st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
+  const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
+  // One-launch path: the chunk's projection fused into the kernel and plain launches after the
+  // session's first push make a push one H2D, one memset and ONE kernel.  Measured
+  // (tools/stream_latency.py, profiles/): that kernel re-reads its weights into registers / LDS at
+  // every launch (~10 us), so for 1-3 steps per push the four small kernels per step are still
+  // quicker (79 vs 96 us for one frame of 64 utterances); from 4 steps on the single launch wins
+  // (16 frames: 690 vs 880 us).  UIS_FLAG_RESIDENT forces it, UIS_FLAG_STEPWISE forbids it.
+  bool stepwise = !ss.resident || h->resident_off ||
+                  (max_new < UIS_STREAM_RESIDENT_MIN_STEPS && !(ss.st.flags & UIS_FLAG_RESIDENT));
+  // the chunk's gi0 / mse0: inside the one-launch kernel when the frames need no padding and the
+  // chunk's rows fit the kernel's LDS list, else by the two once-per-chunk kernels
+  const bool fused = !stepwise && m.D == m.Dp && F <= (int64_t)UIS_RES_HEAD_TILES * 16 * 6;
+  if (!fused && (rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
+  HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
+  st.push_F = fused ? (int)F : 0;
+  bool ran_resident = false;
+  if (!stepwise) {
+    // every step of this push in ONE launch (the kernel runs max over utterances of
+    // avail - utt_step steps; utterances without new frames sit them out)
+    HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
+    h->inlaunch_failed = false;
+    // Every push is a COOPERATIVE launch: the kernel spins on in-launch barriers and needs all its
+    // workgroups co-resident, which only that launch path checks against whatever else runs on the
+    // device at that moment (another handle's decode, a second session).  A plain launch of the
+    // same grid saves 15-19 us of host time per push; it is opt-in (UIS_STREAM_PLAIN_LAUNCH=1) for
+    // callers that own the device, and used only after the session's first push went through the
+    // cooperative path.
+    static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
+    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+                               one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st,
+                               !(ss.coop_checked && plain_ok));
+    if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
+      h->resident_off = true; stepwise = true;
+      if (fused) {  // ... and they need the chunk's gi0 / mse0
+        if ((rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
+        st.push_F = 0;
+      }
+    } else if (rc) return rc;
+    else { ran_resident = true; ss.coop_checked = true; }
+  }
+  if (stepwise && (rc = enqueue_steps(h, lch, st, lds.total, (int)max_new))) return rc;
+  uint32_t abort_word = 0;
+  if (ran_resident) HIPCHK(hipMemcpyAsync(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // the staging block and the caller's frames may be reused
+  if (abort_word)  // an in-launch barrier gave up mid-push: the session's state is not trustworthy any more
+    return fail(UIS_ERR_HIP, "in-launch barrier failed during uis_stream_push; close the session (uis_stream_end) and reopen it "
+                             "with UIS_FLAG_STEPWISE");
+  for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
+  ss.steps_run += max_new;
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  uis_handle::Stream& ss = h->stream_state;
+  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
+  const int U = ss.U;
+  std::vector<int64_t> lab_off(U);
+  int64_t F = 0;
+  for (int u = 0; u < U; ++u) { lab_off[u] = F; F += ss.have[u]; }
+  if (F > 0 && !labels_out) return fail(UIS_ERR_INVALID_ARG, "labels_out is null");
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+  if (ss.persist && ss.pm_running) {
+    // the resident launch back-traces every utterance and writes into the mailbox
+    unsigned char* const pm = ss.pm_block.as<unsigned char>();
+    memcpy(pm + ss.pm_o_laboff, lab_off.data(), (size_t)U * 8);
+    rc = pm_command(h, UIS_PM_LABELS, 0, false);
+    if (rc == UIS_OK) {
+      if (F > 0) memcpy(labels_out, pm + ss.pm_o_labels, (size_t)F * 4);
+      if (scores_out) memcpy(scores_out, pm + ss.pm_o_scores, (size_t)U * 4);
+      h->last_U = U; h->last_B = ss.B; h->nb_valid = false;
+      h->last_overflow.assign(reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow),
+                              reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow) + U);
+      h->last_beam_scores.assign(reinterpret_cast<const float*>(pm + ss.pm_o_bscores),
+                                 reinterpret_cast<const float*>(pm + ss.pm_o_bscores) + (size_t)U * ss.B);
+      return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
+    }
+    if (rc != 1) return rc;  // (1: the launch had left -- its tables are back in global memory)
+  }
+  if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
+  if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
+  {
+    const UisPoison poison = UisPoison::from_env();
+    HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
+    HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
+  // frames received = steps run, from the host's own count: the `avail` table of the last push may
+  // live in a chunk buffer this path did not fill (pushes taken by the persistent launch)
+  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, h->stream));
+  DecodeState stl = ss.st;
+  stl.avail = ss.d_have;
+  hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, h->stream, stl, ss.labels.as<int32_t>(),
+                     ss.scores.as<float>(), ss.d_beam_scores);
+  HIPCHK(hipGetLastError());
+  if (F > 0) HIPCHK(hipMemcpyAsync(labels_out, ss.labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+  if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, ss.scores.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
+  h->last_U = U; h->last_B = ss.B;
+  h->nb_valid = false;  // (the "last decode" of uis_last_decode_info / _shape is this session from here on: the readout follows)
+  h->last_overflow.assign(U, 0);
+  h->last_beam_scores.assign((size_t)U * ss.B, INFINITY);
+  HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, (size_t)U * ss.B * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
+}
+
+UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!h->stream_state.active) return UIS_OK;
+  HIPCHK(hipSetDevice(h->device));
+  const int rc_quit = pm_quit(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  stream_free(h);
+  return rc_quit;
+}
