@@ -367,6 +367,36 @@ int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out,
 int32_t uis_stream_end(uis_handle* h);
 
 /*
+ * Primed sessions: start the online decode of an open session's utterances from a LABELED PREFIX (enrolment,
+ * a corrected opening, a recording continued across a seam).  Afterwards the session is in the state it would
+ * hold had it received the prefix frames and its beam contained only the given hypothesis: the state
+ * _update_beam_state (uisrnn/uisrnn.py:388-453) leaves along that trace, formed with the decode's own
+ * arithmetic.  Every later uis_stream_push / _labels / _nbest behaves as in any session: labels are the prefix
+ * followed by what is decoded, scores the prefix's negative log-likelihood plus the continuation, and
+ * uis_stream_nbest's stable_out is at least the prefix length.
+ *   frames, offsets : host, packed as for uis_score_labels; offsets is [n_utt + 1] for the SESSION's n_utt.
+ *                     Utterance u's prefix has P_u = offsets[u+1] - offsets[u] frames; P_u = 0 leaves that
+ *                     utterance exactly as it is.  Prefix frames count against the session's max_frames
+ *   labels     : host int32 [offsets[n_utt]], first-appearance form per utterance
+ *   scores_out : host float32 [n_utt] or NULL: the prefix's negative log-likelihood (what uis_score_labels gives,
+ *                bit for bit), 0 where P_u = 0
+ * All or nothing -- after an error no utterance has changed and the session stays usable:
+ *   UIS_ERR_INVALID_ARG  no session; offsets[0] != 0 or decreasing; an utterance with P_u > 0 that has already
+ *                        received (or been primed with) frames; P_u > max_frames; a negative label or one past
+ *                        first-appearance form (a prefix cannot be an invalid trace); a prefix whose negative
+ *                        log-likelihood is not finite (the message names the utterance)
+ *   UIS_ERR_CLUSTER_CAP  a prefix with more clusters than the session's max_clusters
+ *   UIS_ERR_OOM          as uis_score_labels
+ * In a UIS_FLAG_PERSISTENT session the resident launch leaves the device for this call (as for
+ * uis_stream_nbest) and the next push starts a new one.  It leaves once the checks of the arguments have
+ * passed and before the prefix is run (the launch occupies every compute unit): a call refused for a
+ * non-finite likelihood or with UIS_ERR_OOM leaves every table as it was but has cost the resident launch;
+ * one refused for its arguments (everything else above) has not.
+ */
+int32_t uis_stream_prime(uis_handle* h, const float* frames, const int64_t* offsets,
+                         const int32_t* labels, float* scores_out);
+
+/*
  * Sequence-match accuracy on the device -- the step after predict() in the reference's demo
  * (demo.py:61-66; uisrnn/evals.py:40-73: confusion matrix + scipy linear_sum_assignment).
  * For every utterance u (labels offsets[u] .. offsets[u+1] of both sequences) matched_out[u]

@@ -327,6 +327,8 @@ def load_library(path=None):
   lib.uis_stream_labels.argtypes = [ctypes.c_void_p, i32p, _fp, i32p]
   lib.uis_stream_end.restype = i32
   lib.uis_stream_end.argtypes = [ctypes.c_void_p]
+  lib.uis_stream_prime.restype = i32
+  lib.uis_stream_prime.argtypes = [ctypes.c_void_p, _fp, i64p, i32p, _fp]
   lib.uis_last_decode_nbest.restype = i32
   lib.uis_last_decode_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p]
   lib.uis_stream_nbest.restype = i32
@@ -369,7 +371,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -641,6 +643,49 @@ class Decoder:
     rc = self._lib.uis_stream_push(self._handle, frames.ctypes.data_as(_fp) if len(frames) else None, self._stream_counts_ptr)
     self._check(rc, 'uis_stream_push')
     self._stream_have += counts
+
+  def stream_received(self):
+    """Frames per utterance the open session holds (pushed or primed): int64 [n_utt]."""
+    return self._stream_have.copy()
+
+  def stream_prime(self, chunks, labels):
+    """Prime utterances of the open session with labeled prefixes (uis_stream_prime).
+
+    chunks: one [P_u, D] array (or None / empty) per utterance; labels: one int sequence in first-appearance
+    form (or None / empty) per utterance, P_u entries.  Returns the float32 prefix scores [n_utt] (0 where
+    nothing was primed).  A refusal (HipLibraryError with .status) leaves the session as it was."""
+    if len(chunks) != self._stream_n or len(labels) != self._stream_n:
+      raise ValueError('one chunk and one label sequence (or None) per utterance')
+    dim = self.observation_dim
+    parts, lab_parts = [], []
+    counts = np.zeros(self._stream_n, dtype=np.int64)
+    for u, (chunk, lab) in enumerate(zip(chunks, labels)):
+      n = 0 if chunk is None else len(chunk)
+      n_lab = 0 if lab is None else len(lab)
+      if n != n_lab:
+        raise ValueError('utterance {}: {} labels for a prefix of {} frames'.format(u, n_lab, n))
+      if n == 0:
+        continue
+      arr = np.ascontiguousarray(chunk, dtype=np.float32)
+      if arr.ndim != 2 or arr.shape[1] != dim:
+        raise ValueError('chunk does not match observation_dim')
+      parts.append(arr)
+      lab_parts.append(np.asarray(lab, dtype=np.int32).reshape(-1))
+      counts[u] = n
+    frames = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, dim), dtype=np.float32)
+    flat = np.ascontiguousarray(np.concatenate(lab_parts)) if lab_parts else np.zeros(0, dtype=np.int32)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    scores = np.zeros(self._stream_n, dtype=np.float32)
+    rc = self._lib.uis_stream_prime(
+        self._handle, frames.ctypes.data_as(_fp) if len(frames) else None,
+        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+        flat.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(flat) else None, scores.ctypes.data_as(_fp))
+    if rc != UIS_OK:   # (UIS_ERR_CLUSTER_CAP is a refusal here, not a result with flags)
+      err = HipLibraryError('uis_stream_prime failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    self._stream_have += counts
+    return scores
 
   def stream_labels(self):
     """Best-hypothesis labels of everything received so far: (list of int32 arrays, scores, overflow, status)."""

@@ -21,6 +21,7 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_select_rs.hip'),
     os.path.join(_HERE, 'csrc', 'uis_eval.hip'),
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_prime.hip'),
     os.path.join(_HERE, 'csrc', 'uis_nbest.hip'),
     os.path.join(_HERE, 'csrc', 'uis_stream.hip'),
     os.path.join(_HERE, 'csrc', 'uis_workspace.hip'),

@@ -176,6 +176,7 @@ struct HandleMem {
   HostBuf h_out;   // pinned landing block of uis_decode_f64's labels and scores
   DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
+  DevBuf sc_prime;  // uis_stream_prime's commit tables (the forced run itself uses the sc_* above)
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
 };
 
@@ -2360,6 +2361,9 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ scoring a given labeling
 #include "uis_score.hip"
+
+// ------------------------------------------------------------------ priming a session with a labeled prefix
+#include "uis_prime.hip"
 
 // ------------------------------------------------------------------ n-best readout
 #include "uis_nbest.hip"

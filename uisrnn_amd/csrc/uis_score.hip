@@ -15,7 +15,10 @@
 //                    the step loss per frame (k_score_loss), the float32 sum per utterance in frame
 //                    order (k_score_sum)
 // A frame-row r is one (chain, position) pair; rows are position-major: row(p, i) = fbase[p] + i for the
-// i-th longest chain.  The GRU of a chain's last row is not run (its state is never read).
+// i-th longest chain.  The GRU of a chain's last row is not run (its state is never read) -- except in PRIME mode
+// (score_run's `keep`, uis_prime.hip): there every chain runs to its end, the recurrence and the mean scan cover the
+// last row too, and each chain's final hidden states and running mean are what a session is primed with.  The rows a
+// scoring call computes and the kernels that compute them are the same in both modes.
 //
 // #included by uis_decoder.hip after the handle, Launcher and the decode kernels.
 
@@ -162,12 +165,13 @@ __global__ __launch_bounds__(256) void k_score_head(DevModel m, const float* __r
 // The running cluster mean along each chain, in place: row(p, i) holds linear_mean2's output m_{p+1} on entry
 // and M_{p+1} on exit, M_1 = m_1, M_q = uis_mean_update(M_{q-1}, m_q, q - 1)  (uisrnn.py:425-429).
 // One thread per (chain, feature); 8 rows fetched ahead of their updates.
+// `tail` 1 (prime mode): the chain's last row too.
 __global__ __launch_bounds__(256) void k_score_mean_scan(DevModel m, const int32_t* __restrict__ len,
-                                                         const int64_t* __restrict__ fbase, float* mean) {
+                                                         const int64_t* __restrict__ fbase, float* mean, int tail) {
   const int i = blockIdx.y;
   const int d = blockIdx.x * 256 + threadIdx.x;
   if (d >= m.Dp) return;
-  const int nrow = len[i] - 1;  // rows whose mean a later frame reads
+  const int nrow = len[i] - 1 + tail;  // rows whose mean a later frame reads
   constexpr int AHEAD = 8;
   float M = 0.0f;
   for (int p0 = 0; p0 < nrow; p0 += AHEAD) {
@@ -237,6 +241,12 @@ struct ScoreSchedule {
   std::vector<int32_t> row_frame;  // [Fv]
   std::vector<int32_t> row_prev;   // [Fv] row(p - 1, i), -1 at p = 0
   int64_t Fv = 0;
+  // what the traces leave behind, for priming a session (uis_prime.hip); chains here in (utterance, cluster) order
+  std::vector<int32_t> chain_base;  // [U + 1] utterance u's chains: chain_base[u] + cluster
+  std::vector<int32_t> rank;        // [chains] the chain's index i in the longest-first order
+  std::vector<int32_t> chain_blk;   // [chains] block count of the cluster
+  std::vector<int32_t> utt_last;    // [U] last label (-1: no frame)
+  std::vector<int32_t> utt_sum;     // [U] sum(block_counts)
 };
 
 void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int U, const int32_t* labels, ScoreSchedule& s) {
@@ -251,7 +261,13 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
   }
   s.nvalid.assign(U, 0);
   s.prior.assign(F, 0.0);
-  std::vector<int32_t> chain_base(U + 1, 0), chain_len, blk;
+  std::vector<int32_t>& chain_base = s.chain_base;
+  std::vector<int32_t>& rank = s.rank;
+  chain_base.assign(U + 1, 0);
+  s.chain_blk.clear();
+  s.utt_last.assign(U, -1);
+  s.utt_sum.assign(U, 0);
+  std::vector<int32_t> chain_len, blk;
   std::vector<int32_t> frame_chain(F, -1), frame_pos(F, 0);
   for (int u = 0; u < U; ++u) {
     int K = 0, last = -1;
@@ -275,12 +291,16 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
     }
     s.nvalid[u] = (int32_t)(t - offsets[u]);
     chain_base[u + 1] = chain_base[u] + K;
+    s.chain_blk.insert(s.chain_blk.end(), blk.begin(), blk.end());
+    s.utt_last[u] = last;
+    s.utt_sum[u] = (int32_t)sum;
   }
   const int nch = chain_base[U];
   // longest first (counting sort, stable: ties keep (utterance, cluster) order)
   int P = 0;
   for (int c = 0; c < nch; ++c) P = std::max(P, chain_len[c]);
-  std::vector<int32_t> cnt(P + 2, 0), rank(nch);
+  std::vector<int32_t> cnt(P + 2, 0);
+  rank.assign(nch, 0);
   for (int c = 0; c < nch; ++c) ++cnt[P - chain_len[c]];
   for (int k = 1; k <= P + 1; ++k) cnt[k] += cnt[k - 1];
   for (int c = nch - 1; c >= 0; --c) rank[c] = --cnt[P - chain_len[c]];
@@ -304,17 +324,21 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
   }
 }
 
+// `keep` non-null: PRIME mode -- every chain runs to its end (see the head of this file) and the schedule is left in
+// *keep; the buffers (sc_hid, sc_mean, sc_out, sc_utt's offsets) stay as they are until the handle's next scoring call.
 int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_t U, const int32_t* labels, float* scores_out,
-              float* frame_losses_out) {
+              float* frame_losses_out, ScoreSchedule* keep = nullptr) {
   const DevModel& m = h->m;
   const int64_t F = offsets[U];
   const auto t_begin = std::chrono::steady_clock::now();
-  ScoreSchedule s;
+  const bool prime = keep != nullptr;
+  ScoreSchedule s_own;
+  ScoreSchedule& s = prime ? *keep : s_own;
   score_schedule(m, h->alpha, offsets, U, labels, s);
   const auto t_sched = std::chrono::steady_clock::now();
   const int64_t Fv = s.Fv;
   const int P = (int)s.fbase.size(), nch = (int)s.len.size();
-  int maxn = P > 1 ? s.nfr[1] : 0;
+  const int maxn = prime ? (P > 0 ? s.nfr[0] : 0) : (P > 1 ? s.nfr[1] : 0);  // the most chains one recurrence launch runs
   HIPCHK(hipSetDevice(h->device));
   int rc;
   auto need = [](int64_t n, size_t each) { return (size_t)std::max<int64_t>(n, 1) * each; };
@@ -382,9 +406,9 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
   if (Fv > 0) {
     ScoreStep a{};
     a.Fv = Fv; a.row_frame = d_row_frame; a.gi0 = gi0; a.gi_up = h->sc_gi_up.as<float>(); a.hid = h->sc_hid.as<float>();
-    // the recurrence: position p's GRU rows are the chains with a frame at p + 1
-    for (int p = 0; p + 1 < P; ++p) {
-      a.n = s.nfr[p + 1];
+    // the recurrence: position p's GRU rows are the chains with a frame at p + 1 (prime mode: with a frame at p)
+    for (int p = 0; p + (prime ? 0 : 1) < P; ++p) {
+      a.n = prime ? s.nfr[p] : s.nfr[p + 1];
       a.row0 = s.fbase[p];
       a.prev0 = p > 0 ? s.fbase[p - 1] : -1;
       const int nrt = (a.n + 15) / 16;
@@ -394,7 +418,8 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
         LAUNCH(UIS_K_GRU, k_score_gru, dim3((unsigned)dense_grid_blocks(nrt, m.Hp / 16)), dim3(512), 0, m, a);
       }
     }
-    // the heads of every row at once (a chain's last row included: its mean is computed and never read)
+    // the heads of every row at once (a chain's last row included: a scoring call computes its mean from an unwritten
+    // hidden state and never reads it; in prime mode the row is valid and its running mean is the cluster's final one)
     const float* htop = a.hid + (size_t)(m.depth - 1) * Fv * m.Hp;
     float* a1 = h->sc_a1.as<float>();
     float* mean = h->sc_mean.as<float>();
@@ -402,7 +427,9 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
            m.w1, m.b1, m.Hp / 16, m.Hp / 16, htop, a1, (long)Fv);
     LAUNCH(UIS_K_HEAD2, k_score_head<2>, dim3((unsigned)((Fv + 31) / 32), (unsigned)((m.Dp / 16 + 15) / 16)), dim3(256), 0, m,
            m.w2, m.b2, m.Dp / 16, m.Hp / 16, a1, mean, (long)Fv);
-    if (P > 1) LAUNCH(UIS_K_HEAD2, k_score_mean_scan, dim3((unsigned)((m.Dp + 255) / 256), (unsigned)nch), dim3(256), 0, m, d_len, d_fbase, mean);
+    if (P > 1 || prime)
+      LAUNCH(UIS_K_HEAD2, k_score_mean_scan, dim3((unsigned)((m.Dp + 255) / 256), (unsigned)nch), dim3(256), 0, m, d_len, d_fbase, mean,
+             prime ? 1 : 0);
     LAUNCH(UIS_K_SELECT, k_score_loss, dim3((unsigned)((Fv + 3) / 4)), dim3(256), 0, m, (long)Fv, d_row_frame, d_row_prev, d_x, mse0,
            mean, h->sc_prior.as<double>(), loss);
   }
@@ -415,8 +442,8 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     float dev_ms = 0.0f;
     (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
     const auto t_end = std::chrono::steady_clock::now();
-    fprintf(stderr, "uis_score_labels: frames %lld chains %d longest %d schedule_ms %.3f device_ms %.3f total_ms %.3f\n",
-            (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
+    fprintf(stderr, "%s: frames %lld chains %d longest %d schedule_ms %.3f device_ms %.3f total_ms %.3f\n",
+            prime ? "uis_stream_prime (forced run)" : "uis_score_labels", (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
             std::chrono::duration<double, std::milli>(t_end - t_begin).count());
   }
   return UIS_OK;

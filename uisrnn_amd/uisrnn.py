@@ -531,6 +531,89 @@ class UISRNN:
       return self._decode_batch(test_sequences, args, n_best=int(n_best))
     raise TypeError('test_sequences should be either a list or numpy array.')
 
+  def predict_primed(self, test_sequences, prefix_cluster_ids, args):
+    """predict, with the first frames of every sequence already labeled (extension).
+
+    The decode of sequence u starts from the state the model holds after prefix_cluster_ids[u] along its
+    first P_u frames (a session primed with them, OnlineSession.prime) and beam-searches the rest: what
+    predict computes when its beam is told the opening instead of searching for it.
+
+    Args:
+      test_sequences: a [N, D] float array or a list of them (as predict).
+      prefix_cluster_ids: P <= N ids for an array (any hashable kind, renamed by order of first
+        appearance; may be empty), or a list of such sequences for a list.
+      args: inference namespace; look_ahead and test_iteration must be 1 (online decoding).
+    Returns:
+      N ints for an array, a list of such lists for a list; the first P_u are the renamed prefix.
+    Raises:
+      what predict raises; ValueError for look_ahead / test_iteration other than 1, a prefix longer than its
+      sequence or a list mismatch; _capi.HipLibraryError (status UIS_ERR_INVALID_ARG) for a prefix whose
+      likelihood is not finite.
+    """
+    single = isinstance(test_sequences, np.ndarray)
+    if single:
+      seqs, ids = [test_sequences], [prefix_cluster_ids]
+    elif isinstance(test_sequences, list):
+      seqs = test_sequences
+      if not isinstance(prefix_cluster_ids, (list, tuple)) or len(prefix_cluster_ids) != len(seqs):
+        raise ValueError('prefix_cluster_ids must be a list with one id sequence per test sequence.')
+      ids = list(prefix_cluster_ids)
+    else:
+      raise TypeError('test_sequences should be either a list or numpy array.')
+    if int(args.look_ahead) != 1 or int(args.test_iteration) != 1:
+      raise ValueError('predict_primed is online decoding: look_ahead and test_iteration must be 1.')
+    for seq in seqs:
+      self._check_sequence(seq)
+    prefixes = []
+    for seq, seq_ids in zip(seqs, ids):
+      seq_ids = [] if seq_ids is None else (seq_ids.tolist() if isinstance(seq_ids, np.ndarray) else list(seq_ids))
+      if len(seq_ids) > seq.shape[0]:
+        raise ValueError('prefix_cluster_ids has {} ids for a sequence of {} frames.'.format(
+            len(seq_ids), seq.shape[0]))
+      names = {}
+      prefixes.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
+    if not seqs:
+      return []
+    decoder = self._get_decoder()
+    results = [None] * len(seqs)
+    pending = list(range(len(seqs)))
+    cap = _initial_cluster_cap(args)
+
+    def more_room(cap):
+      if cap * 2 > _MAX_CLUSTERS_LIMIT:
+        raise RuntimeError('more than {} clusters per hypothesis'.format(_MAX_CLUSTERS_LIMIT))
+      return cap * 2
+
+    while pending:
+      lens = [seqs[u].shape[0] for u in pending]
+      decoder.stream_begin(len(pending), args.beam_size, max(max(lens), 1), max_clusters=cap)
+      try:
+        try:
+          decoder.stream_prime([seqs[u][:len(prefixes[u])] for u in pending], [prefixes[u] for u in pending])
+        except _capi.HipLibraryError as err:
+          if err.status != _capi.UIS_ERR_CLUSTER_CAP:
+            raise
+          cap = more_room(cap)  # a prefix with more clusters than the tables hold: the batch again, twice the room
+          continue
+        decoder.stream_push([seqs[u][len(prefixes[u]):] if seqs[u].shape[0] > len(prefixes[u]) else None
+                             for u in pending])
+        per_utt, _, overflow, _ = decoder.stream_labels()
+      finally:
+        decoder.stream_end()
+      still = []
+      for k, u in enumerate(pending):
+        if overflow[k]:
+          still.append(u)
+          continue
+        if per_utt[k].size and per_utt[k][0] < 0:
+          raise EmptyBeamError('the beam became empty (max() arg is an empty sequence / list index out of '
+                               'range in the reference): non-finite scores in utterance {}'.format(u))
+        results[u] = per_utt[k].tolist()
+      pending = still
+      if pending:
+        cap = more_room(cap)
+    return results[0] if single else results
+
   def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
     """The model's negative log-likelihood of given labelings (extension).
 
@@ -639,6 +722,58 @@ class OnlineSession:
     if not self.persistent:
       self._decoder.stream_begin(num_utterances, args.beam_size, max_frames, max_clusters=cap)
     self._open = True
+    self._num_utterances = int(num_utterances)
+
+  def prime(self, chunks, cluster_ids):
+    """Start utterances from a labeled prefix (uis_stream_prime; extension).
+
+    The session is afterwards in the state it would hold had it received the prefix frames with its beam
+    holding only the given labeling: labels() returns the prefix followed by what is decoded, scores are the
+    prefix's negative log-likelihood plus the continuation, stable_frames() is at least the prefix length,
+    and the prefix frames count against max_frames.
+
+    Args:
+      chunks: a list with one [P_u, D] float64 array or None per utterance: the prefix frames.
+      cluster_ids: a list with one sequence of P_u ids (any hashable kind; renamed by order of first
+        appearance, as score_labels does) or None per utterance.
+    Returns:
+      a list with the prefix's negative log-likelihood (float) per utterance, None where nothing was primed.
+    Raises:
+      TypeError / ValueError: a chunk that predict would refuse, in predict's words.
+      ValueError: a length mismatch, or an utterance that has already received or been primed with frames.
+      _capi.HipLibraryError: the library's refusals (status UIS_ERR_CLUSTER_CAP: a prefix with more clusters
+        than the session's max_clusters; UIS_ERR_INVALID_ARG: a prefix longer than max_frames or one whose
+        likelihood is not finite).  The session is then as it was.
+    """
+    n_utt = self._num_utterances
+    if not isinstance(chunks, (list, tuple)) or not isinstance(cluster_ids, (list, tuple)):
+      raise TypeError('chunks and cluster_ids must be lists with one entry (or None) per utterance.')
+    if len(chunks) != n_utt or len(cluster_ids) != n_utt:
+      raise ValueError('one chunk and one id sequence (or None) per utterance ({} utterances).'.format(n_utt))
+    labels, frames = [None] * n_utt, [None] * n_utt
+    received = self._decoder.stream_received()
+    for u, (chunk, ids) in enumerate(zip(chunks, cluster_ids)):
+      if isinstance(ids, np.ndarray):
+        ids = ids.tolist()
+      n_ids = 0 if ids is None else len(ids)
+      if chunk is None:
+        if n_ids:
+          raise ValueError('utterance {}: {} cluster ids but no frames.'.format(u, n_ids))
+        continue
+      self._model._check_sequence(chunk)  # pylint: disable=protected-access
+      if chunk.shape[0] != n_ids:
+        raise ValueError('utterance {}: cluster_ids has {} ids for a prefix of {} frames.'.format(
+            u, n_ids, chunk.shape[0]))
+      if not n_ids:
+        continue
+      if received[u]:
+        raise ValueError('utterance {} has already received {} frames: a prefix goes in front of '
+                         'everything.'.format(u, int(received[u])))
+      names = {}
+      labels[u] = np.array([names.setdefault(i, len(names)) for i in ids], dtype=np.int32)
+      frames[u] = chunk
+    scores = self._decoder.stream_prime(frames, labels)
+    return [float(scores[u]) if labels[u] is not None else None for u in range(n_utt)]
 
   def push(self, chunks):
     """chunks: a list with one [n, D] float64 array (or None) per utterance, or one [U, n, D]
