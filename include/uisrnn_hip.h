@@ -348,7 +348,8 @@ int32_t uis_rnn_step(uis_handle* h, const float* x, const float* h_in, float* me
  * (bit for bit).  One session per handle; uis_decode is refused while it is open.
  *
  *   uis_stream_begin  opts->test_iteration and look_ahead must be 1; max_frames = the most frames
- *                     any utterance will receive in this session (4 * beam_size bytes each).
+ *                     any utterance will receive in this session (4 * beam_size bytes each) -- with
+ *                     uis_stream_commit (below): the most it holds between two commits.
  *                     opts->flags: UIS_FLAG_PERSISTENT keeps the decode kernel on the device
  *                     between pushes (lowest latency, occupies the whole device; UIS_ERR_UNSUPPORTED
  *                     where the session's shape does not allow it)
@@ -470,6 +471,43 @@ int32_t uis_last_decode_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out
                               float* scores_out, int32_t* counts_out);
 int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int64_t capacity,
                          float* scores_out, int32_t* counts_out, int64_t* stable_out);
+
+/*
+ * Session commits: endless online decoding in a fixed window.  uis_stream_commit hands out the labels of an open
+ * session that are final, drops their back-pointer records and gives the room back: max_frames is then the WINDOW,
+ * the frames received and not yet committed, and a stream of any length can be pushed through it.  From the first
+ * commit on, uis_stream_push's capacity check, uis_stream_labels, uis_stream_nbest and its stable_out all speak
+ * about the window (committed labels are the caller's to keep: window labels follow them).  A session that never
+ * commits behaves exactly as before.  No decode kernel is involved.  Per utterance u, with have = the frames in the
+ * window and stable = what uis_stream_nbest reports:
+ *   cut     horizon == NULL or horizon[u] < 0: cut = stable.  Otherwise cut = max(stable, have - horizon[u]): frames
+ *           older than the newest horizon[u] are decided in favour of the best hypothesis (a decision horizon, the
+ *           bound on the delay that the stable prefix alone does not give)
+ *   prune   only if cut > stable: every live hypothesis whose ancestor at step cut - 1 is not rank 0's -- whose
+ *           labels differ from rank 0's somewhere in [0, cut) -- leaves the beam.  Survivors keep their order, their
+ *           scores and all their state; rank 0 always survives; horizon[u] == 0 collapses the beam onto rank 0.
+ *           dropped_out[u] = the number removed
+ *   commit  c = cut & ~1 (even, so the beam tables keep the parity of the step count).  labels_out receives rank 0's
+ *           labels of window frames [0, c), packed in utterance order; counts_out[u] = c.  The window then starts c
+ *           frames later.  Cluster ids stay what they were: first-appearance form over the WHOLE stream
+ * An utterance with nothing in its window, with an emptied beam or flagged in the overflow word commits 0 and is
+ * left alone.  Scores are not rebased: they go on growing with the stream (float32).  A window that a commit has
+ * emptied (c = have) holds exactly one hypothesis: until the utterance's next frame uis_stream_labels reports its
+ * score with no labels, and uis_stream_nbest counts_out 1, that score, a row of no labels and stable_out 0.
+ *   horizon     : host int32 [n_utt] or NULL
+ *   labels_out  : host int32, capacity slots; capacity >= the frames in the window (sum over utterances)
+ *   counts_out  : host int32 [n_utt]
+ *   dropped_out : host int32 [n_utt] or NULL
+ * All or nothing: UIS_ERR_INVALID_ARG (no session open, capacity too small) touches nothing; UIS_ERR_OOM (the prior
+ * tables, which grow with the frames ever received, could not be lengthened) leaves the session as it was.  In a
+ * UIS_FLAG_PERSISTENT session the resident launch leaves the device for this call (as for uis_stream_nbest) and the
+ * next push starts a new one.  An utterance that has committed frames cannot be primed, also when its window is
+ * empty; one cannot receive more than 2^31 - 256 frames in one session (uis_stream_push: UIS_ERR_UNSUPPORTED).
+ * uis_stream_committed: committed_out host int64 [n_utt], the frames committed so far per utterance.
+ */
+int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int32_t* labels_out, int64_t capacity,
+                          int32_t* counts_out, int32_t* dropped_out);
+int32_t uis_stream_committed(uis_handle* h, int64_t* committed_out);
 
 /*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the

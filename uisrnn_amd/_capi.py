@@ -333,6 +333,10 @@ def load_library(path=None):
   lib.uis_last_decode_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p]
   lib.uis_stream_nbest.restype = i32
   lib.uis_stream_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p, i64p]
+  lib.uis_stream_commit.restype = i32
+  lib.uis_stream_commit.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, i32p]
+  lib.uis_stream_committed.restype = i32
+  lib.uis_stream_committed.argtypes = [ctypes.c_void_p, i64p]
   lib.uis_eval_accuracy.restype = i32
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
@@ -371,7 +375,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_stream_commit', 'uis_stream_committed', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -645,7 +649,7 @@ class Decoder:
     self._stream_have += counts
 
   def stream_received(self):
-    """Frames per utterance the open session holds (pushed or primed): int64 [n_utt]."""
+    """Frames per utterance the open session holds (pushed or primed, not yet committed): int64 [n_utt]."""
     return self._stream_have.copy()
 
   def stream_prime(self, chunks, labels):
@@ -686,6 +690,43 @@ class Decoder:
       raise err
     self._stream_have += counts
     return scores
+
+  def stream_commit(self, horizon=None):
+    """Hand out the labels that are final and move the session's window behind them (uis_stream_commit).
+
+    horizon: None (only the stable prefix is committed), or one int per utterance (negative: none for that
+    utterance): frames older than the newest `horizon` are decided in favour of the best hypothesis, and the
+    hypotheses that disagree with it there leave the beam.  Returns (labels, dropped): per utterance the int32
+    labels committed by this call (an even number of them), and int32 [n_utt] hypotheses pruned.  Afterwards
+    stream_received(), stream_labels() and stream_nbest() speak about the window: the frames not yet committed."""
+    n_utt = self._stream_n
+    hz_ptr = None
+    if horizon is not None:
+      hz = np.ascontiguousarray(horizon, dtype=np.int32).reshape(-1)
+      if hz.shape[0] != n_utt:
+        raise ValueError('one horizon per utterance')
+      hz_ptr = hz.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    total = int(self._stream_have.sum())
+    labels = np.empty(max(total, 1), dtype=np.int32)
+    counts = np.zeros(n_utt, dtype=np.int32)
+    dropped = np.zeros(n_utt, dtype=np.int32)
+    rc = self._lib.uis_stream_commit(
+        self._handle, hz_ptr, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
+        counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dropped.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != UIS_OK:
+      err = HipLibraryError('uis_stream_commit failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    self._stream_have -= counts
+    return [labels[bounds[u]:bounds[u + 1]].copy() for u in range(n_utt)], dropped
+
+  def stream_committed(self):
+    """Frames per utterance committed so far (uis_stream_committed): int64 [n_utt]."""
+    out = np.zeros(self._stream_n, dtype=np.int64)
+    self._check(self._lib.uis_stream_committed(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+                'uis_stream_committed')
+    return out
 
   def stream_labels(self):
     """Best-hypothesis labels of everything received so far: (list of int32 arrays, scores, overflow, status)."""

@@ -161,6 +161,7 @@ struct StreamMem {
   // host memory (h_stage) and mirrored in chunk_x
   HostBuf h_stage;
   HostBuf pm_block;  // the persistent launch's mailbox (host-coherent)
+  HostBuf h_land;    // uis_stream_commit's pinned landing block
 };
 
 // Every device and pinned buffer of a handle outside its session, likewise.
@@ -177,6 +178,7 @@ struct HandleMem {
   DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
   DevBuf sc_prime;  // uis_stream_prime's commit tables (the forced run itself uses the sc_* above)
+  DevBuf sc_commit;  // uis_stream_commit's horizon / committed / dropped words
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
 };
 
@@ -210,7 +212,13 @@ struct uis_handle : HandleMem {
     bool active = false;
     int U = 0, B = 0, Kmax = 0, S = 0;
     int64_t cap = 0;                  // frames per utterance the session can hold
-    std::vector<int32_t> have;        // frames received per utterance
+    std::vector<int32_t> have;        // frames per utterance in the window: received or primed, not yet committed
+    std::vector<int64_t> committed;   // frames per utterance handed out by uis_stream_commit (have + committed = received)
+    int64_t log_len = 0;              // entries of st.logblk / st.logden
+    std::vector<float> win_score;     // rank 0's score at the last commit: what an utterance whose window the commit emptied still has
+    // everything committed, nothing received since: ONE hypothesis lives (all survivors shared the ancestor at the
+    // last step), its labels are the committed ones and its score is win_score; the readouts' kernels see N = 0
+    bool window_emptied(int u) const { return have[u] == 0 && committed[u] > 0; }
     DecodeState st{};
     int32_t* d_avail = nullptr;
     int32_t* d_have = nullptr;        // frames received per utterance, refreshed for every back-trace
@@ -2367,3 +2375,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ n-best readout
 #include "uis_nbest.hip"
+
+// ------------------------------------------------------------------ committing a session's final labels
+#include "uis_commit.hip"

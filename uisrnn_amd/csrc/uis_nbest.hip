@@ -282,5 +282,11 @@ UIS_EXPORT int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labe
   std::vector<int32_t> overflow;
   if ((rc = nbest_run(h, groups, false, ss.B, off, n_best, labels_out, capacity, scores_out, counts_out, stable_out, &overflow)))
     return rc;
+  for (int u = 0; u < U; ++u) {  // a window that a commit emptied: the one hypothesis that lives, no labels left to show
+    if (!ss.window_emptied(u)) continue;
+    if (counts_out) counts_out[u] = 1;
+    if (scores_out) scores_out[(size_t)u * n_best] = ss.win_score[u];
+    stable_out[u] = 0;
+  }
   return cluster_cap_status(count_cluster_cap(overflow), ss.Kmax);
 }

@@ -132,9 +132,9 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   for (int u = 0; u < U; ++u) {
     const int64_t P = offsets[u + 1] - offsets[u];
     if (P == 0) continue;
-    if (ss.have[u] != 0)
+    if (ss.committed[u] + ss.have[u] != 0)  // (an utterance whose window is empty after a commit has received frames all the same)
       return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has already received or been primed with " +
-                                           std::to_string(ss.have[u]) + " frames: a prefix goes in front of everything");
+                                           std::to_string((long long)(ss.committed[u] + ss.have[u])) + " frames: a prefix goes in front of everything");
     if (P > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + ": the prefix exceeds the session's max_frames");
     int K = 0;
     for (int64_t t = offsets[u]; t < offsets[u + 1]; ++t) {

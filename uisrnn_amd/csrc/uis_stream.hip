@@ -179,6 +179,17 @@ int pm_quit(uis_handle* h) {
   return pm_reap(h);
 }
 
+// uis_stream_labels: an utterance whose window a commit emptied still has its one hypothesis and its score
+void stream_emptied_windows(uis_handle* h, float* scores_out) {
+  uis_handle::Stream& ss = h->stream_state;
+  for (int u = 0; u < ss.U; ++u) {
+    if (!ss.window_emptied(u)) continue;
+    if (scores_out) scores_out[u] = ss.win_score[u];
+    h->last_beam_scores[(size_t)u * ss.B] = ss.win_score[u];
+    for (int k = 1; k < ss.B; ++k) h->last_beam_scores[(size_t)u * ss.B + k] = INFINITY;
+  }
+}
+
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
@@ -203,6 +214,9 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   ss.poison = UisPoison::from_env();
   ss.U = U; ss.B = B; ss.Kmax = Kmax; ss.S = S; ss.cap = max_frames;
   ss.have.assign(U, 0);
+  ss.committed.assign(U, 0);
+  ss.win_score.assign(U, 0.0f);
+  ss.log_len = max_frames + 2;
   DecodeState& st = ss.st;
   st.U = U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = 1; st.tau = 1; st.flags = opts->flags | (agent_flags_env() ? UIS_FLAG_AGENT_FLAGS : 0u);
   st.max_rows = U * B;
@@ -319,7 +333,12 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   int64_t F = 0, max_new = 0;
   for (int u = 0; u < U; ++u) {
     if (counts[u] < 0) return fail(UIS_ERR_INVALID_ARG, "negative frame count");
-    if ((int64_t)ss.have[u] + counts[u] > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames");
+    if ((int64_t)ss.have[u] + counts[u] > ss.cap)
+      return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames (the window of frames not yet committed: "
+                                       "uis_stream_commit makes room)");
+    // (pool_cnt / beam_sum count everything an utterance ever received, in int32)
+    if (ss.committed[u] + ss.have[u] + counts[u] > 0x7fffff00LL)
+      return fail(UIS_ERR_UNSUPPORTED, "utterance would have received more than 2^31 - 256 frames in this session");
     F += counts[u];
     max_new = std::max<int64_t>(max_new, counts[u]);
   }
@@ -513,6 +532,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
                               reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow) + U);
       h->last_beam_scores.assign(reinterpret_cast<const float*>(pm + ss.pm_o_bscores),
                                  reinterpret_cast<const float*>(pm + ss.pm_o_bscores) + (size_t)U * ss.B);
+      stream_emptied_windows(h, scores_out);
       return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
     }
     if (rc != 1) return rc;  // (1: the launch had left -- its tables are back in global memory)
@@ -542,6 +562,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
   HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, (size_t)U * ss.B * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  stream_emptied_windows(h, scores_out);
   return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
 }
 

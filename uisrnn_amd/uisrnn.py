@@ -467,13 +467,14 @@ class UISRNN:
     self._check_sequence(test_sequence)
     return self._decode_batch([test_sequence], args)[0]
 
-  def online(self, num_utterances, args, max_frames, persistent=False):
-    """An OnlineSession (streaming decode; extension, see the class)."""
+  def online(self, num_utterances, args, max_frames, persistent=False, horizon=None):
+    """An OnlineSession (streaming decode; extension, see the class).  horizon: None, or the decision
+    horizon in frames of a session that commits by itself when a push does not fit its window."""
     if args.look_ahead != 1:
       raise ValueError('online decoding needs look_ahead 1')
     if self.transition_bias is None:
       raise TypeError('transition_bias is None: the model was never fit or loaded')
-    return OnlineSession(self, num_utterances, args, max_frames, persistent)
+    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon)
 
   def predict(self, test_sequences, args):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
@@ -698,6 +699,16 @@ class OnlineSession:
       hyps = session.nbest(3)              # per utterance (labelings, scores) of the three best hypotheses
       final = session.stable_frames()      # per utterance: labels()[u][:final[u]] can no longer change
 
+  A stream longer than max_frames: commit() hands out the labels that are final and moves the session's
+  window of max_frames frames behind them; the session keeps them, and labels() / nbest() / stable_frames()
+  go on answering for the whole stream.  With horizon=L given to model.online a push that does not fit
+  commits by itself, deciding every frame older than the newest L (max_frames >= L + largest chunk + 1):
+
+    with model.online(1, inference_args, max_frames=64, horizon=32) as session:
+      for chunk in microphone:             # for ever
+        session.push([chunk])
+        final = session.commit()           # optional: the labels that became final, to pass on now
+
   persistent=True (UIS_FLAG_PERSISTENT): the decode kernel stays on the GPU between pushes and is
   fed through a mailbox in pinned host memory -- the lowest push latency (no launch, no copy
   engine), at the price of occupying the whole device until the session closes or has been idle
@@ -705,8 +716,15 @@ class OnlineSession:
   silently uses ordinary launches.
   """
 
-  def __init__(self, model, num_utterances, args, max_frames, persistent=False):
+  _final = None   # per utterance the labels committed so far (a list per utterance once the session is open)
+
+  def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None):
+    if horizon is not None and (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 0):
+      raise ValueError('horizon must be None or a non-negative integer.')
     self._model = model
+    self._horizon = None if horizon is None else int(horizon)
+    self._max_frames = int(max_frames)
+    self._final = [[] for _ in range(int(num_utterances))]   # the committed labels, per utterance
     self._beam_size = int(args.beam_size)
     self._decoder = _capi.Decoder(model.params, model.device_index)  # own handle: one session per handle
     cap = _initial_cluster_cap(args)
@@ -752,6 +770,8 @@ class OnlineSession:
       raise ValueError('one chunk and one id sequence (or None) per utterance ({} utterances).'.format(n_utt))
     labels, frames = [None] * n_utt, [None] * n_utt
     received = self._decoder.stream_received()
+    if self._final is not None:   # (committed frames have been received all the same, whatever the window holds)
+      received = received + np.array([len(f) for f in self._final], dtype=np.int64)
     for u, (chunk, ids) in enumerate(zip(chunks, cluster_ids)):
       if isinstance(ids, np.ndarray):
         ids = ids.tolist()
@@ -778,6 +798,8 @@ class OnlineSession:
   def push(self, chunks):
     """chunks: a list with one [n, D] float64 array (or None) per utterance, or one [U, n, D]
     float64 array when every utterance received the same number of frames."""
+    if self._horizon is not None:
+      self._make_room(chunks)
     if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
       if chunks.dtype != float:
         raise TypeError('test_sequence should be a numpy array of float type.')
@@ -803,13 +825,68 @@ class OnlineSession:
       return
     self._decoder.stream_push(chunks)
 
+  def _make_room(self, chunks):
+    """horizon given: a push whose chunk does not fit the window commits first."""
+    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
+      sizes = np.full(len(chunks), chunks.shape[1], dtype=np.int64)
+    else:
+      sizes = np.array([0 if c is None else len(c) for c in chunks], dtype=np.int64)
+    if len(sizes) != self._num_utterances:
+      return   # (stream_push refuses it in its own words)
+    if ((self._decoder.stream_received() + sizes) <= self._max_frames).all():
+      return
+    self.commit(self._horizon)
+    if ((self._decoder.stream_received() + sizes) > self._max_frames).any():
+      raise ValueError('a chunk of {} frames does not fit the session\'s window after a commit: max_frames ({}) must be '
+                       'at least horizon + chunk + 1 = {}.'.format(int(sizes.max()), self._max_frames,
+                                                                   self._horizon + int(sizes.max()) + 1))
+
+  def commit(self, horizon=None):
+    """Hand out the labels that are final and give their room back to the session (uis_stream_commit).
+
+    Without a horizon the stable prefix (stable_frames()) is committed, rounded down to an even count: the
+    session's results do not change, only its window moves.  With horizon=L frames older than the newest L are
+    decided in favour of the currently best hypothesis as well, and the hypotheses that disagree with it there
+    leave the beam: the bound on the delay that the stable prefix alone does not give.
+
+    Args:
+      horizon: None, an int for all utterances, or a list with an int or None per utterance.
+    Returns:
+      per utterance the list of labels that became final in this call (in stream order; cluster ids stay
+      those of the whole stream).  The session keeps them: labels(), nbest() and stable_frames() go on
+      answering for everything received.
+    """
+    n_utt = self._num_utterances
+    if horizon is None:
+      hz = None
+    elif isinstance(horizon, (int, np.integer)) and not isinstance(horizon, bool):
+      if horizon < 0:
+        raise ValueError('horizon must be non-negative.')
+      hz = [int(horizon)] * n_utt
+    else:
+      if len(horizon) != n_utt:
+        raise ValueError('one horizon (or None) per utterance ({} utterances).'.format(n_utt))
+      hz = [-1 if x is None else int(x) for x in horizon]
+      if any(x < -1 for x in hz):
+        raise ValueError('horizon must be non-negative.')
+    new, _ = self._decoder.stream_commit(hz)
+    out = [x.tolist() for x in new]
+    for u in range(n_utt):
+      self._final[u].extend(out[u])
+    return out
+
+  @property
+  def committed(self):
+    """Per utterance, the number of frames committed so far."""
+    return [int(x) for x in self._decoder.stream_committed()]
+
   def labels(self):
     per_utt, _, overflow, _ = self._decoder.stream_labels()
     if overflow.any():
       raise RuntimeError('utterance(s) {} need more than max_clusters clusters per hypothesis; '
                          'open the session with a larger args.max_clusters'.format(
                              np.flatnonzero(overflow).tolist()))
-    return [x.tolist() for x in per_utt]
+    return [self._final[u] + x.tolist() for u, x in enumerate(per_utt)]
 
   def _nbest(self, n_best):
     if n_best is None:
@@ -826,14 +903,15 @@ class OnlineSession:
   def nbest(self, n_best=None):
     """Every hypothesis of the current beam for everything received: per utterance the pair
     (labelings, scores) of UISRNN.predict_nbest; labelings[0] is what labels() returns.  An utterance
-    that has received nothing yet has no hypothesis: ([], []).
+    that has received nothing yet has no hypothesis: ([], []).  After commit() the labelings are those of the
+    whole stream, committed part first; an utterance whose window a commit emptied has its one hypothesis.
 
     Cost: a back-trace of every requested rank and a download of n_best labels per frame received.
     In a persistent session the resident launch has to leave the device for it and the next push
     starts a new one (a launch plus the kernel's weight load): read every few pushes, not after each,
     or the session loses most of what persistent=True buys."""
     out = self._nbest(n_best)
-    return [([row.tolist() for row in out['labels'][u][:int(out['counts'][u])]],
+    return [([self._final[u] + row.tolist() for row in out['labels'][u][:int(out['counts'][u])]],
              [float(x) for x in out['scores'][u][:int(out['counts'][u])]])
             for u in range(len(out['labels']))]
 
@@ -845,7 +923,7 @@ class OnlineSession:
     Cost: that of nbest(1) -- the readout runs and the best hypothesis' labels are downloaded -- and,
     like nbest, it makes a persistent session's resident launch leave the device.  Not for polling
     after every push of a persistent session."""
-    return [int(x) for x in self._nbest(1)['stable']]
+    return [len(self._final[u]) + int(x) for u, x in enumerate(self._nbest(1)['stable'])]
 
   def close(self):
     if self._open:
