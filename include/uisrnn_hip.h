@@ -510,6 +510,40 @@ int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int32_t* labels
 int32_t uis_stream_committed(uis_handle* h, int64_t* committed_out);
 
 /*
+ * Session restarts: end some utterances of an open session and reuse their slots in place.  The set of utterances
+ * of a session is fixed by uis_stream_begin; uis_stream_restart lets one of them end -- its final window labels are
+ * handed out -- and leaves its slot in the state uis_stream_begin gives an utterance, so that the next stream can
+ * use it while every other utterance's beam lives on untouched.  It is also how a dead slot comes back: one that
+ * hit the cluster cap (its overflow word is set) or whose beam a non-finite frame emptied.  No decode kernel is
+ * involved.
+ *   which        : host int32 [n_utt]; non-zero = this utterance ends here
+ *   labels_out   : host int32, capacity slots: exactly what uis_stream_labels would write at this moment for the
+ *                  selected utterances -- rank 0's labels of the frames in their windows, packed in utterance order
+ *                  (labels already committed are the caller's, as after any commit).  capacity >= the sum of window
+ *                  frames over the selected utterances
+ *   counts_out   : host int32 [n_utt]: window frames handed out, 0 for an utterance not selected
+ *   scores_out   : host float [n_utt] or NULL: for selected utterances what uis_stream_labels reports (the kept
+ *                  score of a window emptied by a commit, +inf for an emptied beam, 0 for nothing received);
+ *                  entries of utterances not selected are not written
+ *   overflow_out : host int32 [n_utt] or NULL: the selected utterances' overflow words BEFORE the reset; entries
+ *                  not selected are not written
+ * Afterwards every selected utterance has received nothing and committed nothing (uis_stream_committed reports 0),
+ * holds one empty hypothesis of score 0, its overflow word is clear, uis_stream_prime accepts it, and its count
+ * towards the 2^31 - 256 frame limit starts again.  Utterances not selected are untouched, to the bit.
+ * Returns UIS_OK, or UIS_ERR_CLUSTER_CAP when a selected utterance had hit the cap: as in uis_stream_labels
+ * everything is still written, and the restart has still happened.  Otherwise all or nothing: UIS_ERR_INVALID_ARG
+ * (no session open, null which / counts_out, capacity too small, null labels_out with labels due) touches nothing;
+ * UIS_ERR_OOM (scratch) leaves the session as it was.  Selecting nothing is UIS_OK with zero counts and no device
+ * work.  The call does not change what uis_last_decode_info / _shape answer for; like a commit it invalidates the
+ * n-best cache.  In a UIS_FLAG_PERSISTENT session the resident launch leaves the device for this call (after the
+ * host checks, as for uis_stream_commit) and the next push starts a new one.  UIS_POISON_WORKSPACE: everything the
+ * ended stream leaves behind in the slot (its back-pointer rows, pool slots and beam-table rows) is filled with the
+ * word before the reset.  UIS_RESTART_TRACE=1: one line per call on stderr.
+ */
+int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32_t* labels_out, int64_t capacity,
+                           int32_t* counts_out, float* scores_out, int32_t* overflow_out);
+
+/*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the
  * H2D copy of the frame stream is asynchronous and overlaps the input projection of the chunks
  * already on the device.  Pageable memory works too (staged by the runtime).

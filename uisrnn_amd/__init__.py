@@ -15,5 +15,6 @@ output_result = utils.output_result
 UISRNN = _uisrnn.UISRNN
 parallel_predict = _uisrnn.parallel_predict
 OnlineSession = _uisrnn.OnlineSession  # extension: streaming decode
+StreamPool = _uisrnn.StreamPool  # extension: an open-ended set of streams over one session's slots
 EmptyBeamError = _uisrnn.EmptyBeamError
 LookAheadWindowError = _uisrnn.LookAheadWindowError

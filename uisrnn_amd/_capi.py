@@ -337,6 +337,8 @@ def load_library(path=None):
   lib.uis_stream_commit.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, i32p]
   lib.uis_stream_committed.restype = i32
   lib.uis_stream_committed.argtypes = [ctypes.c_void_p, i64p]
+  lib.uis_stream_restart.restype = i32
+  lib.uis_stream_restart.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, _fp, i32p]
   lib.uis_eval_accuracy.restype = i32
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
@@ -375,7 +377,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_stream_commit', 'uis_stream_committed', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -727,6 +729,35 @@ class Decoder:
     self._check(self._lib.uis_stream_committed(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
                 'uis_stream_committed')
     return out
+
+  def stream_restart(self, which):
+    """End the utterances selected by `which` and leave their slots fresh (uis_stream_restart).
+
+    which: one truth value per utterance.  Returns (labels, scores, overflow, status): per utterance the int32
+    labels of its window at this moment (what stream_labels() would give; empty for an utterance not selected),
+    float32 [n_utt] scores and int32 [n_utt] overflow words from before the reset (entries of utterances not
+    selected: nan and 0), and UIS_OK or UIS_ERR_CLUSTER_CAP (a selected utterance had hit the cap; the restart has
+    happened all the same).  A refusal (HipLibraryError with .status) leaves the session as it was."""
+    n_utt = self._stream_n
+    sel = np.ascontiguousarray([1 if w else 0 for w in which], dtype=np.int32)
+    if sel.shape[0] != n_utt:
+      raise ValueError('one selection flag per utterance')
+    total = int(self._stream_have[sel != 0].sum())
+    labels = np.empty(max(total, 1), dtype=np.int32)
+    counts = np.zeros(n_utt, dtype=np.int32)
+    scores = np.full(n_utt, np.nan, dtype=np.float32)
+    overflow = np.zeros(n_utt, dtype=np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    rc = self._lib.uis_stream_restart(
+        self._handle, sel.ctypes.data_as(i32p), labels.ctypes.data_as(i32p), total, counts.ctypes.data_as(i32p),
+        scores.ctypes.data_as(_fp), overflow.ctypes.data_as(i32p))
+    if rc not in (UIS_OK, UIS_ERR_CLUSTER_CAP):
+      err = HipLibraryError('uis_stream_restart failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    self._stream_have[sel != 0] = 0
+    return [labels[bounds[u]:bounds[u + 1]].copy() for u in range(n_utt)], scores, overflow, rc
 
   def stream_labels(self):
     """Best-hypothesis labels of everything received so far: (list of int32 arrays, scores, overflow, status)."""

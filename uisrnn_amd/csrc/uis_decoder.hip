@@ -179,6 +179,7 @@ struct HandleMem {
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
   DevBuf sc_prime;  // uis_stream_prime's commit tables (the forced run itself uses the sc_* above)
   DevBuf sc_commit;  // uis_stream_commit's horizon / committed / dropped words
+  DevBuf sc_restart;  // uis_stream_restart's selection, window counts, label offsets and what comes back
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
 };
 
@@ -2378,3 +2379,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ committing a session's final labels
 #include "uis_commit.hip"
+
+// ------------------------------------------------------------------ ending utterances of a session, reusing their slots
+#include "uis_restart.hip"

@@ -476,6 +476,11 @@ class UISRNN:
       raise TypeError('transition_bias is None: the model was never fit or loaded')
     return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon)
 
+  def online_pool(self, slots, args, max_frames, persistent=False, horizon=None):
+    """A StreamPool over one OnlineSession of `slots` utterances (extension, see the class): for callers
+    whose streams begin and end independently of each other."""
+    return StreamPool(self.online(slots, args, max_frames, persistent, horizon))
+
   def predict(self, test_sequences, args):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
 
@@ -880,6 +885,43 @@ class OnlineSession:
     """Per utterance, the number of frames committed so far."""
     return [int(x) for x in self._decoder.stream_committed()]
 
+  def restart(self, utterances):
+    """End the given utterances and reuse their slots in place (uis_stream_restart; extension).
+
+    Each utterance named hands out its result and is afterwards what it was when the session opened: nothing
+    received, nothing committed, one empty hypothesis.  prime, push, commit, labels, nbest, stable_frames and
+    committed treat the slot as new; every other utterance's beam is untouched.  This is also how a slot comes
+    back that hit the cluster cap or whose beam a non-finite frame emptied.
+
+    Args:
+      utterances: an iterable of utterance indices.
+    Returns:
+      a list with one entry per utterance of the session: (labels, score) for an utterance named -- the labels
+      of its WHOLE stream, committed part first, and the best hypothesis' score as a float -- and None for the
+      others.  Where labels() would have failed for that utterance alone (cluster cap, emptied beam) labels is
+      None; restart does not raise for it.
+    Raises:
+      ValueError: an index out of range or given twice.
+    """
+    n_utt = self._num_utterances
+    which = [0] * n_utt
+    for u in utterances:
+      if isinstance(u, bool) or not isinstance(u, (int, np.integer)) or not 0 <= int(u) < n_utt:
+        raise ValueError('utterance index {!r} is not in [0, {}).'.format(u, n_utt))
+      if which[int(u)]:
+        raise ValueError('utterance {} is given twice.'.format(int(u)))
+      which[int(u)] = 1
+    per_utt, scores, overflow, _ = self._decoder.stream_restart(which)
+    out = [None] * n_utt
+    for u in range(n_utt):
+      if not which[u]:
+        continue
+      window = per_utt[u].tolist()
+      dead = bool(overflow[u]) or (len(window) > 0 and window[0] < 0)
+      out[u] = (None if dead else self._final[u] + window, float(scores[u]))
+      self._final[u] = []
+    return out
+
   def labels(self):
     per_utt, _, overflow, _ = self._decoder.stream_labels()
     if overflow.any():
@@ -930,6 +972,63 @@ class OnlineSession:
       self._decoder.stream_end()
       self._decoder.close()
       self._open = False
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+
+class StreamPool:
+  """An open-ended set of streams over the slots of ONE OnlineSession (extension).
+
+  A stream is opened under a key and takes a free slot; when it finishes, its labels are handed out and the slot is
+  free for the next stream, while the other streams' beams live on (OnlineSession.restart).  One push advances
+  every stream that received frames, in one batch.
+
+    with model.online_pool(64, inference_args, max_frames=2000) as pool:
+      pool.open('call-17')
+      pool.push({'call-17': chunk, 'call-4': other_chunk})
+      labels, score = pool.finish('call-17')
+  """
+
+  def __init__(self, session):
+    self._session = session
+    self._slot = {}   # key -> slot
+    self._free = list(range(session._num_utterances - 1, -1, -1))  # pylint: disable=protected-access
+
+  def open(self, key):
+    """Take a free slot for a new stream.  Returns the slot's index."""
+    if key in self._slot:
+      raise KeyError('stream {!r} is already open'.format(key))
+    if not self._free:
+      raise RuntimeError('no free slot')
+    self._slot[key] = self._free.pop()
+    return self._slot[key]
+
+  def push(self, chunks):
+    """chunks: a dict {key: [n, D] float64 array} with the new frames of the streams that received some."""
+    per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
+    for key, chunk in chunks.items():
+      per_slot[self._slot[key]] = chunk
+    self._session.push(per_slot)
+
+  def labels(self, key):
+    """The currently best labels of everything the stream has received."""
+    return self._session.labels()[self._slot[key]]
+
+  def finish(self, key):
+    """End the stream: (labels, score) of the whole of it (labels None where OnlineSession.restart says so);
+    its slot is free afterwards."""
+    slot = self._slot[key]
+    out = self._session.restart([slot])[slot]
+    del self._slot[key]
+    self._free.append(slot)
+    return out
+
+  def close(self):
+    self._session.close()
 
   def __enter__(self):
     return self
