@@ -473,6 +473,40 @@ int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int
                          float* scores_out, int32_t* counts_out, int64_t* stable_out);
 
 /*
+ * Posterior readout: how sure the decoder is of a label, or of a speaker turn, from the same records.  Per
+ * utterance, over the `live` hypotheses uis_*_nbest(n_best = beam_size) would count, with their float32 scores
+ * s_0 <= s_1 <= ... and labels lab_k[t] over the N frames of the readout (trace[-N:]; a session: the window):
+ *   w_k           = exp(-(s_k - s_0) / temperature) / sum_j exp(-(s_j - s_0) / temperature)
+ *   confidence[t] = sum_k w_k [lab_k[t] == lab_0[t]]    the beam's posterior mass behind the label returned.
+ *                   Label agreement, not permutation invariant: an early extra cluster in an alternative
+ *                   hypothesis lowers the agreement of all later frames
+ *   change[t]     = sum_k w_k [lab_k[t] != lab_k[t-1]]  the posterior of a speaker turn between frames t-1 and
+ *                   t; invariant to how a hypothesis numbers its speakers.  change[0] = 0 always: the first
+ *                   frame of the readout has no predecessor IN the readout -- also the first frame of a committed
+ *                   window and with test_iteration > 1
+ *   temperature    : finite and > 0; 1 is the model's own posterior.  A peaked model needs a larger one to rank
+ *                    its uncertain frames (at D = 256 every weight but w_0 is usually below 1e-11 at 1)
+ *   confidence_out,
+ *   change_out     : host float32, `capacity` floats each, packed in utterance order like uis_decode's labels_out
+ *                    (a session: like uis_stream_labels); either may be NULL
+ *   weights_out    : host float32 [n_utt * beam_size] or NULL: w_k in rank order, 0 past live
+ *   counts_out     : host int32 [n_utt] or NULL: live
+ * live == 0 (an empty utterance, an emptied beam, an utterance flagged in the overflow word): zeros and count 0.
+ * live == 1: confidence is exactly 1.0f, change exactly 0.0f or 1.0f.  A session window that a commit emptied:
+ * count 1, weights_out[u * beam_size] = 1, no frames.  Two calls on the same state return the same bits.
+ * Validity, refusals and status are those of the n-best pair (uis_last_decode_posterior: a decode that returned
+ * UIS_OK or UIS_ERR_CLUSTER_CAP and no open session; uis_stream_posterior: an open session, UIS_ERR_CLUSTER_CAP
+ * with everything still written, the resident launch of a UIS_FLAG_PERSISTENT session leaves for the call).
+ * UIS_ERR_INVALID_ARG (nothing touched): also a temperature that is not finite and > 0, capacity below the
+ * frames in the readout.  The calls leave uis_last_decode_info / _shape, uis_eval_last_decode and a following
+ * uis_*_nbest alone.
+ */
+int32_t uis_last_decode_posterior(uis_handle* h, double temperature, float* confidence_out, float* change_out,
+                                  int64_t capacity, float* weights_out, int32_t* counts_out);
+int32_t uis_stream_posterior(uis_handle* h, double temperature, float* confidence_out, float* change_out,
+                             int64_t capacity, float* weights_out, int32_t* counts_out);
+
+/*
  * Session commits: endless online decoding in a fixed window.  uis_stream_commit hands out the labels of an open
  * session that are final, drops their back-pointer records and gives the room back: max_frames is then the WINDOW,
  * the frames received and not yet committed, and a stream of any length can be pushed through it.  From the first

@@ -333,6 +333,10 @@ def load_library(path=None):
   lib.uis_last_decode_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p]
   lib.uis_stream_nbest.restype = i32
   lib.uis_stream_nbest.argtypes = [ctypes.c_void_p, i32, i32p, ctypes.c_int64, _fp, i32p, i64p]
+  lib.uis_last_decode_posterior.restype = i32
+  lib.uis_last_decode_posterior.argtypes = [ctypes.c_void_p, ctypes.c_double, _fp, _fp, ctypes.c_int64, _fp, i32p]
+  lib.uis_stream_posterior.restype = i32
+  lib.uis_stream_posterior.argtypes = [ctypes.c_void_p, ctypes.c_double, _fp, _fp, ctypes.c_int64, _fp, i32p]
   lib.uis_stream_commit.restype = i32
   lib.uis_stream_commit.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, i32p]
   lib.uis_stream_committed.restype = i32
@@ -377,7 +381,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -599,6 +603,7 @@ class Decoder:
     rc = self._lib.uis_stream_begin(self._handle, int(n_utt), ctypes.byref(opts), int(max_frames))
     self._check(rc, 'uis_stream_begin')
     self._stream_n = int(n_utt)
+    self._stream_beam = int(beam_size)
     self._stream_have = np.zeros(int(n_utt), dtype=np.int64)
     self._stream_counts = np.zeros(int(n_utt), dtype=np.int32)   # (reused by every push: its pointer is bound once)
     self._stream_counts_ptr = self._stream_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
@@ -833,6 +838,46 @@ class Decoder:
     out['stable'] = stable
     out['status'] = rc
     return out
+
+  # ---- posterior readout (uis_last_decode_posterior / uis_stream_posterior)
+  def _posterior(self, call, what, temperature, offsets, beam):
+    n_utt = offsets.shape[0] - 1
+    total = int(offsets[-1])
+    conf = np.zeros(max(total, 1), dtype=np.float32)
+    change = np.zeros(max(total, 1), dtype=np.float32)
+    weights = np.zeros(max(n_utt * beam, 1), dtype=np.float32)
+    counts = np.zeros(max(n_utt, 1), dtype=np.int32)
+    rc = call(self._handle, float(temperature), conf.ctypes.data_as(_fp), change.ctypes.data_as(_fp), total,
+              weights.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    rc = self._check(rc, what)
+    bounds = [(int(offsets[u]), int(offsets[u + 1])) for u in range(n_utt)]
+    return {'confidence': [conf[a:b].copy() for a, b in bounds], 'change': [change[a:b].copy() for a, b in bounds],
+            'weights': weights[:n_utt * beam].reshape(n_utt, beam), 'counts': counts[:n_utt], 'status': rc}
+
+  def last_posterior(self, temperature=1.0):
+    """Per-frame confidence of the last decode's labels from its final beam (uis_last_decode_posterior).
+
+    With w_k = softmax(-scores / temperature) over the live hypotheses, returns a dict: confidence -- per
+    utterance a float32 [N_u] array, the weight of the hypotheses that agree with the best one's label at that
+    frame; change -- likewise, the weight of the hypotheses with a speaker turn between frames t - 1 and t
+    (change[0] = 0); weights float32 [U, beam_size], rank order, 0 past the live ones; counts int32 [U], the live
+    hypotheses (0 for an utterance that hit the cluster cap: zeros everywhere); status."""
+    offsets = self._last_offsets
+    if offsets is None:
+      offsets = np.zeros(1, dtype=np.int64)  # (no decode yet: the library refuses below)
+    n_lib, beam = ctypes.c_int32(0), ctypes.c_int32(0)
+    self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), ctypes.byref(beam)), 'uis_last_decode_shape')
+    if int(n_lib.value) != offsets.shape[0] - 1:  # (as last_nbest: a decode whose layout is not known here)
+      raise HipLibraryError('last_posterior: the library\'s last decode had {} utterances, this object remembers {}'.format(
+          int(n_lib.value), offsets.shape[0] - 1))
+    return self._posterior(self._lib.uis_last_decode_posterior, 'uis_last_decode_posterior', temperature, offsets,
+                           int(beam.value))
+
+  def stream_posterior(self, temperature=1.0):
+    """The same for the open session's window: everything received and not yet committed (uis_stream_posterior).
+    A window that a commit emptied has counts 1, weights[u, 0] = 1 and no frames."""
+    offsets = np.concatenate([[0], np.cumsum(self._stream_have)]).astype(np.int64)
+    return self._posterior(self._lib.uis_stream_posterior, 'uis_stream_posterior', temperature, offsets, self._stream_beam)
 
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
                   labels_ptr, scores_ptr, max_clusters=0, flags=0):

@@ -23,6 +23,7 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),
     os.path.join(_HERE, 'csrc', 'uis_prime.hip'),
     os.path.join(_HERE, 'csrc', 'uis_nbest.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_posterior.hip'),
     os.path.join(_HERE, 'csrc', 'uis_commit.hip'),
     os.path.join(_HERE, 'csrc', 'uis_restart.hip'),
     os.path.join(_HERE, 'csrc', 'uis_stream.hip'),

@@ -181,6 +181,9 @@ struct HandleMem {
   DevBuf sc_commit;  // uis_stream_commit's horizon / committed / dropped words
   DevBuf sc_restart;  // uis_stream_restart's selection, window counts, label offsets and what comes back
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
+  // the posterior readout's own (a following n-best readout finds its buffers as it left them): results, offset tables,
+  // the per-group partial rows of k_posterior; the label table and scores k_nbest_window fills for k_posterior_window
+  DevBuf ps_conf, ps_change, ps_weights, ps_counts, ps_off, ps_part, ps_labels, ps_scores;
 };
 
 }  // namespace
@@ -2376,6 +2379,9 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ n-best readout
 #include "uis_nbest.hip"
+
+// ------------------------------------------------------------------ posterior readout
+#include "uis_posterior.hip"
 
 // ------------------------------------------------------------------ committing a session's final labels
 #include "uis_commit.hip"

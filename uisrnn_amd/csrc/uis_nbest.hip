@@ -23,11 +23,57 @@
 // beam, stale parent ranks are clamped to B - 1, output offsets from a table of the host's) and fill the rows
 // k >= count with -1; count = min(n, live hypotheses), 0 for an utterance flagged in the overflow word.
 //
+// Phases 1 and 2 of k_nbest are __device__ functions: k_posterior (uis_posterior.hip) starts from the same two.
+//
 // #included by uis_decoder.hip after the handle and the decode kernels.
 
 namespace {
 
 #define UIS_NBEST_THREADS 256
+
+// Phases 1 and 2 of k_nbest, shared with k_posterior (uis_posterior.hip); a workgroup of UIS_NBEST_THREADS threads,
+// a __syncthreads() of the caller's after each.
+// 1. segment l: steps hi(l) .. lo(l) walked downwards, hi(0) = T - 1, the last lo = T - N.  Lane l of each wave
+//    follows every entry rank through segment l (wave w: entry ranks 8 w .. 8 w + 7, then + 32 ...) -> bt_map [64][B]
+__device__ __forceinline__ void nbest_segment_maps(const uint32_t* __restrict__ bp, int B, long T, long N, long seg, int nseg,
+                                                   unsigned char* bt_map) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long hi = T - 1 - (long)lane * seg;
+  long lo = hi - seg + 1;
+  if (lo < T - N) lo = T - N;
+  if (lane < nseg) {
+    unsigned char* mine = bt_map + (size_t)lane * B;
+    for (int r0 = 8 * wave; r0 < B; r0 += 8 * (UIS_NBEST_THREADS / 64)) {
+      int r[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[k] = r0 + k < B ? r0 + k : 0;
+      for (long s2 = hi; s2 >= lo; --s2) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          // ranks >= that step's beam width were never written (stale words): clamp, so the walk
+          // stays inside this utterance's records; such entry ranks are never stitched in
+          const int pr = (int)(bp[(size_t)s2 * B + r[k]] >> 16);
+          r[k] = pr < B ? pr : B - 1;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (r0 + k < B) mine[r0 + k] = (unsigned char)r[k];
+    }
+  }
+}
+
+// 2. stitch: hypothesis k's entry rank at every segment (B <= 256 = the workgroup's threads) -> ent [B][64]
+__device__ __forceinline__ void nbest_stitch(int B, int live, int nseg, const unsigned char* bt_map, unsigned char* ent) {
+  const int tid = threadIdx.x;
+  if (tid < live) {
+    int cur = tid;
+    for (int l = 0; l < nseg; ++l) {
+      ent[(size_t)tid * 64 + l] = (unsigned char)cur;
+      cur = bt_map[(size_t)l * B + cur];
+    }
+  }
+}
 
 __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int n, const int64_t* __restrict__ out_off,
                                                              int32_t* __restrict__ labels, float* __restrict__ scores,
@@ -37,7 +83,7 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int
   extern __shared__ __attribute__((aligned(16))) unsigned char nb_lds[];
   const int u = blockIdx.x;
   if (u >= st.U) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int B = st.B;
   int* s_min = reinterpret_cast<int*>(nb_lds);
   unsigned char* bt_map = nb_lds + 16;
@@ -61,39 +107,10 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int
   // segment l: steps hi(l) .. lo(l) walked downwards, hi(0) = T - 1, the last lo = T - N
   const long seg = (N + 63) / 64;
   const int nseg = N > 0 ? (int)((N + seg - 1) / seg) : 0;
-  const long hi = T - 1 - (long)lane * seg;
-  long lo = hi - seg + 1;
-  if (lo < T - N) lo = T - N;
-  // ---- 1. the segment maps (wave w: entry ranks 8 w .. 8 w + 7, then + 32 ...)
-  if (walk && lane < nseg) {
-    unsigned char* mine = bt_map + (size_t)lane * B;
-    for (int r0 = 8 * wave; r0 < B; r0 += 8 * (UIS_NBEST_THREADS / 64)) {
-      int r[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) r[k] = r0 + k < B ? r0 + k : 0;
-      for (long s2 = hi; s2 >= lo; --s2) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          // ranks >= that step's beam width were never written (stale words): clamp, so the walk
-          // stays inside this utterance's records; such entry ranks are never stitched in
-          const int pr = (int)(bp[(size_t)s2 * B + r[k]] >> 16);
-          r[k] = pr < B ? pr : B - 1;
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (r0 + k < B) mine[r0 + k] = (unsigned char)r[k];
-    }
-  }
+  // ---- 1. the segment maps, 2. the stitch
+  if (walk) nbest_segment_maps(bp, B, T, N, seg, nseg, bt_map);
   __syncthreads();
-  // ---- 2. stitch: hypothesis k's entry rank at every segment (B <= 256 = the workgroup's threads)
-  if (walk && tid < live) {
-    int cur = tid;
-    for (int l = 0; l < nseg; ++l) {
-      ent[(size_t)tid * 64 + l] = (unsigned char)cur;
-      cur = bt_map[(size_t)l * B + cur];
-    }
-  }
+  if (walk) nbest_stitch(B, live, nseg, bt_map, ent);
   __syncthreads();
   // ---- 3. the labels: pair p = (segment p / cnt, hypothesis p % cnt) -- neighbours read the same records' rows
   if (walk) {

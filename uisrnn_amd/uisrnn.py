@@ -23,6 +23,16 @@ from uisrnn_amd import weights
 _DEFAULT_MAX_CLUSTERS = 16
 
 
+def _check_temperature(temperature):
+  """The posterior readouts' temperature as a float: a finite number > 0 (ValueError before any device work)."""
+  if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.integer, np.floating)):
+    raise ValueError('temperature must be a finite number > 0.')
+  value = float(temperature)
+  if not np.isfinite(value) or value <= 0.0:
+    raise ValueError('temperature must be a finite number > 0, not {!r}.'.format(temperature))
+  return value
+
+
 def _initial_cluster_cap(args):
   """Device table size (clusters per hypothesis) of the first decode attempt.
 
@@ -242,7 +252,7 @@ class UISRNN:
       raise ValueError('test_sequence does not match the dimension specified '
                        'by args.observation_dim.')
 
-  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0):
+  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -250,6 +260,7 @@ class UISRNN:
 
     n_best > 0 (predict_nbest): an utterance's result is the pair (labelings, scores) of its final
     beam instead of the label list, read right after the decode call whose labels are accepted for it.
+    posterior = a temperature (predict_posteriors): the triple (labels, confidence, change), read likewise.
     """
     decoder = decoder or self._get_decoder(device)
     # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
@@ -278,7 +289,7 @@ class UISRNN:
           level_full, first_err = [], None
           for part in (pending[0::2], pending[1::2]):
             try:
-              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best)
+              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best, posterior)
             except LookAheadWindowError as inner:
               # (a half whose look-ahead window overflowed: its indices and results are numbered inside
               # the half -- hand them up in the caller's numbering, and still decode the other half)
@@ -324,7 +335,7 @@ class UISRNN:
           if not members:
             continue
           try:
-            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best)
+            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best, posterior)
           except LookAheadWindowError as inner:
             # (indices and results are numbered inside `members`: hand them up in the caller's numbering)
             partial = inner.results
@@ -339,7 +350,7 @@ class UISRNN:
             partial = []
             for u in members:
               try:
-                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best)
+                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best, posterior)
                 one_err = inner if len(members) == 1 else None
               except LookAheadWindowError as e1:
                 one, one_err = [None], e1
@@ -366,6 +377,7 @@ class UISRNN:
       still = []
       # (the hypotheses of THIS decode call, before a retry of the flagged utterances replaces its state)
       hyps = decoder.last_nbest(n_best) if n_best else None
+      post = decoder.last_posterior(posterior) if posterior is not None else None
       for k, u in enumerate(pending):
         if out['overflow'][k]:
           still.append(u)
@@ -385,6 +397,8 @@ class UISRNN:
                           [float(x) for x in hyps['scores'][k][:live]])
           elif hyps is not None:  # no frames: the one empty labeling, as predict answers, at score 0
             results[u] = ([[]], [0.0])
+          if post is not None:
+            results[u] = (results[u], post['confidence'][k], post['change'][k])
       pending = still
       if pending:
         # a surviving hypothesis opened more clusters than the device tables
@@ -535,6 +549,40 @@ class UISRNN:
       if not test_sequences:
         return []
       return self._decode_batch(test_sequences, args, n_best=int(n_best))
+    raise TypeError('test_sequences should be either a list or numpy array.')
+
+  def predict_posteriors(self, test_sequences, args, temperature=1.0):
+    """predict, with the beam's per-frame confidence in its answer (extension).
+
+    With w_k = softmax(-score_k / temperature) over the hypotheses of the final beam:
+      confidence[t]: the weight of the hypotheses whose label at frame t is the returned one.  Label agreement, not
+        permutation invariant: an alternative that opened an extra cluster early disagrees on all later frames.
+      change[t]: the weight of the hypotheses with a speaker turn between frames t - 1 and t -- invariant to how a
+        hypothesis numbers its speakers.  change[0] is 0: the first frame returned has no predecessor (with
+        test_iteration > 1 too: the frames returned are the last replay's).
+
+    Args:
+      test_sequences, args: as predict.
+      temperature: a finite number > 0.  1 is the model's own posterior; a sharply peaked model (a trained D = 256
+        one puts all but 1e-3, usually all but 1e-11, on the best hypothesis) needs a larger one to rank its
+        uncertain frames.
+    Returns:
+      for an array the triple (labels, confidence, change): predict's answer and two float32 arrays of its length.
+      For a list, a list of such triples.  One decode, with predict's cap and level retries.
+
+    Raises:
+      what predict raises; ValueError for a temperature that is not a finite number > 0, before any device work.
+    """
+    temperature = _check_temperature(temperature)
+    if isinstance(test_sequences, np.ndarray):
+      self._check_sequence(test_sequences)
+      return self._decode_batch([test_sequences], args, posterior=temperature)[0]
+    if isinstance(test_sequences, list):
+      for test_sequence in test_sequences:
+        self._check_sequence(test_sequence)
+      if not test_sequences:
+        return []
+      return self._decode_batch(test_sequences, args, posterior=temperature)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
   def predict_primed(self, test_sequences, prefix_cluster_ids, args):
@@ -967,6 +1015,22 @@ class OnlineSession:
     after every push of a persistent session."""
     return [len(self._final[u]) + int(x) for u, x in enumerate(self._nbest(1)['stable'])]
 
+  def posteriors(self, temperature=1.0):
+    """The beam's per-frame confidence over the WINDOW -- the frames received and not yet committed (committed
+    labels are final) -- as UISRNN.predict_posteriors defines it: per utterance the triple (confidence, change,
+    weights), two float32 arrays of the window's length and the float32 weights of the live hypotheses, best first.
+    change[0] is 0 also when committed frames precede the window.  An utterance that has received nothing has
+    empty arrays; one whose window a commit emptied has no frames and the weights [1].
+
+    Cost: the walks of nbest() and a download of two floats per frame, whatever the beam; like nbest it makes a
+    persistent session's resident launch leave the device."""
+    temperature = _check_temperature(temperature)
+    out = self._decoder.stream_posterior(temperature)
+    if out['status'] == _capi.UIS_ERR_CLUSTER_CAP:
+      self.labels()  # (raises, naming the utterances)
+    return [(out['confidence'][u], out['change'][u], out['weights'][u][:int(out['counts'][u])].copy())
+            for u in range(len(out['confidence']))]
+
   def close(self):
     if self._open:
       self._decoder.stream_end()
@@ -1017,6 +1081,11 @@ class StreamPool:
   def labels(self, key):
     """The currently best labels of everything the stream has received."""
     return self._session.labels()[self._slot[key]]
+
+  def posteriors(self, key, temperature=1.0):
+    """(confidence, change, weights) of the stream's window: OnlineSession.posteriors for its slot."""
+    temperature = _check_temperature(temperature)
+    return self._session.posteriors(temperature)[self._slot[key]]
 
   def finish(self, key):
     """End the stream: (labels, score) of the whole of it (labels None where OnlineSession.restart says so);
