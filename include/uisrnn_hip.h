@@ -578,6 +578,48 @@ int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32_t* labels_
                            int32_t* counts_out, float* scores_out, int32_t* overflow_out);
 
 /*
+ * Speaker retirement: keep an endless session under max_clusters.  uis_stream_commit gives back the room of old
+ * frames; the cluster tables of a hypothesis only grow, and a step that selects a new cluster at K == max_clusters
+ * sets the utterance's overflow word, after which only uis_stream_restart brings the slot back.  uis_stream_retire
+ * deletes clusters that no live hypothesis can still name.  No decode kernel is involved (an addition: the ABI
+ * version stays).  Per utterance, with have = the frames in the window: cluster index k is RETIRABLE iff for every
+ * live hypothesis r  k < K_r,  k is not among r's labels of the window's frames,  and k is not r's last label (which
+ * matters for a window that a commit emptied: its one hypothesis still continues from it).  Such a cluster was opened
+ * before the window; after a commit or a prime all live hypotheses share that history, so k is the same speaker in
+ * each.  A session that never committed and was not primed has nothing retirable.  Retiring a set R removes the
+ * entries in R from every live hypothesis' cluster lists (the entries above move down in order), K -= |R|, the sum of
+ * block counts loses those of R, the last label and every label of the window's records become
+ * label - #{k in R : k < label}; scores, the step count and the prior tables stay.  The decode continues exactly as
+ * the reference's beam search would from hypotheses with those clusters deleted: the ddCRP denominator
+ * sum(block counts) + alpha shrinks accordingly, so FOR THE PRIOR THE SPEAKER NEVER EXISTED (the one modelling
+ * decision of this call).  Cluster ids of labels handed out afterwards are in the NEW numbering: the caller keeps the
+ * map (uisrnn_amd.OnlineSession does: ids it hands out never change and are never reused).
+ *   which, offsets, clusters : the selection.
+ *                  offsets == NULL (then clusters == NULL): every retirable cluster of every utterance with
+ *                  which[u] != 0 (which == NULL: of every utterance); the others are only queried.
+ *                  offsets != NULL (then which == NULL): host int64 [n_utt + 1], offsets[0] = 0, non-decreasing;
+ *                  clusters host int32 [offsets[n_utt]], utterance u's indices at [offsets[u], offsets[u + 1]),
+ *                  ascending.  An empty selection is a pure query
+ *   retired_out  : host int32 [n_utt * max_clusters]: row u holds counts_out[u] indices, ascending, in the numbering
+ *                  BEFORE the call.  May be NULL only when the selection is explicit and empty
+ *   counts_out   : host int32 [n_utt]: clusters retired
+ *   k_out        : host int32 [n_utt]: the largest K over the live hypotheses AFTER the call (how close the
+ *                  utterance is to max_clusters); 0 without a live hypothesis
+ *   retirable_out, retirable_counts_out : host int32 [n_utt * max_clusters] / [n_utt] or NULL: the retirable
+ *                  indices BEFORE the call, rows as retired_out
+ * An utterance that has received nothing, whose beam is empty or which is flagged in the overflow word has nothing
+ * retirable, is left alone and reports 0: retirement does not revive a dead slot, it is how a live one avoids dying.
+ * All or nothing: UIS_ERR_INVALID_ARG -- no session open, a list that is not ascending, repeats an index or leaves
+ * [0, max_clusters), or, for ANY utterance, names an index that is not retirable -- leaves the whole session as it
+ * was, to the bit; UIS_ERR_OOM (scratch) likewise.  Utterances with nothing retired are untouched, to the bit.  In a
+ * UIS_FLAG_PERSISTENT session the resident launch leaves the device for this call (after the host checks, as for
+ * uis_stream_commit) and the next push starts a new one.  UIS_RETIRE_TRACE=1: one line per call on stderr.
+ */
+int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const int64_t* offsets, const int32_t* clusters,
+                          int32_t* retired_out, int32_t* counts_out, int32_t* k_out, int32_t* retirable_out,
+                          int32_t* retirable_counts_out);
+
+/*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the
  * H2D copy of the frame stream is asynchronous and overlaps the input projection of the chunks
  * already on the device.  Pageable memory works too (staged by the runtime).

@@ -343,6 +343,8 @@ def load_library(path=None):
   lib.uis_stream_committed.argtypes = [ctypes.c_void_p, i64p]
   lib.uis_stream_restart.restype = i32
   lib.uis_stream_restart.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, _fp, i32p]
+  lib.uis_stream_retire.restype = i32
+  lib.uis_stream_retire.argtypes = [ctypes.c_void_p, i32p, i64p, i32p, i32p, i32p, i32p, i32p, i32p]
   lib.uis_eval_accuracy.restype = i32
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
@@ -381,7 +383,7 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -604,6 +606,7 @@ class Decoder:
     self._check(rc, 'uis_stream_begin')
     self._stream_n = int(n_utt)
     self._stream_beam = int(beam_size)
+    self._stream_cap = int(max_clusters) if int(max_clusters) > 0 else 16
     self._stream_have = np.zeros(int(n_utt), dtype=np.int64)
     self._stream_counts = np.zeros(int(n_utt), dtype=np.int32)   # (reused by every push: its pointer is bound once)
     self._stream_counts_ptr = self._stream_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
@@ -763,6 +766,53 @@ class Decoder:
     bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     self._stream_have[sel != 0] = 0
     return [labels[bounds[u]:bounds[u + 1]].copy() for u in range(n_utt)], scores, overflow, rc
+
+  def stream_retire(self, which=None, clusters=None):
+    """Delete clusters that no live hypothesis can still name (uis_stream_retire).
+
+    clusters None: every retirable cluster of the utterances selected by `which` (one truth value per utterance;
+    None: all of them); the others are only queried.  clusters given (then which must be None): one ascending
+    sequence of cluster indices (or None / empty: a query) per utterance.  Returns dict(retired, K, retirable,
+    max_clusters): per utterance the int32 indices retired, in the numbering before the call; int32 [n_utt] the
+    largest K over the live hypotheses afterwards; per utterance the indices that were retirable before the call.
+    A refusal (HipLibraryError with .status UIS_ERR_INVALID_ARG) leaves the session as it was."""
+    n_utt = self._stream_n
+    i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+    which_ptr = off_ptr = sel_ptr = None
+    if clusters is not None:
+      if which is not None:
+        raise ValueError('which and clusters exclude each other')
+      if len(clusters) != n_utt:
+        raise ValueError('one sequence of cluster indices (or None) per utterance')
+      parts = [np.zeros(0, dtype=np.int32) if c is None else np.asarray(c, dtype=np.int32).reshape(-1) for c in clusters]
+      offsets = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+      flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.int32)
+      off_ptr = offsets.ctypes.data_as(i64p)
+      sel_ptr = flat.ctypes.data_as(i32p) if len(flat) else None
+    elif which is not None:
+      sel = np.ascontiguousarray([1 if w else 0 for w in which], dtype=np.int32)
+      if sel.shape[0] != n_utt:
+        raise ValueError('one selection flag per utterance')
+      which_ptr = sel.ctypes.data_as(i32p)
+    cap = self.stream_max_clusters()
+    retired = np.zeros((n_utt, cap), dtype=np.int32)
+    retirable = np.zeros((n_utt, cap), dtype=np.int32)
+    counts = np.zeros(n_utt, dtype=np.int32)
+    able = np.zeros(n_utt, dtype=np.int32)
+    k_out = np.zeros(n_utt, dtype=np.int32)
+    rc = self._lib.uis_stream_retire(
+        self._handle, which_ptr, off_ptr, sel_ptr, retired.ctypes.data_as(i32p), counts.ctypes.data_as(i32p),
+        k_out.ctypes.data_as(i32p), retirable.ctypes.data_as(i32p), able.ctypes.data_as(i32p))
+    if rc != UIS_OK:
+      err = HipLibraryError('uis_stream_retire failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    return {'retired': [retired[u, :counts[u]].copy() for u in range(n_utt)], 'K': k_out,
+            'retirable': [retirable[u, :able[u]].copy() for u in range(n_utt)], 'max_clusters': cap}
+
+  def stream_max_clusters(self):
+    """max_clusters of the open session (what uis_stream_begin made of the option: 0 means 16)."""
+    return self._stream_cap
 
   def stream_labels(self):
     """Best-hypothesis labels of everything received so far: (list of int32 arrays, scores, overflow, status)."""

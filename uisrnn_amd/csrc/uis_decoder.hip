@@ -180,6 +180,7 @@ struct HandleMem {
   DevBuf sc_prime;  // uis_stream_prime's commit tables (the forced run itself uses the sc_* above)
   DevBuf sc_commit;  // uis_stream_commit's horizon / committed / dropped words
   DevBuf sc_restart;  // uis_stream_restart's selection, window counts, label offsets and what comes back
+  DevBuf sc_retire;  // uis_stream_retire's selection, shift tables, lists and counts
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
   // the posterior readout's own (a following n-best readout finds its buffers as it left them): results, offset tables,
   // the per-group partial rows of k_posterior; the label table and scores k_nbest_window fills for k_posterior_window
@@ -2388,3 +2389,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ ending utterances of a session, reusing their slots
 #include "uis_restart.hip"
+
+// ------------------------------------------------------------------ retiring clusters no live hypothesis can name
+#include "uis_retire.hip"

@@ -54,6 +54,16 @@ _DEFAULT_LEVEL_CAP = 32768   # include/uisrnn_hip.h: uis_decode_opts.level_cap's
 _MAX_LEVEL_CAP = 524287      # ... and its maximum
 
 
+def _stable_ids(gone, n):
+  """The first n non-negative integers that are not in the sorted list `gone`."""
+  out, skip, c = [], set(gone), 0
+  while len(out) < n:
+    if c not in skip:
+      out.append(c)
+    c += 1
+  return out
+
+
 class EmptyBeamError(ValueError, IndexError):
   """Every candidate of some decode step was non-finite: no hypothesis survived.
 
@@ -481,19 +491,21 @@ class UISRNN:
     self._check_sequence(test_sequence)
     return self._decode_batch([test_sequence], args)[0]
 
-  def online(self, num_utterances, args, max_frames, persistent=False, horizon=None):
+  def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None):
     """An OnlineSession (streaming decode; extension, see the class).  horizon: None, or the decision
-    horizon in frames of a session that commits by itself when a push does not fit its window."""
+    horizon in frames of a session that commits by itself when a push does not fit its window.  retire_at: None,
+    or the cluster count from which the session retires speakers by itself, down to retire_to (default
+    retire_at // 2): see OnlineSession.retire."""
     if args.look_ahead != 1:
       raise ValueError('online decoding needs look_ahead 1')
     if self.transition_bias is None:
       raise TypeError('transition_bias is None: the model was never fit or loaded')
-    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon)
+    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon, retire_at, retire_to)
 
-  def online_pool(self, slots, args, max_frames, persistent=False, horizon=None):
+  def online_pool(self, slots, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None):
     """A StreamPool over one OnlineSession of `slots` utterances (extension, see the class): for callers
     whose streams begin and end independently of each other."""
-    return StreamPool(self.online(slots, args, max_frames, persistent, horizon))
+    return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to))
 
   def predict(self, test_sequences, args):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
@@ -762,6 +774,11 @@ class OnlineSession:
         session.push([chunk])
         final = session.commit()           # optional: the labels that became final, to pass on now
 
+  A stream with more speakers than args.max_clusters: retire() deletes clusters that no live hypothesis can still
+  name (speakers last heard before the window), and with retire_at=K given to model.online the session does so by
+  itself before a push that could take an utterance past K clusters.  The ids the session hands out never change
+  and are never reused: a speaker who returns after retirement is a new id.
+
   persistent=True (UIS_FLAG_PERSISTENT): the decode kernel stays on the GPU between pushes and is
   fed through a mailbox in pinned host memory -- the lowest push latency (no launch, no copy
   engine), at the price of occupying the whole device until the session closes or has been idle
@@ -770,17 +787,26 @@ class OnlineSession:
   """
 
   _final = None   # per utterance the labels committed so far (a list per utterance once the session is open)
+  _gone = None    # per utterance the sorted ids of the retired clusters (None: nothing was ever retired)
+  _retire_at = None   # the automatic policy: off
+  _retire_to = None
+  _bound = None   # per utterance an upper bound of K: K at the last query plus the frames pushed since
+  _seen = None    # per utterance {id: stream position of its last committed appearance}
 
-  def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None):
+  def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None,
+               retire_to=None):
     if horizon is not None and (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 0):
       raise ValueError('horizon must be None or a non-negative integer.')
+    cap = None if args is None else _initial_cluster_cap(args)
+    self._set_retire_policy(retire_at, retire_to, cap)
     self._model = model
     self._horizon = None if horizon is None else int(horizon)
     self._max_frames = int(max_frames)
     self._final = [[] for _ in range(int(num_utterances))]   # the committed labels, per utterance
     self._beam_size = int(args.beam_size)
     self._decoder = _capi.Decoder(model.params, model.device_index)  # own handle: one session per handle
-    cap = _initial_cluster_cap(args)
+    self._bound = [0] * int(num_utterances)
+    self._seen = [{} for _ in range(int(num_utterances))]
     self.persistent = False
     if persistent:
       try:
@@ -846,11 +872,16 @@ class OnlineSession:
       labels[u] = np.array([names.setdefault(i, len(names)) for i in ids], dtype=np.int32)
       frames[u] = chunk
     scores = self._decoder.stream_prime(frames, labels)
+    if self._bound is not None:
+      for u in range(n_utt):   # (a prefix of P frames has at most P clusters)
+        self._bound[u] += 0 if labels[u] is None else len(labels[u])
     return [float(scores[u]) if labels[u] is not None else None for u in range(n_utt)]
 
   def push(self, chunks):
     """chunks: a list with one [n, D] float64 array (or None) per utterance, or one [U, n, D]
     float64 array when every utterance received the same number of frames."""
+    if self._retire_at is not None:
+      self._keep_under_cap(chunks)
     if self._horizon is not None:
       self._make_room(chunks)
     if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
@@ -923,8 +954,11 @@ class OnlineSession:
       if any(x < -1 for x in hz):
         raise ValueError('horizon must be non-negative.')
     new, _ = self._decoder.stream_commit(hz)
-    out = [x.tolist() for x in new]
+    out = [self._ids(u, x) for u, x in enumerate(new)]
     for u in range(n_utt):
+      if self._retire_at is not None and out[u]:
+        at = len(self._final[u])
+        self._seen[u].update({c: at + t for t, c in enumerate(out[u])})   # (ascending t: the last appearance stays)
       self._final[u].extend(out[u])
     return out
 
@@ -932,6 +966,143 @@ class OnlineSession:
   def committed(self):
     """Per utterance, the number of frames committed so far."""
     return [int(x) for x in self._decoder.stream_committed()]
+
+  # ---- speaker retirement
+
+  def _set_retire_policy(self, retire_at, retire_to, cap):
+    """The automatic policy's two thresholds, checked (ValueError before any device work)."""
+    def whole(x):
+      return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+    if retire_at is None:
+      if retire_to is not None:
+        raise ValueError('retire_to needs retire_at.')
+      return
+    if not whole(retire_at) or retire_at < 1 or (cap is not None and retire_at > cap):
+      raise ValueError('retire_at must be an integer in [1, max_clusters = {}].'.format(cap))
+    if retire_to is None:
+      retire_to = int(retire_at) // 2
+    if not whole(retire_to) or not 0 <= retire_to < retire_at:
+      raise ValueError('retire_to must be an integer in [0, retire_at).')
+    self._retire_at, self._retire_to, self._cap = int(retire_at), int(retire_to), cap
+
+  def _ids(self, u, local):
+    """Cluster indices as the library numbers them now -> the ids of the whole stream: index j is the j-th
+    non-negative integer that is not a retired id.  Negative entries (no label) stay."""
+    values = local.tolist() if isinstance(local, np.ndarray) else [int(v) for v in local]
+    gone = self._gone[u] if self._gone is not None else None
+    if not gone:
+      return values
+    top = max(values, default=-1)
+    table = _stable_ids(gone, top + 1)
+    return [table[v] if v >= 0 else v for v in values]
+
+  def _indices(self, u, ids):
+    """Ids of the whole stream -> the library's present indices, ascending (ValueError for a retired or repeated id)."""
+    gone = self._gone[u] if self._gone is not None else []
+    out = []
+    for c in ids:
+      if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
+        raise ValueError('utterance {}: cluster id {!r} is not a non-negative integer.'.format(u, c))
+      if int(c) in gone:
+        raise ValueError('utterance {}: cluster {} is already retired.'.format(u, int(c)))
+      out.append(int(c) - sum(1 for g in gone if g < int(c)))
+    if len(set(out)) != len(out):
+      raise ValueError('utterance {}: a cluster id is given twice.'.format(u))
+    return sorted(out)
+
+  def _retired(self, result):
+    """Book a stream_retire result: the retired indices become ids that are gone.  Returns them per utterance."""
+    out = []
+    for u, idx in enumerate(result['retired']):
+      ids = self._ids(u, idx)
+      if ids:
+        if self._gone is None:
+          self._gone = [[] for _ in range(self._num_utterances)]
+        self._gone[u] = sorted(self._gone[u] + ids)
+      out.append(ids)
+    return out
+
+  def cluster_counts(self):
+    """Per utterance (K, retirable): the largest cluster count over the live hypotheses -- how close the
+    utterance is to args.max_clusters -- and the ids retire() would accept now.  Changes nothing."""
+    result = self._decoder.stream_retire(clusters=[None] * self._num_utterances)
+    return [(int(result['K'][u]), self._ids(u, result['retirable'][u])) for u in range(self._num_utterances)]
+
+  def retire(self, utterances=None, clusters=None):
+    """Delete clusters that no live hypothesis can still name (uis_stream_retire; extension).
+
+    A cluster is retirable when every live hypothesis has it, none uses it on a frame of the window (the frames
+    not yet committed) and none has it as its last label: a speaker last heard before the window.  Retiring it
+    gives its room back to the utterance, which can then open a new cluster where it would have hit
+    args.max_clusters.  From then on the decode continues as the reference's beam search would from hypotheses
+    with that cluster deleted: the ddCRP prior's denominator shrinks by its block count, so for the prior the
+    speaker never existed, and if the speaker returns a new cluster with a new id is opened.  Ids the session
+    hands out never change and a retired id is never used again.  A session that never committed and was not
+    primed has nothing retirable; a dead utterance (cluster cap, emptied beam) is left alone.
+
+    Args:
+      utterances: an iterable of utterance indices, or None for all of them.
+      clusters: None -- every retirable cluster of `utterances` -- or a list with one iterable of cluster ids (or
+        None: nothing) per utterance of the session; utterances must then be None.
+    Returns:
+      per utterance the list of ids retired by this call.
+    Raises:
+      ValueError: an index out of range or given twice, an id that is negative, repeated or already retired.
+      _capi.HipLibraryError (status UIS_ERR_INVALID_ARG): an id that is not retirable.  The session is then as it was.
+    """
+    n_utt = self._num_utterances
+    if clusters is not None:
+      if utterances is not None:
+        raise ValueError('utterances and clusters exclude each other: clusters has one entry per utterance.')
+      if not isinstance(clusters, (list, tuple)) or len(clusters) != n_utt:
+        raise ValueError('one iterable of cluster ids (or None) per utterance ({} utterances).'.format(n_utt))
+      idx = [None if c is None else self._indices(u, c) for u, c in enumerate(clusters)]
+      return self._retired(self._decoder.stream_retire(clusters=idx))
+    which = None
+    if utterances is not None:
+      which = [0] * n_utt
+      for u in utterances:
+        if isinstance(u, bool) or not isinstance(u, (int, np.integer)) or not 0 <= int(u) < n_utt:
+          raise ValueError('utterance index {!r} is not in [0, {}).'.format(u, n_utt))
+        if which[int(u)]:
+          raise ValueError('utterance {} is given twice.'.format(int(u)))
+        which[int(u)] = 1
+    return self._retired(self._decoder.stream_retire(which=which))
+
+  def _keep_under_cap(self, chunks):
+    """retire_at given: before a push that could take an utterance to retire_at clusters or more, commit (with the
+    session's horizon), query, and retire retirable clusters, least recently heard first, down to retire_to."""
+    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
+      sizes = [int(chunks.shape[1])] * len(chunks)
+    else:
+      sizes = [0 if c is None else len(c) for c in chunks]
+    n_utt = self._num_utterances
+    if len(sizes) != n_utt:
+      return   # (stream_push refuses it in its own words)
+    if max(sizes, default=0) > self._cap - self._retire_at:
+      raise ValueError('a chunk of {} frames is too long for retire_at = {}: every frame can open a cluster, and '
+                       'max_clusters - retire_at = {}.'.format(max(sizes), self._retire_at, self._cap - self._retire_at))
+    due = [u for u in range(n_utt) if sizes[u] and self._bound[u] >= self._retire_at]
+    if due:
+      self.commit([self._horizon if u in due else None for u in range(n_utt)])
+      counts = self.cluster_counts()
+      picks = [None] * n_utt
+      for u in due:
+        k, able = counts[u]
+        if k > self._retire_to and able:
+          able.sort(key=lambda c, seen=self._seen[u]: (seen.get(c, -1), c))
+          picks[u] = able[:k - self._retire_to]
+      if any(picks):
+        self.retire(clusters=picks)
+      for u in range(n_utt):   # (the query answered for every utterance: each bound starts again from its K)
+        self._bound[u] = counts[u][0] - len(picks[u] or ())
+      for u in due:
+        if self._bound[u] + sizes[u] > self._cap:
+          raise RuntimeError('utterance {}: {} speakers are active inside the window and cannot be retired; with {} '
+                             'new frames it could pass max_clusters = {}.  Use a larger args.max_clusters or a '
+                             'shorter horizon.'.format(u, self._bound[u], sizes[u], self._cap))
+    for u in range(n_utt):
+      self._bound[u] += sizes[u]
 
   def restart(self, utterances):
     """End the given utterances and reuse their slots in place (uis_stream_restart; extension).
@@ -964,10 +1135,14 @@ class OnlineSession:
     for u in range(n_utt):
       if not which[u]:
         continue
-      window = per_utt[u].tolist()
+      window = self._ids(u, per_utt[u])
       dead = bool(overflow[u]) or (len(window) > 0 and window[0] < 0)
       out[u] = (None if dead else self._final[u] + window, float(scores[u]))
       self._final[u] = []
+      if self._gone is not None:
+        self._gone[u] = []
+      if self._bound is not None:
+        self._bound[u], self._seen[u] = 0, {}
     return out
 
   def labels(self):
@@ -976,7 +1151,7 @@ class OnlineSession:
       raise RuntimeError('utterance(s) {} need more than max_clusters clusters per hypothesis; '
                          'open the session with a larger args.max_clusters'.format(
                              np.flatnonzero(overflow).tolist()))
-    return [self._final[u] + x.tolist() for u, x in enumerate(per_utt)]
+    return [self._final[u] + self._ids(u, x) for u, x in enumerate(per_utt)]
 
   def _nbest(self, n_best):
     if n_best is None:
@@ -1001,7 +1176,7 @@ class OnlineSession:
     starts a new one (a launch plus the kernel's weight load): read every few pushes, not after each,
     or the session loses most of what persistent=True buys."""
     out = self._nbest(n_best)
-    return [([self._final[u] + row.tolist() for row in out['labels'][u][:int(out['counts'][u])]],
+    return [([self._final[u] + self._ids(u, row) for row in out['labels'][u][:int(out['counts'][u])]],
              [float(x) for x in out['scores'][u][:int(out['counts'][u])]])
             for u in range(len(out['labels']))]
 
@@ -1086,6 +1261,16 @@ class StreamPool:
     """(confidence, change, weights) of the stream's window: OnlineSession.posteriors for its slot."""
     temperature = _check_temperature(temperature)
     return self._session.posteriors(temperature)[self._slot[key]]
+
+  def retire(self, key, clusters=None):
+    """OnlineSession.retire for the stream's slot: every retirable cluster, or the given ids.  Returns the ids
+    retired."""
+    slot = self._slot[key]
+    if clusters is None:
+      return self._session.retire([slot])[slot]
+    per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
+    per_slot[slot] = clusters
+    return self._session.retire(clusters=per_slot)[slot]
 
   def finish(self, key):
     """End the stream: (labels, score) of the whole of it (labels None where OnlineSession.restart says so);
