@@ -22,6 +22,7 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_eval.hip'),
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),
     os.path.join(_HERE, 'csrc', 'uis_prime.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_beam_view.h'),
     os.path.join(_HERE, 'csrc', 'uis_nbest.hip'),
     os.path.join(_HERE, 'csrc', 'uis_posterior.hip'),
     os.path.join(_HERE, 'csrc', 'uis_commit.hip'),

@@ -23,17 +23,12 @@
 // uploads longer ones (at least twice the length, upload_log_tables' arithmetic: the common prefix keeps its bits)
 // where they do not; the session is pointed at them after the synchronisation and the old ones are freed then.
 //
-// Order, as uis_stream_prime: checks on the host (nothing touched), a resident launch of a UIS_FLAG_PERSISTENT
-// session leaves (pm_quit: tables are written between launches only), the longer prior tables if needed (an
-// allocation that fails leaves the session as it was), then readout, prune, move, the downloads and ONE
-// synchronisation.  Every store is an ordinary vector store.
+// The order is the scaffold's (uis_stream.hip); this call's own: the longer prior tables are allocated before any
+// scratch (an allocation that fails leaves the session as it was) and swapped in after the synchronisation.
 //
-// #included by uis_decoder.hip after uis_stream.hip (pm_quit) and uis_nbest.hip (k_nbest).
+// #included by uis_decoder.hip after uis_stream.hip (the scaffold) and uis_nbest.hip (k_nbest).
 
 namespace {
-
-#define UIS_COMMIT_THREADS 256
-#define UIS_COMMIT_TILE_WORDS 1024  // k_commit_move: words per tile = one 16-byte access per thread
 
 struct CommitArgs {
   const int32_t* horizon;    // [U] or null: no decision horizon
@@ -50,11 +45,7 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_prune(DecodeState
   const int u = blockIdx.x, tid = threadIdx.x;
   if (u >= st.U) return;
   const int B = st.B, Kmax = st.Kmax;
-  const long N = (long)st.avail[u];
-  const int par = (int)(N & 1);
-  int nb = N > 0 ? st.beam_n[(size_t)par * st.U + u] : 0;
-  nb = nb < 0 ? 0 : (nb > B ? B : nb);
-  const int live = st.overflow[u] ? 0 : nb;   // (k_nbest's rule)
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u);
   if (live == 0) {                            // nothing received, an emptied beam, the cluster cap: left alone
     if (tid == 0) { a.cut_even[u] = 0; a.dropped[u] = 0; }
     return;
@@ -69,14 +60,10 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_prune(DecodeState
     if (tid == 0) a.dropped[u] = 0;
     return;
   }
-  uint32_t* bp = st.bp + (size_t)st.tau * st.off[u] * B;
   // ---- every live rank's ancestor at step cut - 1: its chain through steps N - 1 .. cut
   if (tid < live) {
     int r = tid;
-    for (long s = N - 1; s >= cut; --s) {
-      r = (int)(bp[(size_t)s * B + r] >> 16);
-      if (r >= B) r = B - 1;                  // (stale words are never reached from a live rank; k_nbest's clamp all the same)
-    }
+    for (long s = N - 1; s >= cut; --s) r = rec_parent(bp[(size_t)s * B + r], B);  // (stale words are never reached from a live rank)
     s_anc[tid] = r;
   }
   __syncthreads();
@@ -87,7 +74,6 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_prune(DecodeState
   if (keep) s_src[dest] = tid;
   if (tid == live - 1) s_n = dest + (keep ? 1 : 0);
   // ---- the scalars and the last step's record: read everything, barrier, write (destination ranks overlap sources)
-  const size_t e = ((size_t)par * st.U + u) * B;
   int32_t vK = 0, vlast = 0, vsum = 0;
   float vscore = 0.0f;
   uint32_t vbp = 0;
@@ -95,8 +81,7 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_prune(DecodeState
     vK = st.beam_K[e + tid]; vlast = st.beam_last[e + tid]; vsum = st.beam_sum[e + tid]; vscore = st.beam_score[e + tid];
     vbp = bp[(size_t)(N - 1) * B + tid];
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the loads have returned before the barrier lets anyone store)
-  __syncthreads();
+  loads_before_stores();
   if (keep) {
     st.beam_K[e + dest] = vK; st.beam_last[e + dest] = vlast; st.beam_sum[e + dest] = vsum; st.beam_score[e + dest] = vscore;
     bp[(size_t)(N - 1) * B + dest] = vbp;
@@ -120,72 +105,30 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_prune(DecodeState
 }
 
 // One workgroup per utterance: rows [c, N) of its records move to [0, N - c), then utt_step -= c.  Source and
-// destination overlap whenever N - c > c: ascending tiles, each loaded into registers by all threads before any of
-// them stores it (tile t's destination lies below every later tile's source, so one barrier per tile is enough).
+// destination overlap whenever N - c > c: move_words_down (uis_beam_view.h).
 __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_move(DecodeState st, const int32_t* __restrict__ cut_even) {
-  const int u = blockIdx.x, tid = threadIdx.x;
+  const int u = blockIdx.x;
   if (u >= st.U) return;
   const int c = cut_even[u];
   if (c <= 0) return;
   const long N = (long)st.avail[u];
   uint32_t* dst = st.bp + (size_t)st.tau * st.off[u] * st.B;
-  const uint32_t* src = dst + (size_t)c * st.B;
-  const long words = (N - c) * (long)st.B;
-  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0) {
-    const long nvec = words >> 2;
-    const uint4* s4 = reinterpret_cast<const uint4*>(src);
-    uint4* d4 = reinterpret_cast<uint4*>(dst);
-    for (long base = 0; base < nvec; base += UIS_COMMIT_TILE_WORDS / 4) {
-      const long i = base + tid;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (i < nvec) v = s4[i];
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the tile is in registers before the barrier lets anyone store)
-      __syncthreads();
-      if (i < nvec) d4[i] = v;
-    }
-    // the scalar tail: up to three words, above everything stored so far and below nothing still to be read
-    const long i = (nvec << 2) + tid;
-    uint32_t v = 0;
-    if (i < words) v = src[i];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (i < words) dst[i] = v;
-  } else {
-    for (long base = 0; base < words; base += UIS_COMMIT_TILE_WORDS) {
-      uint32_t v[UIS_COMMIT_TILE_WORDS / UIS_COMMIT_THREADS];
-#pragma unroll
-      for (int k = 0; k < UIS_COMMIT_TILE_WORDS / UIS_COMMIT_THREADS; ++k) {
-        const long i = base + k * UIS_COMMIT_THREADS + tid;
-        v[k] = i < words ? src[i] : 0u;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < UIS_COMMIT_TILE_WORDS / UIS_COMMIT_THREADS; ++k) {
-        const long i = base + k * UIS_COMMIT_THREADS + tid;
-        if (i < words) dst[i] = v[k];
-      }
-    }
-  }
-  if (tid == 0) st.utt_step[u] -= c;
+  move_words_down(dst, dst + (size_t)c * st.B, (N - c) * (long)st.B);
+  if (threadIdx.x == 0) st.utt_step[u] -= c;
 }
 
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int32_t* labels_out, int64_t capacity,
                                      int32_t* counts_out, int32_t* dropped_out) {
-  if (!h || !counts_out) return fail(UIS_ERR_INVALID_ARG, "null handle/counts_out");
+  if (!session_of(h, counts_out != nullptr, "null handle/counts_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const int U = ss.U, B = ss.B;
-  const auto t_begin = std::chrono::steady_clock::now();
-  // ---- the checks: nothing of the session is touched before the last of them has passed
-  std::vector<int64_t> off(U + 1, 0);
+  CallTimer timer{h};
+  // ---- the checks
+  const std::vector<int64_t> off = window_offsets(ss);
   int64_t most = 0;  // frames any utterance can have received once its window is full again
-  for (int u = 0; u < U; ++u) {
-    off[u + 1] = off[u] + ss.have[u];
-    most = std::max<int64_t>(most, ss.committed[u] + ss.have[u]);
-  }
+  for (int u = 0; u < U; ++u) most = std::max<int64_t>(most, ss.committed[u] + ss.have[u]);
   const int64_t F = off[U];
   if (capacity < F)
     return fail(UIS_ERR_INVALID_ARG, "labels_out: " + std::to_string((long long)F) + " int32 slots needed (the frames in the window)");
@@ -195,10 +138,9 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
     if (dropped_out) std::fill(dropped_out, dropped_out + U, 0);
     return UIS_OK;
   }
-  HIPCHK(hipSetDevice(h->device));
   int rc;
-  // a persistent launch leaves first (as for uis_stream_nbest); ss.persist stays set, the next push starts a new one
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
+  DecodeState stc;
+  if ((rc = session_enter(h, &stc))) return rc;
   hipStream_t st = h->stream;
   // ---- the prior tables: long enough for whatever the window can hold after this call
   DevBuf new_blk, new_den;
@@ -208,42 +150,27 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
     new_len = std::max<int64_t>(2 * ss.log_len, most + ss.cap + 2);
     if ((rc = new_blk.alloc((size_t)new_len * 8)) || (rc = new_den.alloc((size_t)new_len * 8))) return rc;
   }
-  // ---- scratch (UIS_POISON_WORKSPACE: filled ahead of the defining writes)
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  // (committed, dropped and rank 0's score are one stretch: they come back in one copy)
-  const size_t o_hz = 0, o_cut = o_hz + up16((size_t)U * 4), o_drop = o_cut + (size_t)U * 4, o_score = o_drop + (size_t)U * 4,
-               total = o_score + up16((size_t)U * 4);
-  if ((rc = h->sc_commit.ensure(total))) return rc;
+  // ---- scratch: [horizon U], then [committed U][dropped U][rank 0's score U] as one stretch (they come back in one copy)
+  ScratchPlan plan;
+  const size_t o_hz = plan.take((size_t)U * 4), o_cut = plan.take((size_t)U * 4), o_drop = plan.take((size_t)U * 4, 4),
+               o_score = plan.take((size_t)U * 4, 4);
   if ((rc = h->nb_labels.ensure((size_t)F * 4))) return rc;
   if ((rc = h->nb_stable.ensure((size_t)U * 8))) return rc;
   if ((rc = h->nb_off.ensure((size_t)U * 8))) return rc;
-  const size_t land = ((size_t)F + 3 * (size_t)U) * 4;  // the pinned landing block: labels, then the three words per utterance
-  if (land > ss.h_land.cap) {
-    hipError_t e = ss.h_land.ensure(land + land / 4 + 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  }
-  {
-    const UisPoison poison = UisPoison::from_env();
-    for (DevBuf* b : {&h->sc_commit, &h->nb_labels, &h->nb_stable, &h->nb_off, &new_blk, &new_den})
-      HIPCHK(poison.device(b->p, b->cap, st));
-    poison.host(ss.h_land.p, ss.h_land.cap);
-  }
+  char* base;  // (the pinned landing block: labels, then the three words per utterance)
+  if ((rc = session_buffers(h, plan, ((size_t)F + 3 * (size_t)U) * 4, &base, {&h->nb_labels, &h->nb_stable, &h->nb_off, &new_blk, &new_den})))
+    return rc;
   if (new_len && (rc = upload_log_tables(h->alpha, new_len, log_host, new_blk.p, new_den.p, st))) return rc;
-  char* base = h->sc_commit.as<char>();
   if (horizon) HIPCHK(hipMemcpyAsync(base + o_hz, horizon, (size_t)U * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(h->nb_off.p, off.data(), (size_t)U * 8, hipMemcpyHostToDevice, st));
-  // frames in the window = steps run since the last commit, from the host's own count (as uis_stream_labels)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, st));
-  DecodeState stc = ss.st;
-  stc.avail = ss.d_have;
   CommitArgs a{};
   a.horizon = horizon ? reinterpret_cast<const int32_t*>(base + o_hz) : nullptr;
   a.stable = h->nb_stable.as<long long>();
   a.cut_even = reinterpret_cast<int32_t*>(base + o_cut);
   a.dropped = reinterpret_cast<int32_t*>(base + o_drop);
   // ---- readout, prune, move
-  HIPCHK(hipEventRecord(h->ev_begin, st));
-  hipLaunchKernelGGL(k_nbest, dim3(U), dim3(UIS_NBEST_THREADS), (size_t)16 + (size_t)128 * B, st, stc, 1, h->nb_off.as<int64_t>(),
+  HIPCHK(timer.begin());
+  hipLaunchKernelGGL(k_nbest, dim3(U), dim3(UIS_NBEST_THREADS), nbest_lds_bytes(B), st, stc, 1, h->nb_off.as<int64_t>(),
                      h->nb_labels.as<int32_t>(), reinterpret_cast<float*>(base + o_score), (int32_t*)nullptr,
                      h->nb_stable.as<long long>());
   HIPCHK(hipGetLastError());
@@ -251,7 +178,7 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_commit_move, dim3(U), dim3(UIS_COMMIT_THREADS), 0, st, stc, (const int32_t*)a.cut_even);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev_end, st));
+  HIPCHK(timer.end());
   int32_t* h_lab = ss.h_land.as<int32_t>();
   int32_t* h_cut = h_lab + F;
   int32_t* h_drop = h_cut + U;
@@ -281,20 +208,15 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
     ss.log_len = new_len;
   }
   h->nb_valid = false;
-  if (const char* e = getenv("UIS_COMMIT_TRACE"); e && atoi(e) != 0) {  // one line per call on stderr (read per call: a test turns it on)
-    float dev_ms = 0.0f;
-    (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
+  if (CallTimer::env("UIS_COMMIT_TRACE"))
     fprintf(stderr, "uis_stream_commit: utterances %d window_frames %lld committed %lld prior_table_entries %lld device_ms %.3f call_ms %.3f\n",
-            U, (long long)F, (long long)out, (long long)ss.log_len, (double)dev_ms,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  }
+            U, (long long)F, (long long)out, (long long)ss.log_len, timer.device_ms(), timer.call_ms());
   return UIS_OK;
 }
 
 UIS_EXPORT int32_t uis_stream_committed(uis_handle* h, int64_t* committed_out) {
-  if (!h || !committed_out) return fail(UIS_ERR_INVALID_ARG, "null handle/committed_out");
+  if (!session_of(h, committed_out != nullptr, "null handle/committed_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   std::copy(ss.committed.begin(), ss.committed.end(), committed_out);
   return UIS_OK;
 }

@@ -177,10 +177,9 @@ struct HandleMem {
   HostBuf h_out;   // pinned landing block of uis_decode_f64's labels and scores
   DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
-  DevBuf sc_prime;  // uis_stream_prime's commit tables (the forced run itself uses the sc_* above)
-  DevBuf sc_commit;  // uis_stream_commit's horizon / committed / dropped words
-  DevBuf sc_restart;  // uis_stream_restart's selection, window counts, label offsets and what comes back
-  DevBuf sc_retire;  // uis_stream_retire's selection, shift tables, lists and counts
+  // the scratch block of one uis_stream_prime / _commit / _restart / _retire call (session_buffers in uis_stream.hip;
+  // every such call synchronises before it returns, so no two are ever live; prime's forced run uses the sc_* above)
+  DevBuf sc_session;
   DevBuf nb_labels, nb_scores, nb_counts, nb_stable, nb_off;  // the n-best readout's own
   // the posterior readout's own (a following n-best readout finds its buffers as it left them): results, offset tables,
   // the per-group partial rows of k_posterior; the label table and scores k_nbest_window fills for k_posterior_window
@@ -2379,6 +2378,7 @@ UIS_EXPORT void uis_host_free(void* p) {
 #include "uis_prime.hip"
 
 // ------------------------------------------------------------------ n-best readout
+#include "uis_beam_view.h"
 #include "uis_nbest.hip"
 
 // ------------------------------------------------------------------ posterior readout

@@ -19,13 +19,13 @@
 //                   lock-step against rank 0's chain, down to the first step at which each has merged with it.
 //   k_nbest_window  window records (DecodeState::bp16, {parent, c_1 .. c_L} per window and rank): one thread per
 //                   (utterance, rank), the plain walk of k_backtrace_window.
-// Both follow k_backtrace's rules (avail for sessions and tau * N otherwise, the parity of T names the final
-// beam, stale parent ranks are clamped to B - 1, output offsets from a table of the host's) and fill the rows
-// k >= count with -1; count = min(n, live hypotheses), 0 for an utterance flagged in the overflow word.
+// Both read the tables through uis_beam_view.h (k_backtrace's rules: avail for sessions and tau * N otherwise, the
+// parity of T names the final beam, stale parent ranks are clamped to B - 1), take their output offsets from a table
+// of the host's and fill the rows k >= count with -1; count = min(n, live hypotheses).
 //
 // Phases 1 and 2 of k_nbest are __device__ functions: k_posterior (uis_posterior.hip) starts from the same two.
 //
-// #included by uis_decoder.hip after the handle and the decode kernels.
+// #included by uis_decoder.hip after uis_beam_view.h.
 
 namespace {
 
@@ -33,15 +33,12 @@ namespace {
 
 // Phases 1 and 2 of k_nbest, shared with k_posterior (uis_posterior.hip); a workgroup of UIS_NBEST_THREADS threads,
 // a __syncthreads() of the caller's after each.
-// 1. segment l: steps hi(l) .. lo(l) walked downwards, hi(0) = T - 1, the last lo = T - N.  Lane l of each wave
-//    follows every entry rank through segment l (wave w: entry ranks 8 w .. 8 w + 7, then + 32 ...) -> bt_map [64][B]
-__device__ __forceinline__ void nbest_segment_maps(const uint32_t* __restrict__ bp, int B, long T, long N, long seg, int nseg,
-                                                   unsigned char* bt_map) {
+// 1. lane l of each wave follows every entry rank through segment l (wave w: entry ranks 8 w .. 8 w + 7, then
+//    + 32 ...) -> bt_map [64][B]
+__device__ __forceinline__ void nbest_segment_maps(const uint32_t* __restrict__ bp, int B, const SegGeom& g, unsigned char* bt_map) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long hi = T - 1 - (long)lane * seg;
-  long lo = hi - seg + 1;
-  if (lo < T - N) lo = T - N;
-  if (lane < nseg) {
+  const long hi = g.hi(lane), lo = g.lo(lane);
+  if (lane < g.nseg) {
     unsigned char* mine = bt_map + (size_t)lane * B;
     for (int r0 = 8 * wave; r0 < B; r0 += 8 * (UIS_NBEST_THREADS / 64)) {
       int r[8];
@@ -49,12 +46,7 @@ __device__ __forceinline__ void nbest_segment_maps(const uint32_t* __restrict__ 
       for (int k = 0; k < 8; ++k) r[k] = r0 + k < B ? r0 + k : 0;
       for (long s2 = hi; s2 >= lo; --s2) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          // ranks >= that step's beam width were never written (stale words): clamp, so the walk
-          // stays inside this utterance's records; such entry ranks are never stitched in
-          const int pr = (int)(bp[(size_t)s2 * B + r[k]] >> 16);
-          r[k] = pr < B ? pr : B - 1;
-        }
+        for (int k = 0; k < 8; ++k) r[k] = rec_parent(bp[(size_t)s2 * B + r[k]], B);  // (stale entry ranks are never stitched in)
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k)
@@ -78,24 +70,16 @@ __device__ __forceinline__ void nbest_stitch(int B, int live, int nseg, const un
 __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int n, const int64_t* __restrict__ out_off,
                                                              int32_t* __restrict__ labels, float* __restrict__ scores,
                                                              int32_t* __restrict__ counts, long long* __restrict__ stable) {
-  // [0, 16): s_min; [16, 16 + 64 B): exit rank of entry rank r through segment l; then [B][64]: entry rank of
-  // hypothesis k at segment l
-  extern __shared__ __attribute__((aligned(16))) unsigned char nb_lds[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char nb_lds[];  // (NbestLds; its word: s_min)
   const int u = blockIdx.x;
   if (u >= st.U) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int B = st.B;
-  int* s_min = reinterpret_cast<int*>(nb_lds);
-  unsigned char* bt_map = nb_lds + 16;
-  unsigned char* ent = bt_map + (size_t)64 * B;
-  const long N = st.avail ? (long)st.avail[u] : (long)(st.off[u + 1] - st.off[u]);
-  const long T = st.avail ? N : (long)st.tau * N;
-  const int par = (int)(T & 1);  // parity holding the final beam
-  int nb = N > 0 ? st.beam_n[(size_t)par * st.U + u] : 0;
-  nb = nb < 0 ? 0 : (nb > B ? B : nb);
-  const int live = st.overflow[u] ? 0 : nb;
+  const NbestLds lds = nbest_lds(nb_lds, B);
+  int* s_min = lds.word;
+  unsigned char *bt_map = lds.bt_map, *ent = lds.ent;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u);
   const int cnt = live < n ? live : n;
-  const size_t e = ((size_t)par * st.U + u) * B;
   if (scores)
     for (int k = tid; k < n; k += UIS_NBEST_THREADS) scores[(size_t)u * n + k] = k < nb ? st.beam_score[e + k] : INFINITY;
   if (counts && tid == 0) counts[u] = cnt;
@@ -103,12 +87,10 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int
   int32_t* out = labels + out_off[u];
   for (long i = (long)cnt * N + tid; i < (long)n * N; i += UIS_NBEST_THREADS) out[i] = -1;
   const bool walk = N > 0 && live > 0;
-  const uint32_t* bp = st.bp + (size_t)st.tau * st.off[u] * B;
-  // segment l: steps hi(l) .. lo(l) walked downwards, hi(0) = T - 1, the last lo = T - N
-  const long seg = (N + 63) / 64;
-  const int nseg = N > 0 ? (int)((N + seg - 1) / seg) : 0;
+  const SegGeom g = seg_geom(T, N);
+  const int nseg = g.nseg;
   // ---- 1. the segment maps, 2. the stitch
-  if (walk) nbest_segment_maps(bp, B, T, N, seg, nseg, bt_map);
+  if (walk) nbest_segment_maps(bp, B, g, bt_map);
   __syncthreads();
   if (walk) nbest_stitch(B, live, nseg, bt_map, ent);
   __syncthreads();
@@ -116,17 +98,8 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int
   if (walk) {
     for (int p = tid; p < nseg * cnt; p += UIS_NBEST_THREADS) {
       const int l = p / cnt, k = p - l * cnt;
-      const long h2 = T - 1 - (long)l * seg;
-      long l2 = h2 - seg + 1;
-      if (l2 < T - N) l2 = T - N;
-      int r = ent[(size_t)k * 64 + l];
       int32_t* row = out + (long)k * N;
-      for (long s2 = h2; s2 >= l2; --s2) {
-        const uint32_t v = bp[(size_t)s2 * B + r];
-        row[s2 - (T - N)] = (int32_t)(v & 0xffffu);
-        r = (int)(v >> 16);
-        if (r >= B) r = B - 1;
-      }
+      walk_segment(bp, B, g, l, ent[(size_t)k * 64 + l], [row, f0 = T - N](long s2, uint32_t v) { row[s2 - f0] = (int32_t)rec_label(v); });
     }
   }
   // ---- the stable prefix (sessions)
@@ -144,17 +117,13 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_nbest(DecodeState st, int
       // the segment above it: chain `tid` beside rank 0's chain, down to the step at which they have merged;
       // not inside the segment = at the boundary (one step below its lowest)
       const int sl = lstar - 1;
-      const long h2 = T - 1 - (long)sl * seg;
-      long l2 = h2 - seg + 1;
-      if (l2 < T - N) l2 = T - N;
+      const long h2 = g.hi(sl), l2 = g.lo(sl);
       int r = ent[(size_t)tid * 64 + sl], r0 = ent[sl];
       long merged = l2 - 1;
       for (long s2 = h2; s2 >= l2; --s2) {
         if (r == r0) { merged = s2; break; }
-        r = (int)(bp[(size_t)s2 * B + r] >> 16);
-        r0 = (int)(bp[(size_t)s2 * B + r0] >> 16);
-        if (r >= B) r = B - 1;
-        if (r0 >= B) r0 = B - 1;
+        r = rec_parent(bp[(size_t)s2 * B + r], B);
+        r0 = rec_parent(bp[(size_t)s2 * B + r0], B);
       }
       atomicMin(s_min, (int)(merged + 1 - (T - N)));
     } else if (tid == 0) {
@@ -176,13 +145,9 @@ __global__ __launch_bounds__(64) void k_nbest_window(DecodeState st, int n, cons
   const long N = (long)(st.off[u + 1] - st.off[u]);
   const long T = (long)st.tau * N;
   const long n_win = (T + L - 1) / L;
-  const int par = (int)(n_win & 1);
-  int nb = N > 0 ? st.beam_n[(size_t)par * st.U + u] : 0;
-  nb = nb < 0 ? 0 : (nb > st.B ? st.B : nb);
-  const int live = st.overflow[u] ? 0 : nb;
-  const int cnt = live < n ? live : n;
-  const size_t e = ((size_t)par * st.U + u) * st.B;
-  if (scores) scores[(size_t)u * n + k] = k < nb ? st.beam_score[e + k] : INFINITY;
+  const BeamView bv = beam_view_at(st, u, N, T, n_win, EMPTY_WINDOW_SHOWS_NOTHING);  // (the windows run name the parity)
+  const int cnt = bv.live < n ? bv.live : n;
+  if (scores) scores[(size_t)u * n + k] = k < bv.nb ? st.beam_score[bv.e + k] : INFINITY;
   if (counts && k == 0) counts[u] = cnt;
   if (N == 0) return;
   int32_t* out = labels + out_off[u] + (long)k * N;
@@ -235,7 +200,7 @@ int nbest_run(uis_handle* h, const std::vector<uis_handle::NbestGroup>& groups, 
     float* g_scores = h->nb_scores.as<float>() + (size_t)g.u0 * n_best;
     int32_t* g_counts = h->nb_counts.as<int32_t>() + g.u0;
     if (!wnd)
-      hipLaunchKernelGGL(k_nbest, dim3(g.st.U), dim3(UIS_NBEST_THREADS), (size_t)16 + (size_t)128 * B, h->stream, g.st, (int)n_best,
+      hipLaunchKernelGGL(k_nbest, dim3(g.st.U), dim3(UIS_NBEST_THREADS), nbest_lds_bytes(B), h->stream, g.st, (int)n_best,
                          g_off, h->nb_labels.as<int32_t>(), g_scores, g_counts,
                          stable_out ? h->nb_stable.as<long long>() + g.u0 : nullptr);
     else
@@ -247,12 +212,7 @@ int nbest_run(uis_handle* h, const std::vector<uis_handle::NbestGroup>& groups, 
   if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, h->nb_scores.p, (size_t)U * n_best * 4, hipMemcpyDeviceToHost, h->stream));
   if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, h->nb_counts.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
   if (stable_out) HIPCHK(hipMemcpyAsync(stable_out, h->nb_stable.p, (size_t)U * 8, hipMemcpyDeviceToHost, h->stream));
-  if (overflow) {
-    overflow->assign(U, 0);
-    for (const uis_handle::NbestGroup& g : groups)
-      if (g.st.U > 0)
-        HIPCHK(hipMemcpyAsync(overflow->data() + g.u0, g.st.overflow, (size_t)g.st.U * 4, hipMemcpyDeviceToHost, h->stream));
-  }
+  if ((rc = download_overflow(h, groups, U, overflow))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   return UIS_OK;
 }
@@ -272,38 +232,19 @@ UIS_EXPORT int32_t uis_last_decode_nbest(uis_handle* h, int32_t n_best, int32_t*
 
 UIS_EXPORT int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int64_t capacity,
                                     float* scores_out, int32_t* counts_out, int64_t* stable_out) {
-  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
-  const int U = ss.U;
   if (n_best < 1 || n_best > ss.B)
     return fail(UIS_ERR_INVALID_ARG, "n_best must be in [1, beam_size = " + std::to_string(ss.B) + "]");
-  std::vector<int64_t> off(U + 1, 0);
-  for (int u = 0; u < U; ++u) off[u + 1] = off[u] + ss.have[u];
-  if (capacity < (int64_t)n_best * off[U])
-    return fail(UIS_ERR_INVALID_ARG, "labels_out: " + std::to_string((long long)n_best * off[U]) + " int32 slots needed");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
-  // A persistent launch leaves first (as for uis_stream_end): its tables are then back in global memory and the
-  // ordinary kernel reads them.  Nothing is launched beside the resident kernel -- it occupies every CU -- and its
-  // mailbox gets no new command; the next push starts a new launch (ss.persist stays set).
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
-  // frames received = steps run, from the host's own count (as uis_stream_labels)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, h->stream));
-  std::vector<uis_handle::NbestGroup> groups(1);
-  groups[0].st = ss.st;
-  groups[0].st.avail = ss.d_have;
-  groups[0].u0 = 0;
+  const std::vector<int64_t> off = window_offsets(ss);
+  if (capacity < (int64_t)n_best * off[ss.U])
+    return fail(UIS_ERR_INVALID_ARG, "labels_out: " + std::to_string((long long)n_best * off[ss.U]) + " int32 slots needed");
   std::vector<int64_t> stable_tmp;
-  if (!stable_out) { stable_tmp.assign(U, 0); stable_out = stable_tmp.data(); }
-  std::vector<int32_t> overflow;
-  if ((rc = nbest_run(h, groups, false, ss.B, off, n_best, labels_out, capacity, scores_out, counts_out, stable_out, &overflow)))
-    return rc;
-  for (int u = 0; u < U; ++u) {  // a window that a commit emptied: the one hypothesis that lives, no labels left to show
-    if (!ss.window_emptied(u)) continue;
-    if (counts_out) counts_out[u] = 1;
-    if (scores_out) scores_out[(size_t)u * n_best] = ss.win_score[u];
-    stable_out[u] = 0;
-  }
-  return cluster_cap_status(count_cluster_cap(overflow), ss.Kmax);
+  if (!stable_out) { stable_tmp.assign(ss.U, 0); stable_out = stable_tmp.data(); }
+  return session_readout(h, [&](const std::vector<uis_handle::NbestGroup>& groups, std::vector<int32_t>* overflow) {
+    if (int rc = nbest_run(h, groups, false, ss.B, off, n_best, labels_out, capacity, scores_out, counts_out, stable_out, overflow))
+      return rc;
+    emptied_windows(ss, counts_out, scores_out, (size_t)n_best, nullptr, 0, stable_out);  // (no labels left to show)
+    return (int)UIS_OK;
+  });
 }

@@ -18,8 +18,7 @@
 //                            an item adds its 8 terms per frame, k ascending, into its own row of a [2][groups][N]
 //                            float scratch;
 //                         4. a thread per frame adds the groups' rows, g ascending, in float64.
-//                       k_nbest's rules to the letter: avail for sessions and tau * N otherwise, the parity of T, the
-//                       clamp of stale parent ranks to B - 1, live from beam_n and the overflow word.
+//                       k_nbest's rules to the letter: the same beam_view() and record decode (uis_beam_view.h).
 //   k_posterior_window  window records (bp16: look_ahead >= 2, beams over 256), not the hot path: k_nbest_window writes
 //                       the labels of every rank into a scratch table, then one workgroup per utterance forms the
 //                       weights and a thread per frame sums k ascending.
@@ -41,24 +40,16 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_posterior(DecodeState st,
                                                                  const int64_t* __restrict__ frame_off, float* __restrict__ conf,
                                                                  float* __restrict__ change, float* part,
                                                                  float* __restrict__ weights, int32_t* __restrict__ counts) {
-  // [0, 16): unused (k_nbest's layout); [16, 16 + 64 B): segment maps; [B][64]: stitched entries; [B] float64 e_k;
-  // [B] float32 w_k
-  extern __shared__ __attribute__((aligned(16))) unsigned char ps_lds[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char ps_lds[];  // (NbestLds, then [B] float64 e_k, [B] float32 w_k)
   const int u = blockIdx.x;
   if (u >= st.U) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int B = st.B;
-  unsigned char* bt_map = ps_lds + 16;
-  unsigned char* ent = bt_map + (size_t)64 * B;
-  double* ek = reinterpret_cast<double*>(ent + (size_t)64 * B);
+  const NbestLds lds = nbest_lds(ps_lds, B);
+  unsigned char *bt_map = lds.bt_map, *ent = lds.ent;
+  double* ek = reinterpret_cast<double*>(lds.more);
   float* w = reinterpret_cast<float*>(ek + B);
-  const long N = st.avail ? (long)st.avail[u] : (long)(st.off[u + 1] - st.off[u]);
-  const long T = st.avail ? N : (long)st.tau * N;
-  const int par = (int)(T & 1);  // parity holding the final beam
-  int nb = N > 0 ? st.beam_n[(size_t)par * st.U + u] : 0;
-  nb = nb < 0 ? 0 : (nb > B ? B : nb);
-  const int live = st.overflow[u] ? 0 : nb;
-  const size_t e = ((size_t)par * st.U + u) * B;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u);
   const int64_t o = frame_off[u];
   if (counts && tid == 0) counts[u] = live;
   // ---- 0. the weights
@@ -79,11 +70,10 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_posterior(DecodeState st,
     for (long t = tid; t < N; t += UIS_NBEST_THREADS) { conf[o + t] = 0.0f; change[o + t] = 0.0f; }
     return;  // (the whole workgroup)
   }
-  const uint32_t* bp = st.bp + (size_t)st.tau * st.off[u] * B;
-  const long seg = (N + 63) / 64;
-  const int nseg = (int)((N + seg - 1) / seg);
+  const SegGeom sg = seg_geom(T, N);
+  const int nseg = sg.nseg;
   // ---- 1. the segment maps, 2. the stitch (k_nbest's)
-  nbest_segment_maps(bp, B, T, N, seg, nseg, bt_map);
+  nbest_segment_maps(bp, B, sg, bt_map);
   __syncthreads();
   nbest_stitch(B, live, nseg, bt_map, ent);
   __syncthreads();
@@ -93,9 +83,7 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_posterior(DecodeState st,
   float* ph = pc + (size_t)groups * N;
   for (int p = tid; p < nseg * groups; p += UIS_NBEST_THREADS) {
     const int l = p / groups, g = p - l * groups;
-    const long h2 = T - 1 - (long)l * seg;
-    long l2 = h2 - seg + 1;
-    if (l2 < T - N) l2 = T - N;
+    const long h2 = sg.hi(l), l2 = sg.lo(l);
     int r0 = ent[l];
     int r[UIS_POST_CHAINS], prev[UIS_POST_CHAINS];
     float wk[UIS_POST_CHAINS];
@@ -111,16 +99,14 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_posterior(DecodeState st,
     const long f0 = T - N;  // the step of the readout's first frame
     for (long s2 = h2; s2 >= l2; --s2) {
       const uint32_t v0 = bp[(size_t)s2 * B + r0];
-      const int lab0 = (int)(v0 & 0xffffu);
-      r0 = (int)(v0 >> 16);
-      if (r0 >= B) r0 = B - 1;
+      const int lab0 = rec_label(v0);
+      r0 = rec_parent(v0, B);
       float c = 0.0f, ch = 0.0f;
 #pragma unroll
       for (int k = 0; k < UIS_POST_CHAINS; ++k) {
         const uint32_t v = bp[(size_t)s2 * B + r[k]];
-        const int lab = (int)(v & 0xffffu);
-        r[k] = (int)(v >> 16);
-        if (r[k] >= B) r[k] = B - 1;
+        const int lab = rec_label(v);
+        r[k] = rec_parent(v, B);
         c += lab == lab0 ? wk[k] : 0.0f;
         ch += prev[k] != lab ? wk[k] : 0.0f;  // the turn between steps s2 and s2 + 1 (not stored at s2 == h2)
         prev[k] = lab;
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(UIS_NBEST_THREADS) void k_posterior(DecodeState st,
     if (l2 > f0) {
 #pragma unroll
       for (int k = 0; k < UIS_POST_CHAINS; ++k) {
-        const int lab = (int)(bp[(size_t)(l2 - 1) * B + r[k]] & 0xffffu);
+        const int lab = rec_label(bp[(size_t)(l2 - 1) * B + r[k]]);
         ch += prev[k] != lab ? wk[k] : 0.0f;
       }
     }
@@ -236,7 +222,7 @@ int posterior_run(uis_handle* h, const std::vector<uis_handle::NbestGroup>& grou
     float* g_weights = h->ps_weights.as<float>() + (size_t)g.u0 * B;
     int32_t* g_counts = h->ps_counts.as<int32_t>() + g.u0;
     if (!wnd) {
-      hipLaunchKernelGGL(k_posterior, dim3(g.st.U), dim3(UIS_NBEST_THREADS), (size_t)16 + (size_t)(128 + 12) * B, h->stream, g.st,
+      hipLaunchKernelGGL(k_posterior, dim3(g.st.U), dim3(UIS_NBEST_THREADS), posterior_lds_bytes(B), h->stream, g.st,
                          temperature, g_off, h->ps_conf.as<float>(), h->ps_change.as<float>(), h->ps_part.as<float>(), g_weights,
                          g_counts);
     } else {
@@ -253,12 +239,7 @@ int posterior_run(uis_handle* h, const std::vector<uis_handle::NbestGroup>& grou
   if (F > 0 && change_out) HIPCHK(hipMemcpyAsync(change_out, h->ps_change.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
   if (weights_out) HIPCHK(hipMemcpyAsync(weights_out, h->ps_weights.p, (size_t)U * B * 4, hipMemcpyDeviceToHost, h->stream));
   if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, h->ps_counts.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  if (overflow) {
-    overflow->assign(U, 0);
-    for (const uis_handle::NbestGroup& g : groups)
-      if (g.st.U > 0)
-        HIPCHK(hipMemcpyAsync(overflow->data() + g.u0, g.st.overflow, (size_t)g.st.U * 4, hipMemcpyDeviceToHost, h->stream));
-  }
+  if ((rc = download_overflow(h, groups, U, overflow))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   return UIS_OK;
 }
@@ -278,33 +259,18 @@ UIS_EXPORT int32_t uis_last_decode_posterior(uis_handle* h, double temperature, 
 
 UIS_EXPORT int32_t uis_stream_posterior(uis_handle* h, double temperature, float* confidence_out, float* change_out,
                                         int64_t capacity, float* weights_out, int32_t* counts_out) {
-  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
-  const int U = ss.U;
   if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(UIS_ERR_INVALID_ARG, "temperature must be finite and > 0");
-  std::vector<int64_t> off(U + 1, 0);
-  for (int u = 0; u < U; ++u) off[u + 1] = off[u] + ss.have[u];
-  if ((confidence_out || change_out) && capacity < off[U])
-    return fail(UIS_ERR_INVALID_ARG, "confidence_out / change_out: " + std::to_string((long long)off[U]) + " float slots needed");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
-  // a persistent launch leaves first (as for uis_stream_nbest); ss.persist stays set, the next push starts a new one
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
-  // frames received = steps run, from the host's own count (as uis_stream_labels)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, h->stream));
-  std::vector<uis_handle::NbestGroup> groups(1);
-  groups[0].st = ss.st;
-  groups[0].st.avail = ss.d_have;
-  groups[0].u0 = 0;
-  std::vector<int32_t> overflow;
-  if ((rc = posterior_run(h, groups, false, ss.B, off, temperature, confidence_out, change_out, capacity, weights_out, counts_out,
-                          &overflow)))
-    return rc;
-  for (int u = 0; u < U; ++u) {  // a window that a commit emptied: the one hypothesis that lives, no frames left to show
-    if (!ss.window_emptied(u)) continue;
-    if (counts_out) counts_out[u] = 1;
-    if (weights_out) weights_out[(size_t)u * ss.B] = 1.0f;
-  }
-  return cluster_cap_status(count_cluster_cap(overflow), ss.Kmax);
+  const std::vector<int64_t> off = window_offsets(ss);
+  if ((confidence_out || change_out) && capacity < off[ss.U])
+    return fail(UIS_ERR_INVALID_ARG, "confidence_out / change_out: " + std::to_string((long long)off[ss.U]) + " float slots needed");
+  return session_readout(h, [&](const std::vector<uis_handle::NbestGroup>& groups, std::vector<int32_t>* overflow) {
+    if (int rc = posterior_run(h, groups, false, ss.B, off, temperature, confidence_out, change_out, capacity, weights_out,
+                               counts_out, overflow))
+      return rc;
+    const float one = 1.0f;
+    emptied_windows(ss, counts_out, weights_out, (size_t)ss.B, &one);  // (no frames left to show)
+    return (int)UIS_OK;
+  });
 }

@@ -31,15 +31,12 @@
 // reference's quirk, uisrnn.py:425-429 -- exactly as k_score_mean_scan's `p`): a chain of `len` frames stores len.
 // Cluster k of the hypothesis sits in slot k of the utterance's pool (S = B * Kmax + B >= Kmax slots).
 //
-// Order: checks on the host (nothing touched), a resident launch of a UIS_FLAG_PERSISTENT session leaves (pm_quit, as
-// for uis_stream_nbest: the tables are then back in global memory and nothing runs beside the commit; the next push
-// starts a new launch -- tables are written between launches only, which keeps the XCD-private-L2 hazard described
-// in uis_stream_begin away), the forced run, the scores read back and checked, THEN the commit, then one
-// synchronisation.  The launch has to leave BEFORE the forced run -- it occupies every CU -- so a call refused after
-// that point (a non-finite NLL, UIS_ERR_OOM) changes no table but has cost the resident launch; a call refused by the
-// host checks has not.  Every store is an ordinary vector store.
+// The order is the scaffold's (uis_stream.hip); this call's own: between leaving the resident launch and the scratch
+// come the forced run and the check of its NLLs, before anything is committed.  The launch has to leave BEFORE the
+// forced run -- it occupies every CU -- so a call refused after that point (a non-finite NLL, UIS_ERR_OOM) changes no
+// table but has cost the resident launch; a call refused by the host checks has not.
 //
-// #included by uis_decoder.hip after uis_stream.hip (pm_quit) and uis_score.hip (score_run).
+// #included by uis_decoder.hip after uis_stream.hip (the scaffold) and uis_score.hip (score_run).
 
 namespace {
 
@@ -115,13 +112,12 @@ __global__ __launch_bounds__(256) void k_prime_bp(DecodeState st, PrimeArgs a) {
 
 UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const int64_t* offsets, const int32_t* labels,
                                     float* scores_out) {
-  if (!h || !offsets) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets");
+  if (!session_of(h, offsets != nullptr, "null handle/offsets")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const DevModel& m = h->m;
   const int U = ss.U;
-  const auto t_begin = std::chrono::steady_clock::now();
-  // ---- the checks: nothing of the session is touched before the last of them has passed
+  CallTimer timer{h};
+  // ---- the checks
   if (offsets[0] != 0) return fail(UIS_ERR_INVALID_ARG, "offsets[0] must be 0");
   for (int u = 0; u < U; ++u)
     if (offsets[u + 1] < offsets[u]) return fail(UIS_ERR_INVALID_ARG, "offsets must be non-decreasing");
@@ -155,10 +151,8 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
     if (scores_out) std::fill(scores_out, scores_out + U, 0.0f);
     return UIS_OK;
   }
-  HIPCHK(hipSetDevice(h->device));
   int rc;
-  // a persistent launch leaves first (as for uis_stream_nbest); ss.persist stays set, the next push starts a new one
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
+  if ((rc = session_enter(h, nullptr))) return rc;  // (no window table: nothing here reads one)
   // ---- the forced run: every chain to its end; the NLLs come back before anything is committed
   ScoreSchedule s;
   std::vector<float> nll(U, 0.0f);
@@ -180,13 +174,12 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
     }
   }
   const int nutt = (int)utts.size();
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_chains = 0, o_utts = o_chains + up16((size_t)nch * sizeof(PrimeChain)), o_blk = o_utts + up16((size_t)nutt * sizeof(PrimeUtt)),
-               o_lab = o_blk + up16((size_t)nch * 4), total = o_lab + up16((size_t)F * 4);
-  if ((rc = h->sc_prime.ensure(total))) return rc;
+  ScratchPlan plan;
+  const size_t o_chains = plan.take((size_t)nch * sizeof(PrimeChain)), o_utts = plan.take((size_t)nutt * sizeof(PrimeUtt)),
+               o_blk = plan.take((size_t)nch * 4), o_lab = plan.take((size_t)F * 4);
+  char* base;
+  if ((rc = session_buffers(h, plan, 0, &base))) return rc;
   hipStream_t st = h->stream;
-  HIPCHK(UisPoison::from_env().device(h->sc_prime.p, h->sc_prime.cap, st));
-  char* base = h->sc_prime.as<char>();
   HIPCHK(hipMemcpyAsync(base + o_chains, chains.data(), (size_t)nch * sizeof(PrimeChain), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(base + o_utts, utts.data(), (size_t)nutt * sizeof(PrimeUtt), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(base + o_blk, s.chain_blk.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
@@ -202,20 +195,17 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   a.mean = h->sc_mean.as<float>();
   a.scores = h->sc_out.as<float>();
   // ---- the commit
-  HIPCHK(hipEventRecord(h->ev_begin, st));
+  HIPCHK(timer.begin());
   hipLaunchKernelGGL(k_prime_commit, dim3((unsigned)(nch + (nutt + 255) / 256)), dim3(256), 0, st, m, ss.st, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_prime_bp, dim3((unsigned)nutt), dim3(256), 0, st, ss.st, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev_end, st));
+  HIPCHK(timer.end());
   HIPCHK(hipStreamSynchronize(st));
   for (const PrimeUtt& p : utts) ss.have[p.utt] = p.P;
   if (scores_out) std::copy(nll.begin(), nll.end(), scores_out);
-  if (score_timing_env()) {
-    float dev_ms = 0.0f;
-    (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
-    fprintf(stderr, "uis_stream_prime: utterances %d chains %d commit_device_ms %.3f call_ms %.3f\n", nutt, nch, (double)dev_ms,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  }
+  if (score_timing_env())
+    fprintf(stderr, "uis_stream_prime: utterances %d chains %d commit_device_ms %.3f call_ms %.3f\n", nutt, nch, timer.device_ms(),
+            timer.call_ms());
   return UIS_OK;
 }

@@ -16,10 +16,8 @@
 // behind in the slot -- its bp rows, its pool slots (mean, hidden states, frame counts) and its rows of the beam
 // tables of both parities -- so that a recycled slot provably depends on nothing of its previous tenant.
 //
-// Order, as uis_stream_commit: checks on the host (nothing touched), a resident launch of a UIS_FLAG_PERSISTENT
-// session leaves (pm_quit: tables are written between launches only), scratch (filled ahead of its defining writes
-// when the knob is set), readout, reset, ONE download, ONE synchronisation, then the host's have / committed /
-// win_score.  Every store is an ordinary vector store.
+// The order is the scaffold's (uis_stream.hip); this call's own: the readout's avail is its own table in the scratch
+// (not the session's d_have), and a call that selects nothing still prints its trace line.
 //
 // #included by uis_decoder.hip after uis_commit.hip.
 
@@ -75,12 +73,11 @@ __global__ __launch_bounds__(UIS_RESTART_THREADS) void k_stream_restart_fill(Dec
 
 UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32_t* labels_out, int64_t capacity,
                                       int32_t* counts_out, float* scores_out, int32_t* overflow_out) {
-  if (!h || !which || !counts_out) return fail(UIS_ERR_INVALID_ARG, "null handle/which/counts_out");
+  if (!session_of(h, which && counts_out, "null handle/which/counts_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const int U = ss.U;
-  const auto t_begin = std::chrono::steady_clock::now();
-  // ---- the checks: nothing of the session is touched before the last of them has passed
+  CallTimer timer{h};
+  // ---- the checks
   int n_sel = 0;
   int64_t F = 0;
   for (int u = 0; u < U; ++u)
@@ -89,39 +86,27 @@ UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32
     return fail(UIS_ERR_INVALID_ARG, "labels_out: " + std::to_string((long long)F) + " int32 slots needed (the window frames of the utterances that end)");
   if (F > 0 && !labels_out) return fail(UIS_ERR_INVALID_ARG, "labels_out is null");
   // UIS_RESTART_TRACE: one line per call on stderr (read per call: a test turns it on)
-  auto trace = [&](bool device_work) {
-    const char* e = getenv("UIS_RESTART_TRACE");
-    if (!e || atoi(e) == 0) return;
-    float dev_ms = 0.0f;
-    if (device_work) (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
-    fprintf(stderr, "uis_stream_restart: utterances %d selected %d labels %lld device_ms %.3f call_ms %.3f persistent %d resident_launches %lld\n",
-            U, n_sel, (long long)F, (double)dev_ms,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), ss.persist ? 1 : 0,
-            (long long)ss.pm_launches);
+  auto trace = [&] {  // (also for a call that selects nothing)
+    if (CallTimer::env("UIS_RESTART_TRACE"))
+      fprintf(stderr, "uis_stream_restart: utterances %d selected %d labels %lld device_ms %.3f call_ms %.3f persistent %d resident_launches %lld\n",
+              U, n_sel, (long long)F, timer.device_ms(), timer.call_ms(), ss.persist ? 1 : 0, (long long)ss.pm_launches);
   };
   if (n_sel == 0) {
     std::fill(counts_out, counts_out + U, 0);
-    trace(false);
+    trace();
     return UIS_OK;
   }
-  HIPCHK(hipSetDevice(h->device));
   int rc;
-  // a persistent launch leaves first (as for uis_stream_commit); ss.persist stays set, the next push starts a new one
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
+  if ((rc = session_enter(h, nullptr))) return rc;  // (the readout's avail is this call's own table: the utterances that end)
   hipStream_t st = h->stream;
   // ---- scratch: [which U][avail U][label offsets U] go up in one copy, [scores U][overflow U][labels F] come back in one
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_which = 0, o_avail = o_which + (size_t)U * 4, o_laboff = up16(o_avail + (size_t)U * 4),
-               o_score = o_laboff + (size_t)U * 8, o_over = o_score + (size_t)U * 4, o_lab = o_over + (size_t)U * 4,
-               total = o_lab + (size_t)F * 4, land = total - o_score;
-  if ((rc = h->sc_restart.ensure(total))) return rc;
-  if (land > ss.h_land.cap) {
-    hipError_t e = ss.h_land.ensure(land + land / 4 + 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  }
-  const UisPoison poison = UisPoison::from_env();
-  HIPCHK(poison.device(h->sc_restart.p, h->sc_restart.cap, st));
-  poison.host(ss.h_land.p, ss.h_land.cap);
+  ScratchPlan plan;
+  const size_t o_which = plan.take((size_t)U * 4), o_avail = plan.take((size_t)U * 4, 4), o_laboff = plan.take((size_t)U * 8),
+               o_score = plan.take((size_t)U * 4, 4), o_over = plan.take((size_t)U * 4, 4), o_lab = plan.take((size_t)F * 4, 4),
+               land = plan.total - o_score;
+  char* base;
+  UisPoison poison;
+  if ((rc = session_buffers(h, plan, land, &base, {}, &poison))) return rc;
   std::vector<char> up(o_score, 0);
   {
     int32_t* w = reinterpret_cast<int32_t*>(up.data() + o_which);
@@ -135,14 +120,13 @@ UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32
       pos += a[u];
     }
   }
-  char* base = h->sc_restart.as<char>();
   HIPCHK(hipMemcpyAsync(base, up.data(), o_score, hipMemcpyHostToDevice, st));
   const int32_t* d_which = reinterpret_cast<const int32_t*>(base + o_which);
   DecodeState stl = ss.st;
   stl.avail = reinterpret_cast<const int32_t*>(base + o_avail);
   stl.lab_off = reinterpret_cast<const int64_t*>(base + o_laboff);
   // ---- readout, reset
-  HIPCHK(hipEventRecord(h->ev_begin, st));
+  HIPCHK(timer.begin());
   hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, st, stl, reinterpret_cast<int32_t*>(base + o_lab),
                      reinterpret_cast<float*>(base + o_score), (float*)nullptr);
   HIPCHK(hipGetLastError());
@@ -154,7 +138,7 @@ UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32
   hipLaunchKernelGGL(k_stream_restart, dim3((U + UIS_RESTART_THREADS - 1) / UIS_RESTART_THREADS), dim3(UIS_RESTART_THREADS), 0, st,
                      ss.st, d_which, reinterpret_cast<int32_t*>(base + o_over));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev_end, st));
+  HIPCHK(timer.end());
   HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_score, land, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   // ---- the host's side
@@ -175,6 +159,6 @@ UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32
     ss.win_score[u] = 0.0f;
   }
   h->nb_valid = false;
-  trace(true);
+  trace();
   return cluster_cap_status(n_over, ss.Kmax);
 }

@@ -25,13 +25,12 @@
 //   k_retire_apply  leaves at once if ANY utterance's status is set (a refusal changes no bit of the session); else
 //                   the scalars, then the lists (in place, source and destination overlap: read, barrier, write, as
 //                   k_commit_prune), then the window's N * B record words, 16 bytes per thread where the utterance's
-//                   records are aligned, a scalar tail, and the scalar path where they are not (k_commit_move's split)
+//                   records are aligned, a scalar tail, and the scalar path where they are not
 // An utterance with an emptied beam or flagged in the overflow word has live = 0: nothing is retirable, it is left
 // alone; one that has received nothing holds the empty hypothesis (K = 0): likewise.
 //
-// Order, as uis_stream_commit: checks on the host (nothing touched), a resident launch of a UIS_FLAG_PERSISTENT
-// session leaves (pm_quit), scratch (filled ahead of its defining writes when UIS_POISON_WORKSPACE is set), the two
-// kernels, ONE download, ONE synchronisation.  Every store is an ordinary vector store.
+// The order is the scaffold's (uis_stream.hip); this call's own: the refusal of a selection is found on the device and
+// reported after the download, with no bit of the session changed.
 //
 // #included by uis_decoder.hip after uis_nbest.hip (nbest_segment_maps, nbest_stitch) and uis_restart.hip.
 
@@ -53,14 +52,6 @@ struct RetireArgs {
   int32_t* words;           // [U][4]: retired, retirable, largest K afterwards, status
 };
 
-// live hypotheses of utterance u in a window of N frames (k_nbest's rule; N = 0: the one hypothesis a commit kept, or
-// the empty one of an utterance that has received nothing)
-__device__ __forceinline__ int retire_live(const DecodeState& st, int u, long N) {
-  int nb = st.beam_n[(size_t)(N & 1) * st.U + u];
-  nb = nb < 0 ? 0 : (nb > st.B ? st.B : nb);
-  return st.overflow[u] ? 0 : nb;
-}
-
 // pre[w] = bits set in mask[0 .. w), w <= nw (one thread; nw <= 129)
 __device__ __forceinline__ void retire_prefix(const uint32_t* mask, int* pre, int nw) {
   int acc = 0;
@@ -73,8 +64,7 @@ __device__ __forceinline__ int retire_below(const uint32_t* mask, const int* pre
 }
 
 __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_scan(DecodeState st, RetireArgs a) {
-  // k_nbest's layout: [0, 16) unused here; [16, 16 + 64 B): exit rank by entry rank and segment; then [B][64]
-  extern __shared__ __attribute__((aligned(16))) unsigned char rt_lds[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char rt_lds[];  // (NbestLds)
   __shared__ uint32_t s_used[UIS_RETIRE_MASK_WORDS], s_sel[UIS_RETIRE_MASK_WORDS], s_able[UIS_RETIRE_MASK_WORDS];
   __shared__ int s_pre_sel[UIS_RETIRE_MASK_WORDS + 1], s_pre_able[UIS_RETIRE_MASK_WORDS + 1];
   __shared__ int s_minK, s_maxK, s_bad;
@@ -82,19 +72,16 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_scan(DecodeState 
   if (u >= st.U) return;
   const int B = st.B, Kmax = st.Kmax;
   const int nw = (Kmax >> 5) + 1;   // words that hold bits 0 .. Kmax
-  unsigned char* bt_map = rt_lds + 16;
-  unsigned char* ent = bt_map + (size_t)64 * B;
-  const long N = (long)st.avail[u];
-  const int live = retire_live(st, u, N);
-  const size_t e = ((size_t)(N & 1) * st.U + u) * B;
+  const NbestLds lds = nbest_lds(rt_lds, B);
+  unsigned char *bt_map = lds.bt_map, *ent = lds.ent;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u, EMPTY_WINDOW_KEEPS_BEAM);
   for (int w = tid; w < UIS_RETIRE_MASK_WORDS; w += UIS_RETIRE_THREADS) { s_used[w] = 0; s_sel[w] = 0; s_able[w] = 0; }
   if (tid == 0) { s_minK = Kmax; s_maxK = 0; s_bad = 0; }
   const bool walk = N > 0 && live > 0;
-  const uint32_t* bp = st.bp + (size_t)st.tau * st.off[u] * B;
-  const long seg = (N + 63) / 64;
-  const int nseg = N > 0 ? (int)((N + seg - 1) / seg) : 0;
+  const SegGeom g = seg_geom(N, N);
+  const int nseg = g.nseg;
   // ---- the chains of the live ranks over the window (k_nbest's phases 1 and 2)
-  if (walk) nbest_segment_maps(bp, B, N, N, seg, nseg, bt_map);
+  if (walk) nbest_segment_maps(bp, B, g, bt_map);
   __syncthreads();
   if (walk) nbest_stitch(B, live, nseg, bt_map, ent);
   __syncthreads();
@@ -102,17 +89,10 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_scan(DecodeState 
   if (walk) {
     for (int p = tid; p < nseg * live; p += UIS_RETIRE_THREADS) {
       const int l = p / live, k = p - l * live;
-      const long h2 = N - 1 - (long)l * seg;
-      long l2 = h2 - seg + 1;
-      if (l2 < 0) l2 = 0;
-      int r = ent[(size_t)k * 64 + l];
-      for (long s2 = h2; s2 >= l2; --s2) {
-        const uint32_t v = bp[(size_t)s2 * B + r];
-        const int lab = (int)(v & 0xffffu);
+      walk_segment(bp, B, g, l, ent[(size_t)k * 64 + l], [&](long, uint32_t v) {
+        const int lab = rec_label(v);
         if (lab < Kmax) atomicOr(&s_used[lab >> 5], 1u << (lab & 31));   // (LDS)
-        r = (int)(v >> 16);
-        if (r >= B) r = B - 1;
-      }
+      });
     }
   }
   // ---- the lasts count as used; min and max K over the live ranks
@@ -184,9 +164,7 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
   const int n_ret = a.words[4 * u + 0];
   if (n_ret <= 0) return;
   const int B = st.B, Kmax = st.Kmax;
-  const long N = (long)st.avail[u];
-  const int live = retire_live(st, u, N);   // (> 0: nothing is retirable without a live hypothesis)
-  const size_t e = ((size_t)(N & 1) * st.U + u) * B;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u, EMPTY_WINDOW_KEEPS_BEAM);   // (live > 0: nothing is retirable without a live hypothesis)
   const int32_t* shift = a.shift + (size_t)u * (Kmax + 1);
   const int32_t* retired = a.retired + (size_t)u * Kmax;
   for (int k = tid; k <= Kmax; k += UIS_RETIRE_THREADS) s_shift[k] = shift[k];
@@ -202,8 +180,7 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
     st.beam_sum[e + r] -= gone;
     if (last > 0 && last <= Kmax) st.beam_last[e + r] = last - s_shift[last];
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the block counts have returned before the barrier lets anyone move them)
-  __syncthreads();
+  loads_before_stores();  // (the block counts have returned before the barrier lets anyone move them)
   // ---- the lists: entry i = (rank i / Kmax, index i % Kmax), ascending tiles.  An entry moves down inside its row,
   // into this tile or an earlier one: every tile is in registers before any of it is stored.
   const long entries = (long)live * Kmax;
@@ -221,18 +198,16 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
         vblk = st.beam_blk[row + k];
       }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    loads_before_stores();
     if (dst >= 0) {
       st.beam_slot[row + dst] = vslot;
       st.beam_blk[row + dst] = vblk;
     }
   }
   // ---- the records of window steps [0, N): every word its own thread's, no overlap
-  uint32_t* bp = st.bp + (size_t)st.tau * st.off[u] * B;
   const long words = N * (long)B;
   auto relabel = [&](uint32_t v) {
-    const uint32_t lab = v & 0xffffu;
+    const uint32_t lab = (uint32_t)rec_label(v);
     return lab <= (uint32_t)Kmax ? (v & 0xffff0000u) | (lab - (uint32_t)s_shift[lab]) : v;
   };
   if ((reinterpret_cast<uintptr_t>(bp) & 15u) == 0) {
@@ -255,12 +230,11 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
 UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const int64_t* offsets, const int32_t* clusters,
                                      int32_t* retired_out, int32_t* counts_out, int32_t* k_out, int32_t* retirable_out,
                                      int32_t* retirable_counts_out) {
-  if (!h || !counts_out || !k_out) return fail(UIS_ERR_INVALID_ARG, "null handle/counts_out/k_out");
+  if (!session_of(h, counts_out && k_out, "null handle/counts_out/k_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const int U = ss.U, B = ss.B, Kmax = ss.Kmax;
-  const auto t_begin = std::chrono::steady_clock::now();
-  // ---- the checks: nothing of the session is touched before the last of them has passed
+  CallTimer timer{h};
+  // ---- the checks
   if (clusters && !offsets) return fail(UIS_ERR_INVALID_ARG, "clusters without offsets");
   if (offsets && which) return fail(UIS_ERR_INVALID_ARG, "which and an explicit selection (offsets) exclude each other");
   std::vector<int32_t> mode(U, UIS_RETIRE_QUERY);
@@ -288,36 +262,24 @@ UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const 
     if (!retired_out) return fail(UIS_ERR_INVALID_ARG, "retired_out is null");
     for (int u = 0; u < U; ++u) mode[u] = !which || which[u] ? UIS_RETIRE_ALL : UIS_RETIRE_QUERY;
   }
-  HIPCHK(hipSetDevice(h->device));
   int rc;
-  // a persistent launch leaves first (as for uis_stream_commit); ss.persist stays set, the next push starts a new one
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
+  DecodeState stc;
+  if ((rc = session_enter(h, &stc))) return rc;
   hipStream_t st = h->stream;
   // ---- scratch: [mode U][offsets U + 1][lists] go up in one copy, [words 4 U][retired U Kmax][retirable U Kmax] come
   // back in one; the shift tables stay on the device
-  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_mode = 0, o_off = up16((size_t)U * 4), o_sel = o_off + (size_t)(U + 1) * 8,
-               o_words = up16(o_sel + (size_t)n_sel * 4), o_ret = o_words + (size_t)U * 16,
-               o_able = o_ret + (size_t)U * Kmax * 4, o_shift = o_able + (size_t)U * Kmax * 4,
-               total = o_shift + (size_t)U * (Kmax + 1) * 4, land = o_shift - o_words;
-  if ((rc = h->sc_retire.ensure(total))) return rc;
-  if (land > ss.h_land.cap) {
-    hipError_t e = ss.h_land.ensure(land + land / 4 + 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  }
-  const UisPoison poison = UisPoison::from_env();
-  HIPCHK(poison.device(h->sc_retire.p, h->sc_retire.cap, st));
-  poison.host(ss.h_land.p, ss.h_land.cap);
+  ScratchPlan plan;
+  const size_t o_mode = plan.take((size_t)U * 4), o_off = plan.take((size_t)(U + 1) * 8), o_sel = plan.take((size_t)n_sel * 4, 4),
+               o_words = plan.take((size_t)U * 16), o_ret = plan.take((size_t)U * Kmax * 4, 4),
+               o_able = plan.take((size_t)U * Kmax * 4, 4), o_shift = plan.take((size_t)U * (Kmax + 1) * 4, 4),
+               land = o_shift - o_words;
+  char* base;
+  if ((rc = session_buffers(h, plan, land, &base))) return rc;
   std::vector<char> up(o_words, 0);
   std::copy(mode.begin(), mode.end(), reinterpret_cast<int32_t*>(up.data() + o_mode));
   if (offsets) std::copy(offsets, offsets + U + 1, reinterpret_cast<int64_t*>(up.data() + o_off));
   if (n_sel > 0) std::copy(clusters, clusters + n_sel, reinterpret_cast<int32_t*>(up.data() + o_sel));
-  char* base = h->sc_retire.as<char>();
   HIPCHK(hipMemcpyAsync(base, up.data(), o_words, hipMemcpyHostToDevice, st));
-  // frames in the window = steps run since the last commit, from the host's own count (as uis_stream_labels)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, st));
-  DecodeState stc = ss.st;
-  stc.avail = ss.d_have;
   RetireArgs a{};
   a.mode = reinterpret_cast<const int32_t*>(base + o_mode);
   a.sel_off = reinterpret_cast<const int64_t*>(base + o_off);
@@ -327,12 +289,12 @@ UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const 
   a.retirable = reinterpret_cast<int32_t*>(base + o_able);
   a.shift = reinterpret_cast<int32_t*>(base + o_shift);
   // ---- scan, apply
-  HIPCHK(hipEventRecord(h->ev_begin, st));
-  hipLaunchKernelGGL(k_retire_scan, dim3(U), dim3(UIS_RETIRE_THREADS), (size_t)16 + (size_t)128 * B, st, stc, a);
+  HIPCHK(timer.begin());
+  hipLaunchKernelGGL(k_retire_scan, dim3(U), dim3(UIS_RETIRE_THREADS), nbest_lds_bytes(B), st, stc, a);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_retire_apply, dim3(U), dim3(UIS_RETIRE_THREADS), 0, st, stc, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev_end, st));
+  HIPCHK(timer.end());
   HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_words, land, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   // ---- the host's side
@@ -354,14 +316,8 @@ UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const 
     n_retired += n;
   }
   if (n_retired) h->nb_valid = false;
-  if (const char* e = getenv("UIS_RETIRE_TRACE"); e && atoi(e) != 0) {  // one line per call on stderr (read per call: a test turns it on)
-    float dev_ms = 0.0f;
-    (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
-    int64_t F = 0;
-    for (int u = 0; u < U; ++u) F += ss.have[u];
+  if (CallTimer::env("UIS_RETIRE_TRACE"))
     fprintf(stderr, "uis_stream_retire: utterances %d window_frames %lld selected %lld retired %lld device_ms %.3f call_ms %.3f\n",
-            U, (long long)F, offsets ? (long long)n_sel : -1ll, (long long)n_retired, (double)dev_ms,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-  }
+            U, (long long)window_offsets(ss)[U], offsets ? (long long)n_sel : -1ll, (long long)n_retired, timer.device_ms(), timer.call_ms());
   return UIS_OK;
 }

@@ -179,15 +179,118 @@ int pm_quit(uis_handle* h) {
   return pm_reap(h);
 }
 
-// uis_stream_labels: an utterance whose window a commit emptied still has its one hypothesis and its score
-void stream_emptied_windows(uis_handle* h, float* scores_out) {
+// ---- the scaffold of a session call between launches: uis_stream_{labels, nbest, posterior, prime, commit, restart,
+// retire, committed}.  THE ORDER, stated here once:
+//   1. session_of and the call's own checks on the host: nothing of the session is touched, and a call refused here
+//      (or one with nothing to do) costs a UIS_FLAG_PERSISTENT session nothing and touches no device;
+//   2. session_enter: the resident launch leaves (pm_quit -- it occupies every CU and the tables are written between
+//      launches only, which keeps the XCD-private-L2 hazard described in uis_stream_begin away; ss.persist stays set,
+//      the next push starts a new launch); frames in the window = steps run, from the host's own count `have` (the
+//      `avail` table of the last push may live in a chunk buffer this path did not fill);
+//   3. session_buffers: one ScratchPlan laid out in the one grow-only buffer sc_session, the pinned landing block, and
+//      their fills (UIS_POISON_WORKSPACE: ahead of the defining writes);
+//   4. the kernels between CallTimer::begin / end, ONE download, ONE hipStreamSynchronize;
+//   5. the host's bookkeeping (have / committed / win_score, nb_valid), the call's trace line.
+// Every store of every kernel is an ordinary vector store.
+
+// the null-argument and no-session refusals (false: refused, UIS_ERR_INVALID_ARG with its message is recorded)
+bool session_of(uis_handle* h, bool args = true, const char* null_msg = "null handle") {
+  if (!h || !args) return !fail(UIS_ERR_INVALID_ARG, null_msg);
+  return h->stream_state.active || !fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
+}
+
+// [U + 1] prefix sums of the frames in the utterances' windows
+std::vector<int64_t> window_offsets(const uis_handle::Stream& ss) {
+  std::vector<int64_t> off(ss.U + 1, 0);
+  for (int u = 0; u < ss.U; ++u) off[u + 1] = off[u] + ss.have[u];
+  return off;
+}
+
+// `view`: the session's tables with avail = the window's frame counts (null: the first half only -- uis_stream_prime
+// reads no window, uis_stream_restart's readout has an avail table of its own)
+int session_enter(uis_handle* h, DecodeState* view) {
   uis_handle::Stream& ss = h->stream_state;
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = ss.pm_running ? pm_quit(h) : UIS_OK) return rc;
+  if (!view) return UIS_OK;
+  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)ss.U * 4, hipMemcpyHostToDevice, h->stream));
+  *view = ss.st;
+  view->avail = ss.d_have;
+  return UIS_OK;
+}
+
+// offsets into one block, in the order taken
+struct ScratchPlan {
+  size_t total = 0;
+  size_t take(size_t bytes, size_t align = 16) { const size_t o = (total + align - 1) & ~(align - 1); total = o + bytes; return o; }
+};
+
+// the plan's block in sc_session (-> base), `land` bytes of pinned landing block (0: the call downloads nothing
+// into it; with head-room: calls of a session vary in size), and the fills of both and of the call's `other` buffers
+int session_buffers(uis_handle* h, const ScratchPlan& plan, size_t land, char** base, std::initializer_list<DevBuf*> other = {},
+                    UisPoison* poison_out = nullptr) {
+  uis_handle::Stream& ss = h->stream_state;
+  if (int rc = h->sc_session.ensure(plan.total)) return rc;
+  *base = h->sc_session.as<char>();
+  if (land > ss.h_land.cap) {
+    hipError_t e = ss.h_land.ensure(land + land / 4 + 4096, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  }
+  const UisPoison poison = UisPoison::from_env();
+  HIPCHK(poison.device(h->sc_session.p, h->sc_session.cap, h->stream));
+  for (DevBuf* b : other) HIPCHK(poison.device(b->p, b->cap, h->stream));
+  if (land) poison.host(ss.h_land.p, ss.h_land.cap);
+  if (poison_out) *poison_out = poison;
+  return UIS_OK;
+}
+
+// wall time from the call's entry, device time between begin() and end() (0 for a call that launched nothing);
+// env(): the knob of the call's one line on stderr, read per call (a test turns it on)
+struct CallTimer {
+  uis_handle* h;
+  std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  bool device_work = false;
+  hipError_t begin() { device_work = true; return hipEventRecord(h->ev_begin, h->stream); }
+  hipError_t end() { return hipEventRecord(h->ev_end, h->stream); }
+  static bool env(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }
+  double device_ms() const { float ms = 0.0f; if (device_work) (void)hipEventElapsedTime(&ms, h->ev_begin, h->ev_end); return (double)ms; }
+  double call_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
+};
+
+// an utterance whose window a commit emptied still has its one hypothesis and its score: what the readouts show of
+// it.  counts: 1; rank 0 of its `stride` values: `first` (null: win_score[u]), the `rest` after it: INFINITY; stable: 0;
+// each where the pointer is set
+void emptied_windows(const uis_handle::Stream& ss, int32_t* counts, float* values, size_t stride, const float* first,
+                     int rest = 0, int64_t* stable = nullptr) {
   for (int u = 0; u < ss.U; ++u) {
     if (!ss.window_emptied(u)) continue;
-    if (scores_out) scores_out[u] = ss.win_score[u];
-    h->last_beam_scores[(size_t)u * ss.B] = ss.win_score[u];
-    for (int k = 1; k < ss.B; ++k) h->last_beam_scores[(size_t)u * ss.B + k] = INFINITY;
+    if (counts) counts[u] = 1;
+    if (values) values[(size_t)u * stride] = first ? *first : ss.win_score[u];
+    for (int k = 1; values && k <= rest; ++k) values[(size_t)u * stride + k] = INFINITY;
+    if (stable) stable[u] = 0;
   }
+}
+
+// the readouts' last download: every group's overflow words, utterance order (null: not wanted)
+int download_overflow(uis_handle* h, const std::vector<uis_handle::NbestGroup>& groups, int U, std::vector<int32_t>* overflow) {
+  if (!overflow) return UIS_OK;
+  overflow->assign(U, 0);
+  for (const uis_handle::NbestGroup& g : groups)
+    if (g.st.U > 0)
+      HIPCHK(hipMemcpyAsync(overflow->data() + g.u0, g.st.overflow, (size_t)g.st.U * 4, hipMemcpyDeviceToHost, h->stream));
+  return UIS_OK;
+}
+
+// The common body of uis_stream_nbest / uis_stream_posterior after their checks: enter, the session as the one group,
+// `run` (the readout and its emptied-window fix-up), the overflow words' verdict.
+template <typename Run>
+int session_readout(uis_handle* h, Run run) {
+  uis_handle::Stream& ss = h->stream_state;
+  std::vector<uis_handle::NbestGroup> groups(1);
+  if (int rc = session_enter(h, &groups[0].st)) return rc;  // (u0 = 0)
+  std::vector<int32_t> overflow;
+  if (int rc = run(groups, &overflow)) return rc;
+  return cluster_cap_status(count_cluster_cap(overflow), ss.Kmax);
 }
 
 }  // namespace
@@ -509,13 +612,11 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
 }
 
 UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
-  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const int U = ss.U;
-  std::vector<int64_t> lab_off(U);
-  int64_t F = 0;
-  for (int u = 0; u < U; ++u) { lab_off[u] = F; F += ss.have[u]; }
+  const std::vector<int64_t> lab_off = window_offsets(ss);
+  const int64_t F = lab_off[U];
   if (F > 0 && !labels_out) return fail(UIS_ERR_INVALID_ARG, "labels_out is null");
   HIPCHK(hipSetDevice(h->device));
   int rc;
@@ -532,24 +633,20 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
                               reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow) + U);
       h->last_beam_scores.assign(reinterpret_cast<const float*>(pm + ss.pm_o_bscores),
                                  reinterpret_cast<const float*>(pm + ss.pm_o_bscores) + (size_t)U * ss.B);
-      stream_emptied_windows(h, scores_out);
+      emptied_windows(ss, nullptr, scores_out, 1, nullptr);
+      emptied_windows(ss, nullptr, h->last_beam_scores.data(), ss.B, nullptr, ss.B - 1);
       return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
     }
     if (rc != 1) return rc;  // (1: the launch had left -- its tables are back in global memory)
   }
+  DecodeState stl;
+  if ((rc = session_enter(h, &stl))) return rc;  // (no launch is running here: the mailbox path above took it or found it gone)
   if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
   if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
-  {
-    const UisPoison poison = UisPoison::from_env();
-    HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
-    HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
-  }
+  const UisPoison poison = UisPoison::from_env();
+  HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
+  HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
   HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
-  // frames received = steps run, from the host's own count: the `avail` table of the last push may
-  // live in a chunk buffer this path did not fill (pushes taken by the persistent launch)
-  HIPCHK(hipMemcpyAsync(ss.d_have, ss.have.data(), (size_t)U * 4, hipMemcpyHostToDevice, h->stream));
-  DecodeState stl = ss.st;
-  stl.avail = ss.d_have;
   hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, h->stream, stl, ss.labels.as<int32_t>(),
                      ss.scores.as<float>(), ss.d_beam_scores);
   HIPCHK(hipGetLastError());
@@ -562,7 +659,8 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
   HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, (size_t)U * ss.B * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  stream_emptied_windows(h, scores_out);
+  emptied_windows(ss, nullptr, scores_out, 1, nullptr);
+  emptied_windows(ss, nullptr, h->last_beam_scores.data(), ss.B, nullptr, ss.B - 1);
   return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
 }
 
