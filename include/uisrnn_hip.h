@@ -620,6 +620,41 @@ int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const int64_t* of
                           int32_t* retirable_counts_out);
 
 /*
+ * Export / import: one utterance of a live session as a blob of bytes, and back into a slot that has received
+ * nothing -- another slot, another session (other n_utt, max_frames, max_clusters, flags), another handle, device or
+ * process: checkpoints, moves out of a full session, rebalancing between ranks.  Between two pushes an utterance IS
+ * its tables; the blob holds them and the three host words (window frames, committed, the score at the last commit),
+ * every live hypothesis included, and the decode continues from an imported utterance bit for bit as it would have
+ * in the source.  No decode kernel is involved (an addition: the ABI version stays).  One utterance per call.
+ *   uis_stream_export_bound : host only, no device work.  bytes_out: the capacity uis_stream_export asks for (the
+ *                  largest blob a session of this shape can give).
+ *   uis_stream_export : blob host memory of `capacity` >= that bound bytes; bytes_out: the bytes written (usually far
+ *                  fewer).  Read-only: no table and no host word of the session changes.  The blob is self-describing
+ *                  (magic, format and numerics versions, a model fingerprint: the shape and a 64-bit hash of the
+ *                  parameters as uis_create received them, beam_size), position-independent, ends in a checksum, and
+ *                  CANONICAL: it depends on the utterance's state alone, not on the slot or session it sat in, so
+ *                  export(import(blob)) == blob byte for byte.  csrc/uis_blob.h states the layout.  An utterance that
+ *                  has received nothing exports a valid blob (the empty hypothesis).  Refused, nothing written:
+ *                  UIS_ERR_CLUSTER_CAP for an utterance flagged in the overflow word, UIS_ERR_INVALID_ARG for one
+ *                  whose beam a non-finite frame emptied (there is nothing to move: uis_stream_restart is the way
+ *                  back), for utt out of range and for a capacity below the bound.
+ *   uis_stream_import : all or nothing.  The target utterance must have received nothing (uis_stream_prime's rule).
+ *                  Must match: the model fingerprint, UIS_NUMERICS_VERSION, beam_size.  Must fit: the window's frames
+ *                  <= max_frames, every hypothesis' clusters <= max_clusters (UIS_ERR_CLUSTER_CAP otherwise; equality
+ *                  is accepted, as in uis_stream_prime), its pool slots <= those of the target.  Everything else is
+ *                  UIS_ERR_INVALID_ARG: a blob that is cut short, damaged (checksum) or inconsistent in anything that
+ *                  steers an address or a loop bound -- all decided on the host, before the device is touched; a call
+ *                  refused so costs a UIS_FLAG_PERSISTENT session nothing.  Record words are taken as they are (their
+ *                  readers clamp).  The session's prior tables grow where the utterance's history needs it, as in
+ *                  uis_stream_commit, and the 2^31 - 256 frame limit goes on counting from the imported total.
+ * In a UIS_FLAG_PERSISTENT session the resident launch leaves the device for both calls (after the host checks) and
+ * the next push starts a new one.  UIS_MIGRATE_TRACE=1: one line per call on stderr.
+ */
+int32_t uis_stream_export_bound(uis_handle* h, int32_t utt, int64_t* bytes_out);
+int32_t uis_stream_export(uis_handle* h, int32_t utt, void* blob, int64_t capacity, int64_t* bytes_out);
+int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blob, int64_t bytes);
+
+/*
  * Pinned (page-locked) host memory for the frames / labels handed to uis_decode: with it the
  * H2D copy of the frame stream is asynchronous and overlaps the input projection of the chunks
  * already on the device.  Pageable memory works too (staged by the runtime).

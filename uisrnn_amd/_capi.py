@@ -9,6 +9,7 @@ library is missing or no gfx950 device is usable, the calls raise.
 
 import ctypes
 import os
+import struct
 import sys
 
 import numpy as np
@@ -345,6 +346,12 @@ def load_library(path=None):
   lib.uis_stream_restart.argtypes = [ctypes.c_void_p, i32p, i32p, ctypes.c_int64, i32p, _fp, i32p]
   lib.uis_stream_retire.restype = i32
   lib.uis_stream_retire.argtypes = [ctypes.c_void_p, i32p, i64p, i32p, i32p, i32p, i32p, i32p, i32p]
+  lib.uis_stream_export_bound.restype = i32
+  lib.uis_stream_export_bound.argtypes = [ctypes.c_void_p, i32, i64p]
+  lib.uis_stream_export.restype = i32
+  lib.uis_stream_export.argtypes = [ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.c_int64, i64p]
+  lib.uis_stream_import.restype = i32
+  lib.uis_stream_import.argtypes = [ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.c_int64]
   lib.uis_eval_accuracy.restype = i32
   lib.uis_eval_accuracy.argtypes = [ctypes.c_void_p, i32p, i32p, i64p, i32, i64p]
   lib.uis_eval_accuracy_device.restype = i32
@@ -383,10 +390,31 @@ EXPORTED_SYMBOLS = (
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
     'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
-    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
+    'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
+    'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
+
+
+_BLOB_HEAD = struct.Struct('<4I8iQq' 'q4ifi')   # UisBlobHeader, UisBlobScalars (csrc/uis_blob.h)
+BLOB_MAGIC = 0x42534955
+
+
+def blob_info(blob):
+  """The scalars of a uis_stream_export blob: dict(B, N, committed, live, slots, K, bytes) -- K the largest cluster
+  count over its live hypotheses.  ValueError for bytes that are no such blob (only the head is looked at: the
+  library's import validates everything)."""
+  if len(blob) < _BLOB_HEAD.size + 16:
+    raise ValueError('not a stream blob: too short')
+  f = _BLOB_HEAD.unpack_from(blob, 0)
+  if f[0] != BLOB_MAGIC:
+    raise ValueError('not a stream blob: bad magic')
+  live = f[16]
+  if not 0 <= live <= 256 or len(blob) < _BLOB_HEAD.size + 16 * live:
+    raise ValueError('not a stream blob: bad live count')
+  ks = [struct.unpack_from('<i', blob, _BLOB_HEAD.size + 16 * r)[0] for r in range(live)]
+  return {'B': f[4], 'bytes': f[13], 'committed': f[14], 'N': f[15], 'live': live, 'slots': f[17], 'K': max(ks, default=0)}
 
 
 def last_error(lib):
@@ -412,6 +440,7 @@ class Decoder:
     self._handle = handle
     self.device = int(device)
     self._last_offsets = None  # offsets of the last decode through this object: last_nbest() sizes its buffers from them
+    self._export_buf = None    # stream_export's landing buffer (grow only)
 
   def close(self):
     if getattr(self, '_handle', None):
@@ -809,6 +838,37 @@ class Decoder:
       raise err
     return {'retired': [retired[u, :counts[u]].copy() for u in range(n_utt)], 'K': k_out,
             'retirable': [retirable[u, :able[u]].copy() for u in range(n_utt)], 'max_clusters': cap}
+
+  def stream_export_bound(self, utt=0):
+    """The capacity stream_export needs (uis_stream_export_bound): host only."""
+    out = ctypes.c_int64(0)
+    self._check(self._lib.uis_stream_export_bound(self._handle, int(utt), ctypes.byref(out)), 'uis_stream_export_bound')
+    return int(out.value)
+
+  def stream_export(self, utt):
+    """One utterance of the open session as bytes (uis_stream_export): the library's blob, canonical -- a function
+    of the utterance's state alone.  Changes nothing.  A refusal is a HipLibraryError with .status
+    (UIS_ERR_CLUSTER_CAP: the utterance has hit the cluster cap; UIS_ERR_INVALID_ARG: its beam is empty)."""
+    if self._export_buf is None or len(self._export_buf) < self.stream_export_bound(utt):
+      self._export_buf = ctypes.create_string_buffer(self.stream_export_bound(utt))
+    n = ctypes.c_int64(0)
+    rc = self._lib.uis_stream_export(self._handle, int(utt), self._export_buf, len(self._export_buf), ctypes.byref(n))
+    if rc != UIS_OK:   # (UIS_ERR_CLUSTER_CAP is a refusal here, not a result with flags)
+      err = HipLibraryError('uis_stream_export failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    return ctypes.string_at(self._export_buf, n.value)
+
+  def stream_import(self, utt, blob):
+    """Put an exported utterance into slot `utt` of the open session, which must have received nothing
+    (uis_stream_import).  A refusal (HipLibraryError with .status) leaves the session as it was."""
+    blob = bytes(blob)
+    rc = self._lib.uis_stream_import(self._handle, int(utt), blob, len(blob))
+    if rc != UIS_OK:
+      err = HipLibraryError('uis_stream_import failed ({}): {}'.format(rc, last_error(self._lib)))
+      err.status = rc
+      raise err
+    self._stream_have[int(utt)] = blob_info(blob)['N']
 
   def stream_max_clusters(self):
     """max_clusters of the open session (what uis_stream_begin made of the option: 0 means 16)."""

@@ -143,13 +143,8 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
   if ((rc = session_enter(h, &stc))) return rc;
   hipStream_t st = h->stream;
   // ---- the prior tables: long enough for whatever the window can hold after this call
-  DevBuf new_blk, new_den;
-  std::vector<double> log_host;
-  int64_t new_len = 0;
-  if (most + ss.cap + 2 > ss.log_len) {
-    new_len = std::max<int64_t>(2 * ss.log_len, most + ss.cap + 2);
-    if ((rc = new_blk.alloc((size_t)new_len * 8)) || (rc = new_den.alloc((size_t)new_len * 8))) return rc;
-  }
+  PriorTableGrowth prior;
+  if ((rc = prior.reserve(h, most + ss.cap + 2))) return rc;
   // ---- scratch: [horizon U], then [committed U][dropped U][rank 0's score U] as one stretch (they come back in one copy)
   ScratchPlan plan;
   const size_t o_hz = plan.take((size_t)U * 4), o_cut = plan.take((size_t)U * 4), o_drop = plan.take((size_t)U * 4, 4),
@@ -158,9 +153,9 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
   if ((rc = h->nb_stable.ensure((size_t)U * 8))) return rc;
   if ((rc = h->nb_off.ensure((size_t)U * 8))) return rc;
   char* base;  // (the pinned landing block: labels, then the three words per utterance)
-  if ((rc = session_buffers(h, plan, ((size_t)F + 3 * (size_t)U) * 4, &base, {&h->nb_labels, &h->nb_stable, &h->nb_off, &new_blk, &new_den})))
+  if ((rc = session_buffers(h, plan, ((size_t)F + 3 * (size_t)U) * 4, &base, {&h->nb_labels, &h->nb_stable, &h->nb_off, &prior.blk, &prior.den})))
     return rc;
-  if (new_len && (rc = upload_log_tables(h->alpha, new_len, log_host, new_blk.p, new_den.p, st))) return rc;
+  if ((rc = prior.upload(h))) return rc;
   if (horizon) HIPCHK(hipMemcpyAsync(base + o_hz, horizon, (size_t)U * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(h->nb_off.p, off.data(), (size_t)U * 8, hipMemcpyHostToDevice, st));
   CommitArgs a{};
@@ -198,15 +193,7 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
     ss.committed[u] += c;
     if (c > 0) ss.win_score[u] = h_score[u];
   }
-  if (new_len) {
-    for (DevBuf& b : ss.allocs)  // the tables the session was opened or last grown with: freed, the launches that read them are over
-      if (b.p == (void*)ss.st.logblk || b.p == (void*)ss.st.logden) b.release();
-    ss.st.logblk = new_blk.as<double>();
-    ss.st.logden = new_den.as<double>();
-    ss.allocs.push_back(std::move(new_blk));
-    ss.allocs.push_back(std::move(new_den));
-    ss.log_len = new_len;
-  }
+  prior.swap(h);
   h->nb_valid = false;
   if (CallTimer::env("UIS_COMMIT_TRACE"))
     fprintf(stderr, "uis_stream_commit: utterances %d window_frames %lld committed %lld prior_table_entries %lld device_ms %.3f call_ms %.3f\n",

@@ -30,6 +30,7 @@
 #endif
 
 #include "uis_poison.h"
+#include "uis_blob.h"
 #include "uis_kernels.hip"
 #include "uis_eval.hip"
 #include "uisrnn_hip.h"
@@ -195,6 +196,7 @@ struct uis_handle : HandleMem {
   DevModel m{};
   std::vector<void*> model_allocs;
   double alpha = 1.0;
+  uint64_t model_hash = 0;  // of the parameters as uis_create received them: the model fingerprint of uis_stream_export's blobs (uis_blob.h)
   int n_cu = 0;  // compute units of the device
   int hid_map_seg = 0, hid_map_seg_p = 0, H_model = 0;  // (round 6) HidMap of this model's hidden axis; rnn_hidden_size as the caller gave it
   // the one-launch decode relies on observed, not promised, placement (workgroup b on XCD b % 8,
@@ -2075,6 +2077,25 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
     }
   }
   h->hid_map_seg = hmap.seg; h->hid_map_seg_p = hmap.seg_p; h->H_model = H;
+  {  // the model fingerprint's hash: every parameter in the descriptor's order, on the host
+    uint64_t fp = 0;
+    auto mix = [&](const void* p, size_t bytes) { fp = uis_blob_hash(p, bytes, fp); };
+    for (int l = 0; l < depth; ++l) {
+      mix(d->gru_weight_ih[l], (size_t)3 * H * (l == 0 ? D : H) * 4);
+      mix(d->gru_weight_hh[l], (size_t)3 * H * H * 4);
+      mix(d->gru_bias_ih[l], (size_t)3 * H * 4);
+      mix(d->gru_bias_hh[l], (size_t)3 * H * 4);
+    }
+    mix(d->linear_mean1_weight, (size_t)H * H * 4);
+    mix(d->linear_mean1_bias, (size_t)H * 4);
+    mix(d->linear_mean2_weight, (size_t)D * H * 4);
+    mix(d->linear_mean2_bias, (size_t)D * 4);
+    mix(d->rnn_init_hidden, (size_t)depth * H * 4);
+    mix(d->sigma2, (size_t)D * 4);
+    const double priors[2] = {d->transition_bias, d->crp_alpha};
+    mix(priors, sizeof(priors));
+    h->model_hash = fp;
+  }
   m.G = 3 * m.Hp;
   m.lp_stay = std::log(1.0 - d->transition_bias);  // np.log(1 - transition_bias), uisrnn.py:416
   m.lp_sw = std::log(d->transition_bias);
@@ -2392,3 +2413,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 
 // ------------------------------------------------------------------ retiring clusters no live hypothesis can name
 #include "uis_retire.hip"
+
+// ------------------------------------------------------------------ exporting / importing one utterance of a session
+#include "uis_migrate.hip"

@@ -257,6 +257,37 @@ struct CallTimer {
   double call_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
 
+// The prior tables logblk / logden of a session that must reach further (uis_stream_commit, uis_stream_import): they
+// are indexed by block counts and their sum, which go on growing with the stream.  reserve() BEFORE any scratch (an
+// allocation that fails leaves the session as it was): longer tables where `entries` exceeds what the session has, at
+// least twice the length; blk / den go into session_buffers' `other` list; upload() after it (upload_log_tables'
+// arithmetic: the common prefix keeps its bits); swap() after the synchronisation: the session is pointed at them and
+// the old ones are freed, the launches that read them are over.
+struct PriorTableGrowth {
+  DevBuf blk, den;
+  std::vector<double> host;
+  int64_t len = 0;  // 0: the session's tables are long enough
+  int reserve(uis_handle* h, int64_t entries) {
+    const uis_handle::Stream& ss = h->stream_state;
+    if (entries <= ss.log_len) return UIS_OK;
+    len = std::max<int64_t>(2 * ss.log_len, entries);
+    if (int rc = blk.alloc((size_t)len * 8)) return rc;
+    return den.alloc((size_t)len * 8);
+  }
+  int upload(uis_handle* h) { return len ? upload_log_tables(h->alpha, len, host, blk.p, den.p, h->stream) : UIS_OK; }
+  void swap(uis_handle* h) {
+    if (!len) return;
+    uis_handle::Stream& ss = h->stream_state;
+    for (DevBuf& b : ss.allocs)  // the tables the session was opened or last grown with
+      if (b.p == (void*)ss.st.logblk || b.p == (void*)ss.st.logden) b.release();
+    ss.st.logblk = blk.as<double>();
+    ss.st.logden = den.as<double>();
+    ss.allocs.push_back(std::move(blk));
+    ss.allocs.push_back(std::move(den));
+    ss.log_len = len;
+  }
+};
+
 // an utterance whose window a commit emptied still has its one hypothesis and its score: what the readouts show of
 // it.  counts: 1; rank 0 of its `stride` values: `first` (null: win_score[u]), the `rest` after it: INFINITY; stable: 0;
 // each where the pointer is set

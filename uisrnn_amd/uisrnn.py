@@ -12,7 +12,9 @@ implementation behind this class: without the HIP library and a gfx950 device
 train on the MI355X with the reference's fit semantics.
 """
 
+import struct
 import threading
+import zlib
 
 import numpy as np
 
@@ -62,6 +64,45 @@ def _stable_ids(gone, n):
       out.append(c)
     c += 1
   return out
+
+
+_STATE_TRAILER = struct.Struct('<4sIqqII')   # magic, version, bytes of the library's blob, frames received, labels, retired ids
+
+
+def _pack_state_trailer(core, final, gone):
+  """What only the Python layer knows of an utterance, behind the library's blob `core`: the committed labels the
+  session kept, the retired ids, the total received; a CRC-32 of it all at the end."""
+  info = _capi.blob_info(core)
+  body = _STATE_TRAILER.pack(b'UISP', 1, len(core), info['committed'] + info['N'], len(final), len(gone))
+  body += np.asarray(final, dtype='<i4').tobytes() + np.asarray(gone, dtype='<i4').tobytes()
+  return body + struct.pack('<I', zlib.crc32(body))
+
+
+def _unpack_state(blob):
+  """bytes of OnlineSession.export_state -> (the library's blob, committed labels, retired ids); ValueError for
+  anything else."""
+  try:
+    blob = bytes(blob)
+    info = _capi.blob_info(blob)
+  except (TypeError, ValueError) as err:
+    raise ValueError('not an exported utterance state: {}'.format(err)) from None
+  n_core = info['bytes']
+  if n_core < 0 or len(blob) < n_core + _STATE_TRAILER.size + 4:
+    raise ValueError('not an exported utterance state: cut short.')
+  magic, version, core_bytes, received, n_final, n_gone = _STATE_TRAILER.unpack_from(blob, n_core)
+  end = n_core + _STATE_TRAILER.size + 4 * (n_final + n_gone)
+  if magic != b'UISP' or version != 1 or core_bytes != n_core or len(blob) != end + 4:
+    raise ValueError('not an exported utterance state: bad trailer.')
+  if struct.unpack_from('<I', blob, end)[0] != zlib.crc32(blob[n_core:end]):
+    raise ValueError('not an exported utterance state: the trailer\'s checksum does not match.')
+  if n_final != info['committed'] or received != info['committed'] + info['N']:
+    raise ValueError('not an exported utterance state: the trailer does not belong to the blob.')
+  at = n_core + _STATE_TRAILER.size
+  final = np.frombuffer(blob, dtype='<i4', count=n_final, offset=at).tolist()
+  gone = np.frombuffer(blob, dtype='<i4', count=n_gone, offset=at + 4 * n_final).tolist()
+  if any(c < 0 for c in final) or any(c < 0 for c in gone) or gone != sorted(set(gone)):
+    raise ValueError('not an exported utterance state: bad ids in the trailer.')
+  return blob[:n_core], final, gone
 
 
 class EmptyBeamError(ValueError, IndexError):
@@ -1145,6 +1186,77 @@ class OnlineSession:
         self._bound[u], self._seen[u] = 0, {}
     return out
 
+  # ---- moving and checkpointing utterances
+
+  def _utterance(self, utterance):
+    if isinstance(utterance, bool) or not isinstance(utterance, (int, np.integer)) or not 0 <= int(utterance) < self._num_utterances:
+      raise ValueError('utterance index {!r} is not in [0, {}).'.format(utterance, self._num_utterances))
+    return int(utterance)
+
+  def export_state(self, utterance):
+    """One live utterance as bytes (uis_stream_export; extension): every hypothesis of its beam, its window and
+    what this session knows on top -- the labels committed so far and the retired ids.  Changes nothing.  The
+    bytes go into import_state of any slot that has received nothing: of this session or of another one (other
+    num_utterances, max_frames, max_clusters, persistent or not), in another process or on another GPU, as long as
+    the model and args.beam_size are the same.  There the stream continues bit for bit as it would have here.
+
+    Raises:
+      ValueError: an index out of range.
+      _capi.HipLibraryError: an utterance that has hit the cluster cap (status UIS_ERR_CLUSTER_CAP) or whose beam
+        a non-finite frame emptied (UIS_ERR_INVALID_ARG): there is nothing to move, restart() is the way back.
+    """
+    u = self._utterance(utterance)
+    blob = self._decoder.stream_export(u)
+    gone = self._gone[u] if self._gone is not None else []
+    return blob + _pack_state_trailer(blob, self._final[u], gone)
+
+  def import_state(self, utterance, blob):
+    """Continue an exported utterance in slot `utterance`, which must have received nothing (uis_stream_import).
+    labels(), commit(), nbest(), restart() and retire() hand out the same ids as the source session did, and
+    restart() returns the whole stream.  All or nothing.
+
+    Raises:
+      ValueError: an index out of range, bytes that are not an exported state.
+      _capi.HipLibraryError: the library's refusals (status UIS_ERR_INVALID_ARG: a damaged blob, another model or
+        beam size, a window longer than max_frames, a slot that has received frames; UIS_ERR_CLUSTER_CAP: a
+        hypothesis with more clusters than this session's max_clusters).  The session is then as it was.
+    """
+    u = self._utterance(utterance)
+    core, final, gone = _unpack_state(blob)
+    self._decoder.stream_import(u, core)
+    self._final[u] = final
+    if gone:
+      if self._gone is None:
+        self._gone = [[] for _ in range(self._num_utterances)]
+      self._gone[u] = gone
+    elif self._gone is not None:
+      self._gone[u] = []
+    if self._bound is not None:   # (as after a query: K of the blob; the last committed appearances from the labels)
+      self._bound[u] = _capi.blob_info(core)['K']
+      self._seen[u] = {c: t for t, c in enumerate(final)}
+
+  def snapshot(self):
+    """export_state of every utterance: a list with bytes per utterance, None where an utterance cannot be
+    exported (cluster cap, emptied beam).  With restore(): a checkpoint of the whole session."""
+    out = []
+    for u in range(self._num_utterances):
+      try:
+        out.append(self.export_state(u))
+      except _capi.HipLibraryError as err:
+        if getattr(err, 'status', None) not in (_capi.UIS_ERR_CLUSTER_CAP, _capi.UIS_ERR_INVALID_ARG):
+          raise
+        out.append(None)
+    return out
+
+  def restore(self, states):
+    """import_state of every entry of a snapshot() into the slot of the same index; None entries are left as
+    they are (fresh, in a session that has just been opened)."""
+    if not isinstance(states, (list, tuple)) or len(states) != self._num_utterances:
+      raise ValueError('one state (or None) per utterance ({} utterances).'.format(self._num_utterances))
+    for u, state in enumerate(states):
+      if state is not None:
+        self.import_state(u, state)
+
   def labels(self):
     per_utt, _, overflow, _ = self._decoder.stream_labels()
     if overflow.any():
@@ -1271,6 +1383,22 @@ class StreamPool:
     per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
     per_slot[slot] = clusters
     return self._session.retire(clusters=per_slot)[slot]
+
+  def export(self, key):
+    """OnlineSession.export_state for the stream's slot.  The key stays open."""
+    return self._session.export_state(self._slot[key])
+
+  def adopt(self, key, blob):
+    """Take a free slot, like open, and continue an exported stream in it (OnlineSession.import_state).  Returns
+    the slot's index; a refused blob leaves the pool as it was."""
+    slot = self.open(key)
+    try:
+      self._session.import_state(slot, blob)
+    except Exception:
+      del self._slot[key]
+      self._free.append(slot)
+      raise
+    return slot
 
   def finish(self, key):
     """End the stream: (labels, score) of the whole of it (labels None where OnlineSession.restart says so);
