@@ -312,6 +312,27 @@ int32_t uis_last_decode_info(uis_handle* h, int32_t* overflow_out, float* beam_s
 int32_t uis_last_decode_shape(uis_handle* h, int32_t* n_utt_out, int32_t* beam_size_out);
 
 /*
+ * Which kernel instantiation ran: the entry of the library's kernel tables behind this handle's last uis_decode*
+ * call, or behind the last launch of a uis_stream_push of the open session (a UIS_FLAG_PERSISTENT session: the
+ * launch that stays, however many pushes it has served), as the table lookup itself returned it:
+ *   out[0] family  : UIS_DK_*
+ *   out[1], out[2] : the instantiation's hidden size and observation dim (the model's, padded: 128 / 256 / 512)
+ *   out[3] variant : the compile-time shape class (0 generic, 1 beam 10 / cap 16, 2 beam 20 / cap 11, 3 beam 50 /
+ *                    cap 12 / look_ahead 2); for UIS_DK_RS its kind (bits 16..23 of uis_stats.decode_kernel); for
+ *                    UIS_DK_DEEP 1 = the look_ahead >= 2 kernel
+ *   out[4] persist : 1 = the kernel a UIS_FLAG_PERSISTENT session keeps on the device
+ * UIS_DK_SMALL and UIS_DK_STEPWISE have no table: their family with the model's padded sizes, variant 0.  All zero
+ * after a decode that was refused before it chose a kernel.
+ */
+int32_t uis_last_decode_instantiation(uis_handle* h, int32_t out[5]);
+
+/*
+ * The kernel tables themselves, a row of five int32 (as above) per instantiation: fills at most `cap` rows of
+ * `rows` (may be NULL) and returns the number of rows there are.  Needs no device.
+ */
+int32_t uis_decode_kernel_table(int32_t* rows, int32_t cap);
+
+/*
  * After a decode with UIS_FLAG_DEBUG_SCORES: the candidate scores of every window (look_ahead 1: of
  * every decode step),
  *   scores_out[(((w * n_utt + u) * beam_size + b) * C + c_1) * C ... + c_L],   C = max_clusters + 1

@@ -1089,8 +1089,9 @@ def _decode_and_check(dec, params, seqs, beam, cap, oracle_lib, want_kernel, fla
 
 
 def test_replicated_select_shape_classes(oracle_lib):
-  """Every instantiation of k_decode_rs (uis_select_rs.hip), named by the library itself
-  (uis_stats.decode_kernel), against the oracle bit for bit: the base class and the class with the
+  """Two of k_decode_rs's seven instantiations (uis_select_rs.hip; all of them: tests/test_gpu_instantiations.py), both
+  at hidden size 512 / observation dim 256, named by the library itself (uis_stats.decode_kernel), against the oracle
+  bit for bit: the base class and the class with the
   benchmark's beam / cluster cap as compile-time constants -- ragged batches, with and without row
   de-duplication, and with the one-launch decode REQUIRED (no silent fallback).  Beyond its limits
   (beam_size 17 .. 32, observation_dim 512, 9 .. 16 utterances per XCD) the owner-select kernel

@@ -314,6 +314,10 @@ def load_library(path=None):
   lib.uis_last_decode_info.argtypes = [ctypes.c_void_p, i32p, _fp]
   lib.uis_last_decode_shape.restype = i32
   lib.uis_last_decode_shape.argtypes = [ctypes.c_void_p, i32p, i32p]
+  lib.uis_last_decode_instantiation.restype = i32
+  lib.uis_last_decode_instantiation.argtypes = [ctypes.c_void_p, i32p]
+  lib.uis_decode_kernel_table.restype = i32
+  lib.uis_decode_kernel_table.argtypes = [i32p, i32]
   lib.uis_debug_scores.restype = i32
   lib.uis_debug_scores.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int64]
   lib.uis_model_constants.restype = i32
@@ -388,7 +392,7 @@ def load_library(path=None):
 EXPORTED_SYMBOLS = (
     'uis_abi_version', 'uis_numerics_version', 'uis_build_flags', 'uis_device_count', 'uis_create', 'uis_destroy',
     'uis_decode', 'uis_decode_f64', 'uis_decode_device', 'uis_last_decode_info', 'uis_last_decode_shape',
-    'uis_debug_scores',
+    'uis_last_decode_instantiation', 'uis_decode_kernel_table', 'uis_debug_scores',
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
@@ -415,6 +419,16 @@ def blob_info(blob):
     raise ValueError('not a stream blob: bad live count')
   ks = [struct.unpack_from('<i', blob, _BLOB_HEAD.size + 16 * r)[0] for r in range(live)]
   return {'B': f[4], 'bytes': f[13], 'committed': f[14], 'N': f[15], 'live': live, 'slots': f[17], 'K': max(ks, default=0)}
+
+
+def decode_kernel_table(lib=None):
+  """Every instantiation of the one-launch decode kernels, from the library's own tables (no device needed): a list of
+  (family, Hp, Dp, variant, persist) -- family a name of DECODE_KERNELS."""
+  lib = lib or load_library()
+  n = lib.uis_decode_kernel_table(None, 0)
+  rows = np.zeros((n, 5), dtype=np.int32)
+  lib.uis_decode_kernel_table(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n)
+  return [(DECODE_KERNELS.get(int(r[0]), 'unknown'),) + tuple(int(v) for v in r[1:]) for r in rows]
 
 
 def last_error(lib):
@@ -596,6 +610,13 @@ class Decoder:
         losses.ctypes.data_as(_fp) if want_frame_losses else None)
     self._check(rc, 'uis_score_labels')
     return (scores, losses) if want_frame_losses else scores
+
+  def last_instantiation(self):
+    """(family, Hp, Dp, variant, persist) of the kernel-table entry behind the last decode, or behind the last
+    launch of a stream_push: uis_last_decode_instantiation, family as a name of DECODE_KERNELS."""
+    out = (ctypes.c_int32 * 5)()
+    self._check(self._lib.uis_last_decode_instantiation(self._handle, out), 'uis_last_decode_instantiation')
+    return (DECODE_KERNELS.get(int(out[0]), 'unknown'),) + tuple(int(v) for v in out[1:])
 
   def last_overflow(self, n_utt=None):
     """Per-utterance flags of the last decode: bit 0 = a survivor hit the cluster cap, bit 1 = an

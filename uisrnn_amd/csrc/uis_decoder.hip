@@ -187,6 +187,12 @@ struct HandleMem {
   DevBuf ps_conf, ps_change, ps_weights, ps_counts, ps_off, ps_part, ps_labels, ps_scores;
 };
 
+// Which kernel-table entry a lookup returned (find_kernel fills it from the entry it found): the record behind
+// uis_last_decode_instantiation.  k_decode_small and the launch-per-step path have no table: their family, variant 0.
+struct KernelPick {
+  int32_t family = 0 /* UIS_DK_* */, Hp = 0, Dp = 0, variant = 0, persist = 0 /* 1: from the persist table */;
+};
+
 }  // namespace
 
 struct uis_handle : HandleMem {
@@ -266,6 +272,7 @@ struct uis_handle : HandleMem {
   std::vector<GraphCache> gcache;
   // info of the last decode
   int last_U = 0, last_B = 0;
+  KernelPick last_pick;  // the kernel-table entry behind the last decode / the last launch of a session push
   std::vector<int64_t> io_offsets;  // offsets of the last uis_decode (its labels are still in io_labels)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
@@ -1030,10 +1037,19 @@ typedef void (*RsKernel)(RsArgs);  // k_decode_rs takes its own compact argument
 template <typename Fn> struct KernelEntryOf { int Hp, Dp, variant; Fn fn; };
 typedef KernelEntryOf<DecodeKernel> KernelEntry;
 
+void kernel_table_tag(const void* table, KernelPick* pick);  // (below the tables)
+
+// `pick`: the entry found, as the table itself states it (left alone where there is none).
 template <typename Fn, size_t N>
-Fn find_kernel(const KernelEntryOf<Fn> (&table)[N], int Hp, int Dp, int variant) {
+Fn find_kernel(const KernelEntryOf<Fn> (&table)[N], int Hp, int Dp, int variant, KernelPick* pick = nullptr) {
   for (const KernelEntryOf<Fn>& e : table)
-    if (e.Hp == Hp && e.Dp == Dp && e.variant == variant) return e.fn;
+    if (e.Hp == Hp && e.Dp == Dp && e.variant == variant) {
+      if (pick) {
+        kernel_table_tag(table, pick);
+        pick->Hp = e.Hp; pick->Dp = e.Dp; pick->variant = e.variant;
+      }
+      return e.fn;
+    }
   return nullptr;
 }
 
@@ -1082,13 +1098,28 @@ const KernelEntry persist[] = {
     {256, 256, CLS_NONE, &k_decode_resident<256, 256, true>}};
 }  // namespace kernels
 
-DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L) {
+// Every table with the family it reports (UIS_DK_*) and whether it is the persist table: the one list behind a lookup's
+// record (kernel_table_tag) and uis_decode_kernel_table.
+template <typename F>
+void for_each_kernel_table(F&& f) {
+  f(kernels::rs, UIS_DK_RS, 0); f(kernels::resident, UIS_DK_RESIDENT, 0); f(kernels::big, UIS_DK_BIG, 0);
+  f(kernels::big_ws, UIS_DK_BIG_WS, 0); f(kernels::window, UIS_DK_WINDOW, 0); f(kernels::deep, UIS_DK_DEEP, 0);
+  f(kernels::persist, UIS_DK_RESIDENT, 1);
+}
+
+void kernel_table_tag(const void* table, KernelPick* pick) {
+  for_each_kernel_table([&](const auto& t, int family, int persist) {
+    if (static_cast<const void*>(t) == table) { pick->family = family; pick->persist = persist; }
+  });
+}
+
+DecodeKernel cluster_kernel(const DecodePlan& p, const DevModel& m, int L, KernelPick* pick) {
   switch (p.path) {
-    case DecodePath::BIG_WS: return find_kernel(kernels::big_ws, m.Hp, m.Dp, p.cls);
-    case DecodePath::RESIDENT: return find_kernel(kernels::resident, m.Hp, m.Dp, p.cls);
-    case DecodePath::BIG: return find_kernel(kernels::big, m.Hp, m.Dp, p.cls);
-    case DecodePath::WINDOW: return find_kernel(kernels::window, m.Hp, m.Dp, p.cls);
-    case DecodePath::DEEP: return find_kernel(kernels::deep, m.Hp, m.Dp, L > 1 ? 1 : 0);
+    case DecodePath::BIG_WS: return find_kernel(kernels::big_ws, m.Hp, m.Dp, p.cls, pick);
+    case DecodePath::RESIDENT: return find_kernel(kernels::resident, m.Hp, m.Dp, p.cls, pick);
+    case DecodePath::BIG: return find_kernel(kernels::big, m.Hp, m.Dp, p.cls, pick);
+    case DecodePath::WINDOW: return find_kernel(kernels::window, m.Hp, m.Dp, p.cls, pick);
+    case DecodePath::DEEP: return find_kernel(kernels::deep, m.Hp, m.Dp, L > 1 ? 1 : 0, pick);
     default: return nullptr;
   }
 }
@@ -1319,6 +1350,7 @@ int derive_shape(DecodeCall& c) {
   h->last_overflow.clear(); h->last_beam_scores.clear();
   h->nb_valid = false;  // (... nor uis_last_decode_nbest its hypotheses)
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
+  h->last_pick = KernelPick{};
   const DevModel& m = h->m;
   const int B = opts->beam_size, L = opts->look_ahead, tau = opts->test_iteration;
   int Kmax = opts->max_clusters > 0 ? opts->max_clusters : 16;
@@ -1453,8 +1485,11 @@ int plan_and_place(DecodeCall& c) {
     if (rc != WS_REPLAN) return rc;
     plan_knobs.no_rs = true;
   }
-  c.cluster_kern = c.plan.clustered() && !c.rs ? cluster_kernel(c.plan, m, s.L) : nullptr;
-  c.rs_kern = c.rs ? find_kernel(kernels::rs, m.Hp, m.Dp, c.plan.rs_kind) : nullptr;
+  KernelPick pick;
+  pick.family = c.plan.decode_kernel & 0xff; pick.Hp = m.Hp; pick.Dp = m.Dp;  // (what stays without a table lookup)
+  c.cluster_kern = c.plan.clustered() && !c.rs ? cluster_kernel(c.plan, m, s.L, &pick) : nullptr;
+  c.rs_kern = c.rs ? find_kernel(kernels::rs, m.Hp, m.Dp, c.plan.rs_kind, &pick) : nullptr;
+  h->last_pick = pick;
   return UIS_OK;
 }
 
@@ -2280,6 +2315,27 @@ UIS_EXPORT int32_t uis_last_decode_info(uis_handle* h, int32_t* overflow_out, fl
   if (overflow_out && h->last_U) memcpy(overflow_out, h->last_overflow.data(), (size_t)h->last_U * 4);
   if (beam_scores_out && h->last_U) memcpy(beam_scores_out, h->last_beam_scores.data(), (size_t)h->last_U * h->last_B * 4);
   return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_last_decode_instantiation(uis_handle* h, int32_t out[5]) {
+  if (!h || !out) return fail(UIS_ERR_INVALID_ARG, "null argument");
+  const KernelPick& p = h->last_pick;
+  out[0] = p.family; out[1] = p.Hp; out[2] = p.Dp; out[3] = p.variant; out[4] = p.persist;
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_decode_kernel_table(int32_t* rows, int32_t cap) {
+  int32_t n = 0;
+  for_each_kernel_table([&](const auto& table, int family, int persist) {
+    for (const auto& e : table) {
+      if (rows && n < cap) {
+        int32_t* r = rows + (size_t)5 * n;
+        r[0] = family; r[1] = e.Hp; r[2] = e.Dp; r[3] = e.variant; r[4] = persist;
+      }
+      ++n;
+    }
+  });
+  return n;
 }
 
 UIS_EXPORT int32_t uis_debug_scores(uis_handle* h, float* scores_out, int64_t capacity) {

@@ -114,7 +114,7 @@ int pm_launch(uis_handle* h) {
   HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
   Launcher lch{h, h->stream, false};
   h->inlaunch_failed = false;
-  if (int rc = launch_cluster_kernel(lch, find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+  if (int rc = launch_cluster_kernel(lch, find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE, &h->last_pick), h->n_cu, st.ncl,
                                      one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st))
     return rc;
   ss.pm_running = true;
@@ -618,7 +618,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     // callers that own the device, and used only after the session's first push went through the
     // cooperative path.
     static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
-    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE), h->n_cu, st.ncl,
+    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE, &h->last_pick), h->n_cu, st.ncl,
                                one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st,
                                !(ss.coop_checked && plain_ok));
     if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
@@ -630,7 +630,11 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     } else if (rc) return rc;
     else { ran_resident = true; ss.coop_checked = true; }
   }
-  if (stepwise && (rc = enqueue_steps(h, lch, st, lds.total, (int)max_new))) return rc;
+  if (stepwise) {
+    h->last_pick = KernelPick{};
+    h->last_pick.family = UIS_DK_STEPWISE; h->last_pick.Hp = m.Hp; h->last_pick.Dp = m.Dp;
+    if ((rc = enqueue_steps(h, lch, st, lds.total, (int)max_new))) return rc;
+  }
   uint32_t abort_word = 0;
   if (ran_resident) HIPCHK(hipMemcpyAsync(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));  // the staging block and the caller's frames may be reused
