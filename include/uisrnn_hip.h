@@ -461,6 +461,32 @@ int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offs
                          const int32_t* labels, float* scores_out, float* frame_losses_out);
 
 /*
+ * Every speaker's per-frame loss along a GIVEN labeling: for frame t of an utterance, the row _update_beam_state
+ * (uisrnn/uisrnn.py:388-453) would charge for assigning the frame to each open cluster, or to a new one, given the
+ * labeled history before t -- the _calculate_score row along the fixed trace, of which uis_score_labels'
+ * frame_losses_out is the chosen column.  With K(t) = the clusters opened by the frames before t:
+ *   losses_out[t * width + k], k <  K(t) : step loss of (weighted MSE of x_t against cluster k's running mean as it
+ *                                          stands before frame t, prior lp_stay if k is the previous frame's label,
+ *                                          else (lp_sw + log blk_k) - log(sum blk + alpha))
+ *                              k == K(t) : the new-speaker candidate (MSE against m0, lp_new - log(sum blk + alpha))
+ *                              k >  K(t) : +inf (the padding of _calculate_score and uis_debug_scores)
+ * and every row from the first label past the allowed range on is all +inf (the invalid trace).  Priors in float64 with
+ * the decode's expressions and log tables, the MSE in the order of include/uis_numerics.h, so that
+ *   1. losses_out[t * width + labels[t]] equals uis_score_labels' frame_losses_out[t] bit for bit, and
+ *   2. for the labels of a beam_size 1, look_ahead 1, test_iteration 1 decode, float32(cum_{t-1} + row t) equals that
+ *      decode's uis_debug_scores row of step t bit for bit (cum_t = float32(cum_{t-1} + losses_out[t][labels[t]])).
+ *   frames, offsets, labels : as uis_score_labels
+ *   width      : columns per row, at least (clusters of the utterance's valid trace) + 1 for every utterance and at
+ *                least 1 -- otherwise UIS_ERR_INVALID_ARG, before any device work
+ *   losses_out : host float32 [offsets[n_utt]][width]
+ *   scores_out : host float32 [n_utt] or NULL: what uis_score_labels gives, bit for bit
+ * Refusals and side effects as uis_score_labels: refused while a streaming session is open, leaves the last decode's
+ * results alone, UIS_ERR_OOM: score the list in parts.
+ */
+int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                           const int32_t* labels, int32_t width, float* losses_out, float* scores_out);
+
+/*
  * N-best readout: the labels of EVERY hypothesis of the final beam, not only of rank 0.  A decode
  * leaves the back-pointers of all beam_size ranks and the final beam's scores on the device; these
  * calls only read them (no decode kernel is involved).

@@ -16,5 +16,6 @@ UISRNN = _uisrnn.UISRNN
 parallel_predict = _uisrnn.parallel_predict
 OnlineSession = _uisrnn.OnlineSession  # extension: streaming decode
 StreamPool = _uisrnn.StreamPool  # extension: an open-ended set of streams over one session's slots
+speaker_posteriors = _uisrnn.speaker_posteriors  # extension: soft assignments from UISRNN.score_speakers' rows
 EmptyBeamError = _uisrnn.EmptyBeamError
 LookAheadWindowError = _uisrnn.LookAheadWindowError

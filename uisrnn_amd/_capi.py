@@ -362,6 +362,8 @@ def load_library(path=None):
   lib.uis_eval_accuracy_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, i64p, i32, i64p]
   lib.uis_score_labels.restype = i32
   lib.uis_score_labels.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, _fp, _fp]
+  lib.uis_score_speakers.restype = i32
+  lib.uis_score_speakers.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, i32, _fp, _fp]
   lib.uis_eval_last_decode.restype = i32
   lib.uis_eval_last_decode.argtypes = [ctypes.c_void_p, i32p, i32, i64p]
   lib.uis_host_alloc.restype = i32
@@ -396,7 +398,7 @@ EXPORTED_SYMBOLS = (
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
-    'uis_eval_last_decode', 'uis_score_labels', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
@@ -610,6 +612,43 @@ class Decoder:
         losses.ctypes.data_as(_fp) if want_frame_losses else None)
     self._check(rc, 'uis_score_labels')
     return (scores, losses) if want_frame_losses else scores
+
+  def score_speakers(self, frames, offsets, labels, width, losses_out=None):
+    """Every speaker's per-frame loss along given labelings (uis_score_speakers).
+
+    Args:
+      frames, offsets, labels: as score_labels.
+      width: columns per row: at least the largest cluster count of the utterances + 1.
+      losses_out: a C-contiguous float32 [sum N, width] array to fill instead of a new one (pinned memory, say: at a
+        million frames the copy of the rows into pageable memory is the larger part of what the call adds).
+    Returns:
+      (float32 scores [U] -- score_labels' bits --, float32 losses [sum N, width]): losses[t, k] is the step loss of
+      assigning frame t to its utterance's cluster k given the labels before t, column K(t) the new-speaker candidate,
+      +inf past it and everywhere after an invalid label.
+    """
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    n_utt = offsets.shape[0] - 1
+    total = int(offsets[-1])
+    if frames.ndim != 2 or frames.shape[0] != total:
+      raise ValueError('frames must be [offsets[-1], D]')
+    if total and frames.shape[1] != self.observation_dim:
+      raise ValueError('frames do not match observation_dim')
+    if labels.shape != (total,):
+      raise ValueError('labels must be [offsets[-1]]')
+    width = int(width)
+    scores = np.empty(n_utt, dtype=np.float32)
+    losses = np.empty((total, max(width, 0)), dtype=np.float32) if losses_out is None else losses_out
+    if losses.dtype != np.float32 or losses.shape != (total, max(width, 0)) or not losses.flags['C_CONTIGUOUS']:
+      raise ValueError('losses_out must be a C-contiguous float32 [offsets[-1], width] array')
+    rc = self._lib.uis_score_speakers(
+        self._handle, frames.ctypes.data_as(_fp),
+        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
+        labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), width, losses.ctypes.data_as(_fp),
+        scores.ctypes.data_as(_fp))
+    self._check(rc, 'uis_score_speakers')
+    return scores, losses
 
   def last_instantiation(self):
     """(family, Hp, Dp, variant, persist) of the kernel-table entry behind the last decode, or behind the last

@@ -178,6 +178,9 @@ struct HandleMem {
   HostBuf h_out;   // pinned landing block of uis_decode_f64's labels and scores
   DevBuf ev_a, ev_b, ev_off, ev_out;  // uis_eval_* staging
   DevBuf sc_x, sc_xpad, sc_gi0, sc_mse0, sc_loss, sc_prior, sc_hid, sc_a1, sc_mean, sc_gi_up, sc_rows, sc_chains, sc_utt, sc_out;  // uis_score_labels (its own: the last decode's buffers stay as they are)
+  // uis_score_speakers' own: labels + each frame's row, logblk + logden, the candidate table [F][width] {mean row, block
+  // count}, the frame table [F] {K, sum, last}, the rows [F][width]
+  DevBuf sc_spk_in, sc_spk_log, sc_spk_cand, sc_spk_frame, sc_spk_loss;
   // the scratch block of one uis_stream_prime / _commit / _restart / _retire call (session_buffers in uis_stream.hip;
   // every such call synchronises before it returns, so no two are ever live; prime's forced run uses the sc_* above)
   DevBuf sc_session;

@@ -20,6 +20,12 @@
 // last row too, and each chain's final hidden states and running mean are what a session is primed with.  The rows a
 // scoring call computes and the kernels that compute them are the same in both modes.
 //
+// uis_score_speakers (score_run's `spk`) runs the chains to their ends as PRIME mode does and then reads sc_mean once per
+// (frame, open cluster) instead of once per frame: the whole _calculate_score row along the fixed trace, not only the
+// chosen column.  Which mean row a cluster holds at a frame, its block count, and each frame's K / sum(block_counts) /
+// last label are formed on the device from the labels (k_speakers_tables); the candidates are scored by
+// k_score_speakers.  Nothing the other two modes launch changes.
+//
 // #included by uis_decoder.hip after the handle, Launcher and the decode kernels.
 
 namespace {
@@ -226,6 +232,101 @@ __global__ __launch_bounds__(64) void k_score_sum(const int64_t* __restrict__ of
   if (lane == 0) scores[u] = s;
 }
 
+// frame_row[t] = the frame-row of frame t: row_frame inverted (frames past an invalid label have no row and keep
+// whatever the buffer held: nothing reads them).
+__global__ __launch_bounds__(256) void k_speakers_frame_rows(long Fv, const int32_t* __restrict__ row_frame,
+                                                             int32_t* __restrict__ frame_row) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r < Fv) frame_row[row_frame[r]] = (int32_t)r;
+}
+
+// uis_score_speakers' candidate tables, from the labels: thread (utterance u, cluster k) walks u's valid frames once and
+// leaves, for every frame t, cand[t][k] = {the row of sc_mean that holds cluster k's running mean before frame t (-1: not
+// open yet), its block count}; thread k = 0 also leaves frame[t] = {K(t), sum(block_counts), last label, 0}, K = -1 from
+// the first label past the allowed range on (nvalid[u]: the invalid trace).  Labels and rows are staged 256 frames at a
+// time and read 8 frames ahead of the walk.
+__global__ __launch_bounds__(64) void k_speakers_tables(const int64_t* __restrict__ off, const int32_t* __restrict__ nvalid,
+                                                        const int32_t* __restrict__ labels, const int32_t* __restrict__ frame_row,
+                                                        int width, int2* __restrict__ cand, int4* __restrict__ frame) {
+  __shared__ int32_t s_lab[256], s_row[256];
+  constexpr int AHEAD = 8;
+  const int u = blockIdx.x, k = blockIdx.y * 64 + threadIdx.x;
+  const long f0 = off[u], n = off[u + 1] - f0, nv = nvalid[u];
+  int row = -1, blk = 0, K = 0, sum = 0, last = -1;
+  for (long c0 = 0; c0 < n; c0 += 256) {
+    const int cnt = n - c0 < 256 ? (int)(n - c0) : 256;
+    __syncthreads();
+    for (int j = threadIdx.x; j < cnt; j += 64) {
+      s_lab[j] = labels[f0 + c0 + j];
+      s_row[j] = frame_row[f0 + c0 + j];
+    }
+    __syncthreads();
+    for (int j0 = 0; j0 < cnt; j0 += AHEAD) {
+      int lab[AHEAD], rw[AHEAD];
+#pragma unroll
+      for (int e = 0; e < AHEAD; ++e) {
+        const int j = j0 + e < cnt ? j0 + e : cnt - 1;
+        lab[e] = s_lab[j];
+        rw[e] = s_row[j];
+      }
+#pragma unroll
+      for (int e = 0; e < AHEAD; ++e) {
+        if (j0 + e >= cnt) break;
+        const long t = f0 + c0 + j0 + e;
+        if (c0 + j0 + e >= nv) {
+          if (k == 0) frame[t] = make_int4(-1, 0, -1, 0);
+          continue;
+        }
+        if (k < width) cand[(size_t)t * width + k] = make_int2(row, blk);
+        if (k == 0) frame[t] = make_int4(K, sum, last, 0);
+        const int c = lab[e];
+        if (c == K) { ++K; ++sum; if (c == k) blk = 1; }
+        else if (c != last) { ++sum; if (c == k) ++blk; }
+        if (c == k) row = rw[e];
+        last = c;
+      }
+    }
+  }
+}
+
+// out[t][k], k < width: the step loss of assigning frame t to cluster k given the labeled history before t -- the
+// _calculate_score row along the trace.  k < K(t): the weighted MSE of x_t against the cluster's running mean, prior
+// lp_stay for the last label's cluster, else (lp_sw + logblk[blk]) - logden[sum]; k = K(t): the new-speaker candidate
+// (mse0, lp_new - logden[sum]); k > K(t), and every k past an invalid label: +inf.  The decode's float64 expressions, on
+// the uploaded host tables.  One workgroup per frame: x_t and the weights staged once, a wave per candidate.
+__global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, const float* __restrict__ x,
+                                                        const float* __restrict__ mse0, const float* __restrict__ mean,
+                                                        const int2* __restrict__ cand, const int4* __restrict__ frame,
+                                                        const double* __restrict__ logblk, const double* __restrict__ logden,
+                                                        float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  f32x4* swgt4 = reinterpret_cast<f32x4*>(smem_raw);
+  f32x4* sx4 = swgt4 + m.Dp / 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t t = blockIdx.x;
+  const int4 f = frame[t];  // {K, sum, last}
+  if (f.x > 0) {            // (no open cluster: no MSE to form)
+    const f32x4* xt = reinterpret_cast<const f32x4*>(x + t * m.Dp);
+    const f32x4* wg = reinterpret_cast<const f32x4*>(m.wgt);
+    for (int i = threadIdx.x; i < m.Dp / 4; i += 256) { swgt4[i] = wg[i]; sx4[i] = xt[i]; }
+  }
+  __syncthreads();
+  const float* swgt = reinterpret_cast<const float*>(swgt4);
+  const float* sx = reinterpret_cast<const float*>(sx4);
+  for (int k = wave; k < width; k += 4) {
+    float v = INFINITY;
+    if (k < f.x) {
+      const int2 c = cand[t * width + k];
+      const float mse = wave_weighted_mse(mean + (size_t)c.x * m.Dp, sx, swgt, m.Dp, m.D, lane);
+      const double prior = k == f.z ? m.lp_stay : (m.lp_sw + logblk[c.y]) - logden[f.y];
+      v = uis_step_loss(mse, prior);
+    } else if (k == f.x) {
+      v = uis_step_loss(mse0[t], m.lp_new - logden[f.y]);
+    }
+    if (lane == 0) out[t * width + k] = v;
+  }
+}
+
 static bool score_timing_env() {  // UIS_SCORE_TIMING=1: one line per call on stderr (schedule / device / total ms)
   static const bool v = getenv("UIS_SCORE_TIMING") != nullptr && atoi(getenv("UIS_SCORE_TIMING")) != 0;
   return v;
@@ -247,6 +348,7 @@ struct ScoreSchedule {
   std::vector<int32_t> chain_blk;   // [chains] block count of the cluster
   std::vector<int32_t> utt_last;    // [U] last label (-1: no frame)
   std::vector<int32_t> utt_sum;     // [U] sum(block_counts)
+  std::vector<double> logblk, logden;  // the decode's tables (upload_log_tables, uis_workspace.hip), as far as this call reaches
 };
 
 void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int U, const int32_t* labels, ScoreSchedule& s) {
@@ -254,7 +356,10 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
   int64_t maxN = 0;
   for (int u = 0; u < U; ++u) maxN = std::max<int64_t>(maxN, offsets[u + 1] - offsets[u]);
   // the decode's tables (upload_log_tables, uis_workspace.hip)
-  std::vector<double> logblk(maxN + 2), logden(maxN + 2);
+  std::vector<double>& logblk = s.logblk;
+  std::vector<double>& logden = s.logden;
+  logblk.resize(maxN + 2);
+  logden.resize(maxN + 2);
   for (int64_t n = 0; n < maxN + 2; ++n) {
     logblk[n] = n > 0 ? std::log((double)n) : 0.0;
     logden[n] = std::log((double)n + alpha);
@@ -326,19 +431,28 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
 
 // `keep` non-null: PRIME mode -- every chain runs to its end (see the head of this file) and the schedule is left in
 // *keep; the buffers (sc_hid, sc_mean, sc_out, sc_utt's offsets) stay as they are until the handle's next scoring call.
+// `spk` non-null: uis_score_speakers -- every chain runs to its end as in PRIME mode (a cluster's final mean is what the
+// frames after its last one are scored against), then the candidate tables and the rows; spk->losses_out is
+// [F][spk->width], the host has checked the width.
+struct ScoreSpeakers {
+  int32_t width;
+  float* losses_out;
+};
+
 int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_t U, const int32_t* labels, float* scores_out,
-              float* frame_losses_out, ScoreSchedule* keep = nullptr) {
+              float* frame_losses_out, ScoreSchedule* keep = nullptr, const ScoreSpeakers* spk = nullptr) {
   const DevModel& m = h->m;
   const int64_t F = offsets[U];
   const auto t_begin = std::chrono::steady_clock::now();
-  const bool prime = keep != nullptr;
+  const bool prime = keep != nullptr || spk != nullptr;  // (the recurrence bound, the scan's tail and the valid last row)
   ScoreSchedule s_own;
-  ScoreSchedule& s = prime ? *keep : s_own;
+  ScoreSchedule& s = keep ? *keep : s_own;
   score_schedule(m, h->alpha, offsets, U, labels, s);
   const auto t_sched = std::chrono::steady_clock::now();
   const int64_t Fv = s.Fv;
   const int P = (int)s.fbase.size(), nch = (int)s.len.size();
   const int maxn = prime ? (P > 0 ? s.nfr[0] : 0) : (P > 1 ? s.nfr[1] : 0);  // the most chains one recurrence launch runs
+  const size_t W = spk ? (size_t)spk->width : 0, nlog = s.logblk.size();
   HIPCHK(hipSetDevice(h->device));
   int rc;
   auto need = [](int64_t n, size_t each) { return (size_t)std::max<int64_t>(n, 1) * each; };
@@ -351,11 +465,16 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
       (rc = h->sc_utt.ensure(need(U + 1, 8) + need(U, 4))) || (rc = h->sc_out.ensure(need(U, 4))))
     return rc;
   if (m.D != m.Dp && (rc = h->sc_xpad.ensure(need(F, (size_t)m.Dp * 4)))) return rc;
+  if (spk && ((rc = h->sc_spk_in.ensure(need(F, 8))) || (rc = h->sc_spk_log.ensure(2 * nlog * 8)) ||
+              (rc = h->sc_spk_cand.ensure(need(F, W * 8))) || (rc = h->sc_spk_frame.ensure(need(F, 16))) ||
+              (rc = h->sc_spk_loss.ensure(need(F, W * 4)))))
+    return rc;
   hipStream_t st = h->stream;
   {  // UIS_POISON_WORKSPACE: every sc_* buffer, ahead of the tables and the frames on the same stream
     const UisPoison poison = UisPoison::from_env();
     for (DevBuf* b : {&h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0, &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean,
-                      &h->sc_gi_up, &h->sc_rows, &h->sc_chains, &h->sc_utt, &h->sc_out})
+                      &h->sc_gi_up, &h->sc_rows, &h->sc_chains, &h->sc_utt, &h->sc_out, &h->sc_spk_in, &h->sc_spk_log,
+                      &h->sc_spk_cand, &h->sc_spk_frame, &h->sc_spk_loss})
       HIPCHK(poison.device(b->p, b->cap, st));
   }
   int32_t* d_row_frame = h->sc_rows.as<int32_t>();
@@ -377,6 +496,17 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
   }
   HIPCHK(hipMemcpyAsync(d_off, offsets, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_nvalid, s.nvalid.data(), (size_t)U * 4, hipMemcpyHostToDevice, st));
+  int32_t *d_labels = nullptr, *d_frame_row = nullptr;
+  double *d_logblk = nullptr, *d_logden = nullptr;
+  if (spk && F > 0) {  // the labels and the prior tables (host std::log, as the decode's) travel; each frame's row is formed there
+    d_labels = h->sc_spk_in.as<int32_t>();
+    d_frame_row = d_labels + F;
+    d_logblk = h->sc_spk_log.as<double>();
+    d_logden = d_logblk + nlog;
+    HIPCHK(hipMemcpyAsync(d_labels, labels, (size_t)F * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_logblk, s.logblk.data(), nlog * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_logden, s.logden.data(), nlog * 8, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipEventRecord(h->ev_begin, st));
   Launcher lch{h, st, false};
   const float* d_x = h->sc_x.as<float>();
@@ -434,7 +564,19 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
            mean, h->sc_prior.as<double>(), loss);
   }
   LAUNCH(UIS_K_SELECT, k_score_sum, dim3((unsigned)U), dim3(64), 0, d_off, d_nvalid, loss, h->sc_out.as<float>());
+  if (spk && F > 0) {
+    if (Fv > 0)
+      LAUNCH(UIS_K_SELECT, k_speakers_frame_rows, dim3((unsigned)((Fv + 255) / 256)), dim3(256), 0, (long)Fv, d_row_frame,
+             d_frame_row);
+    LAUNCH(UIS_K_SELECT, k_speakers_tables, dim3((unsigned)U, (unsigned)((W + 63) / 64)), dim3(64), 0, d_off, d_nvalid, d_labels,
+           d_frame_row, (int)W, h->sc_spk_cand.as<int2>(), h->sc_spk_frame.as<int4>());
+    LAUNCH(UIS_K_SELECT, k_score_speakers, dim3((unsigned)F), dim3(256), (size_t)2 * m.Dp * 4, m, (int)W, d_x, mse0,
+           h->sc_mean.as<float>(), h->sc_spk_cand.as<int2>(), h->sc_spk_frame.as<int4>(), d_logblk, d_logden,
+           h->sc_spk_loss.as<float>());
+  }
   HIPCHK(hipEventRecord(h->ev_end, st));
+  if (spk && F > 0)
+    HIPCHK(hipMemcpyAsync(spk->losses_out, h->sc_spk_loss.p, (size_t)F * W * 4, hipMemcpyDeviceToHost, st));
   if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, h->sc_out.p, (size_t)U * 4, hipMemcpyDeviceToHost, st));
   if (frame_losses_out && F > 0) HIPCHK(hipMemcpyAsync(frame_losses_out, loss, (size_t)F * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -443,19 +585,18 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
     const auto t_end = std::chrono::steady_clock::now();
     fprintf(stderr, "%s: frames %lld chains %d longest %d schedule_ms %.3f device_ms %.3f total_ms %.3f\n",
-            prime ? "uis_stream_prime (forced run)" : "uis_score_labels", (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
+            spk ? "uis_score_speakers" : prime ? "uis_stream_prime (forced run)" : "uis_score_labels", (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
             std::chrono::duration<double, std::milli>(t_end - t_begin).count());
   }
   return UIS_OK;
 }
 
-}  // namespace
-
-UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
-                                    const int32_t* labels, float* scores_out, float* frame_losses_out) {
+// The argument checks of uis_score_labels and uis_score_speakers.  *done: n_utt = 0, nothing to score.
+int score_check(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt, const int32_t* labels, bool* done) {
+  *done = false;
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
-  if (n_utt == 0) return UIS_OK;
+  if (n_utt == 0) { *done = true; return UIS_OK; }
   if (offsets[0] != 0) return fail(UIS_ERR_INVALID_ARG, "offsets[0] must be 0");
   for (int u = 0; u < n_utt; ++u)
     if (offsets[u + 1] < offsets[u]) return fail(UIS_ERR_INVALID_ARG, "offsets must be non-decreasing");
@@ -464,5 +605,35 @@ UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const in
   if (F > 0x7fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "more than 2^31 - 1 frames in one call");
   for (int64_t t = 0; t < F; ++t)
     if (labels[t] < 0) return fail(UIS_ERR_INVALID_ARG, "label " + std::to_string(labels[t]) + " at frame " + std::to_string(t) + " is negative");
+  return UIS_OK;
+}
+
+}  // namespace
+
+UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                                    const int32_t* labels, float* scores_out, float* frame_losses_out) {
+  bool done;
+  if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
+  if (done) return UIS_OK;
   return score_run(h, frames, offsets, n_utt, labels, scores_out, frame_losses_out);
+}
+
+UIS_EXPORT int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                                      const int32_t* labels, int32_t width, float* losses_out, float* scores_out) {
+  bool done;
+  if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
+  if (width < 1) return fail(UIS_ERR_INVALID_ARG, "width must be at least 1");
+  if (done) return UIS_OK;
+  const int64_t F = offsets[n_utt];
+  if (F > 0 && !losses_out) return fail(UIS_ERR_INVALID_ARG, "losses_out is null");
+  for (int u = 0; u < n_utt; ++u) {  // the clusters of the valid trace (an invalid label ends it)
+    int K = 0;
+    for (int64_t t = offsets[u]; t < offsets[u + 1] && labels[t] <= K; ++t)
+      if (labels[t] == K) ++K;
+    if (width < K + 1)
+      return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has " + std::to_string(K) + " clusters: width must be at least " +
+                                           std::to_string(K + 1) + ", not " + std::to_string(width));
+  }
+  const ScoreSpeakers spk{width, losses_out};
+  return score_run(h, frames, offsets, n_utt, labels, scores_out, nullptr, nullptr, &spk);
 }

@@ -721,22 +721,8 @@ class UISRNN:
         cap = more_room(cap)
     return results[0] if single else results
 
-  def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
-    """The model's negative log-likelihood of given labelings (extension).
-
-    The neg_likelihood predict's beam search minimises (uisrnn.py:388-453), applied along the
-    given trace from an empty beam state, test_iteration 1: for labels that predict returns with
-    test_iteration 1, the score of that decode, bit for bit.  Ids may be of any hashable kind;
-    they are renamed by order of first appearance, so the result does not depend on the names.
-
-    Args:
-      test_sequences: a [N, D] float array or a list of them (as predict).
-      test_cluster_ids: N ids for an array, or a list of such sequences for a list.
-      per_frame: also return each frame's float32 loss (their float32 running sum is the score).
-    Returns:
-      a float (array) or a list of floats (list); with per_frame, a pair (scores, losses) where
-      losses is a float32 array per sequence.
-    """
+  def _labeled_sequences(self, test_sequences, test_cluster_ids):
+    """The argument checks of score_labels / score_speakers: (single, sequences, int32 labels by first appearance)."""
     single = isinstance(test_sequences, np.ndarray)
     if single:
       seqs, ids = [test_sequences], [test_cluster_ids]
@@ -757,6 +743,25 @@ class UISRNN:
             len(seq_ids), seq.shape[0]))
       names = {}
       labels.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
+    return single, seqs, labels
+
+  def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
+    """The model's negative log-likelihood of given labelings (extension).
+
+    The neg_likelihood predict's beam search minimises (uisrnn.py:388-453), applied along the
+    given trace from an empty beam state, test_iteration 1: for labels that predict returns with
+    test_iteration 1, the score of that decode, bit for bit.  Ids may be of any hashable kind;
+    they are renamed by order of first appearance, so the result does not depend on the names.
+
+    Args:
+      test_sequences: a [N, D] float array or a list of them (as predict).
+      test_cluster_ids: N ids for an array, or a list of such sequences for a list.
+      per_frame: also return each frame's float32 loss (their float32 running sum is the score).
+    Returns:
+      a float (array) or a list of floats (list); with per_frame, a pair (scores, losses) where
+      losses is a float32 array per sequence.
+    """
+    single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
     decoder = self._get_decoder()
     lens = [s.shape[0] for s in seqs]
     out_scores, out_losses = [None] * len(seqs), [None] * len(seqs)
@@ -786,6 +791,67 @@ class UISRNN:
     if single:
       return (out_scores[0], out_losses[0]) if per_frame else out_scores[0]
     return (out_scores, out_losses) if per_frame else out_scores
+
+  def score_speakers(self, test_sequences, test_cluster_ids):
+    """Every speaker's loss at every frame along given labelings (extension).
+
+    Row t of a sequence's result is what the model would charge for assigning frame t to each speaker open so far, or
+    to a new one, given the labels before t: the row _update_beam_state (uisrnn.py:388-453) computes and the decode
+    throws away.  Column k is the k-th speaker by first appearance (ids of any hashable kind, renamed as score_labels
+    does); the column one past the speakers opened before t is the new-speaker candidate, later columns are +inf.
+    The column of the frame's own label is score_labels' per-frame loss, bit for bit.  speaker_posteriors turns the
+    rows into soft assignments.
+
+    Args:
+      test_sequences, test_cluster_ids: as score_labels.
+    Returns:
+      a float32 [N, K + 1] array (array), K the sequence's number of speakers, or a list of them (list).
+    """
+    single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
+    decoder = self._get_decoder()
+    lens = [s.shape[0] for s in seqs]
+    widths = [int(l.max()) + 2 if l.size else 1 for l in labels]
+    out = [None] * len(seqs)
+
+    def run(members):
+      sub_off = np.zeros(len(members) + 1, dtype=np.int64)
+      sub_off[1:] = np.cumsum([lens[u] for u in members])
+      frames = np.empty((int(sub_off[-1]), self.observation_dim), dtype=np.float32)
+      for u, start in zip(members, sub_off[:-1]):
+        frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
+      sub_labels = np.concatenate([labels[u] for u in members])
+      try:
+        _, losses = decoder.score_speakers(frames, sub_off, sub_labels, max(widths[u] for u in members))
+      except _capi.HipLibraryError as err:
+        if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
+          run(members[0::2])  # (as score_labels)
+          run(members[1::2])
+          return
+        raise
+      for k, u in enumerate(members):
+        out[u] = losses[sub_off[k]:sub_off[k + 1], :widths[u]].copy()
+
+    if seqs:
+      run(list(range(len(seqs))))
+    return out[0] if single else out
+
+
+def speaker_posteriors(losses, temperature=1.0):
+  """Soft speaker assignments from UISRNN.score_speakers' rows: the row-wise softmax of -losses / temperature.
+
+  Args:
+    losses: a [N, W] array of per-speaker losses (+inf: no such speaker at that frame).
+    temperature: a finite number > 0, as predict_posteriors.
+  Returns:
+    float64 [N, W]; rows sum to 1, +inf maps to 0, a row that is all +inf (after an invalid label) to NaN.
+  """
+  temperature = _check_temperature(temperature)
+  z = -np.asarray(losses, dtype=np.float64) / temperature
+  if z.ndim != 2:
+    raise ValueError('losses must be a [N, W] array.')
+  with np.errstate(invalid='ignore', divide='ignore'):
+    w = np.exp(z - z.max(axis=1, keepdims=True))
+    return w / w.sum(axis=1, keepdims=True)
 
 
 class OnlineSession:
