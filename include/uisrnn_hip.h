@@ -389,6 +389,40 @@ int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out,
 int32_t uis_stream_end(uis_handle* h);
 
 /*
+ * max_speakers: decode under a per-utterance bound on the clusters a hypothesis holds.
+ *
+ * limit[u] >= 1 is the bound of utterance u, 0 means no bound.  The rule: a hypothesis that already holds
+ * K >= limit[u] clusters has no new-cluster candidate -- what the reference's beam search would do if
+ * _calculate_score gave +inf to the new-cluster entry of such a state.  Nothing else changes: the candidates of the
+ * existing clusters, their priors (the denominators still contain crp_alpha), the float32 accumulation, the prune
+ * order and the tie rules are the unbounded decode's, and a bound that never binds gives its bits.  K is the
+ * hypothesis' cluster count whatever produced it: across test_iteration repetitions, inside a look-ahead window (the
+ * K of the prefix being extended), after uis_stream_prime / _import / _retire.  A hypothesis whose K is already above
+ * the bound (a primed prefix, an imported blob, a lowered limit) is kept: it opens nothing more.  After a retirement
+ * K drops and clusters may open again: the bound is on the clusters held at once, not on the ids ever handed out.
+ * A hypothesis bounded by N <= max_clusters never sets the overflow word.
+ *
+ *   uis_decode_limits      limits: host int32 [n_utt], each in [0, 4096] (else UIS_ERR_INVALID_ARG and the pending
+ *                          table is left as it was); NULL clears a pending table.  The table belongs to the NEXT
+ *                          uis_decode / uis_decode_f64 / uis_decode_device / uis_stream_begin on this handle, which
+ *                          consumes it whether it succeeds or not and must have exactly n_utt utterances (else that
+ *                          call returns UIS_ERR_INVALID_ARG and nothing runs).  A decode without a pending table
+ *                          is unbounded, whatever an earlier call used.
+ *   uis_stream_limits      limits: host int32 [n_utt of the session]: replaces the open session's table between two
+ *                          pushes, all or nothing.  The limits belong to the session's slots, not to the streams in
+ *                          them: uis_stream_restart keeps them, an imported utterance decodes on under the target
+ *                          slot's limit, and blobs do not carry them.  (A UIS_FLAG_PERSISTENT session's resident
+ *                          launch leaves the device for the call, as for the other session calls.)
+ *   uis_stream_get_limits  out: host int32 [n_utt]: the session's table as given (0: no bound)
+ *
+ * uis_score_labels / uis_score_speakers score given labels and know no limits; the n-best, posterior and commit
+ * readouts read what the decode left.
+ */
+int32_t uis_decode_limits(uis_handle* h, const int32_t* limits, int32_t n_utt);
+int32_t uis_stream_limits(uis_handle* h, const int32_t* limits);
+int32_t uis_stream_get_limits(uis_handle* h, int32_t* out);
+
+/*
  * Primed sessions: start the online decode of an open session's utterances from a LABELED PREFIX (enrolment,
  * a corrected opening, a recording continued across a seam).  Afterwards the session is in the state it would
  * hold had it received the prefix frames and its beam contained only the given hypothesis: the state

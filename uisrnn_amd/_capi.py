@@ -332,6 +332,12 @@ def load_library(path=None):
   lib.uis_stream_labels.argtypes = [ctypes.c_void_p, i32p, _fp, i32p]
   lib.uis_stream_end.restype = i32
   lib.uis_stream_end.argtypes = [ctypes.c_void_p]
+  lib.uis_decode_limits.restype = i32
+  lib.uis_decode_limits.argtypes = [ctypes.c_void_p, i32p, i32]
+  lib.uis_stream_limits.restype = i32
+  lib.uis_stream_limits.argtypes = [ctypes.c_void_p, i32p]
+  lib.uis_stream_get_limits.restype = i32
+  lib.uis_stream_get_limits.argtypes = [ctypes.c_void_p, i32p]
   lib.uis_stream_prime.restype = i32
   lib.uis_stream_prime.argtypes = [ctypes.c_void_p, _fp, i64p, i32p, _fp]
   lib.uis_last_decode_nbest.restype = i32
@@ -398,7 +404,8 @@ EXPORTED_SYMBOLS = (
     'uis_model_constants', 'uis_rnn_step', 'uis_stream_begin', 'uis_stream_push',
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
-    'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
+    'uis_stream_get_limits', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
@@ -500,8 +507,18 @@ class Decoder:
     err.status = rc
     raise err
 
+  def set_limits(self, limits):
+    """uis_decode_limits: the max_speakers table (ints, 0 = no bound; None clears) of the NEXT decode* /
+    stream_begin call on this decoder, which consumes it."""
+    if limits is None:
+      self._check(self._lib.uis_decode_limits(self._handle, None, 0), 'uis_decode_limits')
+      return
+    lim = np.ascontiguousarray(limits, dtype=np.int32)
+    self._check(self._lib.uis_decode_limits(
+        self._handle, lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(lim.shape[0])), 'uis_decode_limits')
+
   def decode(self, frames, offsets, beam_size, look_ahead, test_iteration,
-             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0):
+             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None):
     """Decode packed host utterances.
 
     Args:
@@ -524,6 +541,8 @@ class Decoder:
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags,
                      n_streams, level_cap)
     stats = Stats()
+    if limits is not None:
+      self.set_limits(limits)
     rc = self._lib.uis_decode(
         self._handle, frames.ctypes.data_as(_fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -546,7 +565,7 @@ class Decoder:
     return out
 
   def decode_f64(self, sequences, beam_size, look_ahead, test_iteration,
-                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0):
+                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None):
     """Decode a list of [N_u, D] float64 arrays as predict() receives them (uis_decode_f64:
     the library casts to float32 on its own threads while earlier chunks travel to the device).
 
@@ -564,6 +583,8 @@ class Decoder:
     scores = np.empty(n_utt, dtype=np.float32)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
     stats = Stats()
+    if limits is not None:
+      self.set_limits(limits)
     rc = self._lib.uis_decode_f64(
         self._handle, ptrs, lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
         ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
@@ -688,9 +709,12 @@ class Decoder:
     return out
 
   # ---- online decoding (uis_stream_*)
-  def stream_begin(self, n_utt, beam_size, max_frames, max_clusters=0, flags=0):
-    """Open a streaming session for n_utt utterances (test_iteration 1, look_ahead 1)."""
+  def stream_begin(self, n_utt, beam_size, max_frames, max_clusters=0, flags=0, limits=None):
+    """Open a streaming session for n_utt utterances (test_iteration 1, look_ahead 1); `limits`: the slots'
+    max_speakers (ints, 0 = no bound)."""
     opts = make_opts(beam_size, 1, 1, max_clusters, flags, 0)
+    if limits is not None:
+      self.set_limits(limits)
     rc = self._lib.uis_stream_begin(self._handle, int(n_utt), ctypes.byref(opts), int(max_frames))
     self._check(rc, 'uis_stream_begin')
     self._stream_n = int(n_utt)
@@ -699,6 +723,21 @@ class Decoder:
     self._stream_have = np.zeros(int(n_utt), dtype=np.int64)
     self._stream_counts = np.zeros(int(n_utt), dtype=np.int32)   # (reused by every push: its pointer is bound once)
     self._stream_counts_ptr = self._stream_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+  def stream_set_limits(self, limits):
+    """uis_stream_limits: replace the open session's max_speakers table (one int per slot, 0 = no bound)."""
+    lim = np.ascontiguousarray(limits, dtype=np.int32)
+    if lim.shape != (self._stream_n,):
+      raise ValueError('one limit per utterance of the session')
+    self._check(self._lib.uis_stream_limits(self._handle, lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                'uis_stream_limits')
+
+  def stream_limits(self):
+    """uis_stream_get_limits: int32 [n_utt], 0 = no bound."""
+    out = np.zeros(self._stream_n, dtype=np.int32)
+    self._check(self._lib.uis_stream_get_limits(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                'uis_stream_get_limits')
+    return out
 
   def stream_push(self, chunks):
     """chunks: one [n_u, D] array (or None / empty) per utterance: its new frames -- or ONE
@@ -1050,12 +1089,14 @@ class Decoder:
     return self._posterior(self._lib.uis_stream_posterior, 'uis_stream_posterior', temperature, offsets, self._stream_beam)
 
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
-                  labels_ptr, scores_ptr, max_clusters=0, flags=0):
+                  labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None):
     """uis_decode on raw HOST pointers (e.g. pinned buffers from uis_host_alloc or torch)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     n_utt = offsets.shape[0] - 1
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, 0)
     stats = Stats()
+    if limits is not None:
+      self.set_limits(limits)
     rc = self._lib.uis_decode(
         self._handle, ctypes.cast(ctypes.c_void_p(int(frames_ptr)), _fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -1109,13 +1150,15 @@ class Decoder:
 
   def decode_device(self, d_frames_ptr, offsets, beam_size, look_ahead,
                     test_iteration, d_labels_ptr, d_scores_ptr, max_clusters=0,
-                    flags=0, n_streams=0):
+                    flags=0, n_streams=0, limits=None):
     """Decode with frames/labels/scores already resident in HBM (raw pointers)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     n_utt = offsets.shape[0] - 1
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags,
                      n_streams)
     stats = Stats()
+    if limits is not None:
+      self.set_limits(limits)
     rc = self._lib.uis_decode_device(
         self._handle, ctypes.c_void_p(int(d_frames_ptr)),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,

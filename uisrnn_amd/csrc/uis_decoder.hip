@@ -172,6 +172,7 @@ struct HandleMem {
   DevBuf beam_n, beam_K, beam_last, beam_sum, beam_score, beam_slot, beam_blk, bp, rows, nrows;
   DevBuf gi_up, a1, counters, beam_scores_out, io_frames, io_labels, io_scores, mse_tab, dbg_scores, utt_nrows, hst;
   DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
+  DevBuf limit, limit_in;  // [U] int32 each: DecodeState::limit, written by every decode, and uis_decode_limits' table it is written from
   DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   HostBuf h_cast;  // uis_decode_f64: the pinned float32 staging buffer the utterances are cast into, chunk by chunk, ahead of each H2D copy
@@ -234,6 +235,7 @@ struct uis_handle : HandleMem {
     // everything committed, nothing received since: ONE hypothesis lives (all survivors shared the ancestor at the
     // last step), its labels are the committed ones and its score is win_score; the readouts' kernels see N = 0
     bool window_emptied(int u) const { return have[u] == 0 && committed[u] > 0; }
+    std::vector<int32_t> limits;      // max_speakers per slot as the caller gave them (0: no bound): uis_stream_begin / uis_stream_limits
     DecodeState st{};
     int32_t* d_avail = nullptr;
     int32_t* d_have = nullptr;        // frames received per utterance, refreshed for every back-trace
@@ -279,6 +281,10 @@ struct uis_handle : HandleMem {
   std::vector<int64_t> io_offsets;  // offsets of the last uis_decode (its labels are still in io_labels)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
+  // max_speakers: the table uis_decode_limits left for the next decode / uis_stream_begin, and the one the running call
+  // took from it (take_limits, at that call's entry: consumed whether the call succeeds or not)
+  std::vector<int32_t> pending_limits, call_limits;
+  bool pending_limits_set = false, call_limits_set = false;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
   // offsets, the record format
@@ -1070,6 +1076,13 @@ const KernelEntryOf<RsKernel> rs[] = {
     {256, 256, RS_BASE, &k_decode_rs<256, 256>}, {256, 128, RS_BASE, &k_decode_rs<256, 128>},
     {128, 256, RS_BASE, &k_decode_rs<128, 256>}, {128, 128, RS_BASE, &k_decode_rs<128, 128>},
     {512, 256, RS_C1, &k_decode_rs<512, 256, 10, 16>}};
+// the same entries for a decode with limits (uis_decode_limits): not a table of its own to the outside -- a decode reports
+// the entry of `rs` it stands for
+const KernelEntryOf<RsKernel> rs_lim[] = {
+    {512, 256, RS_BASE, &k_decode_rs<512, 256, 0, -1>}, {512, 128, RS_BASE, &k_decode_rs<512, 128, 0, -1>},
+    {256, 256, RS_BASE, &k_decode_rs<256, 256, 0, -1>}, {256, 128, RS_BASE, &k_decode_rs<256, 128, 0, -1>},
+    {128, 256, RS_BASE, &k_decode_rs<128, 256, 0, -1>}, {128, 128, RS_BASE, &k_decode_rs<128, 128, 0, -1>},
+    {512, 256, RS_C1, &k_decode_rs<512, 256, 10, -16>}};
 const KernelEntry resident[] = {
     {512, 256, CLS_C1, &k_decode_resident<512, 256, false, 10, 16>}, {512, 512, CLS_C4, &k_decode_resident<512, 512, false, 20, 11>},
     {512, 256, CLS_NONE, &k_decode_resident<512, 256>}, {512, 512, CLS_NONE, &k_decode_resident<512, 512>},
@@ -1143,7 +1156,7 @@ int rs_make_args(const DevModel& m, const DecodeState& st, size_t bp_bytes, RsAr
   a.ncl = st.ncl; a.rx_stride = st.rx_stride; a.step0 = st.step0; a.step1 = st.step1; a.flags = st.flags;
   a.lp_stay = m.lp_stay; a.lp_sw = m.lp_sw; a.lp_new = m.lp_new;
   a.whh = m.whh[0]; a.w1 = m.w1; a.w2 = m.w2; a.bhh = m.bhh[0]; a.b1 = m.b1; a.b2 = m.b2; a.wgt = m.wgt;
-  a.off = st.off; a.resume = st.resume;
+  a.off = st.off; a.resume = st.resume; a.limit = st.limit;
   a.logblk = st.logblk; a.logden = st.logden;
   a.x = st.x; a.gi0 = st.gi0; a.mse0 = st.mse0;
   a.overflow = st.overflow; a.dbg_scores = st.dbg_scores; a.counters = st.counters;
@@ -1353,6 +1366,9 @@ int derive_shape(DecodeCall& c) {
   h->last_overflow.clear(); h->last_beam_scores.clear();
   h->nb_valid = false;  // (... nor uis_last_decode_nbest its hypotheses)
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
+  if (h->call_limits_set && (int64_t)h->call_limits.size() != (int64_t)n_utt)
+    return fail(UIS_ERR_INVALID_ARG, "uis_decode_limits gave " + std::to_string(h->call_limits.size()) + " limits, this decode has " +
+                                         std::to_string(n_utt) + " utterances");
   h->last_pick = KernelPick{};
   const DevModel& m = h->m;
   const int B = opts->beam_size, L = opts->look_ahead, tau = opts->test_iteration;
@@ -1492,6 +1508,7 @@ int plan_and_place(DecodeCall& c) {
   pick.family = c.plan.decode_kernel & 0xff; pick.Hp = m.Hp; pick.Dp = m.Dp;  // (what stays without a table lookup)
   c.cluster_kern = c.plan.clustered() && !c.rs ? cluster_kernel(c.plan, m, s.L, &pick) : nullptr;
   c.rs_kern = c.rs ? find_kernel(kernels::rs, m.Hp, m.Dp, c.plan.rs_kind, &pick) : nullptr;
+  if (c.rs_kern && h->call_limits_set) c.rs_kern = find_kernel(kernels::rs_lim, m.Hp, m.Dp, c.plan.rs_kind);  // (the same entry's twin)
   h->last_pick = pick;
   return UIS_OK;
 }
@@ -1537,6 +1554,10 @@ int upload_tables(DecodeCall& c) {
   const DevModel& m = h->m;
   const DecodeShape& s = c.shape;
   HIPCHK(hipMemcpyAsync(h->off.p, c.offsets, (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
+  // (max_speakers: the caller's table, if there is one; k_init_state writes DecodeState::limit from it in every decode,
+  // so that nothing depends on what an earlier call left there and an unbounded decode pays no copy)
+  if (h->call_limits_set)
+    HIPCHK(hipMemcpyAsync(h->limit_in.p, h->call_limits.data(), (size_t)s.U * 4, hipMemcpyHostToDevice, h->stream));
   if (int rc = upload_log_tables(h->alpha, c.n_log, c.log_host, h->logblk.p, h->logden.p, h->stream)) return rc;
   if (s.wnd)
     HIPCHK(hipMemcpyAsync(h->bp_base.p, c.bp_base.data(), (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -1775,6 +1796,8 @@ void build_group_states(DecodeCall& c) {
     st.off = h->off.as<int64_t>() + u0;
     st.utt_step = h->utt_step.as<int32_t>() + u0;
     st.overflow = h->overflow.as<int32_t>() + u0;
+    st.limit = h->limit.as<int32_t>() + u0;
+    st.limit_in = h->call_limits_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
     st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
@@ -2175,15 +2198,37 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
   return UIS_OK;
 }
 
+// The table uis_decode_limits left becomes the running call's (every entry point that consumes it starts here).
+static void take_limits(uis_handle* h) {
+  if (!h) return;
+  h->call_limits.swap(h->pending_limits);
+  h->call_limits_set = h->pending_limits_set;
+  h->pending_limits.clear();
+  h->pending_limits_set = false;
+}
+
+UIS_EXPORT int32_t uis_decode_limits(uis_handle* h, const int32_t* limits, int32_t n_utt) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!limits) { h->pending_limits.clear(); h->pending_limits_set = false; return UIS_OK; }
+  if (n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_utt");
+  for (int u = 0; u < n_utt; ++u)
+    if (limits[u] < 0 || limits[u] > 4096) return fail(UIS_ERR_INVALID_ARG, "a limit must be in [0, 4096] (0: no bound)");
+  h->pending_limits.assign(limits, limits + n_utt);
+  h->pending_limits_set = true;
+  return UIS_OK;
+}
+
 UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
                                      const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out,
                                      uis_stats* stats) {
+  take_limits(h);
   if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
 }
 
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                               const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
+  if (h && !h->src64) take_limits(h);  // (uis_decode_f64 has taken them)
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
   h->nb_valid = false;  // (a decode refused below leaves nothing for uis_last_decode_nbest either)
   const int64_t F = n_utt ? offsets[n_utt] : 0;
@@ -2239,6 +2284,7 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
 
 UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances, const int64_t* n_frames, int32_t n_utt,
                                   const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
+  take_limits(h);
   if (!h || n_utt < 0 || (n_utt > 0 && (!utterances || !n_frames)))
     return fail(UIS_ERR_INVALID_ARG, "null handle/utterances/n_frames or negative n_utt");
   h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)

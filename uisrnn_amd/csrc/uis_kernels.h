@@ -76,6 +76,7 @@ struct RsArgs {
   const float* wgt;
   const int64_t* off;
   unsigned char* resume;
+  const int32_t* limit;                            // (DecodeState::limit: each wave's word goes into its LDS header)
   // the loop's
   const double* logblk;  const double* logden;     // (counts beyond the LDS copies only)
   const float* x;  const float* gi0;  const float* mse0;
@@ -217,4 +218,9 @@ struct DecodeState {
   // back-pointers per window: bp16[(bp_base[u] + w*B + r)*(L+1)] = {parent, c_1 .. c_L}
   uint16_t* bp16;
   const int64_t* bp_base; // [U]
+
+  // ---- max_speakers: a hypothesis of utterance u that holds limit[u] clusters or more has no new-cluster candidate
+  // (INT32_MAX: no bound).  Written by every call that decodes, whatever the caller asked for.
+  int32_t* limit;            // [U]
+  const int32_t* limit_in;   // [U] or null: the caller's table (0: no bound) k_init_state writes `limit` from; null: no bound
 };

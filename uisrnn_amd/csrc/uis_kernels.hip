@@ -860,6 +860,10 @@ __global__ void k_init_state(DecodeState st) {
   if (u >= st.U) return;
   st.utt_step[u] = 0;
   st.overflow[u] = 0;
+  {  // max_speakers: written by every decode, whatever the caller asked for
+    const int lim = st.limit_in ? st.limit_in[u] : 0;
+    st.limit[u] = lim > 0 ? lim : 0x7fffffff;
+  }
   st.beam_n[u] = 1;            // parity 0
   st.beam_n[st.U + u] = 0;
   size_t e = (size_t)u * st.B;
@@ -963,6 +967,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
   const int step = st.utt_step[u];
   const long off0 = (long)st.off[u], off1 = (long)st.off[u + 1];
   const int nb = st.beam_n[(size_t)tpar * U + u];
+  const int lim = st.limit[u];
   // next step's row counter: its readers (the previous step's GEMMs) finished a launch ago
   if (u == 0 && tid == 0) st.nrows[par ^ 1] = 0;
   for (int i = tid; i < m.Dp; i += 256) swgt[i] = m.wgt[i];
@@ -1065,7 +1070,8 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
       mse = mse_new;
       prior = m.lp_new - ld;
     }
-    const float sc = sscore[b] + uis_step_loss(mse, prior);  // float32 accumulate, uisrnn.py:452
+    float sc = sscore[b] + uis_step_loss(mse, prior);  // float32 accumulate, uisrnn.py:452
+    if (c >= sK[b] && c >= lim) sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
     scscore[i] = sc;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc;
     const bool fin = uis_isfinite(sc);
@@ -1434,6 +1440,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   // plain uniform load would go through the scalar cache, which neighbouring CUs may share and may
   // have filled with this line before the write)
   const float mse_new = RES ? __hip_atomic_load(st.mse0 + frame, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : st.mse0[frame];
+  const int lim = st.limit[u];  // (written between launches only)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
@@ -1533,6 +1540,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
       prior = m.lp_new - my_ld;
     }
     my_sc = sscore[my_b] + uis_step_loss(mse, prior);
+    if (my_c >= sK[my_b] && my_c >= lim) my_sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
     if (uis_isfinite(my_sc)) my_key = ((unsigned long long)uis_score_key(my_sc) << 32) | (unsigned)tid;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + my_b) * (Kmax + 1) + my_c] = my_sc;
   }
@@ -3263,6 +3271,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
 
   // ---- candidate scores
   const float mse_new = st.mse0[frame];
+  const int lim = st.limit[u];
   auto node_of = [&](int i) {  // largest node with cbase[node] <= i
     int lo = 0, hi = n_in;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cbase[mid] <= i) lo = mid; else hi = mid; }
@@ -3310,7 +3319,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
         if (c < Kb) emit(c, mse[sl[e]], (c == lastb) ? m.lp_stay : (m.lp_sw + lb[e]) - ld);
       }
     }
-    emit(Kb, mse_new, m.lp_new - ld);
+    emit(Kb, mse_new, Kb < lim ? m.lp_new - ld : -(double)INFINITY);  // max_speakers: at its bound, a loss of +inf = no candidate
   }
   __syncthreads();
   WSTAMP(2);
@@ -3926,6 +3935,11 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
     for (int i = lane; i < RL.persist_stride / 4; i += 64) reinterpret_cast<int*>(pers_w)[i] = src[i];
     fpos_w = N_w > 0 ? (long)step0 % N_w : 0;
   }
+  if (WS && has_u && lane == 0) {  // the utterance's limit beside the grid words of both table sets (rs_prep reads it there)
+    const int lim_w = st.limit[u_w];
+    reinterpret_cast<int*>(pers_w + RL.off_hdr)[3] = lim_w;
+    reinterpret_cast<int*>(pers_w + RL.set_stride + RL.off_hdr)[3] = lim_w;
+  }
   const f32x4* w1g = reinterpret_cast<const f32x4*>(m.w1) + (size_t)ft1 * NKB * 64;
   const f32x4* w2g = reinterpret_cast<const f32x4*>(m.w2) + (size_t)ft2 * NKB * 64;
 
@@ -4163,7 +4177,7 @@ __global__ __launch_bounds__(512) void k_decode_big(DevModel m, DecodeState st) 
   if (!WIN && t == 0 && blockIdx.x == 0)
     for (int k = 0; k < 9; ++k) st.counters[112 + k] = nrt_hist[k];
 #endif
-  if (WS && s_end < nsteps) {  // more steps to come in another launch
+  if (WS && st.step1 > 0) {  // another launch follows: it reads every utterance's block back, also of a cluster whose utterances have all ended (k_decode_rs)
     if (has_u) {
       int* dst = reinterpret_cast<int*>(st.resume + (size_t)u_w * RL.persist_stride);
       for (int i = lane; i < RL.persist_stride / 4; i += 64) dst[i] = reinterpret_cast<const int*>(pers_w)[i];

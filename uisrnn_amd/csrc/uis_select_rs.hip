@@ -52,7 +52,7 @@ struct RsLds {
   // per utterance, persistent: two table sets (by step parity) + frames per slot + masks
   int off_hyp;                               // {K, last, sum(block_counts), score bits} int32 x 4 [B]: one 16-byte read per hypothesis
   int off_ent;                               // uint32 [B][Kmax]: slot | block count << 16
-  int off_hdr;                               // int32 [4]    {hypotheses, grid stride, its magic, 0}
+  int off_hdr;                               // int32 [4]    {hypotheses, grid stride, its magic, the utterance's cluster limit: written once, in both sets}
   int set_stride;
   int off_pcnt;                              // uint16 [S]   frames assigned to the cluster state in slot s
   int off_flag;                              // uint8 [S]    scratch of rs_back: 1 = referenced by the next beam, 3 = and written by this step
@@ -258,13 +258,13 @@ __device__ __forceinline__ unsigned long long rs_own_sgprs64(unsigned long long 
 __device__ __forceinline__ void rs_own_sgprs(double& v) { v = __builtin_bit_cast(double, rs_own_sgprs64(__builtin_bit_cast(unsigned long long, v))); }
 template <typename T> __device__ __forceinline__ void rs_own_sgprs(T*& v) { v = (T*)rs_own_sgprs64((unsigned long long)v); }
 __device__ __forceinline__ RsArgs rs_own_args(RsArgs a) {
-  static_assert(sizeof(RsArgs) == 264, "a field was added to RsArgs: give it registers of its own below (tests/test_rs_loop_static.py counts the spills)");
+  static_assert(sizeof(RsArgs) == 272, "a field was added to RsArgs: give it registers of its own below (tests/test_rs_loop_static.py counts the spills)");
   rs_own_sgprs(a.U); rs_own_sgprs(a.B); rs_own_sgprs(a.Kmax); rs_own_sgprs(a.S); rs_own_sgprs(a.D); rs_own_sgprs(a.H_units);
   rs_own_sgprs(a.tau); rs_own_sgprs(a.ncl); rs_own_sgprs(a.rx_stride); rs_own_sgprs(a.step0); rs_own_sgprs(a.step1);
   rs_own_sgprs(a.flags);
   rs_own_sgprs(a.lp_stay); rs_own_sgprs(a.lp_sw); rs_own_sgprs(a.lp_new);
   rs_own_sgprs(a.whh); rs_own_sgprs(a.w1); rs_own_sgprs(a.w2); rs_own_sgprs(a.bhh); rs_own_sgprs(a.b1); rs_own_sgprs(a.b2);
-  rs_own_sgprs(a.wgt); rs_own_sgprs(a.off); rs_own_sgprs(a.resume);
+  rs_own_sgprs(a.wgt); rs_own_sgprs(a.off); rs_own_sgprs(a.resume); rs_own_sgprs(a.limit);
   rs_own_sgprs(a.logblk); rs_own_sgprs(a.logden);
   rs_own_sgprs(a.x); rs_own_sgprs(a.gi0); rs_own_sgprs(a.mse0); rs_own_sgprs(a.blk);
   rs_own_sgprs(a.o_mean); rs_own_sgprs(a.o_hid); rs_own_sgprs(a.o_h1); rs_own_sgprs(a.o_hst); rs_own_sgprs(a.o_a1);
@@ -340,7 +340,8 @@ struct RsPrep {
   float bs[3];
 };
 
-template <bool FULL = false, typename View, typename Mid>
+// LIM false: the instantiation of a decode without limits (k_decode_rs with CKL >= 0)
+template <bool FULL = false, bool LIM = true, typename View, typename Mid>
 __device__ __forceinline__ RsPrep rs_prep(const View& a, const RsLds& L, const RsDims dm, int step,
                                           const unsigned char* pers, unsigned char* scr, const double* s_lblk,
                                           const double* s_lden, Mid mid) {
@@ -359,6 +360,7 @@ __device__ __forceinline__ RsPrep rs_prep(const View& a, const RsLds& L, const R
   int* sdst = reinterpret_cast<int*>(scr + L.sc_dst);
   RsPrep P;
   P.nb = shdr[0]; P.Kcur = shdr[1]; P.kmagic = shdr[2];
+  const int lim = LIM ? shdr[3] : 0x7fffffff;  // max_speakers (DecodeState::limit): a hypothesis with this many clusters opens no other
   P.nn = snewlist[0];
   const int nb = P.nb, Kcur = P.Kcur, kmagic = P.kmagic;
   unsigned long long lv[4];
@@ -396,7 +398,9 @@ __device__ __forceinline__ RsPrep rs_prep(const View& a, const RsLds& L, const R
     if (b < nb) {
       const u32x4 h = shyp[b];  // {K, last, sum, score}
       const int Kb = (int)h[0];
-      if (c <= Kb) {
+      // (max_speakers: at its limit a hypothesis' last candidate is cluster Kb - 1.  Arithmetic, not a second branch: the
+      // sign of lim - 1 - Kb; a K above the limit -- a primed or imported one -- keeps its Kb candidates)
+      if (c <= (LIM ? Kb - (int)((unsigned)(lim - 1 - Kb) >> 31) : Kb)) {
         const int sum = (int)h[2];
         double ld = s_lden[sum < UIS_RS_LOGTAB ? sum : 0];  // (no pointer select between LDS and global: two loads)
         if (sum >= UIS_RS_LOGTAB) ld = a.logden()[sum];
@@ -1028,8 +1032,14 @@ __device__ __forceinline__ bool rs_blk_wait_all(__amdgpu_buffer_rsrc_t blk, uint
 // at most 192 candidates (rs_select_ok).  Template parameters beyond the model's padded sizes:
 //   CB, CK  beam_size and max_clusters as compile-time constants (0: run-time values) -- the instantiation
 //           of a shape whose LDS layout then folds into the instruction stream (LABNOTES.md 4.0a)
-template <int HP, int DP, int CB = 0, int CK = 0>
+//   CKL < 0 the twin of the same kernel for a decode with limits (uis_decode_limits): max_clusters -CKL for a shape
+//           class, run-time values at -1.  Without limits the rule is compiled out of rs_prep: the unbounded step loop
+//           is instruction for instruction what it was before there were limits (three instructions per candidate
+//           measured 0.55 % at configs[1])
+template <int HP, int DP, int CB = 0, int CKL = 0>
 __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
+  constexpr bool LIM = CKL < 0;
+  constexpr int CK = CB ? (LIM ? -CKL : CKL) : 0;
   const RsArgs a = rs_own_args(args);
   constexpr int NKB = HP / 16, PER = NKB / UIS_KSPLIT, RC = UIS_RES_RC;
   constexpr int NFT1 = HP / 16, SH1 = 32 / NFT1;
@@ -1125,6 +1135,11 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
     fpos_w = N_w > 0 ? step0 % N_w : 0;
     for (int k = 0; k < w; ++k) prev_base += s_ctl[8 + k];
   }
+  if (LIM && lane == 0) {  // this launch's limit of the wave's utterance beside the grid words of both table sets (rs_prep reads it there)
+    const int lim_w = has_u ? a.limit[u_w] : 0x7fffffff;
+    reinterpret_cast<int*>(pers_w + L.off_hdr)[3] = lim_w;
+    reinterpret_cast<int*>(pers_w + L.set_stride + L.off_hdr)[3] = lim_w;
+  }
 
   f32x4 wg[3][PER];
 #pragma unroll
@@ -1151,7 +1166,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
   unsigned long long ft_acc[4] = {0, 0, 0, 0}, rt_prev2 = rt_prev;
 #endif
 
-  RsPrep prep = rs_prep<false>(av, L, dm, step0, pers_w, scr_w, s_lblk, s_lden, []() {});  // (later steps: prepared inside the previous step's last hand-off)
+  RsPrep prep = rs_prep<false, LIM>(av, L, dm, step0, pers_w, scr_w, s_lblk, s_lden, []() {});  // (later steps: prepared inside the previous step's last hand-off)
   for (int s = step0; s < s_end; ++s) {
     // ---- select, replicated: wave w decides utterance slot w; every workgroup gets the same rows
     RsWin win;
@@ -1378,7 +1393,7 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
       uint32_t pk = 0u;
       auto peek = [&]() { pk = rs_blk_peek_all(blk, fl_off); };
       if (has_u && s + 1 < T_w)
-        prep = rs_prep<false>(av, L, dm, s + 1, pers_w, scr_w, s_lblk, s_lden, peek);
+        prep = rs_prep<false, LIM>(av, L, dm, s + 1, pers_w, scr_w, s_lblk, s_lden, peek);
       else
         peek();
       if (!rs_flag_ready_all(pk, 3u * (uint32_t)s + 3u) && rs_blk_wait_all(blk, fl_off, ab_off, 3u * (uint32_t)s + 3u)) s_ctl[0] = 1;
@@ -1391,7 +1406,11 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
   if (t == 0 && blockIdx.x == 0) for (int k = 0; k < 8; ++k) a.counters[80 + k] = ph_acc[k];
   if (t == 0 && blockIdx.x == 31 * ncl) for (int k = 0; k < 4; ++k) a.counters[72 + k] = ft_acc[k];
 #endif
-  if (s_end < nsteps) {  // more steps to come in another launch: rank 0's copy of the cluster's tables goes to st.resume
+  // Another launch follows (step1 > 0): rank 0's copy of the cluster's tables goes to st.resume -- also where every
+  // utterance of THIS cluster has ended (s_end == nsteps): the next launch reads every cluster's blocks back before it
+  // looks at their lengths, and a block nobody wrote is whatever the memory held (rs_prep then indexes the log tables
+  // with it).  The statistics are flushed by the last launch, from the blocks it read back.
+  if (a.step1 > 0) {
     __syncthreads();
     if (s_ctl[0]) return;
     if (rank == 0) {

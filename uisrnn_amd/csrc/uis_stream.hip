@@ -326,10 +326,28 @@ int session_readout(uis_handle* h, Run run) {
 
 }  // namespace
 
+namespace {
+
+// DecodeState::limit from the caller's table (0: no bound); `dev` must outlive the copy
+int upload_session_limits(uis_handle* h, const std::vector<int32_t>& limits, std::vector<int32_t>& dev) {
+  uis_handle::Stream& ss = h->stream_state;
+  dev.assign((size_t)ss.U, INT32_MAX);
+  for (int u = 0; u < ss.U && u < (int)limits.size(); ++u)
+    if (limits[u] > 0) dev[u] = limits[u];
+  HIPCHK(hipMemcpyAsync(ss.st.limit, dev.data(), (size_t)ss.U * 4, hipMemcpyHostToDevice, h->stream));
+  return UIS_OK;
+}
+
+}  // namespace
+
 UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
+  take_limits(h);
   if (!h || !opts || n_utt < 1 || max_frames < 1) return fail(UIS_ERR_INVALID_ARG, "null handle/opts, n_utt < 1 or max_frames < 1");
   uis_handle::Stream& ss = h->stream_state;
   if (ss.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is already open on this handle");
+  if (h->call_limits_set && (int64_t)h->call_limits.size() != (int64_t)n_utt)
+    return fail(UIS_ERR_INVALID_ARG, "uis_decode_limits gave " + std::to_string(h->call_limits.size()) + " limits, this session has " +
+                                         std::to_string(n_utt) + " utterances");
   const DevModel& m = h->m;
   const int B = opts->beam_size;
   const int Kmax = opts->max_clusters > 0 ? opts->max_clusters : 16;
@@ -368,6 +386,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   SALLOC(d_off, U + 1, false);
   SALLOC(st.utt_step, U, false);
   SALLOC(st.overflow, U, false);
+  SALLOC(st.limit, U, false);
   SALLOC(ss.d_avail, U, true);
   SALLOC(ss.d_have, U, true);
   SALLOC(ss.d_foff, U, true);
@@ -447,12 +466,16 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   std::vector<int64_t> off(U + 1);
   for (int u = 0; u <= U; ++u) off[u] = (int64_t)u * max_frames;  // capacity offsets: they address the back-pointers
   std::vector<double> log_host;
+  std::vector<int32_t> limit_dev;
   HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
+  ss.limits.assign((size_t)U, 0);
+  if (h->call_limits_set) ss.limits = h->call_limits;
   if ((rc = upload_log_tables(h->alpha, max_frames + 2, log_host, d_logblk, d_logden, h->stream))) return rc;
   st.off = d_off; st.logblk = d_logblk; st.logden = d_logden;
   st.avail = ss.d_avail; st.foff = ss.d_foff; st.lab_off = ss.d_lab_off;
   hipLaunchKernelGGL(k_init_state, dim3((U + 255) / 256), dim3(256), 0, h->stream, st);
   HIPCHK(hipGetLastError());
+  if ((rc = upload_session_limits(h, ss.limits, limit_dev))) return rc;  // (behind k_init_state, which has written "no bound")
   HIPCHK(hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
   ss.active = true;
   return UIS_OK;
@@ -707,4 +730,27 @@ UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
   HIPCHK(hipStreamSynchronize(h->stream));
   stream_free(h);
   return rc_quit;
+}
+
+// max_speakers of an open session.  The table belongs to the slots, not to the streams in them: restarts, imports and
+// retirements leave it alone, blobs do not carry it.  All or nothing: a table with a value out of range changes none.
+UIS_EXPORT int32_t uis_stream_limits(uis_handle* h, const int32_t* limits) {
+  if (!session_of(h, limits != nullptr, "null handle/limits")) return UIS_ERR_INVALID_ARG;
+  uis_handle::Stream& ss = h->stream_state;
+  for (int u = 0; u < ss.U; ++u)
+    if (limits[u] < 0 || limits[u] > 4096) return fail(UIS_ERR_INVALID_ARG, "a limit must be in [0, 4096] (0: no bound)");
+  if (int rc = session_enter(h, nullptr)) return rc;  // (the resident launch leaves: the table is written between launches)
+  const std::vector<int32_t> next(limits, limits + ss.U);
+  std::vector<int32_t> dev;
+  if (int rc = upload_session_limits(h, next, dev)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  ss.limits = next;
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_stream_get_limits(uis_handle* h, int32_t* out) {
+  if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
+  const uis_handle::Stream& ss = h->stream_state;
+  for (int u = 0; u < ss.U; ++u) out[u] = ss.limits[u];
+  return UIS_OK;
 }

@@ -145,6 +145,8 @@ std::vector<WsItem> workspace_list(DecodeCall& c) {
     ENSURE(bp16, (size_t)std::max<int64_t>(c.bp_base[U], 1) * (L + 1) * 2);
     ENSURE(bp_base, (U + 1) * 8);
   }
+  ENSURE(limit, U * 4);  // (last: every view above stays where it was measured)
+  if (h->call_limits_set) ENSURE(limit_in, U * 4);
 #undef ENSURE
   return want;
 }

@@ -35,7 +35,43 @@ def _check_temperature(temperature):
   return value
 
 
-def _initial_cluster_cap(args):
+_MAX_SPEAKERS_LIMIT = 4096  # (the library's own limit: uis_decode_limits)
+
+
+def _check_max_speakers(max_speakers, args, n_utt):
+  """The max_speakers keyword as the library's table: None (no utterance is bounded) or a list of n_utt ints, 0 = no
+  bound.  max_speakers=None falls back to args.max_speakers, the way max_clusters rides on the args object.
+  ValueError -- before any device work -- for a bool, a float that is not whole, a negative, a value above 4096 or a
+  sequence of the wrong length."""
+  if max_speakers is None:
+    max_speakers = getattr(args, 'max_speakers', None)
+  if max_speakers is None:
+    return None
+
+  def one(value):
+    if value is None:
+      return 0
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+      raise ValueError('max_speakers must be None, 0 or an integer in [1, {}], not {!r}.'.format(
+          _MAX_SPEAKERS_LIMIT, value))
+    if isinstance(value, (float, np.floating)) and (not np.isfinite(value) or value != int(value)):
+      raise ValueError('max_speakers must be a whole number, not {!r}.'.format(value))
+    if not 0 <= int(value) <= _MAX_SPEAKERS_LIMIT:
+      raise ValueError('max_speakers must be in [0, {}], not {!r}.'.format(_MAX_SPEAKERS_LIMIT, value))
+    return int(value)
+
+  if isinstance(max_speakers, np.ndarray) and max_speakers.ndim == 0:
+    max_speakers = max_speakers.item()   # (a 0-d array is a scalar)
+  if isinstance(max_speakers, (list, tuple, np.ndarray)):
+    values = [one(v) for v in (max_speakers.tolist() if isinstance(max_speakers, np.ndarray) else max_speakers)]
+    if len(values) != int(n_utt):
+      raise ValueError('max_speakers has {} entries for {} utterances.'.format(len(values), n_utt))
+  else:
+    values = [one(max_speakers)] * int(n_utt)
+  return values if any(values) else None
+
+
+def _initial_cluster_cap(args, limits=None):
   """Device table size (clusters per hypothesis) of the first decode attempt.
 
   The fast select kernel and the one-launch decode need beam_size * (cap + 1) <= 256
@@ -50,6 +86,13 @@ def _initial_cluster_cap(args):
   fits = 256 // max(int(args.beam_size), 1) - 1
   if int(args.look_ahead) == 1 and 8 <= fits < _DEFAULT_MAX_CLUSTERS:
     return fits
+  # max_speakers: every utterance bounded by at most L, and a beam so wide that the rule above has left the fast
+  # select: a cap of L brings it back where beam_size * (L + 1) <= 256.  A hypothesis that may not open cluster L + 1
+  # cannot overflow it, and the results are the same bits under any sufficient cap.
+  # (look_ahead 1 only: the fast select is that path's; at look_ahead 2 a cap of 4 measured 2.4 % slower than the
+  # beam 50 / cap 12 shape class -- profiles/limit_rate.json)
+  if int(args.look_ahead) == 1 and limits and all(limits) and fits < 8 and int(args.beam_size) * (max(limits) + 1) <= 256:
+    return max(limits)
   return _DEFAULT_MAX_CLUSTERS
 _MAX_CLUSTERS_LIMIT = 4096   # (the library's own limit: uis_decode_opts.max_clusters)
 _DEFAULT_LEVEL_CAP = 32768   # include/uisrnn_hip.h: uis_decode_opts.level_cap's default ...
@@ -303,7 +346,8 @@ class UISRNN:
       raise ValueError('test_sequence does not match the dimension specified '
                        'by args.observation_dim.')
 
-  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None):
+  def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
+                    limits=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -312,14 +356,20 @@ class UISRNN:
     n_best > 0 (predict_nbest): an utterance's result is the pair (labelings, scores) of its final
     beam instead of the label list, read right after the decode call whose labels are accepted for it.
     posterior = a temperature (predict_posteriors): the triple (labels, confidence, change), read likewise.
+    limits (_check_max_speakers): None, or one int per sequence (0 = no bound); every regrouping below -- the
+    overflow retry's subsets, the halves after UIS_ERR_OOM, the look-ahead retry's groups -- takes its members' entries.
     """
     decoder = decoder or self._get_decoder(device)
+
+    def lim_of(members):
+      return None if limits is None else [limits[u] for u in members]
+
     # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
     level_cap = level_cap or int(getattr(args, 'level_cap', 0) or 0)
     n_utt = len(sequences)
     results = [None] * n_utt
     pending = list(range(n_utt))
-    cap = _initial_cluster_cap(args)
+    cap = _initial_cluster_cap(args, limits)
     stats = None
     while pending:
       # the float64 arrays go to the library as they are (uis_decode_f64): it casts to float32
@@ -330,7 +380,8 @@ class UISRNN:
       sub_off[1:] = np.cumsum([s.shape[0] for s in sub])
       try:
         out = decoder.decode_f64(sub, args.beam_size, args.look_ahead,
-                                 args.test_iteration, max_clusters=cap, flags=flags, level_cap=level_cap)
+                                 args.test_iteration, max_clusters=cap, flags=flags, level_cap=level_cap,
+                                 **({} if limits is None else {'limits': lim_of(pending)}))
       except _capi.HipLibraryError as err:
         if err.status == _capi.UIS_ERR_OOM and len(pending) > 1:
           # the decode state of this many utterances does not fit the device (or the pinned staging
@@ -340,7 +391,8 @@ class UISRNN:
           level_full, first_err = [], None
           for part in (pending[0::2], pending[1::2]):
             try:
-              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best, posterior)
+              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best, posterior,
+                                                lim_of(part))
             except LookAheadWindowError as inner:
               # (a half whose look-ahead window overflowed: its indices and results are numbered inside
               # the half -- hand them up in the caller's numbering, and still decode the other half)
@@ -386,7 +438,8 @@ class UISRNN:
           if not members:
             continue
           try:
-            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best, posterior)
+            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best, posterior,
+                                         lim_of(members))
           except LookAheadWindowError as inner:
             # (indices and results are numbered inside `members`: hand them up in the caller's numbering)
             partial = inner.results
@@ -401,7 +454,8 @@ class UISRNN:
             partial = []
             for u in members:
               try:
-                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best, posterior)
+                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best, posterior,
+                                                                          lim_of([u]))
                 one_err = inner if len(members) == 1 else None
               except LookAheadWindowError as e1:
                 one, one_err = [None], e1
@@ -460,7 +514,7 @@ class UISRNN:
               'more than {} clusters per hypothesis'.format(_MAX_CLUSTERS_LIMIT))
     with self._state_lock:  # (parallel_predict: the last worker to finish wins, whole)
       self.last_stats = stats
-      self._single_pass = cap == _initial_cluster_cap(args)  # no retry: one decode covered everything
+      self._single_pass = cap == _initial_cluster_cap(args, limits)  # no retry: one decode covered everything
     return results
 
   def predict_and_evaluate(self, test_sequences, test_cluster_ids, args):
@@ -515,12 +569,13 @@ class UISRNN:
                          for ids, p in zip(test_cluster_ids, predicted)]
     return predicted, [float(m) / int(n) for m, n in zip(matched, lens)]
 
-  def predict_single(self, test_sequence, args):
+  def predict_single(self, test_sequence, args, max_speakers=None):
     """Predict labels for one test sequence (uisrnn/uisrnn.py:479-562).
 
     Args:
       test_sequence: 2-dim float64 numpy array [N, D].
       args: inference namespace (beam_size, look_ahead, test_iteration).
+      max_speakers: see predict (extension).
 
     Returns:
       list of N ints: the predicted cluster id per frame.
@@ -530,30 +585,39 @@ class UISRNN:
       ValueError: wrong rank or observation dimension.
     """
     self._check_sequence(test_sequence)
-    return self._decode_batch([test_sequence], args)[0]
+    return self._decode_batch([test_sequence], args, limits=_check_max_speakers(max_speakers, args, 1))[0]
 
-  def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None):
+  def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
+             max_speakers=None):
     """An OnlineSession (streaming decode; extension, see the class).  horizon: None, or the decision
     horizon in frames of a session that commits by itself when a push does not fit its window.  retire_at: None,
     or the cluster count from which the session retires speakers by itself, down to retire_to (default
-    retire_at // 2): see OnlineSession.retire."""
+    retire_at // 2): see OnlineSession.retire.  max_speakers: None, an int or one entry per utterance: the slots'
+    bounds (OnlineSession.set_max_speakers)."""
+    limits = _check_max_speakers(max_speakers, args, num_utterances)
     if args.look_ahead != 1:
       raise ValueError('online decoding needs look_ahead 1')
     if self.transition_bias is None:
       raise TypeError('transition_bias is None: the model was never fit or loaded')
-    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon, retire_at, retire_to)
+    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon, retire_at, retire_to, limits)
 
-  def online_pool(self, slots, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None):
+  def online_pool(self, slots, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
+                  max_speakers=None):
     """A StreamPool over one OnlineSession of `slots` utterances (extension, see the class): for callers
     whose streams begin and end independently of each other."""
-    return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to))
+    return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers))
 
-  def predict(self, test_sequences, args):
+  def predict(self, test_sequences, args, max_speakers=None):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
 
     A list is decoded as ONE lock-step batch on the GPU (the reference loops
     over it serially); the results are the same as calling predict_single on
     each element.
+
+    max_speakers (extension): None, an int, or a sequence with one entry (an int, 0 or None) per sequence: a
+    hypothesis that already holds that many clusters opens no further one; everything else is the unbounded decode's
+    (DESIGN.md section 24).  None falls back to getattr(args, 'max_speakers', None).  ValueError for a bool, a float
+    that is not whole, a negative, a value above 4096 or a wrong length.
 
     Raises:
       TypeError: test_sequences is neither a list nor a numpy array.
@@ -564,21 +628,23 @@ class UISRNN:
         have); the exception names them and carries the other utterances' results.
     """
     if isinstance(test_sequences, np.ndarray):
-      return self.predict_single(test_sequences, args)
+      return self.predict_single(test_sequences, args, max_speakers)
     if isinstance(test_sequences, list):
+      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args)
+      return self._decode_batch(test_sequences, args, limits=limits)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
-  def predict_nbest(self, test_sequences, args, n_best=None):
+  def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None):
     """predict, returning every hypothesis of the final beam instead of the best one (extension).
 
     Args:
       test_sequences, args: as predict.
       n_best: the most hypotheses wanted per sequence, in [1, args.beam_size] (default: beam_size).
+      max_speakers: as predict.
     Returns:
       for an array the pair (labelings, scores): at most n_best label lists -- fewer when the final
       beam holds fewer -- best first, and their scores as floats, ascending; labelings[0] is predict's
@@ -595,16 +661,18 @@ class UISRNN:
       raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(args.beam_size))
     if isinstance(test_sequences, np.ndarray):
       self._check_sequence(test_sequences)
-      return self._decode_batch([test_sequences], args, n_best=int(n_best))[0]
+      return self._decode_batch([test_sequences], args, n_best=int(n_best),
+                                limits=_check_max_speakers(max_speakers, args, 1))[0]
     if isinstance(test_sequences, list):
+      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args, n_best=int(n_best))
+      return self._decode_batch(test_sequences, args, n_best=int(n_best), limits=limits)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
-  def predict_posteriors(self, test_sequences, args, temperature=1.0):
+  def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None):
     """predict, with the beam's per-frame confidence in its answer (extension).
 
     With w_k = softmax(-score_k / temperature) over the hypotheses of the final beam:
@@ -619,6 +687,7 @@ class UISRNN:
       temperature: a finite number > 0.  1 is the model's own posterior; a sharply peaked model (a trained D = 256
         one puts all but 1e-3, usually all but 1e-11, on the best hypothesis) needs a larger one to rank its
         uncertain frames.
+      max_speakers: as predict.
     Returns:
       for an array the triple (labels, confidence, change): predict's answer and two float32 arrays of its length.
       For a list, a list of such triples.  One decode, with predict's cap and level retries.
@@ -629,16 +698,18 @@ class UISRNN:
     temperature = _check_temperature(temperature)
     if isinstance(test_sequences, np.ndarray):
       self._check_sequence(test_sequences)
-      return self._decode_batch([test_sequences], args, posterior=temperature)[0]
+      return self._decode_batch([test_sequences], args, posterior=temperature,
+                                limits=_check_max_speakers(max_speakers, args, 1))[0]
     if isinstance(test_sequences, list):
+      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args, posterior=temperature)
+      return self._decode_batch(test_sequences, args, posterior=temperature, limits=limits)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
-  def predict_primed(self, test_sequences, prefix_cluster_ids, args):
+  def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
     """predict, with the first frames of every sequence already labeled (extension).
 
     The decode of sequence u starts from the state the model holds after prefix_cluster_ids[u] along its
@@ -650,6 +721,7 @@ class UISRNN:
       prefix_cluster_ids: P <= N ids for an array (any hashable kind, renamed by order of first
         appearance; may be empty), or a list of such sequences for a list.
       args: inference namespace; look_ahead and test_iteration must be 1 (online decoding).
+      max_speakers: as predict.  A prefix with more clusters than its bound is kept: it opens nothing more.
     Returns:
       N ints for an array, a list of such lists for a list; the first P_u are the renamed prefix.
     Raises:
@@ -669,6 +741,7 @@ class UISRNN:
       raise TypeError('test_sequences should be either a list or numpy array.')
     if int(args.look_ahead) != 1 or int(args.test_iteration) != 1:
       raise ValueError('predict_primed is online decoding: look_ahead and test_iteration must be 1.')
+    limits = _check_max_speakers(max_speakers, args, len(seqs))
     for seq in seqs:
       self._check_sequence(seq)
     prefixes = []
@@ -684,7 +757,7 @@ class UISRNN:
     decoder = self._get_decoder()
     results = [None] * len(seqs)
     pending = list(range(len(seqs)))
-    cap = _initial_cluster_cap(args)
+    cap = _initial_cluster_cap(args, limits)
 
     def more_room(cap):
       if cap * 2 > _MAX_CLUSTERS_LIMIT:
@@ -693,7 +766,8 @@ class UISRNN:
 
     while pending:
       lens = [seqs[u].shape[0] for u in pending]
-      decoder.stream_begin(len(pending), args.beam_size, max(max(lens), 1), max_clusters=cap)
+      bound = {} if limits is None else {'limits': [limits[u] for u in pending]}
+      decoder.stream_begin(len(pending), args.beam_size, max(max(lens), 1), max_clusters=cap, **bound)
       try:
         try:
           decoder.stream_prime([seqs[u][:len(prefixes[u])] for u in pending], [prefixes[u] for u in pending])
@@ -901,7 +975,7 @@ class OnlineSession:
   _seen = None    # per utterance {id: stream position of its last committed appearance}
 
   def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None,
-               retire_to=None):
+               retire_to=None, limits=None):
     if horizon is not None and (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 0):
       raise ValueError('horizon must be None or a non-negative integer.')
     cap = None if args is None else _initial_cluster_cap(args)
@@ -915,18 +989,31 @@ class OnlineSession:
     self._bound = [0] * int(num_utterances)
     self._seen = [{} for _ in range(int(num_utterances))]
     self.persistent = False
+    bound = {} if limits is None else {'limits': limits}
     if persistent:
       try:
         self._decoder.stream_begin(num_utterances, args.beam_size, max_frames, max_clusters=cap,
-                                   flags=_capi.UIS_FLAG_PERSISTENT)
+                                   flags=_capi.UIS_FLAG_PERSISTENT, **bound)
         self.persistent = True
       except _capi.HipLibraryError as err:
         if err.status != _capi.UIS_ERR_UNSUPPORTED:
           raise
     if not self.persistent:
-      self._decoder.stream_begin(num_utterances, args.beam_size, max_frames, max_clusters=cap)
+      self._decoder.stream_begin(num_utterances, args.beam_size, max_frames, max_clusters=cap, **bound)
     self._open = True
     self._num_utterances = int(num_utterances)
+
+  def set_max_speakers(self, values):
+    """Replace the slots' bounds between two pushes (uis_stream_limits): None, an int, or one entry (an int, 0 or
+    None) per utterance.  A hypothesis that holds at least its utterance's bound opens no further cluster; one
+    already above a lowered bound is kept.  The bounds belong to the slots: restart keeps them, an imported stream
+    decodes on under its new slot's, snapshots do not carry them.  ValueError as predict's max_speakers."""
+    limits = _check_max_speakers(0 if values is None else values, None, self._num_utterances)
+    self._decoder.stream_set_limits(limits if limits is not None else [0] * self._num_utterances)
+
+  def max_speakers(self):
+    """The slots' bounds: a list with an int or None (no bound) per utterance."""
+    return [int(v) if v else None for v in self._decoder.stream_limits()]
 
   def prime(self, chunks, cluster_ids):
     """Start utterances from a labeled prefix (uis_stream_prime; extension).
@@ -1415,12 +1502,18 @@ class StreamPool:
     self._slot = {}   # key -> slot
     self._free = list(range(session._num_utterances - 1, -1, -1))  # pylint: disable=protected-access
 
-  def open(self, key):
-    """Take a free slot for a new stream.  Returns the slot's index."""
+  def open(self, key, max_speakers=None):
+    """Take a free slot for a new stream.  Returns the slot's index.  max_speakers: None (the slot keeps the bound it
+    has), 0 (no bound) or the bound the slot gets for this stream."""
     if key in self._slot:
       raise KeyError('stream {!r} is already open'.format(key))
     if not self._free:
       raise RuntimeError('no free slot')
+    if max_speakers is not None:
+      limit = _check_max_speakers([max_speakers], None, 1)
+      values = self._session.max_speakers()
+      values[self._free[-1]] = limit[0] if limit else 0
+      self._session.set_max_speakers(values)
     self._slot[key] = self._free.pop()
     return self._slot[key]
 
@@ -1485,7 +1578,7 @@ class StreamPool:
     self.close()
 
 
-def parallel_predict(model, test_sequences, args, num_processes=4, devices=None):
+def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None):
   """Drop-in for uisrnn.parallel_predict (uisrnn/uisrnn.py:593-623).
 
   The reference maps utterances over a forkserver process pool.  Here the
@@ -1498,6 +1591,7 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None)
   Args:
     devices: optional explicit list of HIP device indices (repeats allowed --
       used by the tests to exercise the path on a single-GPU box).
+    max_speakers: as UISRNN.predict (extension); every shard takes its members' entries.
 
   Raises:
     TypeError: test_sequences is not a list.
@@ -1506,13 +1600,14 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None)
     raise TypeError('test_sequences must be a list.')
   for test_sequence in test_sequences:
     model._check_sequence(test_sequence)  # pylint: disable=protected-access
+  limits = _check_max_speakers(max_speakers, args, len(test_sequences))
   if not test_sequences:
     return []
   if devices is None:
     n_dev = max(_capi.load_library().uis_device_count(), 1)
     devices = list(range(max(1, min(int(num_processes), n_dev))))
   if len(devices) == 1:
-    return model._decode_batch(test_sequences, args, device=devices[0])  # pylint: disable=protected-access
+    return model._decode_batch(test_sequences, args, device=devices[0], limits=limits)  # pylint: disable=protected-access
   import threading  # pylint: disable=import-outside-toplevel
   from uisrnn_amd import distributed  # pylint: disable=import-outside-toplevel
   shards = distributed.shard_utterances(
@@ -1526,7 +1621,8 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None)
   def run(worker, shard):
     try:
       if shard:
-        out = worker.decode([test_sequences[i] for i in shard], args)
+        out = worker.decode([test_sequences[i] for i in shard], args,
+                            None if limits is None else [limits[i] for i in shard])
         for i, labels in zip(shard, out):
           results[i] = labels
     except Exception as exc:  # pylint: disable=broad-except
@@ -1556,9 +1652,9 @@ class _Worker:
     self._decoder = (_capi.Decoder(model.params, device) if self._own
                      else model._get_decoder(device))  # pylint: disable=protected-access
 
-  def decode(self, sequences, args):
+  def decode(self, sequences, args, limits=None):
     return self._model._decode_batch(  # pylint: disable=protected-access
-        sequences, args, decoder=self._decoder)
+        sequences, args, decoder=self._decoder, limits=limits)
 
   def close(self):
     if self._own:
