@@ -423,6 +423,38 @@ int32_t uis_stream_limits(uis_handle* h, const int32_t* limits);
 int32_t uis_stream_get_limits(uis_handle* h, int32_t* out);
 
 /*
+ * Per-frame transition_bias: decode (and score) under soft and hard turn priors.
+ *
+ * bias[t] in [0, 1] is the probability that frame t of the NEXT call that takes frames changes speaker -- the model's
+ * scalar transition_bias made time-varying (a speaker-change detector's output, a segment boundary, the inside of a
+ * word); NaN means "the model's own".  For every frame the library forms, in float64 with the C library's log and the
+ * expressions of uis_create, (log(1 - b), log(b), log(b) + log(crp_alpha)); the step that decides frame t reads them
+ * wherever it reads the model's three words today: a look_ahead-1 step, sub-step j of a look-ahead window (its own
+ * frame), the second pass of test_iteration 2 (frame t % n).  Nothing else changes -- the ddCRP terms, the float32
+ * accumulation, the prune order, the tie rules, max_speakers -- and an all-NaN table, or one holding exactly the model's
+ * value, gives the decode without a table bit for bit.
+ *
+ * log(0) = -inf makes a candidate's loss +inf, and every select drops such a candidate: b = 0 keeps the frame with the
+ * previous speaker (only the candidate of the last label is finite), b = 1 makes it change.  A contradiction -- b = 1 under
+ * max_speakers 1, or b = 0 at a frame no hypothesis has a previous label for -- leaves an empty beam, reported as ever
+ * (labels -1, score +inf).
+ *
+ *   uis_frame_bias   bias: host float64 [n_frames], each in [0, 1] or NaN (else UIS_ERR_INVALID_ARG, and the pending
+ *                    table stays as it was); bias == NULL or n_frames == 0 clears a pending table.  The table belongs
+ *                    to the NEXT uis_decode / uis_decode_f64 / uis_decode_device / uis_stream_push / uis_score_labels /
+ *                    uis_score_speakers on this handle, in that call's frame order (utterance-major; a push: the
+ *                    chunk's), and must hold exactly that call's frame count (else that call returns
+ *                    UIS_ERR_INVALID_ARG and nothing runs).  The call consumes it whether it succeeds or not; a call
+ *                    without a pending table uses the model's value, whatever an earlier call used.
+ *
+ * uis_stream_prime (its prefix is scored with the model's value) and a push into a UIS_FLAG_PERSISTENT session (whose
+ * resident launch would need the table through its mailbox) refuse a pending table with UIS_ERR_UNSUPPORTED, consume it
+ * and stay usable.  A decode with a table runs the kernels with the owner-side selects: where the decode without one
+ * reports k_decode_rs or k_decode_big<WS>, uis_last_decode_instantiation reports k_decode_resident or k_decode_big.
+ */
+int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames);
+
+/*
  * Primed sessions: start the online decode of an open session's utterances from a LABELED PREFIX (enrolment,
  * a corrected opening, a recording continued across a seam).  Afterwards the session is in the state it would
  * hold had it received the prefix frames and its beam contained only the given hypothesis: the state

@@ -338,6 +338,8 @@ def load_library(path=None):
   lib.uis_stream_limits.argtypes = [ctypes.c_void_p, i32p]
   lib.uis_stream_get_limits.restype = i32
   lib.uis_stream_get_limits.argtypes = [ctypes.c_void_p, i32p]
+  lib.uis_frame_bias.restype = i32
+  lib.uis_frame_bias.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64]
   lib.uis_stream_prime.restype = i32
   lib.uis_stream_prime.argtypes = [ctypes.c_void_p, _fp, i64p, i32p, _fp]
   lib.uis_last_decode_nbest.restype = i32
@@ -405,7 +407,7 @@ EXPORTED_SYMBOLS = (
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
-    'uis_stream_get_limits', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_stream_get_limits', 'uis_frame_bias', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
@@ -517,8 +519,18 @@ class Decoder:
     self._check(self._lib.uis_decode_limits(
         self._handle, lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(lim.shape[0])), 'uis_decode_limits')
 
+  def set_frame_bias(self, bias):
+    """uis_frame_bias: the per-frame transition_bias (float64, one value per frame in the call's frame order, NaN = the
+    model's; None clears) of the NEXT decode* / stream_push / score_* call on this decoder, which consumes it."""
+    if bias is None:
+      self._check(self._lib.uis_frame_bias(self._handle, None, 0), 'uis_frame_bias')
+      return
+    b = np.ascontiguousarray(bias, dtype=np.float64).reshape(-1)
+    self._check(self._lib.uis_frame_bias(
+        self._handle, b.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(b.shape[0])), 'uis_frame_bias')
+
   def decode(self, frames, offsets, beam_size, look_ahead, test_iteration,
-             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None):
+             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None):
     """Decode packed host utterances.
 
     Args:
@@ -543,6 +555,8 @@ class Decoder:
     stats = Stats()
     if limits is not None:
       self.set_limits(limits)
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_decode(
         self._handle, frames.ctypes.data_as(_fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -565,7 +579,7 @@ class Decoder:
     return out
 
   def decode_f64(self, sequences, beam_size, look_ahead, test_iteration,
-                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None):
+                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None):
     """Decode a list of [N_u, D] float64 arrays as predict() receives them (uis_decode_f64:
     the library casts to float32 on its own threads while earlier chunks travel to the device).
 
@@ -585,6 +599,8 @@ class Decoder:
     stats = Stats()
     if limits is not None:
       self.set_limits(limits)
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_decode_f64(
         self._handle, ptrs, lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
         ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
@@ -604,7 +620,7 @@ class Decoder:
       out['beam_scores'] = beam_scores
     return out
 
-  def score_labels(self, frames, offsets, labels, want_frame_losses=False):
+  def score_labels(self, frames, offsets, labels, want_frame_losses=False, bias=None):
     """The model's NLL of given labelings (uis_score_labels).
 
     Args:
@@ -626,6 +642,8 @@ class Decoder:
       raise ValueError('labels must be [offsets[-1]]')
     scores = np.empty(n_utt, dtype=np.float32)
     losses = np.empty(total, dtype=np.float32) if want_frame_losses else None
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_score_labels(
         self._handle, frames.ctypes.data_as(_fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -634,7 +652,7 @@ class Decoder:
     self._check(rc, 'uis_score_labels')
     return (scores, losses) if want_frame_losses else scores
 
-  def score_speakers(self, frames, offsets, labels, width, losses_out=None):
+  def score_speakers(self, frames, offsets, labels, width, losses_out=None, bias=None):
     """Every speaker's per-frame loss along given labelings (uis_score_speakers).
 
     Args:
@@ -663,6 +681,8 @@ class Decoder:
     losses = np.empty((total, max(width, 0)), dtype=np.float32) if losses_out is None else losses_out
     if losses.dtype != np.float32 or losses.shape != (total, max(width, 0)) or not losses.flags['C_CONTIGUOUS']:
       raise ValueError('losses_out must be a C-contiguous float32 [offsets[-1], width] array')
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_score_speakers(
         self._handle, frames.ctypes.data_as(_fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -739,10 +759,11 @@ class Decoder:
                 'uis_stream_get_limits')
     return out
 
-  def stream_push(self, chunks):
+  def stream_push(self, chunks, bias=None):
     """chunks: one [n_u, D] array (or None / empty) per utterance: its new frames -- or ONE
     [n_utt, n, D] array when every utterance has the same number of new frames (one cast, no
-    per-utterance Python work: the low-latency way to feed a live session)."""
+    per-utterance Python work: the low-latency way to feed a live session).  bias: this push's per-frame
+    transition_bias, float64 in the chunk's own frame order (utterance-major), or None (set_frame_bias)."""
     if len(chunks) != self._stream_n:
       raise ValueError('one chunk (or None) per utterance')
     dim = self.observation_dim
@@ -751,6 +772,8 @@ class Decoder:
         raise ValueError('chunk does not match observation_dim')
       frames = np.ascontiguousarray(chunks, dtype=np.float32)
       counts = np.full(self._stream_n, chunks.shape[1], dtype=np.int32)
+      if bias is not None:
+        self.set_frame_bias(bias)
       rc = self._lib.uis_stream_push(
           self._handle, frames.ctypes.data_as(_fp) if frames.size else None,
           counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
@@ -782,6 +805,8 @@ class Decoder:
     if frames64.shape[0] and frames64.shape[1] != dim:
       raise ValueError('chunk does not match observation_dim')
     frames = frames64.astype(np.float32, copy=False)
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_stream_push(self._handle, frames.ctypes.data_as(_fp) if len(frames) else None, self._stream_counts_ptr)
     self._check(rc, 'uis_stream_push')
     self._stream_have += counts
@@ -1089,7 +1114,7 @@ class Decoder:
     return self._posterior(self._lib.uis_stream_posterior, 'uis_stream_posterior', temperature, offsets, self._stream_beam)
 
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
-                  labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None):
+                  labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None, bias=None):
     """uis_decode on raw HOST pointers (e.g. pinned buffers from uis_host_alloc or torch)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     n_utt = offsets.shape[0] - 1
@@ -1097,6 +1122,8 @@ class Decoder:
     stats = Stats()
     if limits is not None:
       self.set_limits(limits)
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_decode(
         self._handle, ctypes.cast(ctypes.c_void_p(int(frames_ptr)), _fp),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
@@ -1150,7 +1177,7 @@ class Decoder:
 
   def decode_device(self, d_frames_ptr, offsets, beam_size, look_ahead,
                     test_iteration, d_labels_ptr, d_scores_ptr, max_clusters=0,
-                    flags=0, n_streams=0, limits=None):
+                    flags=0, n_streams=0, limits=None, bias=None):
     """Decode with frames/labels/scores already resident in HBM (raw pointers)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     n_utt = offsets.shape[0] - 1
@@ -1159,6 +1186,8 @@ class Decoder:
     stats = Stats()
     if limits is not None:
       self.set_limits(limits)
+    if bias is not None:
+      self.set_frame_bias(bias)
     rc = self._lib.uis_decode_device(
         self._handle, ctypes.c_void_p(int(d_frames_ptr)),
         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,

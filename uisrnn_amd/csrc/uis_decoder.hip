@@ -158,6 +158,7 @@ struct ProfileEvents {
 struct StreamMem {
   std::vector<DevBuf> allocs;  // the session's state, one allocation per table (uis_stream_begin)
   DevBuf chunk_x, chunk_pad, chunk_gi0, chunk_mse0, labels, scores;
+  DevBuf chunk_bias;  // [chunk frames][3] float64: DecodeState::bias3 of a push with a uis_frame_bias table
   // one push = one H2D copy: [foff U x int64][avail U x int32, padded][frames] staged in pinned
   // host memory (h_stage) and mirrored in chunk_x
   HostBuf h_stage;
@@ -173,6 +174,7 @@ struct HandleMem {
   DevBuf gi_up, a1, counters, beam_scores_out, io_frames, io_labels, io_scores, mse_tab, dbg_scores, utt_nrows, hst;
   DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
   DevBuf limit, limit_in;  // [U] int32 each: DecodeState::limit, written by every decode, and uis_decode_limits' table it is written from
+  DevBuf bias3;  // [frames][3] float64: DecodeState::bias3 of a decode with a uis_frame_bias table (the workspace's last view)
   DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   HostBuf h_cast;  // uis_decode_f64: the pinned float32 staging buffer the utterances are cast into, chunk by chunk, ahead of each H2D copy
@@ -182,6 +184,7 @@ struct HandleMem {
   // uis_score_speakers' own: labels + each frame's row, logblk + logden, the candidate table [F][width] {mean row, block
   // count}, the frame table [F] {K, sum, last}, the rows [F][width]
   DevBuf sc_spk_in, sc_spk_log, sc_spk_cand, sc_spk_frame, sc_spk_loss;
+  DevBuf sc_spk_bias;  // ... and the call's {lp_stay, lp_sw, lp_new} per frame, where uis_frame_bias left a table
   // the scratch block of one uis_stream_prime / _commit / _restart / _retire call (session_buffers in uis_stream.hip;
   // every such call synchronises before it returns, so no two are ever live; prime's forced run uses the sc_* above)
   DevBuf sc_session;
@@ -285,6 +288,10 @@ struct uis_handle : HandleMem {
   // took from it (take_limits, at that call's entry: consumed whether the call succeeds or not)
   std::vector<int32_t> pending_limits, call_limits;
   bool pending_limits_set = false, call_limits_set = false;
+  // per-frame transition_bias: {lp_stay, lp_sw, lp_new} per frame as uis_frame_bias formed them for the next call that
+  // takes frames, and the running call's (take_bias, at that call's entry: consumed whether the call succeeds or not)
+  std::vector<double> pending_bias3, call_bias3;
+  bool pending_bias_set = false, call_bias_set = false;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
   // offsets, the record format
@@ -813,6 +820,9 @@ struct DecodeShape {
   bool wnd;                    // the window machinery decodes (look_ahead >= 2, wide beams, select tables beyond LDS)
   size_t select_lds;           // select_lds_layout(...).total (without wnd)
   size_t window_scratch;       // window_scratch_layout(...).total
+  // the call has a per-frame transition_bias table (uis_frame_bias).  k_decode_rs and k_decode_big<WS> form their priors
+  // in rs_prep, which knows no table: such a decode runs the kernels with the owner-side selects
+  bool biased = false;
 };
 
 enum class DecodePath { STEPWISE, GRAPH, RESIDENT, RS, BIG, BIG_WS, WINDOW, DEEP, SMALL };
@@ -922,7 +932,7 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
                    big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B) <= 157 * 1024;
 
   if (resident) {
-    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0;
+    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0 || s.biased;
     const int per_xcd = (U + p.ncl - 1) / p.ncl;
     // (k_decode_rs keeps frame numbers in 32 bits and reads the frame stream through 4 GB descriptors with 32-bit byte
     // offsets: a row of gi0 is 3 Hp floats, a row of x Dp)
@@ -1390,6 +1400,9 @@ int derive_shape(DecodeCall& c) {
     maxN = std::max(maxN, n);
   }
   const int64_t F = n_utt ? offsets[n_utt] : 0;
+  if (h->call_bias_set && (int64_t)h->call_bias3.size() != 3 * F)
+    return fail(UIS_ERR_INVALID_ARG, "uis_frame_bias gave " + std::to_string(h->call_bias3.size() / 3) + " values, this decode has " +
+                                         std::to_string(F) + " frames");
   bool ragged_list = false;  // (utterances of different lengths)
   for (int u = 1; u < n_utt; ++u) ragged_list = ragged_list || offsets[u + 1] - offsets[u] != offsets[1] - offsets[0];
   if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
@@ -1474,7 +1487,7 @@ int derive_shape(DecodeCall& c) {
     for (int u = 0; u < U; ++u)
       c.bp_base[u + 1] = c.bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
   c.shape = DecodeShape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, c.h_frames != nullptr,
-                        wnd, (size_t)lds.total, c.wsl.total};
+                        wnd, (size_t)lds.total, c.wsl.total, h->call_bias_set};
   return UIS_OK;
 }
 
@@ -1558,6 +1571,9 @@ int upload_tables(DecodeCall& c) {
   // so that nothing depends on what an earlier call left there and an unbounded decode pays no copy)
   if (h->call_limits_set)
     HIPCHK(hipMemcpyAsync(h->limit_in.p, h->call_limits.data(), (size_t)s.U * 4, hipMemcpyHostToDevice, h->stream));
+  // (uis_frame_bias: the whole table ahead of the first launch, also of a decode in several)
+  if (h->call_bias_set && s.F > 0)
+    HIPCHK(hipMemcpyAsync(h->bias3.p, h->call_bias3.data(), (size_t)s.F * 24, hipMemcpyHostToDevice, h->stream));
   if (int rc = upload_log_tables(h->alpha, c.n_log, c.log_host, h->logblk.p, h->logden.p, h->stream)) return rc;
   if (s.wnd)
     HIPCHK(hipMemcpyAsync(h->bp_base.p, c.bp_base.data(), (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -1798,6 +1814,7 @@ void build_group_states(DecodeCall& c) {
     st.overflow = h->overflow.as<int32_t>() + u0;
     st.limit = h->limit.as<int32_t>() + u0;
     st.limit_in = h->call_limits_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
+    st.bias3 = h->call_bias_set ? h->bias3.as<double>() : nullptr;  // (indexed by the packed frame, like mse0)
     st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
@@ -2218,17 +2235,67 @@ UIS_EXPORT int32_t uis_decode_limits(uis_handle* h, const int32_t* limits, int32
   return UIS_OK;
 }
 
+// The same for uis_frame_bias' table, at every entry point that takes frames.
+static void take_bias(uis_handle* h) {
+  if (!h) return;
+  h->call_bias3.swap(h->pending_bias3);
+  h->call_bias_set = h->pending_bias_set;
+  h->pending_bias3.clear();
+  h->pending_bias_set = false;
+}
+
+// The running call's table must cover exactly its frames.
+static int check_bias_frames(uis_handle* h, int64_t n_frames) {
+  if (h->call_bias_set && (int64_t)h->call_bias3.size() != 3 * n_frames)
+    return fail(UIS_ERR_INVALID_ARG, "uis_frame_bias gave " + std::to_string(h->call_bias3.size() / 3) + " values, this call has " +
+                                         std::to_string(n_frames) + " frames");
+  return UIS_OK;
+}
+
+// Calls that cannot honour a table refuse a pending one (and consume it).
+static int refuse_bias(uis_handle* h, const char* who) {
+  take_bias(h);
+  if (!h || !h->call_bias_set) return UIS_OK;
+  h->call_bias_set = false;
+  h->call_bias3.clear();
+  return fail(UIS_ERR_UNSUPPORTED, std::string(who) + " takes no per-frame transition_bias (uis_frame_bias): the pending table is dropped");
+}
+
+UIS_EXPORT int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!bias || n_frames == 0) { h->pending_bias3.clear(); h->pending_bias_set = false; return UIS_OK; }
+  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
+  for (int64_t t = 0; t < n_frames; ++t)
+    if (!(std::isnan(bias[t]) || (bias[t] >= 0.0 && bias[t] <= 1.0)))
+      return fail(UIS_ERR_INVALID_ARG, "transition_bias at frame " + std::to_string(t) + " is outside [0, 1] (NaN: the model's)");
+  const DevModel& m = h->m;
+  std::vector<double>& w = h->pending_bias3;
+  w.resize((size_t)n_frames * 3);
+  for (int64_t t = 0; t < n_frames; ++t) {
+    const double b = bias[t];
+    double* o = w.data() + 3 * t;
+    if (std::isnan(b)) { o[0] = m.lp_stay; o[1] = m.lp_sw; o[2] = m.lp_new; continue; }
+    // uis_create's expressions, with the C library's log (log(0) = -inf: a hard constraint, dropped by every select)
+    o[0] = std::log(1.0 - b);
+    o[1] = std::log(b);
+    o[2] = o[1] + m.l_alpha;
+  }
+  h->pending_bias_set = true;
+  return UIS_OK;
+}
+
 UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
                                      const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out,
                                      uis_stats* stats) {
   take_limits(h);
+  take_bias(h);
   if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
 }
 
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                               const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
-  if (h && !h->src64) take_limits(h);  // (uis_decode_f64 has taken them)
+  if (h && !h->src64) { take_limits(h); take_bias(h); }  // (uis_decode_f64 has taken them)
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
   h->nb_valid = false;  // (a decode refused below leaves nothing for uis_last_decode_nbest either)
   const int64_t F = n_utt ? offsets[n_utt] : 0;
@@ -2285,6 +2352,7 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
 UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances, const int64_t* n_frames, int32_t n_utt,
                                   const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
   take_limits(h);
+  take_bias(h);
   if (!h || n_utt < 0 || (n_utt > 0 && (!utterances || !n_frames)))
     return fail(UIS_ERR_INVALID_ARG, "null handle/utterances/n_frames or negative n_utt");
   h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)

@@ -223,4 +223,20 @@ struct DecodeState {
   // (INT32_MAX: no bound).  Written by every call that decodes, whatever the caller asked for.
   int32_t* limit;            // [U]
   const int32_t* limit_in;   // [U] or null: the caller's table (0: no bound) k_init_state writes `limit` from; null: no bound
+
+  // ---- per-frame transition_bias (uis_frame_bias): {lp_stay, lp_sw, lp_new} of every frame, indexed like mse0 (the
+  // packed frame stream; a session: the chunk's rows).  Formed on the host with the C library's log; a frame without a
+  // value of its own holds the model's three words.  Null: the call has no table and every frame uses DevModel's.
+  const double* bias3;       // [frames][3] or null
 };
+
+// The three prior words of the step that decides `frame` (uniform over the workgroup: one null test, then scalar loads).
+struct StepPriors { double lp_stay, lp_sw, lp_new; };
+__device__ __forceinline__ StepPriors step_priors(const DevModel& m, const DecodeState& st, long frame) {
+  StepPriors p{m.lp_stay, m.lp_sw, m.lp_new};
+  if (st.bias3) {
+    const double* t = st.bias3 + 3 * (size_t)frame;
+    p.lp_stay = t[0]; p.lp_sw = t[1]; p.lp_new = t[2];
+  }
+  return p;
+}

@@ -1006,6 +1006,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
 
   // ---- round trip 2, part 1: this thread's candidate (the first 256) -- prior-table entries
   const float mse_new = st.mse0[frame];
+  const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
@@ -1065,10 +1066,10 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     float mse; double prior;
     if (c < sK[b]) {  // existing cluster, uisrnn.py:409-420
       mse = smse[sslot[b * Kmax + c]];
-      prior = (c == slast[b]) ? m.lp_stay : (m.lp_sw + lb) - ld;
+      prior = (c == slast[b]) ? pr.lp_stay : (pr.lp_sw + lb) - ld;
     } else {          // new cluster, uisrnn.py:440-446
       mse = mse_new;
-      prior = m.lp_new - ld;
+      prior = pr.lp_new - ld;
     }
     float sc = sscore[b] + uis_step_loss(mse, prior);  // float32 accumulate, uisrnn.py:452
     if (c >= sK[b] && c >= lim) sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
@@ -1441,6 +1442,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   // have filled with this line before the write)
   const float mse_new = RES ? __hip_atomic_load(st.mse0 + frame, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : st.mse0[frame];
   const int lim = st.limit[u];  // (written between launches only)
+  const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's; uploaded before the launch)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
@@ -1534,10 +1536,10 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     float mse; double prior;
     if (my_c < sK[my_b]) {
       mse = smse[sslot[my_b * Kmax + my_c]];
-      prior = (my_c == slast[my_b]) ? m.lp_stay : (m.lp_sw + my_lb) - my_ld;
+      prior = (my_c == slast[my_b]) ? pr.lp_stay : (pr.lp_sw + my_lb) - my_ld;
     } else {
       mse = mse_new;
-      prior = m.lp_new - my_ld;
+      prior = pr.lp_new - my_ld;
     }
     my_sc = sscore[my_b] + uis_step_loss(mse, prior);
     if (my_c >= sK[my_b] && my_c >= lim) my_sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
@@ -3272,6 +3274,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
   // ---- candidate scores
   const float mse_new = st.mse0[frame];
   const int lim = st.limit[u];
+  const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: the sub-step's own frame)
   auto node_of = [&](int i) {  // largest node with cbase[node] <= i
     int lo = 0, hi = n_in;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cbase[mid] <= i) lo = mid; else hi = mid; }
@@ -3316,10 +3319,10 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = c0 + e;
-        if (c < Kb) emit(c, mse[sl[e]], (c == lastb) ? m.lp_stay : (m.lp_sw + lb[e]) - ld);
+        if (c < Kb) emit(c, mse[sl[e]], (c == lastb) ? pr.lp_stay : (pr.lp_sw + lb[e]) - ld);
       }
     }
-    emit(Kb, mse_new, Kb < lim ? m.lp_new - ld : -(double)INFINITY);  // max_speakers: at its bound, a loss of +inf = no candidate
+    emit(Kb, mse_new, Kb < lim ? pr.lp_new - ld : -(double)INFINITY);  // max_speakers: at its bound, a loss of +inf = no candidate
   }
   __syncthreads();
   WSTAMP(2);

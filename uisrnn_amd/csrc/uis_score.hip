@@ -294,7 +294,8 @@ __global__ __launch_bounds__(64) void k_speakers_tables(const int64_t* __restric
 // lp_stay for the last label's cluster, else (lp_sw + logblk[blk]) - logden[sum]; k = K(t): the new-speaker candidate
 // (mse0, lp_new - logden[sum]); k > K(t), and every k past an invalid label: +inf.  The decode's float64 expressions, on
 // the uploaded host tables.  One workgroup per frame: x_t and the weights staged once, a wave per candidate.
-__global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, const float* __restrict__ x,
+// bias3 (uis_frame_bias): frame t's {lp_stay, lp_sw, lp_new} in the model's place, or null.
+__global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, const double* __restrict__ bias3, const float* __restrict__ x,
                                                         const float* __restrict__ mse0, const float* __restrict__ mean,
                                                         const int2* __restrict__ cand, const int4* __restrict__ frame,
                                                         const double* __restrict__ logblk, const double* __restrict__ logden,
@@ -305,6 +306,8 @@ __global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, c
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t t = blockIdx.x;
   const int4 f = frame[t];  // {K, sum, last}
+  double lp_stay = m.lp_stay, lp_sw = m.lp_sw, lp_new = m.lp_new;
+  if (bias3) { lp_stay = bias3[3 * t]; lp_sw = bias3[3 * t + 1]; lp_new = bias3[3 * t + 2]; }
   if (f.x > 0) {            // (no open cluster: no MSE to form)
     const f32x4* xt = reinterpret_cast<const f32x4*>(x + t * m.Dp);
     const f32x4* wg = reinterpret_cast<const f32x4*>(m.wgt);
@@ -318,10 +321,10 @@ __global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, c
     if (k < f.x) {
       const int2 c = cand[t * width + k];
       const float mse = wave_weighted_mse(mean + (size_t)c.x * m.Dp, sx, swgt, m.Dp, m.D, lane);
-      const double prior = k == f.z ? m.lp_stay : (m.lp_sw + logblk[c.y]) - logden[f.y];
+      const double prior = k == f.z ? lp_stay : (lp_sw + logblk[c.y]) - logden[f.y];
       v = uis_step_loss(mse, prior);
     } else if (k == f.x) {
-      v = uis_step_loss(mse0[t], m.lp_new - logden[f.y]);
+      v = uis_step_loss(mse0[t], lp_new - logden[f.y]);
     }
     if (lane == 0) out[t * width + k] = v;
   }
@@ -351,7 +354,9 @@ struct ScoreSchedule {
   std::vector<double> logblk, logden;  // the decode's tables (upload_log_tables, uis_workspace.hip), as far as this call reaches
 };
 
-void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int U, const int32_t* labels, ScoreSchedule& s) {
+// bias3: the call's per-frame {lp_stay, lp_sw, lp_new} (uis_frame_bias; [F][3], host) or null: the model's at every frame.
+void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int U, const int32_t* labels, ScoreSchedule& s,
+                    const double* bias3 = nullptr) {
   const int64_t F = offsets[U];
   int64_t maxN = 0;
   for (int u = 0; u < U; ++u) maxN = std::max<int64_t>(maxN, offsets[u + 1] - offsets[u]);
@@ -382,10 +387,12 @@ void score_schedule(const DevModel& m, double alpha, const int64_t* offsets, int
     for (; t < offsets[u + 1]; ++t) {
       const int c = labels[t];
       if (c > K) break;  // invalid trace (uisrnn.py:406-408): +inf from here on
+      const double lp_stay = bias3 ? bias3[3 * t] : m.lp_stay, lp_sw = bias3 ? bias3[3 * t + 1] : m.lp_sw;
+      const double lp_new = bias3 ? bias3[3 * t + 2] : m.lp_new;
       double prior;
-      if (c == last) prior = m.lp_stay;
-      else if (c < K) prior = (m.lp_sw + logblk[blk[c]]) - logden[sum];
-      else prior = m.lp_new - logden[sum];
+      if (c == last) prior = lp_stay;
+      else if (c < K) prior = (lp_sw + logblk[blk[c]]) - logden[sum];
+      else prior = lp_new - logden[sum];
       s.prior[t] = prior;
       if (c == K) { blk.push_back(1); ++sum; ++K; chain_len.push_back(0); }
       else if (c != last) { ++blk[c]; ++sum; }
@@ -447,7 +454,9 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
   const bool prime = keep != nullptr || spk != nullptr;  // (the recurrence bound, the scan's tail and the valid last row)
   ScoreSchedule s_own;
   ScoreSchedule& s = keep ? *keep : s_own;
-  score_schedule(m, h->alpha, offsets, U, labels, s);
+  // (uis_frame_bias: the scoring entry points took the table and checked its length; a priming run never has one)
+  const double* bias3 = (!keep && h->call_bias_set) ? h->call_bias3.data() : nullptr;
+  score_schedule(m, h->alpha, offsets, U, labels, s, bias3);
   const auto t_sched = std::chrono::steady_clock::now();
   const int64_t Fv = s.Fv;
   const int P = (int)s.fbase.size(), nch = (int)s.len.size();
@@ -469,12 +478,13 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
               (rc = h->sc_spk_cand.ensure(need(F, W * 8))) || (rc = h->sc_spk_frame.ensure(need(F, 16))) ||
               (rc = h->sc_spk_loss.ensure(need(F, W * 4)))))
     return rc;
+  if (spk && bias3 && (rc = h->sc_spk_bias.ensure(need(F, 24)))) return rc;
   hipStream_t st = h->stream;
   {  // UIS_POISON_WORKSPACE: every sc_* buffer, ahead of the tables and the frames on the same stream
     const UisPoison poison = UisPoison::from_env();
     for (DevBuf* b : {&h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0, &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean,
                       &h->sc_gi_up, &h->sc_rows, &h->sc_chains, &h->sc_utt, &h->sc_out, &h->sc_spk_in, &h->sc_spk_log,
-                      &h->sc_spk_cand, &h->sc_spk_frame, &h->sc_spk_loss})
+                      &h->sc_spk_cand, &h->sc_spk_frame, &h->sc_spk_loss, &h->sc_spk_bias})
       HIPCHK(poison.device(b->p, b->cap, st));
   }
   int32_t* d_row_frame = h->sc_rows.as<int32_t>();
@@ -506,6 +516,7 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     HIPCHK(hipMemcpyAsync(d_labels, labels, (size_t)F * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_logblk, s.logblk.data(), nlog * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_logden, s.logden.data(), nlog * 8, hipMemcpyHostToDevice, st));
+    if (bias3) HIPCHK(hipMemcpyAsync(h->sc_spk_bias.p, bias3, (size_t)F * 24, hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipEventRecord(h->ev_begin, st));
   Launcher lch{h, st, false};
@@ -570,7 +581,8 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
              d_frame_row);
     LAUNCH(UIS_K_SELECT, k_speakers_tables, dim3((unsigned)U, (unsigned)((W + 63) / 64)), dim3(64), 0, d_off, d_nvalid, d_labels,
            d_frame_row, (int)W, h->sc_spk_cand.as<int2>(), h->sc_spk_frame.as<int4>());
-    LAUNCH(UIS_K_SELECT, k_score_speakers, dim3((unsigned)F), dim3(256), (size_t)2 * m.Dp * 4, m, (int)W, d_x, mse0,
+    LAUNCH(UIS_K_SELECT, k_score_speakers, dim3((unsigned)F), dim3(256), (size_t)2 * m.Dp * 4, m, (int)W,
+           bias3 ? h->sc_spk_bias.as<double>() : (const double*)nullptr, d_x, mse0,
            h->sc_mean.as<float>(), h->sc_spk_cand.as<int2>(), h->sc_spk_frame.as<int4>(), d_logblk, d_logden,
            h->sc_spk_loss.as<float>());
   }
@@ -612,16 +624,20 @@ int score_check(uis_handle* h, const float* frames, const int64_t* offsets, int3
 
 UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                     const int32_t* labels, float* scores_out, float* frame_losses_out) {
+  take_bias(h);
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
+  if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;
   if (done) return UIS_OK;
   return score_run(h, frames, offsets, n_utt, labels, scores_out, frame_losses_out);
 }
 
 UIS_EXPORT int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                       const int32_t* labels, int32_t width, float* losses_out, float* scores_out) {
+  take_bias(h);
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
+  if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;
   if (width < 1) return fail(UIS_ERR_INVALID_ARG, "width must be at least 1");
   if (done) return UIS_OK;
   const int64_t F = offsets[n_utt];

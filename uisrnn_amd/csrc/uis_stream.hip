@@ -482,6 +482,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
 }
 
 UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
+  take_bias(h);  // (uis_frame_bias: this push's table, in the chunk's own frame order; consumed whatever happens below)
   if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
   uis_handle::Stream& ss = h->stream_state;
   if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
@@ -499,6 +500,11 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     F += counts[u];
     max_new = std::max<int64_t>(max_new, counts[u]);
   }
+  if (int rcb = check_bias_frames(h, F)) return rcb;
+  // (the resident launch of a UIS_FLAG_PERSISTENT session reads its priors from the kernel arguments it was launched with;
+  // a table would have to travel through the mailbox, whose layout is a protocol of its own: DESIGN.md section 9, "Open")
+  if (h->call_bias_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no per-frame transition_bias (uis_frame_bias): the table is dropped");
   if (F == 0) return UIS_OK;
   if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
   HIPCHK(hipSetDevice(h->device));
@@ -575,6 +581,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if ((rc = ss.chunk_x.ensure(need))) return rc;
   if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
   if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
+  if (h->call_bias_set && (rc = ss.chunk_bias.ensure((size_t)F * 24))) return rc;
   // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
   // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
   ss.poison = UisPoison::from_env();
@@ -583,7 +590,11 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
     HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
     HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_bias.p, ss.chunk_bias.cap, h->stream));
   }
+  // (the table's rows are the chunk's: row foff[u] + step, as mse0; call_bias3 lives until the synchronize below)
+  if (h->call_bias_set)
+    HIPCHK(hipMemcpyAsync(ss.chunk_bias.p, h->call_bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
   int64_t* h_foff = ss.h_stage.as<int64_t>();
   int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + (size_t)U * 8);
   {
@@ -613,6 +624,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   Launcher lch{h, h->stream, false};
   DecodeState st = ss.st;
   st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
+  st.bias3 = h->call_bias_set ? ss.chunk_bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
   const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
   // One-launch path: the chunk's projection fused into the kernel and plain launches after the
   // session's first push make a push one H2D, one memset and ONE kernel.  Measured

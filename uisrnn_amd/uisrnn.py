@@ -71,6 +71,67 @@ def _check_max_speakers(max_speakers, args, n_utt):
   return values if any(values) else None
 
 
+def _check_transition_bias(transition_bias, lengths, single=False, offline=True):
+  """The transition_bias keyword as the library's table: None (the model's value everywhere) or one float64 array per
+  utterance, of that utterance's length (NaN: the model's value at that frame).
+
+  transition_bias: None; a scalar (every frame of every utterance); one array per utterance (None for an utterance
+  without values of its own); with `single` (one sequence) also that sequence's one array.  lengths: the utterances'
+  frame counts.  offline: the utterances start here -- a first value of 0 ("stay with the previous speaker") leaves no
+  hypothesis at all and is refused; a session's chunk may well begin with one.
+  ValueError -- before any device work -- for a bool, a wrong count or length, a value outside [0, 1] and +-inf."""
+  if transition_bias is None:
+    return None
+  lengths = [int(n) for n in lengths]
+
+  def refuse_kind(value):
+    if isinstance(value, (bool, np.bool_)) or (isinstance(value, np.ndarray) and value.dtype == np.bool_):
+      raise ValueError('transition_bias must be numbers in [0, 1] (or NaN for the model\'s value), not a bool.')
+
+  def one(value, n, who):
+    if value is None:
+      return np.full(n, np.nan, dtype=np.float64)
+    refuse_kind(value)
+    if isinstance(value, (list, tuple)):
+      for v in value:
+        refuse_kind(v)
+    try:
+      arr = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+      raise ValueError('transition_bias of {} is not an array of numbers.'.format(who)) from err
+    if arr.ndim != 1 or arr.shape[0] != n:
+      raise ValueError('transition_bias of {} has shape {} for {} frames.'.format(who, arr.shape, n))
+    return np.ascontiguousarray(arr)
+
+  if isinstance(transition_bias, np.ndarray) and transition_bias.ndim == 0:
+    refuse_kind(transition_bias)
+    transition_bias = transition_bias.item()   # (a 0-d array is a scalar)
+  refuse_kind(transition_bias)
+  if isinstance(transition_bias, (int, float, np.integer, np.floating)):
+    tables = [np.full(n, float(transition_bias), dtype=np.float64) for n in lengths]
+  elif not isinstance(transition_bias, (list, tuple, np.ndarray)):
+    raise ValueError('transition_bias must be None, a number or arrays of numbers, not {!r}.'.format(type(transition_bias)))
+  elif single and len(lengths) == 1 and not (
+      len(transition_bias) == 1 and isinstance(transition_bias[0], (list, tuple, np.ndarray))):
+    tables = [one(transition_bias, lengths[0], 'the sequence')]
+  else:
+    if isinstance(transition_bias, np.ndarray) and transition_bias.dtype != object and transition_bias.ndim == 1:
+      raise ValueError('transition_bias for a list of sequences must be a number or one array per sequence.')
+    if len(transition_bias) != len(lengths):
+      raise ValueError('transition_bias has {} entries for {} utterances.'.format(len(transition_bias), len(lengths)))
+    tables = [one(v, n, 'utterance {}'.format(u)) for u, (v, n) in enumerate(zip(transition_bias, lengths))]
+  for u, b in enumerate(tables):
+    bad = ~np.isnan(b) & ~((b >= 0.0) & (b <= 1.0))
+    if bad.any():
+      t = int(np.flatnonzero(bad)[0])
+      raise ValueError('transition_bias of utterance {} is {!r} at frame {}: a value must be in [0, 1] or NaN.'.format(
+          u, float(b[t]), t))
+    if offline and b.shape[0] and b[0] == 0.0:
+      raise ValueError('transition_bias of utterance {} is 0 at its first frame: there is no previous speaker to stay '
+                       'with, no hypothesis could exist.'.format(u))
+  return tables
+
+
 def _initial_cluster_cap(args, limits=None):
   """Device table size (clusters per hypothesis) of the first decode attempt.
 
@@ -347,7 +408,7 @@ class UISRNN:
                        'by args.observation_dim.')
 
   def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
-                    limits=None):
+                    limits=None, bias=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -358,11 +419,16 @@ class UISRNN:
     posterior = a temperature (predict_posteriors): the triple (labels, confidence, change), read likewise.
     limits (_check_max_speakers): None, or one int per sequence (0 = no bound); every regrouping below -- the
     overflow retry's subsets, the halves after UIS_ERR_OOM, the look-ahead retry's groups -- takes its members' entries.
+    bias (_check_transition_bias): None, or one float64 array per sequence: the per-frame transition_bias table, which
+    follows the same regroupings.
     """
     decoder = decoder or self._get_decoder(device)
 
     def lim_of(members):
       return None if limits is None else [limits[u] for u in members]
+
+    def bias_of(members):
+      return None if bias is None else [bias[u] for u in members]
 
     # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
     level_cap = level_cap or int(getattr(args, 'level_cap', 0) or 0)
@@ -381,7 +447,8 @@ class UISRNN:
       try:
         out = decoder.decode_f64(sub, args.beam_size, args.look_ahead,
                                  args.test_iteration, max_clusters=cap, flags=flags, level_cap=level_cap,
-                                 **({} if limits is None else {'limits': lim_of(pending)}))
+                                 **({} if limits is None else {'limits': lim_of(pending)}),
+                                 **({} if bias is None else {'bias': np.concatenate(bias_of(pending))}))
       except _capi.HipLibraryError as err:
         if err.status == _capi.UIS_ERR_OOM and len(pending) > 1:
           # the decode state of this many utterances does not fit the device (or the pinned staging
@@ -392,7 +459,7 @@ class UISRNN:
           for part in (pending[0::2], pending[1::2]):
             try:
               part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best, posterior,
-                                                lim_of(part))
+                                                lim_of(part), bias_of(part))
             except LookAheadWindowError as inner:
               # (a half whose look-ahead window overflowed: its indices and results are numbered inside
               # the half -- hand them up in the caller's numbering, and still decode the other half)
@@ -439,7 +506,7 @@ class UISRNN:
             continue
           try:
             partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best, posterior,
-                                         lim_of(members))
+                                         lim_of(members), bias_of(members))
           except LookAheadWindowError as inner:
             # (indices and results are numbered inside `members`: hand them up in the caller's numbering)
             partial = inner.results
@@ -455,7 +522,7 @@ class UISRNN:
             for u in members:
               try:
                 one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best, posterior,
-                                                                          lim_of([u]))
+                                                                          lim_of([u]), bias_of([u]))
                 one_err = inner if len(members) == 1 else None
               except LookAheadWindowError as e1:
                 one, one_err = [None], e1
@@ -569,13 +636,13 @@ class UISRNN:
                          for ids, p in zip(test_cluster_ids, predicted)]
     return predicted, [float(m) / int(n) for m, n in zip(matched, lens)]
 
-  def predict_single(self, test_sequence, args, max_speakers=None):
+  def predict_single(self, test_sequence, args, max_speakers=None, transition_bias=None):
     """Predict labels for one test sequence (uisrnn/uisrnn.py:479-562).
 
     Args:
       test_sequence: 2-dim float64 numpy array [N, D].
       args: inference namespace (beam_size, look_ahead, test_iteration).
-      max_speakers: see predict (extension).
+      max_speakers, transition_bias: see predict (extensions).
 
     Returns:
       list of N ints: the predicted cluster id per frame.
@@ -585,7 +652,8 @@ class UISRNN:
       ValueError: wrong rank or observation dimension.
     """
     self._check_sequence(test_sequence)
-    return self._decode_batch([test_sequence], args, limits=_check_max_speakers(max_speakers, args, 1))[0]
+    return self._decode_batch([test_sequence], args, limits=_check_max_speakers(max_speakers, args, 1),
+                              bias=_check_transition_bias(transition_bias, [test_sequence.shape[0]], single=True))[0]
 
   def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
              max_speakers=None):
@@ -607,7 +675,7 @@ class UISRNN:
     whose streams begin and end independently of each other."""
     return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers))
 
-  def predict(self, test_sequences, args, max_speakers=None):
+  def predict(self, test_sequences, args, max_speakers=None, transition_bias=None):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
 
     A list is decoded as ONE lock-step batch on the GPU (the reference loops
@@ -619,6 +687,13 @@ class UISRNN:
     (DESIGN.md section 24).  None falls back to getattr(args, 'max_speakers', None).  ValueError for a bool, a float
     that is not whole, a negative, a value above 4096 or a wrong length.
 
+    transition_bias (extension): the probability of a speaker change per frame, in the place of
+    the model's scalar -- None, a number (every frame), or one array per sequence of that sequence's length (for a single
+    sequence: its one array); NaN means the model's value at that frame.  0 keeps a frame with the previous speaker,
+    1 makes it change; constraints that contradict each other (or max_speakers) empty the beam: EmptyBeamError.
+    ValueError, before any device work, for a bool, a wrong length or count, a value outside [0, 1], +-inf, or 0 at a
+    sequence's first frame.
+
     Raises:
       TypeError: test_sequences is neither a list nor a numpy array.
       EmptyBeamError: non-finite scores emptied an utterance's beam (the reference raises
@@ -628,23 +703,24 @@ class UISRNN:
         have); the exception names them and carries the other utterances' results.
     """
     if isinstance(test_sequences, np.ndarray):
-      return self.predict_single(test_sequences, args, max_speakers)
+      return self.predict_single(test_sequences, args, max_speakers, transition_bias)
     if isinstance(test_sequences, list):
       limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
+      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args, limits=limits)
+      return self._decode_batch(test_sequences, args, limits=limits, bias=bias)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
-  def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None):
+  def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None):
     """predict, returning every hypothesis of the final beam instead of the best one (extension).
 
     Args:
       test_sequences, args: as predict.
       n_best: the most hypotheses wanted per sequence, in [1, args.beam_size] (default: beam_size).
-      max_speakers: as predict.
+      max_speakers, transition_bias: as predict.
     Returns:
       for an array the pair (labelings, scores): at most n_best label lists -- fewer when the final
       beam holds fewer -- best first, and their scores as floats, ascending; labelings[0] is predict's
@@ -662,17 +738,19 @@ class UISRNN:
     if isinstance(test_sequences, np.ndarray):
       self._check_sequence(test_sequences)
       return self._decode_batch([test_sequences], args, n_best=int(n_best),
-                                limits=_check_max_speakers(max_speakers, args, 1))[0]
+                                limits=_check_max_speakers(max_speakers, args, 1),
+                                bias=_check_transition_bias(transition_bias, [test_sequences.shape[0]], single=True))[0]
     if isinstance(test_sequences, list):
       limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
+      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args, n_best=int(n_best), limits=limits)
+      return self._decode_batch(test_sequences, args, n_best=int(n_best), limits=limits, bias=bias)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
-  def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None):
+  def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None, transition_bias=None):
     """predict, with the beam's per-frame confidence in its answer (extension).
 
     With w_k = softmax(-score_k / temperature) over the hypotheses of the final beam:
@@ -687,7 +765,7 @@ class UISRNN:
       temperature: a finite number > 0.  1 is the model's own posterior; a sharply peaked model (a trained D = 256
         one puts all but 1e-3, usually all but 1e-11, on the best hypothesis) needs a larger one to rank its
         uncertain frames.
-      max_speakers: as predict.
+      max_speakers, transition_bias: as predict.
     Returns:
       for an array the triple (labels, confidence, change): predict's answer and two float32 arrays of its length.
       For a list, a list of such triples.  One decode, with predict's cap and level retries.
@@ -699,14 +777,16 @@ class UISRNN:
     if isinstance(test_sequences, np.ndarray):
       self._check_sequence(test_sequences)
       return self._decode_batch([test_sequences], args, posterior=temperature,
-                                limits=_check_max_speakers(max_speakers, args, 1))[0]
+                                limits=_check_max_speakers(max_speakers, args, 1),
+                                bias=_check_transition_bias(transition_bias, [test_sequences.shape[0]], single=True))[0]
     if isinstance(test_sequences, list):
       limits = _check_max_speakers(max_speakers, args, len(test_sequences))
       for test_sequence in test_sequences:
         self._check_sequence(test_sequence)
+      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
       if not test_sequences:
         return []
-      return self._decode_batch(test_sequences, args, posterior=temperature, limits=limits)
+      return self._decode_batch(test_sequences, args, posterior=temperature, limits=limits, bias=bias)
     raise TypeError('test_sequences should be either a list or numpy array.')
 
   def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
@@ -819,7 +899,7 @@ class UISRNN:
       labels.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
     return single, seqs, labels
 
-  def score_labels(self, test_sequences, test_cluster_ids, per_frame=False):
+  def score_labels(self, test_sequences, test_cluster_ids, per_frame=False, transition_bias=None):
     """The model's negative log-likelihood of given labelings (extension).
 
     The neg_likelihood predict's beam search minimises (uisrnn.py:388-453), applied along the
@@ -831,13 +911,17 @@ class UISRNN:
       test_sequences: a [N, D] float array or a list of them (as predict).
       test_cluster_ids: N ids for an array, or a list of such sequences for a list.
       per_frame: also return each frame's float32 loss (their float32 running sum is the score).
+      transition_bias: as predict (a first value of 0 is allowed here: that frame's loss is +inf): the labeling is
+        scored under the per-frame priors, so that the labels of a test_iteration-1 decode under the same table score
+        that decode's score.
     Returns:
       a float (array) or a list of floats (list); with per_frame, a pair (scores, losses) where
       losses is a float32 array per sequence.
     """
     single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
-    decoder = self._get_decoder()
     lens = [s.shape[0] for s in seqs]
+    bias = _check_transition_bias(transition_bias, lens, single=single, offline=False)
+    decoder = self._get_decoder()
     out_scores, out_losses = [None] * len(seqs), [None] * len(seqs)
 
     def run(members):
@@ -849,7 +933,9 @@ class UISRNN:
       sub_labels = (np.concatenate([labels[u] for u in members]) if members else
                     np.zeros(0, dtype=np.int32))
       try:
-        scores, losses = decoder.score_labels(frames, sub_off, sub_labels, want_frame_losses=True)
+        scores, losses = decoder.score_labels(
+            frames, sub_off, sub_labels, want_frame_losses=True,
+            bias=None if bias is None or not members else np.concatenate([bias[u] for u in members]))
       except _capi.HipLibraryError as err:
         if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
           run(members[0::2])  # (as _decode_batch: alternating members, each half may halve again)
@@ -866,7 +952,7 @@ class UISRNN:
       return (out_scores[0], out_losses[0]) if per_frame else out_scores[0]
     return (out_scores, out_losses) if per_frame else out_scores
 
-  def score_speakers(self, test_sequences, test_cluster_ids):
+  def score_speakers(self, test_sequences, test_cluster_ids, transition_bias=None):
     """Every speaker's loss at every frame along given labelings (extension).
 
     Row t of a sequence's result is what the model would charge for assigning frame t to each speaker open so far, or
@@ -877,14 +963,15 @@ class UISRNN:
     rows into soft assignments.
 
     Args:
-      test_sequences, test_cluster_ids: as score_labels.
+      test_sequences, test_cluster_ids, transition_bias: as score_labels.
     Returns:
       a float32 [N, K + 1] array (array), K the sequence's number of speakers, or a list of them (list).
     """
     single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
-    decoder = self._get_decoder()
     lens = [s.shape[0] for s in seqs]
     widths = [int(l.max()) + 2 if l.size else 1 for l in labels]
+    bias = _check_transition_bias(transition_bias, lens, single=single, offline=False)
+    decoder = self._get_decoder()
     out = [None] * len(seqs)
 
     def run(members):
@@ -895,7 +982,9 @@ class UISRNN:
         frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
       sub_labels = np.concatenate([labels[u] for u in members])
       try:
-        _, losses = decoder.score_speakers(frames, sub_off, sub_labels, max(widths[u] for u in members))
+        _, losses = decoder.score_speakers(
+            frames, sub_off, sub_labels, max(widths[u] for u in members),
+            bias=None if bias is None else np.concatenate([bias[u] for u in members]))
       except _capi.HipLibraryError as err:
         if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
           run(members[0::2])  # (as score_labels)
@@ -1071,9 +1160,32 @@ class OnlineSession:
         self._bound[u] += 0 if labels[u] is None else len(labels[u])
     return [float(scores[u]) if labels[u] is not None else None for u in range(n_utt)]
 
-  def push(self, chunks):
+  def _push_bias(self, chunks, transition_bias):
+    """push's transition_bias as the library's flat table: the chunk's frames, utterance by utterance."""
+    if transition_bias is None:
+      return None
+    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
+      sizes = [chunks.shape[1]] * len(chunks)
+      if isinstance(transition_bias, np.ndarray) and transition_bias.ndim == 2:
+        transition_bias = list(transition_bias)   # ([U, n]: one row per utterance)
+    else:
+      sizes = [0 if c is None else len(c) for c in chunks]
+    tables = _check_transition_bias(transition_bias, sizes, offline=False)
+    return np.concatenate(tables) if tables else np.zeros(0, dtype=np.float64)
+
+  def push(self, chunks, transition_bias=None):
     """chunks: a list with one [n, D] float64 array (or None) per utterance, or one [U, n, D]
-    float64 array when every utterance received the same number of frames."""
+    float64 array when every utterance received the same number of frames.
+
+    transition_bias: this push's per-frame probability of a speaker change, in the chunk's own
+    layout -- None, a number, one array (or None) per utterance of its chunk's length, or a [U, n] array beside a
+    [U, n, D] chunk; NaN = the model's value.  A push without it decodes with the model's value, whatever the last one
+    used.  ValueError as predict's; a persistent session refuses a table (HipLibraryError, UIS_ERR_UNSUPPORTED) and
+    stays usable."""
+    bias = self._push_bias(chunks, transition_bias)
+    if bias is not None and not bias.size:
+      bias = None
+    extra = {} if bias is None else {'bias': bias}
     if self._retire_at is not None:
       self._keep_under_cap(chunks)
     if self._horizon is not None:
@@ -1094,14 +1206,14 @@ class OnlineSession:
           if chunk is not None and len(chunk):
             self._model._check_sequence(np.asarray(chunk))
       try:
-        self._decoder.stream_push(chunks)
+        self._decoder.stream_push(chunks, **extra)
       except ValueError:
         for chunk in chunks:   # (which chunk, in the reference's words)
           if chunk is not None and len(chunk):
             self._model._check_sequence(np.asarray(chunk))
         raise
       return
-    self._decoder.stream_push(chunks)
+    self._decoder.stream_push(chunks, **extra)
 
   def _make_room(self, chunks):
     """horizon given: a push whose chunk does not fit the window commits first."""
@@ -1517,12 +1629,19 @@ class StreamPool:
     self._slot[key] = self._free.pop()
     return self._slot[key]
 
-  def push(self, chunks):
-    """chunks: a dict {key: [n, D] float64 array} with the new frames of the streams that received some."""
+  def push(self, chunks, transition_bias=None):
+    """chunks: a dict {key: [n, D] float64 array} with the new frames of the streams that received some.
+    transition_bias: None, a number, or a dict {key: array of the chunk's length} for the streams that have values of
+    their own (OnlineSession.push)."""
     per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
     for key, chunk in chunks.items():
       per_slot[self._slot[key]] = chunk
-    self._session.push(per_slot)
+    if isinstance(transition_bias, dict):
+      bias_slot = [None] * len(per_slot)
+      for key, values in transition_bias.items():
+        bias_slot[self._slot[key]] = values
+      transition_bias = bias_slot
+    self._session.push(per_slot, transition_bias)
 
   def labels(self, key):
     """The currently best labels of everything the stream has received."""
@@ -1578,7 +1697,7 @@ class StreamPool:
     self.close()
 
 
-def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None):
+def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None, transition_bias=None):
   """Drop-in for uisrnn.parallel_predict (uisrnn/uisrnn.py:593-623).
 
   The reference maps utterances over a forkserver process pool.  Here the
@@ -1591,7 +1710,7 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
   Args:
     devices: optional explicit list of HIP device indices (repeats allowed --
       used by the tests to exercise the path on a single-GPU box).
-    max_speakers: as UISRNN.predict (extension); every shard takes its members' entries.
+    max_speakers, transition_bias: as UISRNN.predict (extensions); every shard takes its members' entries.
 
   Raises:
     TypeError: test_sequences is not a list.
@@ -1601,13 +1720,14 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
   for test_sequence in test_sequences:
     model._check_sequence(test_sequence)  # pylint: disable=protected-access
   limits = _check_max_speakers(max_speakers, args, len(test_sequences))
+  bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
   if not test_sequences:
     return []
   if devices is None:
     n_dev = max(_capi.load_library().uis_device_count(), 1)
     devices = list(range(max(1, min(int(num_processes), n_dev))))
   if len(devices) == 1:
-    return model._decode_batch(test_sequences, args, device=devices[0], limits=limits)  # pylint: disable=protected-access
+    return model._decode_batch(test_sequences, args, device=devices[0], limits=limits, bias=bias)  # pylint: disable=protected-access
   import threading  # pylint: disable=import-outside-toplevel
   from uisrnn_amd import distributed  # pylint: disable=import-outside-toplevel
   shards = distributed.shard_utterances(
@@ -1622,7 +1742,8 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
     try:
       if shard:
         out = worker.decode([test_sequences[i] for i in shard], args,
-                            None if limits is None else [limits[i] for i in shard])
+                            None if limits is None else [limits[i] for i in shard],
+                            None if bias is None else [bias[i] for i in shard])
         for i, labels in zip(shard, out):
           results[i] = labels
     except Exception as exc:  # pylint: disable=broad-except
@@ -1652,9 +1773,9 @@ class _Worker:
     self._decoder = (_capi.Decoder(model.params, device) if self._own
                      else model._get_decoder(device))  # pylint: disable=protected-access
 
-  def decode(self, sequences, args, limits=None):
+  def decode(self, sequences, args, limits=None, bias=None):
     return self._model._decode_batch(  # pylint: disable=protected-access
-        sequences, args, decoder=self._decoder, limits=limits)
+        sequences, args, decoder=self._decoder, limits=limits, bias=bias)
 
   def close(self):
     if self._own:
