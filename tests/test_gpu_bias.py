@@ -554,9 +554,9 @@ def test_session_operations_between_biased_pushes(oracle_lib):
       want, _ = ref.commit(4)
       assert out[0].tolist() == want
       able = ref.retirable()
-      if able:
-        dec.stream_retire(clusters=[able[:1], []])
-        ref.retire(able[:1])
+      assert able, 'nothing to retire: pick another walk'
+      dec.stream_retire(clusters=[able[:1], []])
+      ref.retire(able[:1])
       push(seq[22:30], other[6:10], table[22:30], side_table[6:10])
       nb = dec.stream_nbest(beam)
       cnt = int(nb['counts'][0])
