@@ -64,6 +64,8 @@ def decode_kernel_name(code):
 
 _fp = ctypes.POINTER(ctypes.c_float)
 _fpp = ctypes.POINTER(_fp)
+_i32p = ctypes.POINTER(ctypes.c_int32)
+_i64p = ctypes.POINTER(ctypes.c_int64)
 
 
 class ModelDesc(ctypes.Structure):
@@ -159,6 +161,24 @@ def _f32(a):
 
 def _ptr(a):
   return a.ctypes.data_as(_fp)
+
+
+def _i32(a):
+  return a.ctypes.data_as(_i32p)
+
+
+def _i64(a):
+  return a.ctypes.data_as(_i64p)
+
+
+def _offsets(counts):
+  """int64 [U + 1]: where each utterance begins in a buffer packed by these counts, and where the last one ends."""
+  return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def _cut(flat, offsets):
+  """A packed buffer as one array (a copy) per utterance."""
+  return [flat[offsets[u]:offsets[u + 1]].copy() for u in range(len(offsets) - 1)]
 
 
 def make_desc(params):
@@ -283,8 +303,7 @@ def load_library(path=None):
         '{} was built for ABI {} but this package expects {}: rebuild with '
         '`python -m uisrnn_amd.build --force`'.format(path, lib.uis_abi_version(), UIS_ABI_VERSION))
   i32 = ctypes.c_int32
-  i32p = ctypes.POINTER(ctypes.c_int32)
-  i64p = ctypes.POINTER(ctypes.c_int64)
+  i32p, i64p = _i32p, _i64p
   lib.uis_abi_version.restype = i32
   lib.uis_abi_version.argtypes = []
   lib.uis_numerics_version.restype = i32
@@ -438,13 +457,23 @@ def decode_kernel_table(lib=None):
   lib = lib or load_library()
   n = lib.uis_decode_kernel_table(None, 0)
   rows = np.zeros((n, 5), dtype=np.int32)
-  lib.uis_decode_kernel_table(rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n)
+  lib.uis_decode_kernel_table(_i32(rows), n)
   return [(DECODE_KERNELS.get(int(r[0]), 'unknown'),) + tuple(int(v) for v in r[1:]) for r in rows]
 
 
 def last_error(lib):
   msg = lib.uis_last_error()
   return msg.decode('utf-8', 'replace') if msg else ''
+
+
+def _raise_status(lib, rc, what):
+  """The failed call `what` as an exception: ValueError for UIS_ERR_DIM_MISMATCH, else HipLibraryError with .status."""
+  msg = last_error(lib)
+  if rc == UIS_ERR_DIM_MISMATCH:
+    raise ValueError(msg)
+  err = HipLibraryError('{} failed ({}): {}'.format(what, rc, msg))
+  err.status = rc
+  raise err
 
 
 class Decoder:
@@ -499,15 +528,12 @@ class Decoder:
         mean.ctypes.data_as(_fp), h_out.ctypes.data_as(_fp)), 'uis_rnn_step')
     return mean, h_out
 
-  def _check(self, rc, what):
-    if rc == UIS_OK or rc == UIS_ERR_CLUSTER_CAP:
+  def _check(self, rc, what, ok=(UIS_OK, UIS_ERR_CLUSTER_CAP)):
+    """rc if it is one of `ok`, else the exception.  UIS_ERR_CLUSTER_CAP is a result with per-utterance flags for the
+    calls that decode or read out; the calls for which it is a refusal pass ok=(UIS_OK,)."""
+    if rc in ok:
       return rc
-    msg = last_error(self._lib)
-    if rc == UIS_ERR_DIM_MISMATCH:
-      raise ValueError(msg)
-    err = HipLibraryError('{} failed ({}): {}'.format(what, rc, msg))
-    err.status = rc
-    raise err
+    _raise_status(self._lib, rc, what)
 
   def set_limits(self, limits):
     """uis_decode_limits: the max_speakers table (ints, 0 = no bound; None clears) of the NEXT decode* /
@@ -516,8 +542,7 @@ class Decoder:
       self._check(self._lib.uis_decode_limits(self._handle, None, 0), 'uis_decode_limits')
       return
     lim = np.ascontiguousarray(limits, dtype=np.int32)
-    self._check(self._lib.uis_decode_limits(
-        self._handle, lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(lim.shape[0])), 'uis_decode_limits')
+    self._check(self._lib.uis_decode_limits(self._handle, _i32(lim), int(lim.shape[0])), 'uis_decode_limits')
 
   def set_frame_bias(self, bias):
     """uis_frame_bias: the per-frame transition_bias (float64, one value per frame in the call's frame order, NaN = the
@@ -528,6 +553,49 @@ class Decoder:
     b = np.ascontiguousarray(bias, dtype=np.float64).reshape(-1)
     self._check(self._lib.uis_frame_bias(
         self._handle, b.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(b.shape[0])), 'uis_frame_bias')
+
+  def _packed(self, frames, offsets, labels=None):
+    """Packed utterances, checked: float32 frames [sum N, D], int64 offsets [U + 1] and, if given, int32 labels
+    [sum N]."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if labels is not None:
+      labels = np.ascontiguousarray(labels, dtype=np.int32)
+    total = int(offsets[-1])
+    if frames.ndim != 2 or frames.shape[0] != total:
+      raise ValueError('frames must be [offsets[-1], D]')
+    if total and frames.shape[1] != self.observation_dim:
+      raise ValueError('frames do not match observation_dim')
+    if labels is not None and labels.shape != (total,):
+      raise ValueError('labels must be [offsets[-1]]')
+    return frames, offsets, labels
+
+  def _run_decode(self, call, what, opts, frames, counts, offsets, labels, scores, limits, bias):
+    """One decode call of the library -- uis_decode, uis_decode_f64 and uis_decode_device take the same arguments in
+    the same places: `frames`, `labels` and `scores` as ctypes passes them on, `counts` the int64 array in third place
+    (the offsets; the lengths for uis_decode_f64).  `offsets` is kept, as it is, as the layout of this decode, for
+    last_nbest and last_posterior: an array the caller of the wrapper may still write to comes as a copy.  Returns
+    {'stats', 'status'}."""
+    stats = Stats()
+    # the tables are those of the NEXT call on the handle, which consumes them: limits, bias, the decode -- nothing between
+    if limits is not None:
+      self.set_limits(limits)
+    if bias is not None:
+      self.set_frame_bias(bias)
+    rc = self._check(call(self._handle, frames, _i64(counts), offsets.shape[0] - 1, ctypes.byref(opts), labels, scores,
+                          ctypes.byref(stats)), what)
+    self._last_offsets = offsets
+    return {'stats': stats.as_dict(), 'status': rc}
+
+  def _with_decode_info(self, out, n_utt, beam_size, want_beam_scores):
+    """decode()'s dict with the overflow words (and the beam's scores) of the decode just made (uis_last_decode_info)."""
+    out['overflow'] = np.zeros(n_utt, dtype=np.int32)
+    if want_beam_scores:
+      out['beam_scores'] = np.empty((n_utt, int(beam_size)), dtype=np.float32)
+    self._check(self._lib.uis_last_decode_info(
+        self._handle, _i32(out['overflow']), _ptr(out['beam_scores']) if want_beam_scores else None),
+                'uis_last_decode_info')
+    return out
 
   def decode(self, frames, offsets, beam_size, look_ahead, test_iteration,
              max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None):
@@ -540,43 +608,15 @@ class Decoder:
       dict with labels (int32 [sum N]), scores (float32 [U]), overflow
       (int32 [U]), stats (dict) and optionally beam_scores [U, beam_size].
     """
-    frames = np.ascontiguousarray(frames, dtype=np.float32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    frames, offsets, _ = self._packed(frames, offsets)
     n_utt = offsets.shape[0] - 1
-    total = int(offsets[-1])
-    if frames.ndim != 2 or frames.shape[0] != total:
-      raise ValueError('frames must be [offsets[-1], D]')
-    if total and frames.shape[1] != self.observation_dim:
-      raise ValueError('frames do not match observation_dim')
-    labels = np.empty(total, dtype=np.int32)
+    labels = np.empty(int(offsets[-1]), dtype=np.int32)
     scores = np.empty(n_utt, dtype=np.float32)
-    opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags,
-                     n_streams, level_cap)
-    stats = Stats()
-    if limits is not None:
-      self.set_limits(limits)
-    if bias is not None:
-      self.set_frame_bias(bias)
-    rc = self._lib.uis_decode(
-        self._handle, frames.ctypes.data_as(_fp),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        scores.ctypes.data_as(_fp), ctypes.byref(stats))
-    rc = self._check(rc, 'uis_decode')
-    self._last_offsets = offsets.copy()
-    out = {'labels': labels, 'scores': scores, 'stats': stats.as_dict(),
-           'status': rc}
-    overflow = np.zeros(n_utt, dtype=np.int32)
-    beam_scores = (np.empty((n_utt, int(beam_size)), dtype=np.float32)
-                   if want_beam_scores else None)
-    rc2 = self._lib.uis_last_decode_info(
-        self._handle, overflow.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        beam_scores.ctypes.data_as(_fp) if want_beam_scores else None)
-    self._check(rc2, 'uis_last_decode_info')
-    out['overflow'] = overflow
-    if want_beam_scores:
-      out['beam_scores'] = beam_scores
-    return out
+    opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
+    out = self._run_decode(self._lib.uis_decode, 'uis_decode', opts, _ptr(frames), offsets, offsets.copy(),
+                           _i32(labels), _ptr(scores), limits, bias)
+    out.update(labels=labels, scores=scores)
+    return self._with_decode_info(out, n_utt, beam_size, want_beam_scores)
 
   def decode_f64(self, sequences, beam_size, look_ahead, test_iteration,
                  max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None):
@@ -591,34 +631,15 @@ class Decoder:
       if s.ndim != 2 or (s.shape[0] and s.shape[1] != self.observation_dim):
         raise ValueError('frames do not match observation_dim')
     lens = np.array([s.shape[0] for s in seqs], dtype=np.int64)
-    total = int(lens.sum())
+    offsets = _offsets(lens)
     ptrs = (ctypes.c_void_p * max(n_utt, 1))(*[s.ctypes.data if s.shape[0] else None for s in seqs])
-    labels = np.empty(total, dtype=np.int32)
+    labels = np.empty(int(offsets[-1]), dtype=np.int32)
     scores = np.empty(n_utt, dtype=np.float32)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
-    stats = Stats()
-    if limits is not None:
-      self.set_limits(limits)
-    if bias is not None:
-      self.set_frame_bias(bias)
-    rc = self._lib.uis_decode_f64(
-        self._handle, ptrs, lens.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        ctypes.byref(opts), labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        scores.ctypes.data_as(_fp), ctypes.byref(stats))
-    rc = self._check(rc, 'uis_decode_f64')
-    self._last_offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    out = {'labels': labels, 'scores': scores, 'stats': stats.as_dict(), 'status': rc}
-    overflow = np.zeros(n_utt, dtype=np.int32)
-    beam_scores = (np.empty((n_utt, int(beam_size)), dtype=np.float32)
-                   if want_beam_scores else None)
-    rc2 = self._lib.uis_last_decode_info(
-        self._handle, overflow.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        beam_scores.ctypes.data_as(_fp) if want_beam_scores else None)
-    self._check(rc2, 'uis_last_decode_info')
-    out['overflow'] = overflow
-    if want_beam_scores:
-      out['beam_scores'] = beam_scores
-    return out
+    out = self._run_decode(self._lib.uis_decode_f64, 'uis_decode_f64', opts, ptrs, lens, offsets,
+                           _i32(labels), _ptr(scores), limits, bias)
+    out.update(labels=labels, scores=scores)
+    return self._with_decode_info(out, n_utt, beam_size, want_beam_scores)
 
   def score_labels(self, frames, offsets, labels, want_frame_losses=False, bias=None):
     """The model's NLL of given labelings (uis_score_labels).
@@ -629,26 +650,15 @@ class Decoder:
     Returns:
       float32 scores [U], and with want_frame_losses also the float32 per-frame losses [sum N].
     """
-    frames = np.ascontiguousarray(frames, dtype=np.float32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    frames, offsets, labels = self._packed(frames, offsets, labels)
     n_utt = offsets.shape[0] - 1
-    total = int(offsets[-1])
-    if frames.ndim != 2 or frames.shape[0] != total:
-      raise ValueError('frames must be [offsets[-1], D]')
-    if total and frames.shape[1] != self.observation_dim:
-      raise ValueError('frames do not match observation_dim')
-    if labels.shape != (total,):
-      raise ValueError('labels must be [offsets[-1]]')
     scores = np.empty(n_utt, dtype=np.float32)
-    losses = np.empty(total, dtype=np.float32) if want_frame_losses else None
+    losses = np.empty(int(offsets[-1]), dtype=np.float32) if want_frame_losses else None
     if bias is not None:
       self.set_frame_bias(bias)
     rc = self._lib.uis_score_labels(
-        self._handle, frames.ctypes.data_as(_fp),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scores.ctypes.data_as(_fp),
-        losses.ctypes.data_as(_fp) if want_frame_losses else None)
+        self._handle, _ptr(frames), _i64(offsets), n_utt, _i32(labels), _ptr(scores),
+        _ptr(losses) if want_frame_losses else None)
     self._check(rc, 'uis_score_labels')
     return (scores, losses) if want_frame_losses else scores
 
@@ -665,17 +675,9 @@ class Decoder:
       assigning frame t to its utterance's cluster k given the labels before t, column K(t) the new-speaker candidate,
       +inf past it and everywhere after an invalid label.
     """
-    frames = np.ascontiguousarray(frames, dtype=np.float32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    frames, offsets, labels = self._packed(frames, offsets, labels)
     n_utt = offsets.shape[0] - 1
     total = int(offsets[-1])
-    if frames.ndim != 2 or frames.shape[0] != total:
-      raise ValueError('frames must be [offsets[-1], D]')
-    if total and frames.shape[1] != self.observation_dim:
-      raise ValueError('frames do not match observation_dim')
-    if labels.shape != (total,):
-      raise ValueError('labels must be [offsets[-1]]')
     width = int(width)
     scores = np.empty(n_utt, dtype=np.float32)
     losses = np.empty((total, max(width, 0)), dtype=np.float32) if losses_out is None else losses_out
@@ -684,10 +686,7 @@ class Decoder:
     if bias is not None:
       self.set_frame_bias(bias)
     rc = self._lib.uis_score_speakers(
-        self._handle, frames.ctypes.data_as(_fp),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), width, losses.ctypes.data_as(_fp),
-        scores.ctypes.data_as(_fp))
+        self._handle, _ptr(frames), _i64(offsets), n_utt, _i32(labels), width, _ptr(losses), _ptr(scores))
     self._check(rc, 'uis_score_speakers')
     return scores, losses
 
@@ -709,8 +708,7 @@ class Decoder:
     self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), ctypes.byref(beam)),
                 'uis_last_decode_shape')
     overflow = np.zeros(max(int(n_lib.value), 1), dtype=np.int32)
-    self._check(self._lib.uis_last_decode_info(
-        self._handle, overflow.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), None), 'uis_last_decode_info')
+    self._check(self._lib.uis_last_decode_info(self._handle, _i32(overflow), None), 'uis_last_decode_info')
     overflow = overflow[:int(n_lib.value)]
     if n_utt is not None and int(n_utt) != overflow.shape[0]:
       padded = np.zeros(int(n_utt), dtype=np.int32)
@@ -742,21 +740,19 @@ class Decoder:
     self._stream_cap = int(max_clusters) if int(max_clusters) > 0 else 16
     self._stream_have = np.zeros(int(n_utt), dtype=np.int64)
     self._stream_counts = np.zeros(int(n_utt), dtype=np.int32)   # (reused by every push: its pointer is bound once)
-    self._stream_counts_ptr = self._stream_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    self._stream_counts_ptr = self._stream_counts.ctypes.data_as(_i32p)
 
   def stream_set_limits(self, limits):
     """uis_stream_limits: replace the open session's max_speakers table (one int per slot, 0 = no bound)."""
     lim = np.ascontiguousarray(limits, dtype=np.int32)
     if lim.shape != (self._stream_n,):
       raise ValueError('one limit per utterance of the session')
-    self._check(self._lib.uis_stream_limits(self._handle, lim.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
-                'uis_stream_limits')
+    self._check(self._lib.uis_stream_limits(self._handle, _i32(lim)), 'uis_stream_limits')
 
   def stream_limits(self):
     """uis_stream_get_limits: int32 [n_utt], 0 = no bound."""
     out = np.zeros(self._stream_n, dtype=np.int32)
-    self._check(self._lib.uis_stream_get_limits(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
-                'uis_stream_get_limits')
+    self._check(self._lib.uis_stream_get_limits(self._handle, _i32(out)), 'uis_stream_get_limits')
     return out
 
   def stream_push(self, chunks, bias=None):
@@ -776,7 +772,7 @@ class Decoder:
         self.set_frame_bias(bias)
       rc = self._lib.uis_stream_push(
           self._handle, frames.ctypes.data_as(_fp) if frames.size else None,
-          counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+          counts.ctypes.data_as(_i32p))
       self._check(rc, 'uis_stream_push')
       self._stream_have += counts
       return
@@ -841,16 +837,12 @@ class Decoder:
       counts[u] = n
     frames = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0, dim), dtype=np.float32)
     flat = np.ascontiguousarray(np.concatenate(lab_parts)) if lab_parts else np.zeros(0, dtype=np.int32)
-    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    offsets = _offsets(counts)
     scores = np.zeros(self._stream_n, dtype=np.float32)
     rc = self._lib.uis_stream_prime(
-        self._handle, frames.ctypes.data_as(_fp) if len(frames) else None,
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-        flat.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(flat) else None, scores.ctypes.data_as(_fp))
-    if rc != UIS_OK:   # (UIS_ERR_CLUSTER_CAP is a refusal here, not a result with flags)
-      err = HipLibraryError('uis_stream_prime failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
+        self._handle, _ptr(frames) if len(frames) else None, _i64(offsets),
+        _i32(flat) if len(flat) else None, _ptr(scores))
+    self._check(rc, 'uis_stream_prime', ok=(UIS_OK,))
     self._stream_have += counts
     return scores
 
@@ -868,27 +860,20 @@ class Decoder:
       hz = np.ascontiguousarray(horizon, dtype=np.int32).reshape(-1)
       if hz.shape[0] != n_utt:
         raise ValueError('one horizon per utterance')
-      hz_ptr = hz.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+      hz_ptr = _i32(hz)
     total = int(self._stream_have.sum())
     labels = np.empty(max(total, 1), dtype=np.int32)
     counts = np.zeros(n_utt, dtype=np.int32)
     dropped = np.zeros(n_utt, dtype=np.int32)
-    rc = self._lib.uis_stream_commit(
-        self._handle, hz_ptr, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
-        counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dropped.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    if rc != UIS_OK:
-      err = HipLibraryError('uis_stream_commit failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
-    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rc = self._lib.uis_stream_commit(self._handle, hz_ptr, _i32(labels), total, _i32(counts), _i32(dropped))
+    self._check(rc, 'uis_stream_commit', ok=(UIS_OK,))
     self._stream_have -= counts
-    return [labels[bounds[u]:bounds[u + 1]].copy() for u in range(n_utt)], dropped
+    return _cut(labels, _offsets(counts)), dropped
 
   def stream_committed(self):
     """Frames per utterance committed so far (uis_stream_committed): int64 [n_utt]."""
     out = np.zeros(self._stream_n, dtype=np.int64)
-    self._check(self._lib.uis_stream_committed(self._handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-                'uis_stream_committed')
+    self._check(self._lib.uis_stream_committed(self._handle, _i64(out)), 'uis_stream_committed')
     return out
 
   def stream_restart(self, which):
@@ -908,17 +893,10 @@ class Decoder:
     counts = np.zeros(n_utt, dtype=np.int32)
     scores = np.full(n_utt, np.nan, dtype=np.float32)
     overflow = np.zeros(n_utt, dtype=np.int32)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    rc = self._lib.uis_stream_restart(
-        self._handle, sel.ctypes.data_as(i32p), labels.ctypes.data_as(i32p), total, counts.ctypes.data_as(i32p),
-        scores.ctypes.data_as(_fp), overflow.ctypes.data_as(i32p))
-    if rc not in (UIS_OK, UIS_ERR_CLUSTER_CAP):
-      err = HipLibraryError('uis_stream_restart failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
-    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rc = self._check(self._lib.uis_stream_restart(
+        self._handle, _i32(sel), _i32(labels), total, _i32(counts), _ptr(scores), _i32(overflow)), 'uis_stream_restart')
     self._stream_have[sel != 0] = 0
-    return [labels[bounds[u]:bounds[u + 1]].copy() for u in range(n_utt)], scores, overflow, rc
+    return _cut(labels, _offsets(counts)), scores, overflow, rc
 
   def stream_retire(self, which=None, clusters=None):
     """Delete clusters that no live hypothesis can still name (uis_stream_retire).
@@ -930,7 +908,6 @@ class Decoder:
     largest K over the live hypotheses afterwards; per utterance the indices that were retirable before the call.
     A refusal (HipLibraryError with .status UIS_ERR_INVALID_ARG) leaves the session as it was."""
     n_utt = self._stream_n
-    i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
     which_ptr = off_ptr = sel_ptr = None
     if clusters is not None:
       if which is not None:
@@ -938,15 +915,15 @@ class Decoder:
       if len(clusters) != n_utt:
         raise ValueError('one sequence of cluster indices (or None) per utterance')
       parts = [np.zeros(0, dtype=np.int32) if c is None else np.asarray(c, dtype=np.int32).reshape(-1) for c in clusters]
-      offsets = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+      offsets = _offsets([len(x) for x in parts])
       flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.int32)
-      off_ptr = offsets.ctypes.data_as(i64p)
-      sel_ptr = flat.ctypes.data_as(i32p) if len(flat) else None
+      off_ptr = _i64(offsets)
+      sel_ptr = _i32(flat) if len(flat) else None
     elif which is not None:
       sel = np.ascontiguousarray([1 if w else 0 for w in which], dtype=np.int32)
       if sel.shape[0] != n_utt:
         raise ValueError('one selection flag per utterance')
-      which_ptr = sel.ctypes.data_as(i32p)
+      which_ptr = _i32(sel)
     cap = self.stream_max_clusters()
     retired = np.zeros((n_utt, cap), dtype=np.int32)
     retirable = np.zeros((n_utt, cap), dtype=np.int32)
@@ -954,12 +931,8 @@ class Decoder:
     able = np.zeros(n_utt, dtype=np.int32)
     k_out = np.zeros(n_utt, dtype=np.int32)
     rc = self._lib.uis_stream_retire(
-        self._handle, which_ptr, off_ptr, sel_ptr, retired.ctypes.data_as(i32p), counts.ctypes.data_as(i32p),
-        k_out.ctypes.data_as(i32p), retirable.ctypes.data_as(i32p), able.ctypes.data_as(i32p))
-    if rc != UIS_OK:
-      err = HipLibraryError('uis_stream_retire failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
+        self._handle, which_ptr, off_ptr, sel_ptr, _i32(retired), _i32(counts), _i32(k_out), _i32(retirable), _i32(able))
+    self._check(rc, 'uis_stream_retire', ok=(UIS_OK,))
     return {'retired': [retired[u, :counts[u]].copy() for u in range(n_utt)], 'K': k_out,
             'retirable': [retirable[u, :able[u]].copy() for u in range(n_utt)], 'max_clusters': cap}
 
@@ -977,10 +950,7 @@ class Decoder:
       self._export_buf = ctypes.create_string_buffer(self.stream_export_bound(utt))
     n = ctypes.c_int64(0)
     rc = self._lib.uis_stream_export(self._handle, int(utt), self._export_buf, len(self._export_buf), ctypes.byref(n))
-    if rc != UIS_OK:   # (UIS_ERR_CLUSTER_CAP is a refusal here, not a result with flags)
-      err = HipLibraryError('uis_stream_export failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
+    self._check(rc, 'uis_stream_export', ok=(UIS_OK,))
     return ctypes.string_at(self._export_buf, n.value)
 
   def stream_import(self, utt, blob):
@@ -988,10 +958,7 @@ class Decoder:
     (uis_stream_import).  A refusal (HipLibraryError with .status) leaves the session as it was."""
     blob = bytes(blob)
     rc = self._lib.uis_stream_import(self._handle, int(utt), blob, len(blob))
-    if rc != UIS_OK:
-      err = HipLibraryError('uis_stream_import failed ({}): {}'.format(rc, last_error(self._lib)))
-      err.status = rc
-      raise err
+    self._check(rc, 'uis_stream_import', ok=(UIS_OK,))
     self._stream_have[int(utt)] = blob_info(blob)['N']
 
   def stream_max_clusters(self):
@@ -1000,29 +967,44 @@ class Decoder:
 
   def stream_labels(self):
     """Best-hypothesis labels of everything received so far: (list of int32 arrays, scores, overflow, status)."""
-    total = int(self._stream_have.sum())
-    labels = np.empty(max(total, 1), dtype=np.int32)
+    labels = np.empty(max(int(self._stream_have.sum()), 1), dtype=np.int32)
     scores = np.empty(self._stream_n, dtype=np.float32)
     overflow = np.zeros(self._stream_n, dtype=np.int32)
-    rc = self._lib.uis_stream_labels(
-        self._handle, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), scores.ctypes.data_as(_fp),
-        overflow.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    rc = self._check(rc, 'uis_stream_labels')
-    bounds = np.concatenate([[0], np.cumsum(self._stream_have)]).astype(np.int64)
-    per_utt = [labels[bounds[u]:bounds[u + 1]].copy() for u in range(self._stream_n)]
-    return per_utt, scores, overflow, rc
+    rc = self._check(self._lib.uis_stream_labels(self._handle, _i32(labels), _ptr(scores), _i32(overflow)),
+                     'uis_stream_labels')
+    return _cut(labels, _offsets(self._stream_have)), scores, overflow, rc
 
   def stream_end(self):
     self._check(self._lib.uis_stream_end(self._handle), 'uis_stream_end')
 
+  def _last_layout(self, who):
+    """(offsets, beam_size) of the last decode, for `who` to size its buffers: the offsets this object remembers,
+    checked against what the library says of its last decode (uis_last_decode_shape)."""
+    offsets = self._last_offsets
+    if offsets is None:
+      offsets = np.zeros(1, dtype=np.int64)  # (no decode yet: the library refuses the readout itself)
+    n_lib, beam = ctypes.c_int32(0), ctypes.c_int32(0)
+    self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), ctypes.byref(beam)),
+                'uis_last_decode_shape')
+    if int(n_lib.value) != offsets.shape[0] - 1:  # (a decode that did not go through this object's wrappers: its layout is not known here)
+      raise HipLibraryError('{}: the library\'s last decode had {} utterances, this object remembers {}'.format(
+          who, int(n_lib.value), offsets.shape[0] - 1))
+    return offsets, int(beam.value)
+
   # ---- n-best readout (uis_last_decode_nbest / uis_stream_nbest)
-  @staticmethod
-  def _nbest_split(labels, scores, counts, offsets, n_best):
-    per_utt = []
-    for u in range(offsets.shape[0] - 1):
-      n = int(offsets[u + 1] - offsets[u])
-      per_utt.append(labels[n_best * int(offsets[u]):n_best * int(offsets[u + 1])].reshape(n_best, n).copy())
-    return {'labels': per_utt, 'scores': scores.reshape(offsets.shape[0] - 1, n_best), 'counts': counts}
+  def _nbest(self, call, what, n_best, offsets, *more):
+    """One n-best call of the library over utterances laid out by `offsets`; `more`: the call's further arguments.
+    Returns (last_nbest's dict, status)."""
+    n_best = int(n_best)
+    n_utt = offsets.shape[0] - 1
+    total = max(n_best, 0) * int(offsets[-1])
+    labels = np.empty(max(total, 1), dtype=np.int32)
+    scores = np.empty(max(n_utt * max(n_best, 0), 1), dtype=np.float32)
+    counts = np.zeros(max(n_utt, 1), dtype=np.int32)
+    rc = self._check(call(self._handle, n_best, _i32(labels), total, _ptr(scores), _i32(counts), *more), what)
+    per_utt = [labels[n_best * int(a):n_best * int(b)].reshape(n_best, int(b - a)).copy()
+               for a, b in zip(offsets[:-1], offsets[1:])]
+    return {'labels': per_utt, 'scores': scores[:n_utt * n_best].reshape(n_utt, n_best), 'counts': counts[:n_utt]}, rc
 
   def last_nbest(self, n_best):
     """Every hypothesis of the last decode's final beam (uis_last_decode_nbest).
@@ -1031,44 +1013,16 @@ class Decoder:
     form of decode()'s labels, rows >= counts[u] filled with -1; scores float32 [U, n_best], ascending,
     +inf padded; counts int32 [U] = min(n_best, live hypotheses), 0 for an utterance that hit the
     cluster cap."""
-    offsets = self._last_offsets
-    if offsets is None:
-      offsets = np.zeros(1, dtype=np.int64)  # (no decode yet: the library refuses below)
-    n_best = int(n_best)
-    n_utt = offsets.shape[0] - 1
-    n_lib = ctypes.c_int32(0)
-    self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), None), 'uis_last_decode_shape')
-    if int(n_lib.value) != n_utt:  # (a decode that did not go through this object's wrappers: its layout is not known here)
-      raise HipLibraryError('last_nbest: the library\'s last decode had {} utterances, this object remembers {}'.format(
-          int(n_lib.value), n_utt))
-    total = max(n_best, 0) * int(offsets[-1])
-    labels = np.empty(max(total, 1), dtype=np.int32)
-    scores = np.empty(max(n_utt * max(n_best, 0), 1), dtype=np.float32)
-    counts = np.zeros(max(n_utt, 1), dtype=np.int32)
-    rc = self._lib.uis_last_decode_nbest(
-        self._handle, n_best, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
-        scores.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    self._check(rc, 'uis_last_decode_nbest')
-    return self._nbest_split(labels, scores[:n_utt * n_best], counts[:n_utt], offsets, n_best)
+    offsets, _ = self._last_layout('last_nbest')
+    return self._nbest(self._lib.uis_last_decode_nbest, 'uis_last_decode_nbest', n_best, offsets)[0]
 
   def stream_nbest(self, n_best):
     """Every hypothesis of the open session's beam for everything received so far (uis_stream_nbest).
 
     The dict of last_nbest() plus stable (int64 [U]: leading frames whose labels are final) and status."""
-    n_best = int(n_best)
-    offsets = np.concatenate([[0], np.cumsum(self._stream_have)]).astype(np.int64)
-    n_utt = self._stream_n
-    total = max(n_best, 0) * int(offsets[-1])
-    labels = np.empty(max(total, 1), dtype=np.int32)
-    scores = np.empty(max(n_utt * max(n_best, 0), 1), dtype=np.float32)
-    counts = np.zeros(n_utt, dtype=np.int32)
-    stable = np.zeros(n_utt, dtype=np.int64)
-    rc = self._lib.uis_stream_nbest(
-        self._handle, n_best, labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), total,
-        scores.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        stable.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
-    rc = self._check(rc, 'uis_stream_nbest')
-    out = self._nbest_split(labels, scores[:n_utt * n_best], counts, offsets, n_best)
+    stable = np.zeros(self._stream_n, dtype=np.int64)
+    out, rc = self._nbest(self._lib.uis_stream_nbest, 'uis_stream_nbest', n_best, _offsets(self._stream_have),
+                          _i64(stable))
     out['stable'] = stable
     out['status'] = rc
     return out
@@ -1081,11 +1035,9 @@ class Decoder:
     change = np.zeros(max(total, 1), dtype=np.float32)
     weights = np.zeros(max(n_utt * beam, 1), dtype=np.float32)
     counts = np.zeros(max(n_utt, 1), dtype=np.int32)
-    rc = call(self._handle, float(temperature), conf.ctypes.data_as(_fp), change.ctypes.data_as(_fp), total,
-              weights.ctypes.data_as(_fp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
-    rc = self._check(rc, what)
-    bounds = [(int(offsets[u]), int(offsets[u + 1])) for u in range(n_utt)]
-    return {'confidence': [conf[a:b].copy() for a, b in bounds], 'change': [change[a:b].copy() for a, b in bounds],
+    rc = self._check(call(self._handle, float(temperature), _ptr(conf), _ptr(change), total, _ptr(weights),
+                          _i32(counts)), what)
+    return {'confidence': _cut(conf, offsets), 'change': _cut(change, offsets),
             'weights': weights[:n_utt * beam].reshape(n_utt, beam), 'counts': counts[:n_utt], 'status': rc}
 
   def last_posterior(self, temperature=1.0):
@@ -1096,44 +1048,24 @@ class Decoder:
     frame; change -- likewise, the weight of the hypotheses with a speaker turn between frames t - 1 and t
     (change[0] = 0); weights float32 [U, beam_size], rank order, 0 past the live ones; counts int32 [U], the live
     hypotheses (0 for an utterance that hit the cluster cap: zeros everywhere); status."""
-    offsets = self._last_offsets
-    if offsets is None:
-      offsets = np.zeros(1, dtype=np.int64)  # (no decode yet: the library refuses below)
-    n_lib, beam = ctypes.c_int32(0), ctypes.c_int32(0)
-    self._check(self._lib.uis_last_decode_shape(self._handle, ctypes.byref(n_lib), ctypes.byref(beam)), 'uis_last_decode_shape')
-    if int(n_lib.value) != offsets.shape[0] - 1:  # (as last_nbest: a decode whose layout is not known here)
-      raise HipLibraryError('last_posterior: the library\'s last decode had {} utterances, this object remembers {}'.format(
-          int(n_lib.value), offsets.shape[0] - 1))
-    return self._posterior(self._lib.uis_last_decode_posterior, 'uis_last_decode_posterior', temperature, offsets,
-                           int(beam.value))
+    offsets, beam = self._last_layout('last_posterior')
+    return self._posterior(self._lib.uis_last_decode_posterior, 'uis_last_decode_posterior', temperature, offsets, beam)
 
   def stream_posterior(self, temperature=1.0):
     """The same for the open session's window: everything received and not yet committed (uis_stream_posterior).
     A window that a commit emptied has counts 1, weights[u, 0] = 1 and no frames."""
-    offsets = np.concatenate([[0], np.cumsum(self._stream_have)]).astype(np.int64)
-    return self._posterior(self._lib.uis_stream_posterior, 'uis_stream_posterior', temperature, offsets, self._stream_beam)
+    return self._posterior(self._lib.uis_stream_posterior, 'uis_stream_posterior', temperature,
+                           _offsets(self._stream_have), self._stream_beam)
 
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
                   labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None, bias=None):
     """uis_decode on raw HOST pointers (e.g. pinned buffers from uis_host_alloc or torch)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n_utt = offsets.shape[0] - 1
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, 0)
-    stats = Stats()
-    if limits is not None:
-      self.set_limits(limits)
-    if bias is not None:
-      self.set_frame_bias(bias)
-    rc = self._lib.uis_decode(
-        self._handle, ctypes.cast(ctypes.c_void_p(int(frames_ptr)), _fp),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        ctypes.byref(opts),
-        ctypes.cast(ctypes.c_void_p(int(labels_ptr)), ctypes.POINTER(ctypes.c_int32)),
-        ctypes.cast(ctypes.c_void_p(int(scores_ptr)), _fp) if scores_ptr else None,
-        ctypes.byref(stats))
-    rc = self._check(rc, 'uis_decode')
-    self._last_offsets = offsets.copy()
-    return {'stats': stats.as_dict(), 'status': rc}
+    return self._run_decode(
+        self._lib.uis_decode, 'uis_decode', opts, ctypes.cast(ctypes.c_void_p(int(frames_ptr)), _fp), offsets,
+        offsets.copy(), ctypes.cast(ctypes.c_void_p(int(labels_ptr)), _i32p),
+        ctypes.cast(ctypes.c_void_p(int(scores_ptr)), _fp) if scores_ptr else None, limits, bias)
 
   # ---- evaluation on the device (uis_eval_*)
   @staticmethod
@@ -1150,11 +1082,8 @@ class Decoder:
     offsets, n_utt, matched = self._eval_args(offsets)
     if labels_a.shape != labels_b.shape or labels_a.shape[0] != int(offsets[-1]):
       raise ValueError('both label arrays must hold offsets[-1] entries')
-    i32p = ctypes.POINTER(ctypes.c_int32)
     self._check(self._lib.uis_eval_accuracy(
-        self._handle, labels_a.ctypes.data_as(i32p), labels_b.ctypes.data_as(i32p),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        matched.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), 'uis_eval_accuracy')
+        self._handle, _i32(labels_a), _i32(labels_b), _i64(offsets), n_utt, _i64(matched)), 'uis_eval_accuracy')
     return matched[:n_utt]
 
   def eval_matched_device(self, d_labels_a_ptr, d_labels_b_ptr, offsets):
@@ -1162,17 +1091,15 @@ class Decoder:
     offsets, n_utt, matched = self._eval_args(offsets)
     self._check(self._lib.uis_eval_accuracy_device(
         self._handle, ctypes.c_void_p(int(d_labels_a_ptr)), ctypes.c_void_p(int(d_labels_b_ptr)),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        matched.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), 'uis_eval_accuracy_device')
+        _i64(offsets), n_utt, _i64(matched)), 'uis_eval_accuracy_device')
     return matched[:n_utt]
 
   def eval_last_decode(self, truth, n_utt):
     """Matched positions of the last decode()'s labels (still in HBM) against `truth`."""
     truth = np.ascontiguousarray(truth, dtype=np.int32)
     matched = np.zeros(max(int(n_utt), 1), dtype=np.int64)
-    self._check(self._lib.uis_eval_last_decode(
-        self._handle, truth.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(n_utt),
-        matched.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), 'uis_eval_last_decode')
+    self._check(self._lib.uis_eval_last_decode(self._handle, _i32(truth), int(n_utt), _i64(matched)),
+                'uis_eval_last_decode')
     return matched[:int(n_utt)]
 
   def decode_device(self, d_frames_ptr, offsets, beam_size, look_ahead,
@@ -1180,23 +1107,11 @@ class Decoder:
                     flags=0, n_streams=0, limits=None, bias=None):
     """Decode with frames/labels/scores already resident in HBM (raw pointers)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n_utt = offsets.shape[0] - 1
-    opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags,
-                     n_streams)
-    stats = Stats()
-    if limits is not None:
-      self.set_limits(limits)
-    if bias is not None:
-      self.set_frame_bias(bias)
-    rc = self._lib.uis_decode_device(
-        self._handle, ctypes.c_void_p(int(d_frames_ptr)),
-        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_utt,
-        ctypes.byref(opts), ctypes.c_void_p(int(d_labels_ptr)),
-        ctypes.c_void_p(int(d_scores_ptr) if d_scores_ptr else None),
-        ctypes.byref(stats))
-    rc = self._check(rc, 'uis_decode_device')
-    self._last_offsets = offsets.copy()
-    return {'stats': stats.as_dict(), 'status': rc}
+    opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams)
+    return self._run_decode(
+        self._lib.uis_decode_device, 'uis_decode_device', opts, ctypes.c_void_p(int(d_frames_ptr)), offsets,
+        offsets.copy(), ctypes.c_void_p(int(d_labels_ptr)),
+        ctypes.c_void_p(int(d_scores_ptr) if d_scores_ptr else None), limits, bias)
 
 
 def flatten_params(params):
@@ -1272,14 +1187,8 @@ class Trainer:
     self._lengths = None
 
   def _check(self, rc, what):
-    if rc == UIS_OK:
-      return
-    msg = last_error(self._lib)
-    if rc == UIS_ERR_DIM_MISMATCH:
-      raise ValueError(msg)
-    err = HipLibraryError('{} failed ({}): {}'.format(what, rc, msg))
-    err.status = rc
-    raise err
+    if rc != UIS_OK:
+      _raise_status(self._lib, rc, what)
 
   def close(self):
     if getattr(self, '_handle', None):
@@ -1299,18 +1208,15 @@ class Trainer:
     offsets[1:] = np.cumsum(rows)
     pool = _f32(np.concatenate([np.asarray(s).reshape(-1, self.observation_dim)
                                 for s in sub_sequences], axis=0))
-    self._check(self._lib.uis_train_set_data(
-        self._handle, _ptr(pool), offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-        len(rows)), 'uis_train_set_data')
+    self._check(self._lib.uis_train_set_data(self._handle, _ptr(pool), _i64(offsets), len(rows)), 'uis_train_set_data')
     self._lengths = np.asarray(rows)
 
   def step(self, batch_idx, want_losses=True):
     """One iteration on the sub-sequences batch_idx (longest first): (loss, loss1, loss2, loss3)."""
     idx = np.ascontiguousarray(batch_idx, dtype=np.int32)
     out = np.zeros(4, dtype=np.float32)
-    self._check(self._lib.uis_train_step(
-        self._handle, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
-        _ptr(out) if want_losses else None), 'uis_train_step')
+    self._check(self._lib.uis_train_step(self._handle, _i32(idx), len(idx), _ptr(out) if want_losses else None),
+                'uis_train_step')
     return tuple(float(v) for v in out) if want_losses else None
 
   def flat_params(self):

@@ -160,6 +160,38 @@ _DEFAULT_LEVEL_CAP = 32768   # include/uisrnn_hip.h: uis_decode_opts.level_cap's
 _MAX_LEVEL_CAP = 524287      # ... and its maximum
 
 
+def _more_room(cap):
+  """The cluster cap of the next attempt, after a hypothesis has opened more clusters than `cap`: twice the room."""
+  if cap * 2 > _MAX_CLUSTERS_LIMIT:
+    raise RuntimeError('more than {} clusters per hypothesis'.format(_MAX_CLUSTERS_LIMIT))
+  return cap * 2
+
+
+def _first_appearance(ids):
+  """Ids of any hashable kind as int32 labels, renamed by order of first appearance."""
+  names = {}
+  return np.array([names.setdefault(i, len(names)) for i in ids], dtype=np.int32)
+
+
+def _sequences_with_ids(test_sequences, cluster_ids, name):
+  """One array with its id sequence, or a list of arrays with a list of id sequences (the argument `name`), as
+  (single, sequences, id sequences)."""
+  if isinstance(test_sequences, np.ndarray):
+    return True, [test_sequences], [cluster_ids]
+  if not isinstance(test_sequences, list):
+    raise TypeError('test_sequences should be either a list or numpy array.')
+  if not isinstance(cluster_ids, (list, tuple)) or len(cluster_ids) != len(test_sequences):
+    raise ValueError('{} must be a list with one id sequence per test sequence.'.format(name))
+  return False, test_sequences, list(cluster_ids)
+
+
+def _chunk_sizes(chunks):
+  """Frames per utterance of a push: of one [U, n, D] array, or of a list with an array (or None) per utterance."""
+  if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
+    return [int(chunks.shape[1])] * len(chunks)
+  return [0 if c is None else len(c) for c in chunks]
+
+
 def _stable_ids(gone, n):
   """The first n non-negative integers that are not in the sorted list `gone`."""
   out, skip, c = [], set(gone), 0
@@ -407,6 +439,35 @@ class UISRNN:
       raise ValueError('test_sequence does not match the dimension specified '
                        'by args.observation_dim.')
 
+  def _offline_arguments(self, test_sequences, args, max_speakers, transition_bias, sequences_first=False):
+    """The offline entry points' arguments, checked: (single, sequences, limits, bias) -- single: one array was given,
+    and the caller hands out result 0; limits and bias as _decode_batch takes them.
+
+    The first bad argument is the one reported, and the order is part of the interface: an array's sequence comes
+    before its bound (the reference's checks first), a list's bound before its sequences -- except with
+    sequences_first, parallel_predict's order.  transition_bias needs the lengths and is always last."""
+    single = isinstance(test_sequences, np.ndarray)
+    if not single and not isinstance(test_sequences, list):
+      raise TypeError('test_sequences should be either a list or numpy array.')
+    seqs = [test_sequences] if single else test_sequences
+    if not (single or sequences_first):
+      limits = _check_max_speakers(max_speakers, args, len(seqs))
+    for seq in seqs:
+      self._check_sequence(seq)
+    if single or sequences_first:
+      limits = _check_max_speakers(max_speakers, args, len(seqs))
+    bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single)
+    return single, seqs, limits, bias
+
+  def _predict(self, test_sequences, args, max_speakers, transition_bias, **readout):
+    """predict / predict_nbest / predict_posteriors: the checked arguments through _decode_batch, whose `readout`
+    keyword (n_best or posterior) selects what an utterance's result is."""
+    single, seqs, limits, bias = self._offline_arguments(test_sequences, args, max_speakers, transition_bias)
+    if not seqs:
+      return []
+    results = self._decode_batch(seqs, args, limits=limits, bias=bias, **readout)
+    return results[0] if single else results
+
   def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
                     limits=None, bias=None):
     """Decode a list of validated sequences in one lock-step batch.
@@ -424,165 +485,156 @@ class UISRNN:
     """
     decoder = decoder or self._get_decoder(device)
 
-    def lim_of(members):
-      return None if limits is None else [limits[u] for u in members]
+    def take(members):
+      """What one decode call is handed for these sequences: the arrays, and their entries of limits and bias as
+      decode_f64's keywords (a table that is None is no keyword at all)."""
+      tables = {}
+      if limits is not None:
+        tables['limits'] = [limits[u] for u in members]
+      if bias is not None:
+        tables['bias'] = np.concatenate([bias[u] for u in members])
+      return [sequences[u] for u in members], tables
 
-    def bias_of(members):
-      return None if bias is None else [bias[u] for u in members]
+    def decode(members, level_cap):
+      """The results of sequences[u] for u in members, in that order.  Everything below is numbered inside `members`;
+      a LookAheadWindowError that leaves here is too."""
+      n_utt = len(members)
+      results = [None] * n_utt
+      failed, errors = [], []   # the utterances whose look-ahead window fits no capacity, and what said so
 
-    # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
-    level_cap = level_cap or int(getattr(args, 'level_cap', 0) or 0)
-    n_utt = len(sequences)
-    results = [None] * n_utt
-    pending = list(range(n_utt))
-    cap = _initial_cluster_cap(args, limits)
-    stats = None
-    while pending:
-      # the float64 arrays go to the library as they are (uis_decode_f64): it casts to float32
-      # once, like torch.from_numpy(seq).float() (uisrnn.py:525), on its own threads while the
-      # earlier chunks are already travelling to the device
-      sub = [sequences[u] for u in pending]
-      sub_off = np.zeros(len(pending) + 1, dtype=np.int64)
-      sub_off[1:] = np.cumsum([s.shape[0] for s in sub])
-      try:
-        out = decoder.decode_f64(sub, args.beam_size, args.look_ahead,
-                                 args.test_iteration, max_clusters=cap, flags=flags, level_cap=level_cap,
-                                 **({} if limits is None else {'limits': lim_of(pending)}),
-                                 **({} if bias is None else {'bias': np.concatenate(bias_of(pending))}))
-      except _capi.HipLibraryError as err:
-        if err.status == _capi.UIS_ERR_OOM and len(pending) > 1:
-          # the decode state of this many utterances does not fit the device (or the pinned staging
-          # block the host): the reference's predict takes a list of any size (uisrnn.py:588-589), so
-          # the list goes in two halves, one after the other -- alternating members, so that a list
-          # dealt longest-first stays even -- and each half may halve again
-          level_full, first_err = [], None
-          for part in (pending[0::2], pending[1::2]):
-            try:
-              part_labels = self._decode_batch([sequences[u] for u in part], args, flags, device, decoder, level_cap, n_best, posterior,
-                                                lim_of(part), bias_of(part))
-            except LookAheadWindowError as inner:
-              # (a half whose look-ahead window overflowed: its indices and results are numbered inside
-              # the half -- hand them up in the caller's numbering, and still decode the other half)
-              part_labels = inner.results
-              level_full.extend(part[k] for k in inner.utterances)
-              first_err = first_err or inner
-            for u, labels in zip(part, part_labels):
-              results[u] = labels
-          with self._state_lock:
-            self._single_pass = False  # several decodes: no single resident label buffer
-          if first_err is not None:
-            level_full = sorted(level_full)
-            exc = LookAheadWindowError('{} (utterances {})'.format(
-                str(first_err).split(' (utterances')[0], level_full))
-            exc.status, exc.utterances, exc.results = first_err.status, tuple(level_full), results
-            raise exc from first_err
-          return results
-        if err.status != _capi.UIS_ERR_UNSUPPORTED or args.look_ahead < 2:
-          raise
-        # a look-ahead window of some utterances held more assignment prefixes than a level has
-        # room for (bit 1 of their flags).  The flags come from the library, sized by the library:
-        # a decode that was refused for its OPTIONS (look_ahead > 1024, beam_size > 32767) never
-        # started and leaves no flags behind -- that error goes up as it is.
-        flags_now = decoder.last_overflow()
-        if flags_now.shape[0] != len(pending):
-          raise
-        level_full = [u for k, u in enumerate(pending) if flags_now[k] & 2]
-        if not level_full:
-          raise
-        # The others' results are valid but were not handed out: decode them again on their own, at the
-        # same capacity.  The affected ones get eight times the room per level (the library's default is
-        # 32768 hypotheses per level, its maximum 524287), again and again; what ends the retries is the
-        # maximum, or the device's memory (UIS_ERR_OOM for a single utterance).
-        rest = [u for u in pending if u not in level_full]
-        failed, first_err = [], None
-        groups = [(rest, level_cap)]
-        now_cap = level_cap or _DEFAULT_LEVEL_CAP
-        if now_cap < _MAX_LEVEL_CAP:
-          groups.append((level_full, min(now_cap * 8, _MAX_LEVEL_CAP)))
-        else:
-          failed, first_err = list(level_full), err
-        for members, cap_level in groups:
-          if not members:
-            continue
+      def regroup(part, part_cap):
+        """Decode the utterances `part` as a group of their own.  A look-ahead overflow in there is numbered inside
+        the group: its utterances join `failed` under their numbers here, the other results are kept."""
+        try:
+          part_results = decode([members[k] for k in part], part_cap)
+        except LookAheadWindowError as inner:
+          part_results = inner.results
+          failed.extend(part[k] for k in inner.utterances)
+          errors.append(inner)
+        for u, labels in zip(part, part_results):
+          results[u] = labels
+
+      def regrouped():
+        with self._state_lock:
+          self._single_pass = False  # several decodes: no single resident label buffer
+        if failed:
+          failed.sort()
+          exc = LookAheadWindowError('{} (utterances {})'.format(str(errors[0]).split(' (utterances')[0], failed))
+          exc.status, exc.utterances, exc.results = _capi.UIS_ERR_UNSUPPORTED, tuple(failed), results
+          raise exc from errors[0]
+        return results
+
+      pending = list(range(n_utt))
+      first_cap = cap = None
+      stats = None
+      while pending:
+        # the float64 arrays go to the library as they are (uis_decode_f64): it casts to float32
+        # once, like torch.from_numpy(seq).float() (uisrnn.py:525), on its own threads while the
+        # earlier chunks are already travelling to the device
+        sub, tables = take(members if len(pending) == n_utt else [members[u] for u in pending])
+        if cap is None:
+          first_cap = cap = _initial_cluster_cap(args, tables.get('limits'))
+        sub_off = np.zeros(len(pending) + 1, dtype=np.int64)
+        sub_off[1:] = np.cumsum([s.shape[0] for s in sub])
+        try:
+          out = decoder.decode_f64(sub, args.beam_size, args.look_ahead, args.test_iteration,
+                                   max_clusters=cap, flags=flags, level_cap=level_cap, **tables)
+        except _capi.HipLibraryError as err:
+          if err.status == _capi.UIS_ERR_OOM and len(pending) > 1:
+            # the decode state of this many utterances does not fit the device (or the pinned staging
+            # block the host): the reference's predict takes a list of any size (uisrnn.py:588-589), so
+            # the list goes in two halves, one after the other -- alternating members, so that a list
+            # dealt longest-first stays even -- and each half may halve again.  (A half whose look-ahead
+            # window overflowed still lets the other half decode.)
+            regroup(pending[0::2], level_cap)
+            regroup(pending[1::2], level_cap)
+            return regrouped()
+          if err.status != _capi.UIS_ERR_UNSUPPORTED or args.look_ahead < 2:
+            raise
+          # a look-ahead window of some utterances held more assignment prefixes than a level has
+          # room for (bit 1 of their flags).  The flags come from the library, sized by the library:
+          # a decode that was refused for its OPTIONS (look_ahead > 1024, beam_size > 32767) never
+          # started and leaves no flags behind -- that error goes up as it is.
+          flags_now = decoder.last_overflow()
+          if flags_now.shape[0] != len(pending):
+            raise
+          level_full = [u for k, u in enumerate(pending) if flags_now[k] & 2]
+          if not level_full:
+            raise
+          # The others' results are valid but were not handed out: decode them again on their own, at the
+          # same capacity.  The affected ones get eight times the room per level (the library's default is
+          # 32768 hypotheses per level, its maximum 524287), again and again; what ends the retries is the
+          # maximum, or the device's memory (UIS_ERR_OOM for a single utterance).
+          rest = [u for u in pending if u not in level_full]
+          now_cap = level_cap or _DEFAULT_LEVEL_CAP
+          more = min(now_cap * 8, _MAX_LEVEL_CAP)
+          if now_cap >= _MAX_LEVEL_CAP:   # (no more room to give)
+            failed.extend(level_full)
+            errors.append(err)
+          if rest:
+            regroup(rest, level_cap)
           try:
-            partial = self._decode_batch([sequences[u] for u in members], args, flags, device, decoder, cap_level, n_best, posterior,
-                                         lim_of(members), bias_of(members))
-          except LookAheadWindowError as inner:
-            # (indices and results are numbered inside `members`: hand them up in the caller's numbering)
-            partial = inner.results
-            failed.extend(members[k] for k in inner.utterances)
-            first_err = first_err or inner
+            if now_cap < _MAX_LEVEL_CAP:
+              regroup(level_full, more)
           except _capi.HipLibraryError as inner:
-            if inner.status != _capi.UIS_ERR_OOM or members is rest:
+            if inner.status != _capi.UIS_ERR_OOM:
               raise
             # One utterance's window does not fit the device at this capacity (the halving inside that call got down
             # to a single utterance and still met UIS_ERR_OOM).  Which one is not known here: the others of this group
             # would fit -- decode the members one by one and name only those that do not (round 6).
-            partial = []
-            for u in members:
-              try:
-                one = [None] if len(members) == 1 else self._decode_batch([sequences[u]], args, flags, device, decoder, cap_level, n_best, posterior,
-                                                                          lim_of([u]), bias_of([u]))
-                one_err = inner if len(members) == 1 else None
-              except LookAheadWindowError as e1:
-                one, one_err = [None], e1
-              except _capi.HipLibraryError as e1:
-                if e1.status != _capi.UIS_ERR_OOM:
-                  raise
-                one, one_err = [None], e1
-              partial.extend(one)
-              if one_err is not None:
+            for u in level_full:
+              alone = inner   # (a group of one: that call was this utterance's)
+              if len(level_full) > 1:
+                try:
+                  regroup([u], more)
+                  alone = None
+                except _capi.HipLibraryError as again:
+                  if again.status != _capi.UIS_ERR_OOM:
+                    raise
+                  alone = again
+              if alone is not None:
                 failed.append(u)
-                first_err = first_err or one_err
-          for u, labels in zip(members, partial):
-            results[u] = labels
-        with self._state_lock:
-          self._single_pass = False
-        if failed:
-          failed = sorted(failed)
-          exc = LookAheadWindowError('{} (utterances {})'.format(str(first_err).split(' (utterances')[0], failed))
-          exc.status, exc.utterances, exc.results = _capi.UIS_ERR_UNSUPPORTED, tuple(failed), results
-          raise exc from first_err
-        return results
-      if stats is None:
-        stats = out['stats']
-      still = []
-      # (the hypotheses of THIS decode call, before a retry of the flagged utterances replaces its state)
-      hyps = decoder.last_nbest(n_best) if n_best else None
-      post = decoder.last_posterior(posterior) if posterior is not None else None
-      for k, u in enumerate(pending):
-        if out['overflow'][k]:
-          still.append(u)
-        else:
-          labels = out['labels'][sub_off[k]:sub_off[k + 1]]
-          if labels.size and labels[0] < 0:
-            # every candidate of some step was non-finite (nan/inf in the input or the
-            # weights): the reference ends up indexing an empty beam_set
-            # (uisrnn/uisrnn.py:561) and raises the same exception type
-            raise EmptyBeamError('the beam became empty (max() arg is an empty sequence / list '
-                                 'index out of range in the reference): non-finite scores in '
-                                 'utterance {}'.format(u))
-          results[u] = labels.tolist()
-          if hyps is not None and labels.size:
-            live = int(hyps['counts'][k])
-            results[u] = ([row.tolist() for row in hyps['labels'][k][:live]],
-                          [float(x) for x in hyps['scores'][k][:live]])
-          elif hyps is not None:  # no frames: the one empty labeling, as predict answers, at score 0
-            results[u] = ([[]], [0.0])
-          if post is not None:
-            results[u] = (results[u], post['confidence'][k], post['change'][k])
-      pending = still
-      if pending:
-        # a surviving hypothesis opened more clusters than the device tables
-        # hold: decode those utterances again with twice the room
-        cap *= 2
-        if cap > _MAX_CLUSTERS_LIMIT:
-          raise RuntimeError(
-              'more than {} clusters per hypothesis'.format(_MAX_CLUSTERS_LIMIT))
-    with self._state_lock:  # (parallel_predict: the last worker to finish wins, whole)
-      self.last_stats = stats
-      self._single_pass = cap == _initial_cluster_cap(args, limits)  # no retry: one decode covered everything
-    return results
+                errors.append(alone)
+          return regrouped()
+        if stats is None:
+          stats = out['stats']
+        still = []
+        # (the hypotheses of THIS decode call, before a retry of the flagged utterances replaces its state)
+        hyps = decoder.last_nbest(n_best) if n_best else None
+        post = decoder.last_posterior(posterior) if posterior is not None else None
+        for k, u in enumerate(pending):
+          if out['overflow'][k]:
+            still.append(u)
+          else:
+            labels = out['labels'][sub_off[k]:sub_off[k + 1]]
+            if labels.size and labels[0] < 0:
+              # every candidate of some step was non-finite (nan/inf in the input or the
+              # weights): the reference ends up indexing an empty beam_set
+              # (uisrnn/uisrnn.py:561) and raises the same exception type
+              raise EmptyBeamError('the beam became empty (max() arg is an empty sequence / list '
+                                   'index out of range in the reference): non-finite scores in '
+                                   'utterance {}'.format(u))
+            results[u] = labels.tolist()
+            if hyps is not None and labels.size:
+              live = int(hyps['counts'][k])
+              results[u] = ([row.tolist() for row in hyps['labels'][k][:live]],
+                            [float(x) for x in hyps['scores'][k][:live]])
+            elif hyps is not None:  # no frames: the one empty labeling, as predict answers, at score 0
+              results[u] = ([[]], [0.0])
+            if post is not None:
+              results[u] = (results[u], post['confidence'][k], post['change'][k])
+        pending = still
+        if pending:
+          # a surviving hypothesis opened more clusters than the device tables
+          # hold: decode those utterances again with twice the room
+          cap = _more_room(cap)
+      with self._state_lock:  # (parallel_predict: the last worker to finish wins, whole)
+        self.last_stats = stats
+        self._single_pass = cap == first_cap  # no retry: one decode covered everything
+      return results
+
+    # (args.level_cap, like args.max_clusters, is an extension: where the retries of a look-ahead window start)
+    return decode(list(range(len(sequences))), level_cap or int(getattr(args, 'level_cap', 0) or 0))
 
   def predict_and_evaluate(self, test_sequences, test_cluster_ids, args):
     """predict() followed by the demo's accuracy step with the labels kept on the device.
@@ -651,9 +703,8 @@ class UISRNN:
       TypeError: test_sequence is not a float numpy array.
       ValueError: wrong rank or observation dimension.
     """
-    self._check_sequence(test_sequence)
-    return self._decode_batch([test_sequence], args, limits=_check_max_speakers(max_speakers, args, 1),
-                              bias=_check_transition_bias(transition_bias, [test_sequence.shape[0]], single=True))[0]
+    self._check_sequence(test_sequence)   # (a list too is refused here, in the reference's words)
+    return self._predict(test_sequence, args, max_speakers, transition_bias)
 
   def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
              max_speakers=None):
@@ -702,17 +753,7 @@ class UISRNN:
         prefixes inside a window than the device tables hold (a limit the reference does not
         have); the exception names them and carries the other utterances' results.
     """
-    if isinstance(test_sequences, np.ndarray):
-      return self.predict_single(test_sequences, args, max_speakers, transition_bias)
-    if isinstance(test_sequences, list):
-      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
-      for test_sequence in test_sequences:
-        self._check_sequence(test_sequence)
-      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
-      if not test_sequences:
-        return []
-      return self._decode_batch(test_sequences, args, limits=limits, bias=bias)
-    raise TypeError('test_sequences should be either a list or numpy array.')
+    return self._predict(test_sequences, args, max_speakers, transition_bias)
 
   def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None):
     """predict, returning every hypothesis of the final beam instead of the best one (extension).
@@ -735,20 +776,7 @@ class UISRNN:
       raise ValueError('n_best must be an integer in [1, args.beam_size].')
     if not 1 <= int(n_best) <= int(args.beam_size):
       raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(args.beam_size))
-    if isinstance(test_sequences, np.ndarray):
-      self._check_sequence(test_sequences)
-      return self._decode_batch([test_sequences], args, n_best=int(n_best),
-                                limits=_check_max_speakers(max_speakers, args, 1),
-                                bias=_check_transition_bias(transition_bias, [test_sequences.shape[0]], single=True))[0]
-    if isinstance(test_sequences, list):
-      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
-      for test_sequence in test_sequences:
-        self._check_sequence(test_sequence)
-      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
-      if not test_sequences:
-        return []
-      return self._decode_batch(test_sequences, args, n_best=int(n_best), limits=limits, bias=bias)
-    raise TypeError('test_sequences should be either a list or numpy array.')
+    return self._predict(test_sequences, args, max_speakers, transition_bias, n_best=int(n_best))
 
   def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None, transition_bias=None):
     """predict, with the beam's per-frame confidence in its answer (extension).
@@ -774,20 +802,7 @@ class UISRNN:
       what predict raises; ValueError for a temperature that is not a finite number > 0, before any device work.
     """
     temperature = _check_temperature(temperature)
-    if isinstance(test_sequences, np.ndarray):
-      self._check_sequence(test_sequences)
-      return self._decode_batch([test_sequences], args, posterior=temperature,
-                                limits=_check_max_speakers(max_speakers, args, 1),
-                                bias=_check_transition_bias(transition_bias, [test_sequences.shape[0]], single=True))[0]
-    if isinstance(test_sequences, list):
-      limits = _check_max_speakers(max_speakers, args, len(test_sequences))
-      for test_sequence in test_sequences:
-        self._check_sequence(test_sequence)
-      bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
-      if not test_sequences:
-        return []
-      return self._decode_batch(test_sequences, args, posterior=temperature, limits=limits, bias=bias)
-    raise TypeError('test_sequences should be either a list or numpy array.')
+    return self._predict(test_sequences, args, max_speakers, transition_bias, posterior=temperature)
 
   def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
     """predict, with the first frames of every sequence already labeled (extension).
@@ -809,16 +824,7 @@ class UISRNN:
       sequence or a list mismatch; _capi.HipLibraryError (status UIS_ERR_INVALID_ARG) for a prefix whose
       likelihood is not finite.
     """
-    single = isinstance(test_sequences, np.ndarray)
-    if single:
-      seqs, ids = [test_sequences], [prefix_cluster_ids]
-    elif isinstance(test_sequences, list):
-      seqs = test_sequences
-      if not isinstance(prefix_cluster_ids, (list, tuple)) or len(prefix_cluster_ids) != len(seqs):
-        raise ValueError('prefix_cluster_ids must be a list with one id sequence per test sequence.')
-      ids = list(prefix_cluster_ids)
-    else:
-      raise TypeError('test_sequences should be either a list or numpy array.')
+    single, seqs, ids = _sequences_with_ids(test_sequences, prefix_cluster_ids, 'prefix_cluster_ids')
     if int(args.look_ahead) != 1 or int(args.test_iteration) != 1:
       raise ValueError('predict_primed is online decoding: look_ahead and test_iteration must be 1.')
     limits = _check_max_speakers(max_speakers, args, len(seqs))
@@ -830,20 +836,13 @@ class UISRNN:
       if len(seq_ids) > seq.shape[0]:
         raise ValueError('prefix_cluster_ids has {} ids for a sequence of {} frames.'.format(
             len(seq_ids), seq.shape[0]))
-      names = {}
-      prefixes.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
+      prefixes.append(_first_appearance(seq_ids))
     if not seqs:
       return []
     decoder = self._get_decoder()
     results = [None] * len(seqs)
     pending = list(range(len(seqs)))
     cap = _initial_cluster_cap(args, limits)
-
-    def more_room(cap):
-      if cap * 2 > _MAX_CLUSTERS_LIMIT:
-        raise RuntimeError('more than {} clusters per hypothesis'.format(_MAX_CLUSTERS_LIMIT))
-      return cap * 2
-
     while pending:
       lens = [seqs[u].shape[0] for u in pending]
       bound = {} if limits is None else {'limits': [limits[u] for u in pending]}
@@ -854,7 +853,7 @@ class UISRNN:
         except _capi.HipLibraryError as err:
           if err.status != _capi.UIS_ERR_CLUSTER_CAP:
             raise
-          cap = more_room(cap)  # a prefix with more clusters than the tables hold: the batch again, twice the room
+          cap = _more_room(cap)  # a prefix with more clusters than the tables hold: the batch again, twice the room
           continue
         decoder.stream_push([seqs[u][len(prefixes[u]):] if seqs[u].shape[0] > len(prefixes[u]) else None
                              for u in pending])
@@ -872,21 +871,12 @@ class UISRNN:
         results[u] = per_utt[k].tolist()
       pending = still
       if pending:
-        cap = more_room(cap)
+        cap = _more_room(cap)
     return results[0] if single else results
 
   def _labeled_sequences(self, test_sequences, test_cluster_ids):
     """The argument checks of score_labels / score_speakers: (single, sequences, int32 labels by first appearance)."""
-    single = isinstance(test_sequences, np.ndarray)
-    if single:
-      seqs, ids = [test_sequences], [test_cluster_ids]
-    elif isinstance(test_sequences, list):
-      seqs = test_sequences
-      if not isinstance(test_cluster_ids, (list, tuple)) or len(test_cluster_ids) != len(seqs):
-        raise ValueError('test_cluster_ids must be a list with one id sequence per test sequence.')
-      ids = list(test_cluster_ids)
-    else:
-      raise TypeError('test_sequences should be either a list or numpy array.')
+    single, seqs, ids = _sequences_with_ids(test_sequences, test_cluster_ids, 'test_cluster_ids')
     for seq in seqs:
       self._check_sequence(seq)
     labels = []
@@ -895,9 +885,41 @@ class UISRNN:
       if len(seq_ids) != seq.shape[0]:
         raise ValueError('test_cluster_ids has {} ids for a sequence of {} frames.'.format(
             len(seq_ids), seq.shape[0]))
-      names = {}
-      labels.append(np.array([names.setdefault(i, len(names)) for i in seq_ids], dtype=np.int32))
+      labels.append(_first_appearance(seq_ids))
     return single, seqs, labels
+
+  def _score_in_halves(self, seqs, labels, bias, call, cut):
+    """score_labels / score_speakers: one library call over the packed sequences, or -- when their state does not fit
+    the device (UIS_ERR_OOM) -- over halves of them, as _decode_batch: alternating members, each half may halve again.
+
+    call(decoder, members, frames, offsets, flat labels, bias=flat table or None) is the library call for the
+    utterances `members`; cut(its result, k, u, rows) is what utterance u, the k-th of them with the frames `rows`,
+    gets.  Returns that per utterance."""
+    lens = [s.shape[0] for s in seqs]
+    decoder = self._get_decoder()
+    out = [None] * len(seqs)
+
+    def run(members):
+      sub_off = np.zeros(len(members) + 1, dtype=np.int64)
+      sub_off[1:] = np.cumsum([lens[u] for u in members])
+      frames = np.empty((int(sub_off[-1]), self.observation_dim), dtype=np.float32)
+      for u, start in zip(members, sub_off[:-1]):
+        frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
+      try:
+        result = call(decoder, members, frames, sub_off, np.concatenate([labels[u] for u in members]),
+                      bias=None if bias is None else np.concatenate([bias[u] for u in members]))
+      except _capi.HipLibraryError as err:
+        if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
+          run(members[0::2])
+          run(members[1::2])
+          return
+        raise
+      for k, u in enumerate(members):
+        out[u] = cut(result, k, u, slice(sub_off[k], sub_off[k + 1]))
+
+    if seqs:
+      run(list(range(len(seqs))))
+    return out
 
   def score_labels(self, test_sequences, test_cluster_ids, per_frame=False, transition_bias=None):
     """The model's negative log-likelihood of given labelings (extension).
@@ -919,35 +941,12 @@ class UISRNN:
       losses is a float32 array per sequence.
     """
     single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
-    lens = [s.shape[0] for s in seqs]
-    bias = _check_transition_bias(transition_bias, lens, single=single, offline=False)
-    decoder = self._get_decoder()
-    out_scores, out_losses = [None] * len(seqs), [None] * len(seqs)
-
-    def run(members):
-      sub_off = np.zeros(len(members) + 1, dtype=np.int64)
-      sub_off[1:] = np.cumsum([lens[u] for u in members])
-      frames = np.empty((int(sub_off[-1]), self.observation_dim), dtype=np.float32)
-      for u, start in zip(members, sub_off[:-1]):
-        frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
-      sub_labels = (np.concatenate([labels[u] for u in members]) if members else
-                    np.zeros(0, dtype=np.int32))
-      try:
-        scores, losses = decoder.score_labels(
-            frames, sub_off, sub_labels, want_frame_losses=True,
-            bias=None if bias is None or not members else np.concatenate([bias[u] for u in members]))
-      except _capi.HipLibraryError as err:
-        if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
-          run(members[0::2])  # (as _decode_batch: alternating members, each half may halve again)
-          run(members[1::2])
-          return
-        raise
-      for k, u in enumerate(members):
-        out_scores[u] = float(scores[k])
-        out_losses[u] = losses[sub_off[k]:sub_off[k + 1]].copy()
-
-    if seqs:
-      run(list(range(len(seqs))))
+    bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single, offline=False)
+    out = self._score_in_halves(
+        seqs, labels, bias,
+        lambda decoder, members, *packed, bias: decoder.score_labels(*packed, want_frame_losses=True, bias=bias),
+        lambda result, k, u, rows: (float(result[0][k]), result[1][rows].copy()))
+    out_scores, out_losses = [score for score, _ in out], [losses for _, losses in out]
     if single:
       return (out_scores[0], out_losses[0]) if per_frame else out_scores[0]
     return (out_scores, out_losses) if per_frame else out_scores
@@ -968,34 +967,13 @@ class UISRNN:
       a float32 [N, K + 1] array (array), K the sequence's number of speakers, or a list of them (list).
     """
     single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
-    lens = [s.shape[0] for s in seqs]
     widths = [int(l.max()) + 2 if l.size else 1 for l in labels]
-    bias = _check_transition_bias(transition_bias, lens, single=single, offline=False)
-    decoder = self._get_decoder()
-    out = [None] * len(seqs)
-
-    def run(members):
-      sub_off = np.zeros(len(members) + 1, dtype=np.int64)
-      sub_off[1:] = np.cumsum([lens[u] for u in members])
-      frames = np.empty((int(sub_off[-1]), self.observation_dim), dtype=np.float32)
-      for u, start in zip(members, sub_off[:-1]):
-        frames[start:start + lens[u]] = seqs[u]  # float64 -> float32 (RNE), as predict
-      sub_labels = np.concatenate([labels[u] for u in members])
-      try:
-        _, losses = decoder.score_speakers(
-            frames, sub_off, sub_labels, max(widths[u] for u in members),
-            bias=None if bias is None else np.concatenate([bias[u] for u in members]))
-      except _capi.HipLibraryError as err:
-        if err.status == _capi.UIS_ERR_OOM and len(members) > 1:
-          run(members[0::2])  # (as score_labels)
-          run(members[1::2])
-          return
-        raise
-      for k, u in enumerate(members):
-        out[u] = losses[sub_off[k]:sub_off[k + 1], :widths[u]].copy()
-
-    if seqs:
-      run(list(range(len(seqs))))
+    bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single, offline=False)
+    out = self._score_in_halves(
+        seqs, labels, bias,
+        lambda decoder, members, *packed, bias: decoder.score_speakers(
+            *packed, max(widths[u] for u in members), bias=bias)[1],
+        lambda losses, k, u, rows: losses[rows, :widths[u]].copy())
     return out[0] if single else out
 
 
@@ -1151,8 +1129,7 @@ class OnlineSession:
       if received[u]:
         raise ValueError('utterance {} has already received {} frames: a prefix goes in front of '
                          'everything.'.format(u, int(received[u])))
-      names = {}
-      labels[u] = np.array([names.setdefault(i, len(names)) for i in ids], dtype=np.int32)
+      labels[u] = _first_appearance(ids)
       frames[u] = chunk
     scores = self._decoder.stream_prime(frames, labels)
     if self._bound is not None:
@@ -1164,13 +1141,10 @@ class OnlineSession:
     """push's transition_bias as the library's flat table: the chunk's frames, utterance by utterance."""
     if transition_bias is None:
       return None
-    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
-      sizes = [chunks.shape[1]] * len(chunks)
-      if isinstance(transition_bias, np.ndarray) and transition_bias.ndim == 2:
-        transition_bias = list(transition_bias)   # ([U, n]: one row per utterance)
-    else:
-      sizes = [0 if c is None else len(c) for c in chunks]
-    tables = _check_transition_bias(transition_bias, sizes, offline=False)
+    if (isinstance(chunks, np.ndarray) and chunks.ndim == 3 and
+        isinstance(transition_bias, np.ndarray) and transition_bias.ndim == 2):
+      transition_bias = list(transition_bias)   # ([U, n] beside [U, n, D]: one row per utterance)
+    tables = _check_transition_bias(transition_bias, _chunk_sizes(chunks), offline=False)
     return np.concatenate(tables) if tables else np.zeros(0, dtype=np.float64)
 
   def push(self, chunks, transition_bias=None):
@@ -1217,10 +1191,7 @@ class OnlineSession:
 
   def _make_room(self, chunks):
     """horizon given: a push whose chunk does not fit the window commits first."""
-    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
-      sizes = np.full(len(chunks), chunks.shape[1], dtype=np.int64)
-    else:
-      sizes = np.array([0 if c is None else len(c) for c in chunks], dtype=np.int64)
+    sizes = np.array(_chunk_sizes(chunks), dtype=np.int64)
     if len(sizes) != self._num_utterances:
       return   # (stream_push refuses it in its own words)
     if ((self._decoder.stream_received() + sizes) <= self._max_frames).all():
@@ -1378,10 +1349,7 @@ class OnlineSession:
   def _keep_under_cap(self, chunks):
     """retire_at given: before a push that could take an utterance to retire_at clusters or more, commit (with the
     session's horizon), query, and retire retirable clusters, least recently heard first, down to retire_to."""
-    if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
-      sizes = [int(chunks.shape[1])] * len(chunks)
-    else:
-      sizes = [0 if c is None else len(c) for c in chunks]
+    sizes = _chunk_sizes(chunks)
     n_utt = self._num_utterances
     if len(sizes) != n_utt:
       return   # (stream_push refuses it in its own words)
@@ -1431,11 +1399,10 @@ class OnlineSession:
     n_utt = self._num_utterances
     which = [0] * n_utt
     for u in utterances:
-      if isinstance(u, bool) or not isinstance(u, (int, np.integer)) or not 0 <= int(u) < n_utt:
-        raise ValueError('utterance index {!r} is not in [0, {}).'.format(u, n_utt))
-      if which[int(u)]:
-        raise ValueError('utterance {} is given twice.'.format(int(u)))
-      which[int(u)] = 1
+      u = self._utterance(u)
+      if which[u]:
+        raise ValueError('utterance {} is given twice.'.format(u))
+      which[u] = 1
     per_utt, scores, overflow, _ = self._decoder.stream_restart(which)
     out = [None] * n_utt
     for u in range(n_utt):
@@ -1717,10 +1684,8 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
   """
   if not isinstance(test_sequences, list):
     raise TypeError('test_sequences must be a list.')
-  for test_sequence in test_sequences:
-    model._check_sequence(test_sequence)  # pylint: disable=protected-access
-  limits = _check_max_speakers(max_speakers, args, len(test_sequences))
-  bias = _check_transition_bias(transition_bias, [s.shape[0] for s in test_sequences])
+  _, _, limits, bias = model._offline_arguments(  # pylint: disable=protected-access
+      test_sequences, args, max_speakers, transition_bias, sequences_first=True)
   if not test_sequences:
     return []
   if devices is None:
