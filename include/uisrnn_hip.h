@@ -455,6 +455,45 @@ int32_t uis_stream_get_limits(uis_handle* h, int32_t* out);
 int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames);
 
 /*
+ * Known speakers: decode under partial speaker labels.
+ *
+ * tags[t] names who speaks at frame t of the NEXT decode: 0 = unknown, 1 .. 127 = a known speaker (a corrected segment,
+ * an enrolled voice, a channel or ASR speaker tag; two snippets known to be the same person carry the same tag, two known
+ * to differ carry different ones).  Every hypothesis holds a partial, injective binding of tags to its clusters.  At a
+ * frame with tag g > 0, a hypothesis with K clusters has these candidates: if g is bound to cluster c*, only c*;
+ * otherwise the clusters c < K that carry no tag, and the new cluster K (still subject to max_speakers) -- and the
+ * candidate that wins binds g to its cluster.  At a frame with tag 0 every candidate is as without a table, clusters
+ * that carry a tag included, and nothing is bound.  The same rule holds for sub-step j of a look-ahead window (its own
+ * frame's tag, the binding of the prefix it extends) and for the later passes of test_iteration >= 2 (the tag of frame
+ * t % n; bindings persist).  Nothing else changes -- the priors, the ddCRP terms, the float32 accumulation, the prune
+ * order, the tie rules, max_speakers, uis_frame_bias -- and an all-zero table gives the decode without one bit for bit.
+ *
+ * A disallowed candidate has a loss of +inf, which every select drops.  A contradiction -- two tags under
+ * max_speakers 1, a bias of 0 at a frame whose tag is bound to another cluster -- leaves an empty beam, reported as
+ * ever (labels -1, score +inf).  Returned labels stay first-appearance integers: frames with equal tags get equal labels,
+ * frames with different tags different ones.
+ *
+ *   uis_frame_speakers   tags: host uint8 [n_frames], each in 0 .. 127 (a larger value: UIS_ERR_INVALID_ARG, and the
+ *                        pending table stays as it was); tags == NULL or n_frames == 0 clears a pending table.  The
+ *                        table belongs to the NEXT uis_decode / uis_decode_f64 / uis_decode_device on this handle, in
+ *                        that call's frame order (utterance-major), and must hold exactly that call's frame count (else
+ *                        that call returns UIS_ERR_INVALID_ARG and nothing runs).  The call consumes it whether it
+ *                        succeeds or not; a call without a pending table decodes without one, whatever an earlier call
+ *                        used.
+ *
+ * Refused with UIS_ERR_UNSUPPORTED, the table consumed and the handle usable: every uis_stream_* call made while a table
+ * is pending (sessions, priming and blobs carry no bindings yet), uis_score_labels and uis_score_speakers (their labels
+ * are given), and a decode whose test_iteration * N reaches 2^24 (a cluster's tag shares its block-count word).  The
+ * refused call has done nothing but drop the table -- and whatever other pending table it would have consumed
+ * (uis_frame_bias, uis_decode_limits).  That holds for uis_stream_end as well: refused, it leaves the session OPEN, and
+ * the same call made again (no table is pending any more) closes it; a caller whose cleanup path may run with a table
+ * pending clears it first (uis_frame_speakers(h, NULL, 0)) or calls uis_stream_end twice.  A decode
+ * with a table runs the kernels with the owner-side selects, as one with uis_frame_bias does: where the decode without
+ * one reports k_decode_rs or k_decode_big<WS>, uis_last_decode_instantiation reports k_decode_resident or k_decode_big.
+ */
+int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames);
+
+/*
  * Primed sessions: start the online decode of an open session's utterances from a LABELED PREFIX (enrolment,
  * a corrected opening, a recording continued across a seam).  Afterwards the session is in the state it would
  * hold had it received the prefix frames and its beam contained only the given hypothesis: the state

@@ -175,6 +175,7 @@ struct HandleMem {
   DevBuf lv_n, lv_K, lv_last, lv_sum, lv_score, lv_origin, lv_path, lv_slot, lv_blk, scratch, bp16, bp_base, cluster_ctl, resume, split_tab, scatter_tab, stage;
   DevBuf limit, limit_in;  // [U] int32 each: DecodeState::limit, written by every decode, and uis_decode_limits' table it is written from
   DevBuf bias3;  // [frames][3] float64: DecodeState::bias3 of a decode with a uis_frame_bias table (the workspace's last view)
+  DevBuf hint;   // [frames] uint8: DecodeState::hint of a decode with a uis_frame_speakers table (behind bias3: the workspace's last view)
   DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   HostBuf h_cast;  // uis_decode_f64: the pinned float32 staging buffer the utterances are cast into, chunk by chunk, ahead of each H2D copy
@@ -292,6 +293,10 @@ struct uis_handle : HandleMem {
   // takes frames, and the running call's (take_bias, at that call's entry: consumed whether the call succeeds or not)
   std::vector<double> pending_bias3, call_bias3;
   bool pending_bias_set = false, call_bias_set = false;
+  // known speakers: one tag per frame (0 unknown, 1 .. 127) as uis_frame_speakers left them for the next decode, and the
+  // running call's (take_hint, at that call's entry: consumed whether the call succeeds or not)
+  std::vector<uint8_t> pending_hint, call_hint;
+  bool pending_hint_set = false, call_hint_set = false;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
   // offsets, the record format
@@ -823,6 +828,10 @@ struct DecodeShape {
   // the call has a per-frame transition_bias table (uis_frame_bias).  k_decode_rs and k_decode_big<WS> form their priors
   // in rs_prep, which knows no table: such a decode runs the kernels with the owner-side selects
   bool biased = false;
+  // the call has a per-frame speaker table (uis_frame_speakers).  The bindings ride in the block-count words, which the
+  // replicated selects of k_decode_rs and k_decode_big<WS> keep in a layout of their own: excluded like `biased`
+  // 
+  bool hinted = false;
 };
 
 enum class DecodePath { STEPWISE, GRAPH, RESIDENT, RS, BIG, BIG_WS, WINDOW, DEEP, SMALL };
@@ -932,7 +941,7 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
                    big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B) <= 157 * 1024;
 
   if (resident) {
-    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0 || s.biased;
+    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0 || s.biased || s.hinted;
     const int per_xcd = (U + p.ncl - 1) / p.ncl;
     // (k_decode_rs keeps frame numbers in 32 bits and reads the frame stream through 4 GB descriptors with 32-bit byte
     // offsets: a row of gi0 is 3 Hp floats, a row of x Dp)
@@ -1403,6 +1412,9 @@ int derive_shape(DecodeCall& c) {
   if (h->call_bias_set && (int64_t)h->call_bias3.size() != 3 * F)
     return fail(UIS_ERR_INVALID_ARG, "uis_frame_bias gave " + std::to_string(h->call_bias3.size() / 3) + " values, this decode has " +
                                          std::to_string(F) + " frames");
+  if (h->call_hint_set && (int64_t)h->call_hint.size() != F)
+    return fail(UIS_ERR_INVALID_ARG, "uis_frame_speakers gave " + std::to_string(h->call_hint.size()) + " tags, this decode has " +
+                                         std::to_string(F) + " frames");
   bool ragged_list = false;  // (utterances of different lengths)
   for (int u = 1; u < n_utt; ++u) ragged_list = ragged_list || offsets[u + 1] - offsets[u] != offsets[1] - offsets[0];
   if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
@@ -1416,6 +1428,9 @@ int derive_shape(DecodeCall& c) {
   if (F > 0 && (!c.d_frames || !c.d_labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels_out is null");
   const int64_t maxT = (int64_t)tau * maxN;
   if (maxT > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "test_iteration * N too large");
+  // (a cluster's tag shares its block-count word: the count keeps bits 0 .. 23)
+  if (h->call_hint_set && maxT >= ((int64_t)1 << 24))
+    return fail(UIS_ERR_UNSUPPORTED, "a decode with known speakers (uis_frame_speakers) needs test_iteration * N below 2^24");
   HIPCHK(hipSetDevice(h->device));
 
   const int U = n_utt;
@@ -1487,7 +1502,7 @@ int derive_shape(DecodeCall& c) {
     for (int u = 0; u < U; ++u)
       c.bp_base[u + 1] = c.bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
   c.shape = DecodeShape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, c.h_frames != nullptr,
-                        wnd, (size_t)lds.total, c.wsl.total, h->call_bias_set};
+                        wnd, (size_t)lds.total, c.wsl.total, h->call_bias_set, h->call_hint_set};
   return UIS_OK;
 }
 
@@ -1574,6 +1589,9 @@ int upload_tables(DecodeCall& c) {
   // (uis_frame_bias: the whole table ahead of the first launch, also of a decode in several)
   if (h->call_bias_set && s.F > 0)
     HIPCHK(hipMemcpyAsync(h->bias3.p, h->call_bias3.data(), (size_t)s.F * 24, hipMemcpyHostToDevice, h->stream));
+  // (uis_frame_speakers: likewise the whole tag table)
+  if (h->call_hint_set && s.F > 0)
+    HIPCHK(hipMemcpyAsync(h->hint.p, h->call_hint.data(), (size_t)s.F, hipMemcpyHostToDevice, h->stream));
   if (int rc = upload_log_tables(h->alpha, c.n_log, c.log_host, h->logblk.p, h->logden.p, h->stream)) return rc;
   if (s.wnd)
     HIPCHK(hipMemcpyAsync(h->bp_base.p, c.bp_base.data(), (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -1815,6 +1833,7 @@ void build_group_states(DecodeCall& c) {
     st.limit = h->limit.as<int32_t>() + u0;
     st.limit_in = h->call_limits_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
     st.bias3 = h->call_bias_set ? h->bias3.as<double>() : nullptr;  // (indexed by the packed frame, like mse0)
+    st.hint = h->call_hint_set ? h->hint.as<uint8_t>() : nullptr;   // (likewise)
     st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
@@ -2261,6 +2280,36 @@ static int refuse_bias(uis_handle* h, const char* who) {
   return fail(UIS_ERR_UNSUPPORTED, std::string(who) + " takes no per-frame transition_bias (uis_frame_bias): the pending table is dropped");
 }
 
+// The same for uis_frame_speakers' table, at the decode entry points.
+static void take_hint(uis_handle* h) {
+  if (!h) return;
+  h->call_hint.swap(h->pending_hint);
+  h->call_hint_set = h->pending_hint_set;
+  h->pending_hint.clear();
+  h->pending_hint_set = false;
+}
+
+// Calls that cannot honour a speaker table refuse a pending one (and consume it).
+static int refuse_hint(uis_handle* h, const char* who) {
+  take_hint(h);
+  if (!h || !h->call_hint_set) return UIS_OK;
+  h->call_hint_set = false;
+  h->call_hint.clear();
+  return fail(UIS_ERR_UNSUPPORTED, std::string(who) + " takes no known speakers (uis_frame_speakers): the pending table is dropped");
+}
+
+UIS_EXPORT int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!tags || n_frames == 0) { h->pending_hint.clear(); h->pending_hint_set = false; return UIS_OK; }
+  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
+  for (int64_t t = 0; t < n_frames; ++t)
+    if (tags[t] > 127)
+      return fail(UIS_ERR_INVALID_ARG, "the speaker tag at frame " + std::to_string(t) + " is above 127 (0: unknown)");
+  h->pending_hint.assign(tags, tags + n_frames);
+  h->pending_hint_set = true;
+  return UIS_OK;
+}
+
 UIS_EXPORT int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
   if (!bias || n_frames == 0) { h->pending_bias3.clear(); h->pending_bias_set = false; return UIS_OK; }
@@ -2289,13 +2338,14 @@ UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const
                                      uis_stats* stats) {
   take_limits(h);
   take_bias(h);
+  take_hint(h);
   if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
 }
 
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                               const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
-  if (h && !h->src64) { take_limits(h); take_bias(h); }  // (uis_decode_f64 has taken them)
+  if (h && !h->src64) { take_limits(h); take_bias(h); take_hint(h); }  // (uis_decode_f64 has taken them)
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
   h->nb_valid = false;  // (a decode refused below leaves nothing for uis_last_decode_nbest either)
   const int64_t F = n_utt ? offsets[n_utt] : 0;
@@ -2353,6 +2403,7 @@ UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances
                                   const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
   take_limits(h);
   take_bias(h);
+  take_hint(h);
   if (!h || n_utt < 0 || (n_utt > 0 && (!utterances || !n_frames)))
     return fail(UIS_ERR_INVALID_ARG, "null handle/utterances/n_frames or negative n_utt");
   h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)

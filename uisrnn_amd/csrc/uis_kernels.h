@@ -228,7 +228,20 @@ struct DecodeState {
   // packed frame stream; a session: the chunk's rows).  Formed on the host with the C library's log; a frame without a
   // value of its own holds the model's three words.  Null: the call has no table and every frame uses DevModel's.
   const double* bias3;       // [frames][3] or null
+
+  // ---- known speakers (uis_frame_speakers): one tag per frame, indexed like mse0; 0 = unknown, 1 .. 127 = a known
+  // speaker.  A hypothesis' binding of tags to clusters rides in its block-count words (UIS_BLK_* below), so whatever
+  // moves a hypothesis' tables moves its binding.  Null: the call has no table.
+  const uint8_t* hint;       // [frames] or null
 };
+
+// A block-count word (beam_blk / lv_blk and their LDS copies): the count in bits 0 .. 23 (it never exceeds tau * N,
+// which a decode with a tag table keeps below 2^24), the cluster's tag in bits 24 .. 30 (0: the cluster carries none).
+// Without a table every tag is 0 and the word is the count.
+#define UIS_BLK_TAG_SHIFT 24
+#define UIS_BLK_COUNT_MASK 0x00ffffff
+__device__ __forceinline__ int blk_count(int w) { return w & UIS_BLK_COUNT_MASK; }
+__device__ __forceinline__ int blk_tag(int w) { return w >> UIS_BLK_TAG_SHIFT; }
 
 // The three prior words of the step that decides `frame` (uniform over the workgroup: one null test, then scalar loads).
 struct StepPriors { double lp_stay, lp_sw, lp_new; };
@@ -239,4 +252,19 @@ __device__ __forceinline__ StepPriors step_priors(const DevModel& m, const Decod
     p.lp_stay = t[0]; p.lp_sw = t[1]; p.lp_new = t[2];
   }
   return p;
+}
+
+// The tag of the frame a step decides (uniform over the workgroup: one null test, then one load); 0: the frame is
+// unknown, or the call has no table, and the step is today's.
+__device__ __forceinline__ int step_tag(const DecodeState& st, long frame) {
+  return st.hint ? (int)st.hint[frame] : 0;
+}
+
+// A frame with tag g > 0 against a hypothesis of K clusters whose block-count words are row[0 .. K): if g is bound, only
+// its cluster may take the frame; otherwise the clusters without a tag and the new cluster K may (the winner binds g).
+__device__ __forceinline__ bool tag_allows(const int* row, int K, int c, int g) {
+  int bound = -1;
+  for (int k = 0; k < K; ++k) bound = blk_tag(row[k]) == g ? k : bound;
+  if (bound >= 0) return c == bound;
+  return c >= K || blk_tag(row[c]) == 0;
 }

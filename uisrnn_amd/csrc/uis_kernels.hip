@@ -1007,13 +1007,14 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
   // ---- round trip 2, part 1: this thread's candidate (the first 256) -- prior-table entries
   const float mse_new = st.mse0[frame];
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's)
+  const int g = step_tag(st, frame);  // (uis_frame_speakers: this frame's known speaker, 0 = unknown or no table)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
     while (tid >= sbase[my_b + 1]) ++my_b;
     my_c = tid - sbase[my_b];
     my_ld = st.logden[ssum[my_b]];
-    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[sblk[my_b * Kmax + my_c]];
+    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
   }
 
   // ---- A: weighted MSE of the frame against every live cluster state.
@@ -1061,7 +1062,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
       while (i >= sbase[b + 1]) ++b;
       c = i - sbase[b];
       ld = st.logden[ssum[b]];
-      lb = (c < sK[b] && c != slast[b]) ? st.logblk[sblk[b * Kmax + c]] : 0.0;
+      lb = (c < sK[b] && c != slast[b]) ? st.logblk[blk_count(sblk[b * Kmax + c])] : 0.0;
     }
     float mse; double prior;
     if (c < sK[b]) {  // existing cluster, uisrnn.py:409-420
@@ -1073,6 +1074,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     }
     float sc = sscore[b] + uis_step_loss(mse, prior);  // float32 accumulate, uisrnn.py:452
     if (c >= sK[b] && c >= lim) sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
+    if (g && !tag_allows(sblk + b * Kmax, sK[b], c, g)) sc = INFINITY;  // known speakers: g's cluster, or one without a tag
     scscore[i] = sc;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc;
     const bool fin = uis_isfinite(sc);
@@ -1155,8 +1157,9 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     const int Knew = Kb + (is_new ? 1 : 0);
     if (c2 < Knew && c2 < Kmax) {
       int slot, blk;
-      if (c2 == c) { slot = sdst[r]; blk = is_new ? 1 : sblk[b * Kmax + c] + (c != slast[b] ? 1 : 0); }
-      else { slot = sslot[b * Kmax + c2]; blk = sblk[b * Kmax + c2]; }
+      if (c2 == c) {  // (a tagged frame binds its tag to the cluster that takes it; a bound cluster keeps its tag)
+        slot = sdst[r]; blk = (is_new ? 1 : sblk[b * Kmax + c] + (c != slast[b] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
+      } else { slot = sslot[b * Kmax + c2]; blk = sblk[b * Kmax + c2]; }
       st.beam_slot[(bnxt + r) * Kmax + c2] = slot;
       st.beam_blk[(bnxt + r) * Kmax + c2] = blk;
     }
@@ -1443,6 +1446,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   const float mse_new = RES ? __hip_atomic_load(st.mse0 + frame, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : st.mse0[frame];
   const int lim = st.limit[u];  // (written between launches only)
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's; uploaded before the launch)
+  const int g = step_tag(st, frame);  // (uis_frame_speakers: this frame's known speaker, 0 = unknown or no table; likewise)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
@@ -1450,7 +1454,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     my_b = (int)(bc >> 16);
     my_c = (int)(bc & 0xffffu);
     my_ld = st.logden[ssum[my_b]];
-    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[sblk[my_b * Kmax + my_c]];
+    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
   }
   const int Dp = DPT ? DPT : m.Dp;
   const float* pmean = st.pool_mean + (size_t)u * S * Dp;
@@ -1543,6 +1547,8 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     }
     my_sc = sscore[my_b] + uis_step_loss(mse, prior);
     if (my_c >= sK[my_b] && my_c >= lim) my_sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
+    // known speakers (tagged frames only): g's cluster, or one without a tag -- read off the hypothesis' own row of sblk
+    if (g && !tag_allows(sblk + my_b * Kmax, sK[my_b], my_c, g)) my_sc = INFINITY;
     if (uis_isfinite(my_sc)) my_key = ((unsigned long long)uis_score_key(my_sc) << 32) | (unsigned)tid;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + my_b) * (Kmax + 1) + my_c] = my_sc;
   }
@@ -1679,7 +1685,8 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   // the one changed entry of each winner's tables (the rest is being copied by waves 1-3)
   if (isw && wc < Kmax) {
     const bool is_new = wc == Kb;
-    const int blk_new = is_new ? 1 : sblk[wb * Kmax + wc] + (wc != slast[wb] ? 1 : 0);
+    // (a tagged frame binds its tag to the cluster that takes it; a bound cluster keeps its tag)
+    const int blk_new = (is_new ? 1 : sblk[wb * Kmax + wc] + (wc != slast[wb] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
     if (KEEP) {
       nslot[r * Kmax + wc] = dst;
       nblk[r * Kmax + wc] = blk_new;
@@ -3275,6 +3282,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
   const float mse_new = st.mse0[frame];
   const int lim = st.limit[u];
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: the sub-step's own frame)
+  const int g = step_tag(st, frame);  // (uis_frame_speakers: the sub-step's own frame; the binding is the extended prefix's)
   auto node_of = [&](int i) {  // largest node with cbase[node] <= i
     int lo = 0, hi = n_in;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cbase[mid] <= i) lo = mid; else hi = mid; }
@@ -3287,6 +3295,10 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
     const float base_score = in.score[b];
     const double ld = st.logden[in.sum[b]];
     const int origin = (st.dbg_scores && last) ? (in.origin ? in.origin[b] : b) : 0;
+    // known speakers (tagged sub-steps only): the cluster g is bound to in this row, or -1
+    int bound = -1;
+    if (g)
+      for (int k = 0; k < Kb; ++k) bound = blk_tag(in.blk[(size_t)b * Kmax + k]) == g ? k : bound;
     auto emit = [&](int c, float ms, double prior) {
       const float sc = base_score + uis_step_loss(ms, prior);
       const int i = i0 + c;
@@ -3315,14 +3327,20 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
       }
       double lb[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) lb[e] = bk[e] < UIS_WINDOW_LOGTAB ? s_logblk[bk[e]] : st.logblk[bk[e]];
+      for (int e = 0; e < 4; ++e) {
+        const int n = blk_count(bk[e]);
+        lb[e] = n < UIS_WINDOW_LOGTAB ? s_logblk[n] : st.logblk[n];
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = c0 + e;
-        if (c < Kb) emit(c, mse[sl[e]], (c == lastb) ? pr.lp_stay : (pr.lp_sw + lb[e]) - ld);
+        // (known speakers: at a tagged sub-step only g's cluster, or one without a tag, is a candidate)
+        const bool ok = !g || (bound >= 0 ? c == bound : blk_tag(bk[e]) == 0);
+        if (c < Kb) emit(c, mse[sl[e]], !ok ? -(double)INFINITY : (c == lastb) ? pr.lp_stay : (pr.lp_sw + lb[e]) - ld);
       }
     }
-    emit(Kb, mse_new, Kb < lim ? pr.lp_new - ld : -(double)INFINITY);  // max_speakers: at its bound, a loss of +inf = no candidate
+    // max_speakers: at its bound, a loss of +inf = no candidate; known speakers: neither where g has a cluster already
+    emit(Kb, mse_new, (Kb < lim && bound < 0) ? pr.lp_new - ld : -(double)INFINITY);
   }
   __syncthreads();
   WSTAMP(2);
@@ -3502,7 +3520,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
     const int Knew = Kb + (is_new ? 1 : 0);
     if (c2 < Knew) {
       int slot, blk;
-      if (c2 == c) { slot = dstv[r]; blk = is_new ? 1 : in.blk[(size_t)b * Kmax + c] + (c != in.last[b] ? 1 : 0); }
+      if (c2 == c) { slot = dstv[r]; blk = (is_new ? 1 : in.blk[(size_t)b * Kmax + c] + (c != in.last[b] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT); }
       else { slot = in.slot[(size_t)b * Kmax + c2]; blk = in.blk[(size_t)b * Kmax + c2]; }
       out.slot[(size_t)r * Kmax + c2] = slot;
       out.blk[(size_t)r * Kmax + c2] = blk;

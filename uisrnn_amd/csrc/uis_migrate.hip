@@ -233,6 +233,7 @@ unsigned migrate_grid(const MigrateArgs& a, int64_t window_frames, int B) {
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_export_bound(uis_handle* h, int32_t utt, int64_t* bytes_out) {
+  if (int rch = refuse_hint(h, "uis_stream_export_bound")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h, bytes_out != nullptr, "null handle/bytes_out")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   *bytes_out = migrate_bound(h);
@@ -240,6 +241,7 @@ UIS_EXPORT int32_t uis_stream_export_bound(uis_handle* h, int32_t utt, int64_t* 
 }
 
 UIS_EXPORT int32_t uis_stream_export(uis_handle* h, int32_t utt, void* blob, int64_t capacity, int64_t* bytes_out) {
+  if (int rch = refuse_hint(h, "uis_stream_export")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h, blob && bytes_out, "null handle/blob/bytes_out")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
@@ -311,6 +313,7 @@ UIS_EXPORT int32_t uis_stream_export(uis_handle* h, int32_t utt, void* blob, int
 }
 
 UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blob, int64_t bytes) {
+  if (int rch = refuse_hint(h, "uis_stream_import")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h, blob != nullptr, "null handle/blob")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;

@@ -112,8 +112,11 @@ __global__ __launch_bounds__(256) void k_prime_bp(DecodeState st, PrimeArgs a) {
 
 UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const int64_t* offsets, const int32_t* labels,
                                     float* scores_out) {
-  // (the primed prefix is scored with the model's transition_bias: a pending per-frame table is refused, and dropped)
-  if (int rc = refuse_bias(h, "uis_stream_prime")) return rc;
+  // (the primed prefix is scored with the model's transition_bias: a pending per-frame table is refused, and dropped --
+  // and so is a pending speaker table: both are consumed, whichever is reported)
+  const int rcb = refuse_bias(h, "uis_stream_prime");
+  if (int rch = refuse_hint(h, "uis_stream_prime")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (rcb) return rcb;
   if (!session_of(h, offsets != nullptr, "null handle/offsets")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const DevModel& m = h->m;

@@ -625,6 +625,7 @@ int score_check(uis_handle* h, const float* frames, const int64_t* offsets, int3
 UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                     const int32_t* labels, float* scores_out, float* frame_losses_out) {
   take_bias(h);
+  if (int rch = refuse_hint(h, "uis_score_labels")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
   if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;
@@ -635,6 +636,7 @@ UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const in
 UIS_EXPORT int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                       const int32_t* labels, int32_t width, float* losses_out, float* scores_out) {
   take_bias(h);
+  if (int rch = refuse_hint(h, "uis_score_speakers")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
   if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;

@@ -342,6 +342,7 @@ int upload_session_limits(uis_handle* h, const std::vector<int32_t>& limits, std
 
 UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
   take_limits(h);
+  if (int rch = refuse_hint(h, "uis_stream_begin")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!h || !opts || n_utt < 1 || max_frames < 1) return fail(UIS_ERR_INVALID_ARG, "null handle/opts, n_utt < 1 or max_frames < 1");
   uis_handle::Stream& ss = h->stream_state;
   if (ss.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is already open on this handle");
@@ -483,6 +484,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
 
 UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
   take_bias(h);  // (uis_frame_bias: this push's table, in the chunk's own frame order; consumed whatever happens below)
+  if (int rch = refuse_hint(h, "uis_stream_push")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
   uis_handle::Stream& ss = h->stream_state;
   if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
@@ -682,6 +684,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
 }
 
 UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
+  if (int rch = refuse_hint(h, "uis_stream_labels")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U;
@@ -735,6 +738,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
 }
 
 UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
+  if (int rch = refuse_hint(h, "uis_stream_end")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
   if (!h->stream_state.active) return UIS_OK;
   HIPCHK(hipSetDevice(h->device));
@@ -747,6 +751,7 @@ UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
 // max_speakers of an open session.  The table belongs to the slots, not to the streams in them: restarts, imports and
 // retirements leave it alone, blobs do not carry it.  All or nothing: a table with a value out of range changes none.
 UIS_EXPORT int32_t uis_stream_limits(uis_handle* h, const int32_t* limits) {
+  if (int rch = refuse_hint(h, "uis_stream_limits")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h, limits != nullptr, "null handle/limits")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   for (int u = 0; u < ss.U; ++u)
@@ -761,6 +766,7 @@ UIS_EXPORT int32_t uis_stream_limits(uis_handle* h, const int32_t* limits) {
 }
 
 UIS_EXPORT int32_t uis_stream_get_limits(uis_handle* h, int32_t* out) {
+  if (int rch = refuse_hint(h, "uis_stream_get_limits")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
   const uis_handle::Stream& ss = h->stream_state;
   for (int u = 0; u < ss.U; ++u) out[u] = ss.limits[u];

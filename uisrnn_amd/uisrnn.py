@@ -71,6 +71,64 @@ def _check_max_speakers(max_speakers, args, n_utt):
   return values if any(values) else None
 
 
+_MAX_KNOWN_SPEAKERS = 127   # (a cluster's tag is seven bits of its block-count word: include/uisrnn_hip.h)
+
+
+def _check_known_speakers(known_speakers, lengths, single=False):
+  """The known_speakers keyword as the library's table: None (nobody is known) or one uint8 array per utterance of that
+  utterance's length, 0 = unknown, 1 .. 127 = the utterance's names in the order they first appear.
+
+  known_speakers: None; one sequence per utterance (None for an utterance without known speakers) whose entries are None
+  (unknown) or any hashable value (a speaker's name); with single=True the one sequence itself.  Names are compared as
+  dict keys are: 1, 1.0 and True are one speaker, 'a' and b'a' two.  A float NaN equals nothing, itself included, so it
+  cannot name anybody and is refused.  Raises before any device work: ValueError for a wrong count or length, for more
+  than 127 names in one utterance, for a NaN name and for a bool where a sequence is expected, TypeError for an
+  unhashable name."""
+  if known_speakers is None:
+    return None
+
+  def refuse_kind(value, who):
+    if isinstance(value, (bool, np.bool_)):
+      raise ValueError('known_speakers of {} must be a sequence of names (None: unknown), not a bool.'.format(who))
+    if isinstance(value, (str, bytes)) or not isinstance(value, (list, tuple, np.ndarray)):
+      raise ValueError('known_speakers of {} must be a sequence of names (None: unknown), not {!r}.'.format(
+          who, type(value)))
+
+  def one(value, n, who):
+    if value is None:
+      return np.zeros(n, dtype=np.uint8)
+    refuse_kind(value, who)
+    names = value.tolist() if isinstance(value, np.ndarray) else list(value)
+    if len(names) != n:
+      raise ValueError('known_speakers of {} has {} entries for {} frames.'.format(who, len(names), n))
+    tags, table = {}, np.zeros(n, dtype=np.uint8)
+    for t, name in enumerate(names):
+      if name is None:
+        continue
+      if isinstance(name, (float, np.floating)) and name != name:   # pylint: disable=comparison-with-itself
+        raise ValueError('known_speakers of {} has NaN as a name at frame {}: NaN equals no other name, not even '
+                         'itself (None means unknown).'.format(who, t))
+      try:
+        tag = tags.get(name)
+      except TypeError as err:
+        raise TypeError('known_speakers of {} has an unhashable name at frame {}: {!r}.'.format(who, t, name)) from err
+      if tag is None:
+        if len(tags) == _MAX_KNOWN_SPEAKERS:
+          raise ValueError('known_speakers of {} names more than {} speakers.'.format(who, _MAX_KNOWN_SPEAKERS))
+        tag = tags[name] = len(tags) + 1
+      table[t] = tag
+    return table
+
+  if single:
+    return [one(known_speakers, lengths[0], 'the sequence')]
+  refuse_kind(known_speakers, 'a list of sequences')
+  if isinstance(known_speakers, np.ndarray) and known_speakers.dtype != object and known_speakers.ndim == 1:
+    raise ValueError('known_speakers for a list of sequences must be one sequence of names per sequence.')
+  if len(known_speakers) != len(lengths):
+    raise ValueError('known_speakers has {} entries for {} utterances.'.format(len(known_speakers), len(lengths)))
+  return [one(v, n, 'utterance {}'.format(u)) for u, (v, n) in enumerate(zip(known_speakers, lengths))]
+
+
 def _check_transition_bias(transition_bias, lengths, single=False, offline=True):
   """The transition_bias keyword as the library's table: None (the model's value everywhere) or one float64 array per
   utterance, of that utterance's length (NaN: the model's value at that frame).
@@ -439,13 +497,14 @@ class UISRNN:
       raise ValueError('test_sequence does not match the dimension specified '
                        'by args.observation_dim.')
 
-  def _offline_arguments(self, test_sequences, args, max_speakers, transition_bias, sequences_first=False):
-    """The offline entry points' arguments, checked: (single, sequences, limits, bias) -- single: one array was given,
-    and the caller hands out result 0; limits and bias as _decode_batch takes them.
+  def _offline_arguments(self, test_sequences, args, max_speakers, transition_bias, known_speakers=None,
+                         sequences_first=False):
+    """The offline entry points' arguments, checked: (single, sequences, limits, bias, speakers) -- single: one array
+    was given, and the caller hands out result 0; limits, bias and speakers as _decode_batch takes them.
 
     The first bad argument is the one reported, and the order is part of the interface: an array's sequence comes
     before its bound (the reference's checks first), a list's bound before its sequences -- except with
-    sequences_first, parallel_predict's order.  transition_bias needs the lengths and is always last."""
+    sequences_first, parallel_predict's order.  transition_bias and then known_speakers need the lengths and come last."""
     single = isinstance(test_sequences, np.ndarray)
     if not single and not isinstance(test_sequences, list):
       raise TypeError('test_sequences should be either a list or numpy array.')
@@ -457,19 +516,21 @@ class UISRNN:
     if single or sequences_first:
       limits = _check_max_speakers(max_speakers, args, len(seqs))
     bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single)
-    return single, seqs, limits, bias
+    speakers = _check_known_speakers(known_speakers, [s.shape[0] for s in seqs], single=single)
+    return single, seqs, limits, bias, speakers
 
-  def _predict(self, test_sequences, args, max_speakers, transition_bias, **readout):
+  def _predict(self, test_sequences, args, max_speakers, transition_bias, known_speakers=None, **readout):
     """predict / predict_nbest / predict_posteriors: the checked arguments through _decode_batch, whose `readout`
     keyword (n_best or posterior) selects what an utterance's result is."""
-    single, seqs, limits, bias = self._offline_arguments(test_sequences, args, max_speakers, transition_bias)
+    single, seqs, limits, bias, speakers = self._offline_arguments(
+        test_sequences, args, max_speakers, transition_bias, known_speakers)
     if not seqs:
       return []
-    results = self._decode_batch(seqs, args, limits=limits, bias=bias, **readout)
+    results = self._decode_batch(seqs, args, limits=limits, bias=bias, speakers=speakers, **readout)
     return results[0] if single else results
 
   def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
-                    limits=None, bias=None):
+                    limits=None, bias=None, speakers=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -482,17 +543,20 @@ class UISRNN:
     overflow retry's subsets, the halves after UIS_ERR_OOM, the look-ahead retry's groups -- takes its members' entries.
     bias (_check_transition_bias): None, or one float64 array per sequence: the per-frame transition_bias table, which
     follows the same regroupings.
+    speakers (_check_known_speakers): None, or one uint8 array per sequence: the known speakers' tags, likewise.
     """
     decoder = decoder or self._get_decoder(device)
 
     def take(members):
-      """What one decode call is handed for these sequences: the arrays, and their entries of limits and bias as
-      decode_f64's keywords (a table that is None is no keyword at all)."""
+      """What one decode call is handed for these sequences: the arrays, and their entries of limits, bias and speakers
+      as decode_f64's keywords (a table that is None is no keyword at all)."""
       tables = {}
       if limits is not None:
         tables['limits'] = [limits[u] for u in members]
       if bias is not None:
         tables['bias'] = np.concatenate([bias[u] for u in members])
+      if speakers is not None:
+        tables['speakers'] = np.concatenate([speakers[u] for u in members])
       return [sequences[u] for u in members], tables
 
     def decode(members, level_cap):
@@ -688,13 +752,13 @@ class UISRNN:
                          for ids, p in zip(test_cluster_ids, predicted)]
     return predicted, [float(m) / int(n) for m, n in zip(matched, lens)]
 
-  def predict_single(self, test_sequence, args, max_speakers=None, transition_bias=None):
+  def predict_single(self, test_sequence, args, max_speakers=None, transition_bias=None, known_speakers=None):
     """Predict labels for one test sequence (uisrnn/uisrnn.py:479-562).
 
     Args:
       test_sequence: 2-dim float64 numpy array [N, D].
       args: inference namespace (beam_size, look_ahead, test_iteration).
-      max_speakers, transition_bias: see predict (extensions).
+      max_speakers, transition_bias, known_speakers: see predict (extensions).
 
     Returns:
       list of N ints: the predicted cluster id per frame.
@@ -704,7 +768,7 @@ class UISRNN:
       ValueError: wrong rank or observation dimension.
     """
     self._check_sequence(test_sequence)   # (a list too is refused here, in the reference's words)
-    return self._predict(test_sequence, args, max_speakers, transition_bias)
+    return self._predict(test_sequence, args, max_speakers, transition_bias, known_speakers)
 
   def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
              max_speakers=None):
@@ -726,7 +790,7 @@ class UISRNN:
     whose streams begin and end independently of each other."""
     return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers))
 
-  def predict(self, test_sequences, args, max_speakers=None, transition_bias=None):
+  def predict(self, test_sequences, args, max_speakers=None, transition_bias=None, known_speakers=None):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
 
     A list is decoded as ONE lock-step batch on the GPU (the reference loops
@@ -745,6 +809,15 @@ class UISRNN:
     ValueError, before any device work, for a bool, a wrong length or count, a value outside [0, 1], +-inf, or 0 at a
     sequence's first frame.
 
+    known_speakers (extension): who speaks at some frames -- None, or one sequence per sequence
+    of that sequence's length (for a single sequence: its one sequence; None for a sequence nobody is known in), whose
+    entries are None (unknown) or any hashable value, a speaker's name; at most 127 names per sequence.  Frames with
+    equal names get equal labels and frames with different names different labels; an unknown frame may join any
+    speaker.  The labels returned stay first-appearance integers.  Names that contradict max_speakers or
+    transition_bias empty the beam: EmptyBeamError.  Names are compared as dict keys are (1, 1.0 and True are one
+    speaker).  ValueError, before any device work, for a wrong count or length, more than 127 names, a float NaN as a
+    name, or a bool in the place of a sequence; TypeError for an unhashable name.
+
     Raises:
       TypeError: test_sequences is neither a list nor a numpy array.
       EmptyBeamError: non-finite scores emptied an utterance's beam (the reference raises
@@ -753,15 +826,16 @@ class UISRNN:
         prefixes inside a window than the device tables hold (a limit the reference does not
         have); the exception names them and carries the other utterances' results.
     """
-    return self._predict(test_sequences, args, max_speakers, transition_bias)
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers)
 
-  def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None):
+  def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None,
+                    known_speakers=None):
     """predict, returning every hypothesis of the final beam instead of the best one (extension).
 
     Args:
       test_sequences, args: as predict.
       n_best: the most hypotheses wanted per sequence, in [1, args.beam_size] (default: beam_size).
-      max_speakers, transition_bias: as predict.
+      max_speakers, transition_bias, known_speakers: as predict.
     Returns:
       for an array the pair (labelings, scores): at most n_best label lists -- fewer when the final
       beam holds fewer -- best first, and their scores as floats, ascending; labelings[0] is predict's
@@ -776,9 +850,10 @@ class UISRNN:
       raise ValueError('n_best must be an integer in [1, args.beam_size].')
     if not 1 <= int(n_best) <= int(args.beam_size):
       raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(args.beam_size))
-    return self._predict(test_sequences, args, max_speakers, transition_bias, n_best=int(n_best))
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, n_best=int(n_best))
 
-  def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None, transition_bias=None):
+  def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None, transition_bias=None,
+                         known_speakers=None):
     """predict, with the beam's per-frame confidence in its answer (extension).
 
     With w_k = softmax(-score_k / temperature) over the hypotheses of the final beam:
@@ -793,7 +868,7 @@ class UISRNN:
       temperature: a finite number > 0.  1 is the model's own posterior; a sharply peaked model (a trained D = 256
         one puts all but 1e-3, usually all but 1e-11, on the best hypothesis) needs a larger one to rank its
         uncertain frames.
-      max_speakers, transition_bias: as predict.
+      max_speakers, transition_bias, known_speakers: as predict.
     Returns:
       for an array the triple (labels, confidence, change): predict's answer and two float32 arrays of its length.
       For a list, a list of such triples.  One decode, with predict's cap and level retries.
@@ -802,7 +877,7 @@ class UISRNN:
       what predict raises; ValueError for a temperature that is not a finite number > 0, before any device work.
     """
     temperature = _check_temperature(temperature)
-    return self._predict(test_sequences, args, max_speakers, transition_bias, posterior=temperature)
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, posterior=temperature)
 
   def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
     """predict, with the first frames of every sequence already labeled (extension).
@@ -1664,7 +1739,8 @@ class StreamPool:
     self.close()
 
 
-def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None, transition_bias=None):
+def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None, transition_bias=None,
+                     known_speakers=None):
   """Drop-in for uisrnn.parallel_predict (uisrnn/uisrnn.py:593-623).
 
   The reference maps utterances over a forkserver process pool.  Here the
@@ -1677,22 +1753,24 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
   Args:
     devices: optional explicit list of HIP device indices (repeats allowed --
       used by the tests to exercise the path on a single-GPU box).
-    max_speakers, transition_bias: as UISRNN.predict (extensions); every shard takes its members' entries.
+    max_speakers, transition_bias, known_speakers: as UISRNN.predict (extensions); every shard takes its members'
+      entries.
 
   Raises:
     TypeError: test_sequences is not a list.
   """
   if not isinstance(test_sequences, list):
     raise TypeError('test_sequences must be a list.')
-  _, _, limits, bias = model._offline_arguments(  # pylint: disable=protected-access
-      test_sequences, args, max_speakers, transition_bias, sequences_first=True)
+  _, _, limits, bias, speakers = model._offline_arguments(  # pylint: disable=protected-access
+      test_sequences, args, max_speakers, transition_bias, known_speakers, sequences_first=True)
   if not test_sequences:
     return []
   if devices is None:
     n_dev = max(_capi.load_library().uis_device_count(), 1)
     devices = list(range(max(1, min(int(num_processes), n_dev))))
   if len(devices) == 1:
-    return model._decode_batch(test_sequences, args, device=devices[0], limits=limits, bias=bias)  # pylint: disable=protected-access
+    return model._decode_batch(  # pylint: disable=protected-access
+        test_sequences, args, device=devices[0], limits=limits, bias=bias, speakers=speakers)
   import threading  # pylint: disable=import-outside-toplevel
   from uisrnn_amd import distributed  # pylint: disable=import-outside-toplevel
   shards = distributed.shard_utterances(
@@ -1708,7 +1786,8 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
       if shard:
         out = worker.decode([test_sequences[i] for i in shard], args,
                             None if limits is None else [limits[i] for i in shard],
-                            None if bias is None else [bias[i] for i in shard])
+                            None if bias is None else [bias[i] for i in shard],
+                            None if speakers is None else [speakers[i] for i in shard])
         for i, labels in zip(shard, out):
           results[i] = labels
     except Exception as exc:  # pylint: disable=broad-except
@@ -1738,9 +1817,9 @@ class _Worker:
     self._decoder = (_capi.Decoder(model.params, device) if self._own
                      else model._get_decoder(device))  # pylint: disable=protected-access
 
-  def decode(self, sequences, args, limits=None, bias=None):
+  def decode(self, sequences, args, limits=None, bias=None, speakers=None):
     return self._model._decode_batch(  # pylint: disable=protected-access
-        sequences, args, decoder=self._decoder, limits=limits, bias=bias)
+        sequences, args, decoder=self._decoder, limits=limits, bias=bias, speakers=speakers)
 
   def close(self):
     if self._own:
