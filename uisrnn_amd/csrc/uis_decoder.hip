@@ -1179,6 +1179,8 @@ int rs_make_args(const DevModel& m, const DecodeState& st, size_t bp_bytes, RsAr
   a.logblk = st.logblk; a.logden = st.logden;
   a.x = st.x; a.gi0 = st.gi0; a.mse0 = st.mse0;
   a.overflow = st.overflow; a.dbg_scores = st.dbg_scores; a.counters = st.counters;
+  // (the kernel tests the bit every step and reads the pointer behind it only)
+  a.flags = st.dbg_scores ? a.flags | UIS_FLAG_DEBUG_SCORES : a.flags & ~UIS_FLAG_DEBUG_SCORES;
   a.blk = reinterpret_cast<unsigned char*>(st.pool_mean);
   bool ok = true;
   auto at = [&](const void* p, size_t bytes) -> uint32_t {

@@ -234,6 +234,7 @@ struct RsBigView {
   __device__ __forceinline__ int tau() const { return st.tau; }
   __device__ __forceinline__ uint32_t flags() const { return st.flags; }
   __device__ __forceinline__ float mse_fresh(long frame) const { return st.mse0[frame]; }
+  __device__ __forceinline__ bool dbg_on() const { return st.dbg_scores != nullptr; }
   __device__ __forceinline__ float* dbg_scores() const { return st.dbg_scores; }
   __device__ __forceinline__ unsigned long long* counters() const { return st.counters; }
   __device__ __forceinline__ void put_overflow(int u) const { st.overflow[u] = 1; }
@@ -282,6 +283,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rs_desc(const void* p) {
   asm volatile("" : "+s"(q));
   return __builtin_amdgcn_make_buffer_rsrc((void*)q, (short)0, 0xffffffff, 0x00020000);
 }
+// A pointer of the argument block that the step loop needs on a COLD path only (a cluster beyond the cap, the debug
+// scores): read again from the kernel argument segment where it is used, so that the
+// loop keeps no registers for it (k_decode_rs takes RsArgs as its only argument: the block starts the segment).  The
+// empty asm keeps the load inside its branch; hoisted, it would be one more value live across the loop.
+template <typename T>
+__device__ __forceinline__ T* rs_cold_ptr(size_t field_offset) {
+  typedef const unsigned long long __attribute__((address_space(4))) * KargWord;
+  unsigned long long q = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr() + field_offset;
+  asm volatile("" : "+s"(q));
+  return (T*)(*(KargWord)q);
+}
 struct RsView {
   const RsArgs& a;
   typedef __amdgpu_buffer_rsrc_t Blk;
@@ -297,9 +309,11 @@ struct RsView {
   __device__ __forceinline__ int tau() const { return a.tau; }
   __device__ __forceinline__ uint32_t flags() const { return a.flags; }
   __device__ __forceinline__ float mse_fresh(long frame) const { return rs_buf_load_f32(rs_desc(a.mse0), (uint32_t)frame * 4u); }
-  __device__ __forceinline__ float* dbg_scores() const { return a.dbg_scores; }
+  // (rs_make_args sets the flag bit where it sets the pointer: one bit test per step, the pointer only behind it)
+  __device__ __forceinline__ bool dbg_on() const { return (a.flags & UIS_FLAG_DEBUG_SCORES) != 0u; }
+  __device__ __forceinline__ float* dbg_scores() const { return rs_cold_ptr<float>(offsetof(RsArgs, dbg_scores)); }
   __device__ __forceinline__ unsigned long long* counters() const { return a.counters; }
-  __device__ __forceinline__ void put_overflow(int u) const { a.overflow[u] = 1; }
+  __device__ __forceinline__ void put_overflow(int u) const { rs_cold_ptr<int32_t>(offsetof(RsArgs, overflow))[u] = 1; }
   __device__ __forceinline__ void put_beam_score(Blk blk, size_t i, float v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, v, a.o_beam_score); }
   __device__ __forceinline__ void put_bp(Blk blk, size_t i, unsigned v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, __builtin_bit_cast(float, v), a.o_bp); }
   __device__ __forceinline__ void put_beam_n(Blk blk, size_t i, int v) const { rs_buf_store_f32(blk, (uint32_t)i * 4u, __builtin_bit_cast(float, v), a.o_beam_n); }
@@ -583,13 +597,14 @@ __device__ __forceinline__ RsWin rs_front(const View& a, const RsLds& L, const R
       if (uis_isfinite(sc[k])) key[k] = uis_score_key(sc[k]);
     }
   }
-  if (a.dbg_scores()) {  // UIS_FLAG_DEBUG_SCORES: the step's _calculate_score arrays
+  if (a.dbg_on()) {  // UIS_FLAG_DEBUG_SCORES: the step's _calculate_score arrays
+    float* const dbg = a.dbg_scores();
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       if ((k == 0 || nch > k) && P.cslot[k] != -2) {
         const int e = lane + 64 * k;
         const int b = (int)(((unsigned)e * (unsigned)kmagic) >> 20), c = e - b * Kcur;
-        a.dbg_scores()[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc[k];
+        dbg[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc[k];
       }
     }
   }
@@ -742,9 +757,11 @@ __device__ __forceinline__ RsWin rs_front(const View& a, const RsLds& L, const R
 
 // BACK: the next step's tables, masks and counts, the back-pointers -- nothing anybody waits for.
 // `owner`: this workgroup writes what outlives the step to memory.
-template <typename View, typename Mid>
-__device__ __forceinline__ void rs_back(const View& a, const RsLds& L, const RsDims dm, int u, int step,
-                                        long off0, unsigned char* pers, bool owner, const RsWin& w, Mid mid) {
+// STATS false: the caller keeps the decode statistics itself (k_decode_rs: four 32-bit words, one 16-byte update per
+// step); the return value is what it needs for that, the largest K of the next beam.
+template <bool STATS = true, typename View, typename Mid>
+__device__ __forceinline__ int rs_back(const View& a, const RsLds& L, const RsDims dm, int u, int step,
+                                       long off0, unsigned char* pers, bool owner, const RsWin& w, Mid mid) {
   int lane_ = threadIdx.x & 63;
   asm volatile("" : "+v"(lane_));
   const int lane = lane_;
@@ -830,13 +847,16 @@ __device__ __forceinline__ void rs_back(const View& a, const RsLds& L, const RsD
     nhdr[0] = w.keep;
     nhdr[1] = Kc;
     nhdr[2] = (int)rs_magic20((unsigned)Kc);  // e / Kc = (e * magic) >> 20, exact for e < 2048
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(pers + L.off_stats);
-    acc[0] += (unsigned long long)w.nlead;
-    acc[1] += (unsigned long long)w.keep;
-    acc[2] += (unsigned long long)w.C;
-    if ((unsigned long long)Kmaxseen > acc[3]) acc[3] = (unsigned long long)Kmaxseen;
+    if constexpr (STATS) {
+      unsigned long long* acc = reinterpret_cast<unsigned long long*>(pers + L.off_stats);
+      acc[0] += (unsigned long long)w.nlead;
+      acc[1] += (unsigned long long)w.keep;
+      acc[2] += (unsigned long long)w.C;
+      if ((unsigned long long)Kmaxseen > acc[3]) acc[3] = (unsigned long long)Kmaxseen;
+    }
     if (owner) a.put_beam_n(blk, (size_t)nxt * U + u, w.keep);
   }
+  return Kmaxseen;
 }
 
 // The early MSEs, one step ahead: for this wave's utterance u, every slot the NEXT beam references
@@ -1068,14 +1088,19 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
   unsigned char* s_scr = reinterpret_cast<unsigned char*>(spart);
   const size_t spart_bytes = rs_spart_bytes() > (size_t)SLOTS * L.scratch_stride ? rs_spart_bytes()
                                                                                 : (size_t)SLOTS * L.scratch_stride;
-  int* s_ctl = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(spart) + spart_bytes);  // [0] abort [1] steps [2] arrived [8 .. 8 + SLOTS) rows per slot
+  int* s_ctl = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(spart) + spart_bytes);  // [0] abort [1] steps [2] arrived [8, 9] rows per slot, one BYTE each
+  // (a slot emits at most beam_size <= 16 rows: the eight counts are one 64-bit word, and a wave's first row and the
+  // step's row count are byte sums of it -- scalar arithmetic, no per-slot conditions kept across the loop)
+  unsigned char* s_cnt = reinterpret_cast<unsigned char*>(s_ctl + 8);
+  static_assert(UIS_RS_UTT == 8 && UIS_RS_MAXB <= 31, "the row counts of a step are eight bytes whose sums fit a byte");
   f32x4* s_w1 = reinterpret_cast<f32x4*>(s_ctl + 32);
   f32x4* s_w2 = s_w1 + NKB * 64;
   const int head_tiles = rs_head_tiles(B);
   u32x4* s_head = reinterpret_cast<u32x4*>(s_w2 + NKB * 64);
-  long* s_wframe = reinterpret_cast<long*>(s_head + head_tiles * 16);  // [SLOTS] this step's frame of every slot's utterance
-  long* s_wnext = s_wframe + SLOTS;                                    // [SLOTS] ... and the next step's
-  float* s_bias = reinterpret_cast<float*>(s_wnext + SLOTS);           // b_hh r | z | n, b1, b2: this rank's 16 features of each
+  // (32-bit rows of the frame stream: the planner's frames32; the two arrays keep their 2 x SLOTS x 8 bytes of the layout)
+  uint32_t* s_wframe = reinterpret_cast<uint32_t*>(s_head + head_tiles * 16);  // [SLOTS] this step's frame of every slot's utterance
+  uint32_t* s_wnext = s_wframe + 2 * SLOTS;                                    // [SLOTS] ... and the next step's
+  float* s_bias = reinterpret_cast<float*>(s_wnext + 2 * SLOTS);               // b_hh r | z | n, b1, b2: this rank's 16 features of each
   const int ft1 = rank / SH1, tpar1 = rank % SH1;
   const int ft2 = rank / SH2, tpar2 = rank % SH2;
   // where this cluster's words and rows are in the block (scalar: they ride in the buffer instructions' offset field)
@@ -1129,11 +1154,11 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
       const int* src = reinterpret_cast<const int*>(a.resume + (size_t)u * L.persist_stride);
       int* dst = reinterpret_cast<int*>(s_pers + (size_t)k * L.persist_stride);
       for (int i = t; i < L.persist_stride / 4; i += 512) dst[i] = src[i];
-      if (t == 0) s_ctl[8 + k] = reinterpret_cast<const int*>(a.resume + (size_t)U * L.persist_stride)[u];
+      if (t == 0) s_cnt[k] = (unsigned char)reinterpret_cast<const int*>(a.resume + (size_t)U * L.persist_stride)[u];
     }
     __syncthreads();
     fpos_w = N_w > 0 ? step0 % N_w : 0;
-    for (int k = 0; k < w; ++k) prev_base += s_ctl[8 + k];
+    for (int k = 0; k < w; ++k) prev_base += (int)s_cnt[k];
   }
   if (LIM && lane == 0) {  // this launch's limit of the wave's utterance beside the grid words of both table sets (rs_prep reads it there)
     const int lim_w = has_u ? a.limit[u_w] : 0x7fffffff;
@@ -1182,22 +1207,22 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
 #endif
     }
     if (lane == 0) {
-      s_ctl[8 + w] = win.nlead;
-      s_wframe[w] = frame_w;
-      s_wnext[w] = (long)(off0_w + (fpos_w + 1 == N_w ? 0 : fpos_w + 1));  // (after the last step: some frame of the utterance, unused)
+      s_cnt[w] = (unsigned char)win.nlead;
+      s_wframe[w] = (uint32_t)frame_w;
+      s_wnext[w] = (uint32_t)(off0_w + (fpos_w + 1 == N_w ? 0 : fpos_w + 1));  // (after the last step: some frame of the utterance, unused)
     }
     RSTAMP(0);
     __syncthreads();
     if (s_ctl[0]) return;  // a hand-off of the previous step gave up (cl_abort tells the host): all waves leave here
     int nrows = 0;
     {
-      int base = 0;
-#pragma unroll
-      for (int k = 0; k < SLOTS; ++k) {
-        const int c = s_ctl[8 + k];
-        if (k < w) base += c;
-        nrows += c;
-      }
+      // the eight counts as two words; the sum of a word's four bytes is the top byte of its product with 0x01010101
+      // (no carries: at most 4 x 16), and the slots below this wave's are the bytes below bit 8 w
+      const uint32_t c_lo = (uint32_t)__builtin_amdgcn_readfirstlane(s_ctl[8]), c_hi = (uint32_t)__builtin_amdgcn_readfirstlane(s_ctl[9]);
+      const uint32_t b_lo = w < 4 ? c_lo & ((1u << (8 * w)) - 1u) : c_lo;
+      const uint32_t b_hi = w < 4 ? 0u : c_hi & ((1u << (8 * (w - 4))) - 1u);
+      nrows = (int)(((c_lo * 0x01010101u) >> 24) + ((c_hi * 0x01010101u) >> 24));
+      const int base = (int)(((b_lo * 0x01010101u) >> 24) + ((b_hi * 0x01010101u) >> 24));
       if (win.is_lead()) {
         // (the slot's number rides in the top bits of the frame count: the row's frame is s_wframe[that])
         s_head[base + win.ord()] = u32x4{(unsigned)u_w, (unsigned)win.src(), (unsigned)win.dst(), (unsigned)win.nprev() | ((unsigned)w << 16)};
@@ -1273,7 +1298,16 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
       if (act_w) {
         // (the owner of utterance slot r is rank r: it alone writes that utterance's lasting outputs)
         // (the utterance's first frame as a scalar: the back-pointers' base is then scalar arithmetic, not a lane value kept across the loop)
-        rs_back(av, L, dm, u_w, s, __builtin_amdgcn_readfirstlane(off0_w), pers_w, rank == w, win, peek);
+        const int kseen = rs_back<false>(av, L, dm, u_w, s, __builtin_amdgcn_readfirstlane(off0_w), pers_w, rank == w, win, peek);
+        if (lane == 0) {
+          // the utterance's statistics, 32 bits each (fewer than 65535 steps of at most 192 candidates: rs_select_ok):
+          // {rows, winners, candidates, largest K} in the first 16 bytes of off_stats -- one 16-byte read and write
+          u32x4* acc = reinterpret_cast<u32x4*>(pers_w + L.off_stats);
+          u32x4 v = *acc;
+          v[0] += (uint32_t)win.nlead; v[1] += (uint32_t)win.keep; v[2] += (uint32_t)win.C;
+          v[3] = (uint32_t)kseen > v[3] ? (uint32_t)kseen : v[3];
+          *acc = v;
+        }
         fpos_w = fpos_w + 1 == N_w ? 0 : fpos_w + 1;
       } else {
         peek();
@@ -1420,17 +1454,16 @@ __global__ __launch_bounds__(512) void k_decode_rs(RsArgs args) {
         const int* src = reinterpret_cast<const int*>(s_pers + (size_t)k * L.persist_stride);
         int* dst = reinterpret_cast<int*>(a.resume + (size_t)u * L.persist_stride);
         for (int i = t; i < L.persist_stride / 4; i += 512) dst[i] = src[i];
-        if (t == 0) reinterpret_cast<int*>(a.resume + (size_t)U * L.persist_stride)[u] = s_ctl[8 + k];
+        if (t == 0) reinterpret_cast<int*>(a.resume + (size_t)U * L.persist_stride)[u] = (int)s_cnt[k];
       }
     }
     return;
   }
   if (rank < SLOTS && cluster + ncl * rank < U && t == 0) {  // this utterance's statistics, by its owner rank
-    const unsigned long long* acc =
-        reinterpret_cast<const unsigned long long*>(s_pers + (size_t)rank * L.persist_stride + L.off_stats);
-    atomicAdd(&a.counters[0], acc[0]);
-    atomicAdd(&a.counters[1], acc[1]);
-    atomicAdd(&a.counters[2], acc[2]);
-    atomicMax(&a.counters[3], acc[3]);
+    const uint32_t* acc = reinterpret_cast<const uint32_t*>(s_pers + (size_t)rank * L.persist_stride + L.off_stats);
+    atomicAdd(&a.counters[0], (unsigned long long)acc[0]);
+    atomicAdd(&a.counters[1], (unsigned long long)acc[1]);
+    atomicAdd(&a.counters[2], (unsigned long long)acc[2]);
+    atomicMax(&a.counters[3], (unsigned long long)acc[3]);
   }
 }
