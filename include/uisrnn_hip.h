@@ -482,7 +482,7 @@ int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames);
  *                        used.
  *
  * Refused with UIS_ERR_UNSUPPORTED, the table consumed and the handle usable: every uis_stream_* call made while a table
- * is pending (sessions, priming and blobs carry no bindings yet), uis_score_labels and uis_score_speakers (their labels
+ * is pending (a session's tags arrive through uis_stream_speakers, below), uis_score_labels and uis_score_speakers (their labels
  * are given), and a decode whose test_iteration * N reaches 2^24 (a cluster's tag shares its block-count word).  The
  * refused call has done nothing but drop the table -- and whatever other pending table it would have consumed
  * (uis_frame_bias, uis_decode_limits).  That holds for uis_stream_end as well: refused, it leaves the session OPEN, and
@@ -492,6 +492,54 @@ int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames);
  * one reports k_decode_rs or k_decode_big<WS>, uis_last_decode_instantiation reports k_decode_resident or k_decode_big.
  */
 int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames);
+
+/*
+ * Known speakers in streaming sessions.
+ *
+ * The rule is the one above, unchanged: a session pushed under tags, in any chunking and with silent slots, is bit for
+ * bit the uis_decode of the same frames under the same tags at look_ahead 1 and test_iteration 1 -- labels, scores, the
+ * final beam and the n-best rows.  A hypothesis' binding lives in the session's tables between the calls, so it follows
+ * the utterance through uis_stream_commit, uis_stream_retire and uis_stream_export / _import, and ends with it at
+ * uis_stream_restart (the slot's next utterance starts unbound).
+ *
+ *   uis_stream_speakers  tags: host uint8 [n_frames], each in 0 .. 127 (a larger value: UIS_ERR_INVALID_ARG, and the
+ *                        pending table stays as it was); tags == NULL or n_frames == 0 clears a pending table.  The
+ *                        table belongs to the NEXT uis_stream_push or uis_stream_prime on this handle, in that call's
+ *                        own frame order (utterance by utterance, then the chunk's frames), and must hold exactly that
+ *                        call's frame count (else that call returns UIS_ERR_INVALID_ARG and the session is untouched).
+ *                        That call consumes the table whether it succeeds or not.  Every OTHER uis_stream_* call made
+ *                        while the table is pending leaves it pending: it waits for the next push or prime (or for
+ *                        uis_stream_speakers(h, NULL, 0)), across uis_stream_labels, _commit, _end and _begin alike.
+ *                        An all-zero table gives the push without one bit for bit.  Tags, a uis_frame_bias table and
+ *                        uis_stream_limits may all be in force in one push.
+ *
+ * uis_stream_prime with a table binds the primed hypothesis as the decode would along the given labels.  Within one
+ * utterance's prefix the relation tag <-> label must be a partial bijection -- one tag never on two labels, one label never
+ * under two tags -- else UIS_ERR_INVALID_ARG ("the prefix labels contradict its tags") and the session is as it was.
+ *
+ * A UIS_FLAG_PERSISTENT session takes no tags: a push or a prime with a table, and the import of a blob that carries
+ * tags, return UIS_ERR_UNSUPPORTED; the table is dropped and the session stays usable.
+ *
+ * A session is TAGGED once a push, a prime or an import has given it a non-zero tag, until uis_stream_end.  A tagged
+ * session refuses, with UIS_ERR_UNSUPPORTED and before any device work, a push, prime or import that would bring any
+ * utterance's frames received (committed ones included) to 2^24 or more: a cluster's tag shares its block-count word.
+ *
+ * Retirement: a cluster that carries a tag in any live hypothesis can still be named by the next tagged frame, so it is
+ * not retirable -- a query does not list it, a list that names it is refused as any other cluster in use.  The clusters
+ * above a retired one move down with their tags.  A name therefore keeps its cluster for the life of the utterance, one
+ * utterance holds at most 127 names, and max_clusters has to leave room for them: that is the caller's business.
+ *
+ * Blobs: the format is unchanged and a blob without tags is byte-identical to what it was; the tags travel in the
+ * block-count words.  uis_stream_import refuses a blob in which one hypothesis binds a tag twice, or that carries a tag
+ * with 2^24 frames received or more.
+ *
+ *   uis_stream_bindings  out: host int32 [n_utt][128].  out[u][g], g = 1 .. 127: the cluster the best hypothesis of
+ *                        utterance u binds tag g to, in the numbering of uis_stream_labels' labels at this moment; -1:
+ *                        unbound.  out[u][0]: the number of bound tags.  An utterance without a live hypothesis (an
+ *                        emptied beam, the cluster cap) gives 0 and -1 everywhere.  Changes nothing.
+ */
+int32_t uis_stream_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames);
+int32_t uis_stream_bindings(uis_handle* h, int32_t* out /* [n_utt][128] */);
 
 /*
  * Primed sessions: start the online decode of an open session's utterances from a LABELED PREFIX (enrolment,

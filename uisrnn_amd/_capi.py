@@ -361,6 +361,10 @@ def load_library(path=None):
   lib.uis_frame_bias.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64]
   lib.uis_frame_speakers.restype = i32
   lib.uis_frame_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
+  lib.uis_stream_speakers.restype = i32
+  lib.uis_stream_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
+  lib.uis_stream_bindings.restype = i32
+  lib.uis_stream_bindings.argtypes = [ctypes.c_void_p, i32p]
   lib.uis_stream_prime.restype = i32
   lib.uis_stream_prime.argtypes = [ctypes.c_void_p, _fp, i64p, i32p, _fp]
   lib.uis_last_decode_nbest.restype = i32
@@ -428,7 +432,8 @@ EXPORTED_SYMBOLS = (
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
-    'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_host_alloc', 'uis_host_free', 'uis_last_error',
+    'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_stream_speakers', 'uis_stream_bindings',
+    'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
 
@@ -451,6 +456,23 @@ def blob_info(blob):
     raise ValueError('not a stream blob: bad live count')
   ks = [struct.unpack_from('<i', blob, _BLOB_HEAD.size + 16 * r)[0] for r in range(live)]
   return {'B': f[4], 'bytes': f[13], 'committed': f[14], 'N': f[15], 'live': live, 'slots': f[17], 'K': max(ks, default=0)}
+
+
+def blob_max_tag(blob):
+  """The largest speaker tag (bits 24 .. 30 of a block-count word, csrc/uis_blob.h) any live hypothesis of a
+  uis_stream_export blob has bound; 0: the blob carries none.  From the blob's bytes alone; ValueError as blob_info's.
+  Bytes that end inside the lists give 0: the library's import validates everything, and refuses them."""
+  info = blob_info(blob)
+  at = _BLOB_HEAD.size + 16 * info['live']   # the lists: rank by rank, K slot indices, then K block-count words
+  most = 0
+  for r in range(info['live']):
+    k = struct.unpack_from('<i', blob, _BLOB_HEAD.size + 16 * r)[0]
+    if k < 0 or at + 8 * k > len(blob):
+      return 0
+    if k:
+      most = max(most, max(w >> 24 for w in struct.unpack_from('<{}i'.format(k), blob, at + 4 * k)))
+    at += 8 * k
+  return most
 
 
 def decode_kernel_table(lib=None):
@@ -568,6 +590,19 @@ class Decoder:
     tags = np.ascontiguousarray(tags, dtype=np.uint8)
     self._check(self._lib.uis_frame_speakers(
         self._handle, tags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(tags.shape[0])), 'uis_frame_speakers')
+
+  def set_stream_speakers(self, speakers):
+    """uis_stream_speakers: the known speakers (uint8, one tag per frame in the call's own frame order, 0 = unknown,
+    1 .. 127 a speaker; None clears) of the NEXT stream_push / stream_prime on this decoder, which consumes it."""
+    if speakers is None:
+      self._check(self._lib.uis_stream_speakers(self._handle, None, 0), 'uis_stream_speakers')
+      return
+    tags = np.asarray(speakers).reshape(-1)
+    if tags.size and (tags.min() < 0 or tags.max() > 255):
+      raise ValueError('speaker tags must lie in 0 .. 127')
+    tags = np.ascontiguousarray(tags, dtype=np.uint8)
+    self._check(self._lib.uis_stream_speakers(
+        self._handle, tags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(tags.shape[0])), 'uis_stream_speakers')
 
   def _packed(self, frames, offsets, labels=None):
     """Packed utterances, checked: float32 frames [sum N, D], int64 offsets [U + 1] and, if given, int32 labels
@@ -773,11 +808,12 @@ class Decoder:
     self._check(self._lib.uis_stream_get_limits(self._handle, _i32(out)), 'uis_stream_get_limits')
     return out
 
-  def stream_push(self, chunks, bias=None):
+  def stream_push(self, chunks, bias=None, speakers=None):
     """chunks: one [n_u, D] array (or None / empty) per utterance: its new frames -- or ONE
     [n_utt, n, D] array when every utterance has the same number of new frames (one cast, no
     per-utterance Python work: the low-latency way to feed a live session).  bias: this push's per-frame
-    transition_bias, float64 in the chunk's own frame order (utterance-major), or None (set_frame_bias)."""
+    transition_bias, float64 in the chunk's own frame order (utterance-major), or None (set_frame_bias).  speakers:
+    this push's tags, uint8 in the same order, or None (set_stream_speakers)."""
     if len(chunks) != self._stream_n:
       raise ValueError('one chunk (or None) per utterance')
     dim = self.observation_dim
@@ -788,6 +824,8 @@ class Decoder:
       counts = np.full(self._stream_n, chunks.shape[1], dtype=np.int32)
       if bias is not None:
         self.set_frame_bias(bias)
+      if speakers is not None:
+        self.set_stream_speakers(speakers)
       rc = self._lib.uis_stream_push(
           self._handle, frames.ctypes.data_as(_fp) if frames.size else None,
           counts.ctypes.data_as(_i32p))
@@ -821,6 +859,8 @@ class Decoder:
     frames = frames64.astype(np.float32, copy=False)
     if bias is not None:
       self.set_frame_bias(bias)
+    if speakers is not None:
+      self.set_stream_speakers(speakers)
     rc = self._lib.uis_stream_push(self._handle, frames.ctypes.data_as(_fp) if len(frames) else None, self._stream_counts_ptr)
     self._check(rc, 'uis_stream_push')
     self._stream_have += counts
@@ -829,11 +869,12 @@ class Decoder:
     """Frames per utterance the open session holds (pushed or primed, not yet committed): int64 [n_utt]."""
     return self._stream_have.copy()
 
-  def stream_prime(self, chunks, labels):
+  def stream_prime(self, chunks, labels, speakers=None):
     """Prime utterances of the open session with labeled prefixes (uis_stream_prime).
 
     chunks: one [P_u, D] array (or None / empty) per utterance; labels: one int sequence in first-appearance
-    form (or None / empty) per utterance, P_u entries.  Returns the float32 prefix scores [n_utt] (0 where
+    form (or None / empty) per utterance, P_u entries; speakers: the prefixes' tags, uint8 in the call's frame order
+    (utterance-major), or None (set_stream_speakers).  Returns the float32 prefix scores [n_utt] (0 where
     nothing was primed).  A refusal (HipLibraryError with .status) leaves the session as it was."""
     if len(chunks) != self._stream_n or len(labels) != self._stream_n:
       raise ValueError('one chunk and one label sequence (or None) per utterance')
@@ -857,6 +898,8 @@ class Decoder:
     flat = np.ascontiguousarray(np.concatenate(lab_parts)) if lab_parts else np.zeros(0, dtype=np.int32)
     offsets = _offsets(counts)
     scores = np.zeros(self._stream_n, dtype=np.float32)
+    if speakers is not None:
+      self.set_stream_speakers(speakers)
     rc = self._lib.uis_stream_prime(
         self._handle, _ptr(frames) if len(frames) else None, _i64(offsets),
         _i32(flat) if len(flat) else None, _ptr(scores))
@@ -978,6 +1021,13 @@ class Decoder:
     rc = self._lib.uis_stream_import(self._handle, int(utt), blob, len(blob))
     self._check(rc, 'uis_stream_import', ok=(UIS_OK,))
     self._stream_have[int(utt)] = blob_info(blob)['N']
+
+  def stream_bindings(self):
+    """uis_stream_bindings: int32 [n_utt, 128] -- column g (1 .. 127) the cluster the best hypothesis binds tag g to, in
+    the numbering of stream_labels() at this moment, -1 = unbound; column 0 the number of bound tags."""
+    out = np.full((self._stream_n, 128), -1, dtype=np.int32)
+    self._check(self._lib.uis_stream_bindings(self._handle, _i32(out)), 'uis_stream_bindings', ok=(UIS_OK,))
+    return out
 
   def stream_max_clusters(self):
     """max_clusters of the open session (what uis_stream_begin made of the option: 0 means 16)."""

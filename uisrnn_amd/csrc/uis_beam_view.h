@@ -3,7 +3,8 @@
 // backtrace_body, k_backtrace and k_backtrace_window (uis_kernels.hip) carry the older copy of the same rule; they sit
 // inside the one-launch decode kernels and on the benchmark's path and are left exactly as they are.
 //
-// #included by uis_decoder.hip after the handle and the decode kernels (DecodeState), ahead of uis_nbest.hip.
+// #included by uis_decoder.hip after the handle and the decode kernels (DecodeState), ahead of uis_stream.hip
+// (k_stream_bindings) and uis_nbest.hip.
 
 namespace {
 

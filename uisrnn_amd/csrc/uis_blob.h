@@ -8,7 +8,8 @@
 //   scalars   UisBlobScalars, 32 bytes: committed, N (window frames = utt_step), live, n (distinct pool slots),
 //             lists (= sum of K over the live ranks), win_score
 //   ranks     [live] x {K, last, sum, score bits}: 16 bytes per live rank, best first
-//   lists     rank by rank: K slot indices (renumbered into 0 .. n - 1), then K block counts; int32
+//   lists     rank by rank: K slot indices (renumbered into 0 .. n - 1), then K block-count words (the count, and in
+//             bits 24 .. 30 the cluster's speaker tag: 0 in a stream without known speakers, whose blob is unchanged); int32
 //   cnt       [n] int32: frames each slot's cluster has absorbed
 //   mean      [n][Dp] float32: the pool's padded rows, as they are
 //   hid       [n][depth][Hp] float32: the pool's padded / HidMap rows, as they are
@@ -34,6 +35,10 @@
 #define UIS_BLOB_MAX_BEAM 256               // (uis_stream_begin's limits)
 #define UIS_BLOB_MAX_CLUSTERS 4096
 #define UIS_BLOB_MAX_FRAMES 0x7fffff00ll
+// a block-count word of the lists: the count in bits 0 .. 23, the cluster's speaker tag in bits 24 .. 30 (0: none) --
+// uis_kernels.h's UIS_BLK_*, restated because this header stands alone
+#define UIS_BLOB_BLK_TAG_SHIFT 24
+#define UIS_BLOB_BLK_COUNT_MASK 0x00ffffff
 
 struct UisBlobHeader {
   uint32_t magic, format, numerics, look_ahead;
@@ -134,6 +139,7 @@ struct UisBlobInfo {
   UisBlobScalars sc;
   UisBlobLayout lay;
   int32_t max_K;
+  int32_t max_tag;   // the largest speaker tag a live rank has bound (0: the blob carries none)
 };
 
 enum {
@@ -179,19 +185,28 @@ inline int uis_blob_validate(const void* blob, int64_t bytes, const UisBlobShape
   // ---- the ranks and their lists
   int64_t at = 0;
   in.max_K = 0;
+  in.max_tag = 0;
   for (int r = 0; r < sc.live; ++r) {
     UisBlobRank rk;
     memcpy(&rk, b + l.ranks + (int64_t)r * (int64_t)sizeof(rk), sizeof(rk));
     if (rk.K < 0 || rk.K > UIS_BLOB_MAX_CLUSTERS || at + rk.K > sc.lists) { *why = "a rank's cluster count is out of range"; return UIS_BLOB_MALFORMED; }
     if (rk.K == 0 ? rk.last != -1 : (rk.last < 0 || rk.last >= rk.K)) { *why = "a rank's last label is not one of its clusters"; return UIS_BLOB_MALFORMED; }
     int64_t sum = 0;
+    uint64_t seen[2] = {0, 0};   // the tags this rank has bound
     for (int k = 0; k < rk.K; ++k) {
       int32_t slot, blk;
       memcpy(&slot, b + l.lists + (2 * at + k) * 4, 4);
       memcpy(&blk, b + l.lists + (2 * at + rk.K + k) * 4, 4);
       if (slot < 0 || slot >= sc.n) { *why = "a slot index is not below the slot count"; return UIS_BLOB_MALFORMED; }
       if (blk < 0) { *why = "a negative block count"; return UIS_BLOB_MALFORMED; }
-      sum += blk;
+      sum += blk & UIS_BLOB_BLK_COUNT_MASK;
+      const int tag = blk >> UIS_BLOB_BLK_TAG_SHIFT;   // (0 .. 127: blk is not negative)
+      if (!tag) continue;
+      if ((seen[tag >> 6] >> (tag & 63)) & 1u) { *why = "a tag bound twice"; return UIS_BLOB_MALFORMED; }
+      seen[tag >> 6] |= (uint64_t)1 << (tag & 63);
+      if (sc.committed + sc.N >= ((int64_t)1 << UIS_BLOB_BLK_TAG_SHIFT))
+        { *why = "a tag in a stream of 2^24 frames or more (it shares the block-count word)"; return UIS_BLOB_MALFORMED; }
+      if (tag > in.max_tag) in.max_tag = tag;
     }
     if (sum != (int64_t)rk.sum || sum > sc.committed + sc.N) { *why = "a rank's block counts do not add up to its sum"; return UIS_BLOB_MALFORMED; }
     at += rk.K;

@@ -159,6 +159,7 @@ struct StreamMem {
   std::vector<DevBuf> allocs;  // the session's state, one allocation per table (uis_stream_begin)
   DevBuf chunk_x, chunk_pad, chunk_gi0, chunk_mse0, labels, scores;
   DevBuf chunk_bias;  // [chunk frames][3] float64: DecodeState::bias3 of a push with a uis_frame_bias table
+  DevBuf chunk_hint;  // [chunk frames] uint8: DecodeState::hint of a push with a uis_stream_speakers table
   // one push = one H2D copy: [foff U x int64][avail U x int32, padded][frames] staged in pinned
   // host memory (h_stage) and mirrored in chunk_x
   HostBuf h_stage;
@@ -268,6 +269,9 @@ struct uis_handle : HandleMem {
     size_t hdr_stride = 0;
     int64_t pm_launches = 0, pm_commands = 0;
     UisPoison poison;                 // UIS_POISON_WORKSPACE as uis_stream_begin / the running uis_stream_push read it
+    // a push, a prime or an import has given the session a non-zero speaker tag (uis_stream_speakers): from then on, and
+    // until uis_stream_end, no utterance may reach 2^24 frames received (the tag shares the block-count word)
+    bool tagged = false;
   } stream_state;
   size_t dbg_floats = 0;  // what the last decode left in dbg_scores (UIS_FLAG_DEBUG_SCORES)
   UisPoison poison;  // UIS_POISON_WORKSPACE as the running uis_decode* call read it at its entry (one getenv per call)
@@ -297,6 +301,12 @@ struct uis_handle : HandleMem {
   // running call's (take_hint, at that call's entry: consumed whether the call succeeds or not)
   std::vector<uint8_t> pending_hint, call_hint;
   bool pending_hint_set = false, call_hint_set = false;
+  // a session's known speakers: the table uis_stream_speakers left for the next uis_stream_push / uis_stream_prime, in
+  // that call's frame order, and the running call's (take_stream_tags, at that call's entry: consumed whether the call
+  // succeeds or not; every other uis_stream_* call leaves it pending).  call_tagged: the running call's table holds a
+  // non-zero tag
+  std::vector<uint8_t> pending_stream_tags, call_stream_tags;
+  bool pending_stream_tags_set = false, call_stream_tags_set = false, call_tagged = false;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
   // offsets, the record format
@@ -2312,6 +2322,48 @@ UIS_EXPORT int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_
   return UIS_OK;
 }
 
+// The same for uis_stream_speakers' table, at the two entry points that take a session's frames (uis_stream_push,
+// uis_stream_prime); no other call touches it.
+static void take_stream_tags(uis_handle* h) {
+  if (!h) return;
+  h->call_stream_tags.swap(h->pending_stream_tags);
+  h->call_stream_tags_set = h->pending_stream_tags_set;
+  h->pending_stream_tags.clear();
+  h->pending_stream_tags_set = false;
+  h->call_tagged = false;
+  for (uint8_t g : h->call_stream_tags) h->call_tagged = h->call_tagged || g != 0;
+}
+
+// The running call's table must cover exactly its frames.
+static int check_stream_tags_frames(uis_handle* h, int64_t n_frames) {
+  if (h->call_stream_tags_set && (int64_t)h->call_stream_tags.size() != n_frames)
+    return fail(UIS_ERR_INVALID_ARG, "uis_stream_speakers gave " + std::to_string(h->call_stream_tags.size()) + " tags, this call has " +
+                                         std::to_string(n_frames) + " frames");
+  return UIS_OK;
+}
+
+// A cluster's tag shares its block-count word (UIS_BLK_*): once a session holds a tag, or the running call brings one,
+// no utterance may have received 2^24 frames or more.  Host arithmetic, before any device work.
+static int check_tagged_frames(const char* who, bool tagged, int utt, int64_t received) {
+  if (tagged && received >= ((int64_t)1 << UIS_BLK_TAG_SHIFT))
+    return fail(UIS_ERR_UNSUPPORTED, std::string(who) + ": utterance " + std::to_string(utt) + " of a session with known speakers would have "
+                                         "received 2^24 frames or more (a cluster's tag shares its block-count word)");
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_stream_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames) {
+  if (int rch = refuse_hint(h, "uis_stream_speakers")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes)
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  if (!tags || n_frames == 0) { h->pending_stream_tags.clear(); h->pending_stream_tags_set = false; return UIS_OK; }
+  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
+  for (int64_t t = 0; t < n_frames; ++t)
+    if (tags[t] > 127)
+      return fail(UIS_ERR_INVALID_ARG, "the speaker tag at frame " + std::to_string(t) + " is above 127 (0: unknown)");
+  h->pending_stream_tags.assign(tags, tags + n_frames);
+  h->pending_stream_tags_set = true;
+  return UIS_OK;
+}
+
 UIS_EXPORT int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
   if (!bias || n_frames == 0) { h->pending_bias3.clear(); h->pending_bias_set = false; return UIS_OK; }
@@ -2519,6 +2571,7 @@ UIS_EXPORT int32_t uis_debug_scores(uis_handle* h, float* scores_out, int64_t ca
 }
 
 // ------------------------------------------------------------------ streaming sessions
+#include "uis_beam_view.h"
 #include "uis_stream.hip"
 
 
@@ -2625,7 +2678,6 @@ UIS_EXPORT void uis_host_free(void* p) {
 #include "uis_prime.hip"
 
 // ------------------------------------------------------------------ n-best readout
-#include "uis_beam_view.h"
 #include "uis_nbest.hip"
 
 // ------------------------------------------------------------------ posterior readout

@@ -336,6 +336,11 @@ UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blo
                                          std::to_string(ss.Kmax));
   if (sc.n > ss.S)
     return fail(UIS_ERR_INVALID_ARG, "the blob names " + std::to_string(sc.n) + " pool slots, the session has " + std::to_string(ss.S) + " per utterance");
+  // (uis_stream_speakers: a blob whose block-count words carry tags makes the session a tagged one; a persistent
+  // session's pushes could never name them again; the 2^24 bound of a tagged session holds for what arrives, too)
+  if (info.max_tag > 0 && (ss.st.flags & UIS_FLAG_PERSISTENT))
+    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers: the blob carries speaker tags (uis_stream_speakers)");
+  if (int rct = check_tagged_frames("uis_stream_import", ss.tagged || info.max_tag > 0, utt, sc.committed + sc.N)) return rct;
   int rc;
   if ((rc = session_enter(h, nullptr))) return rc;  // (no window table: the target has received nothing)
   hipStream_t st = h->stream;
@@ -367,6 +372,7 @@ UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blo
   ss.have[utt] = sc.N;
   ss.committed[utt] = sc.committed;
   ss.win_score[utt] = sc.win_score;
+  ss.tagged = ss.tagged || info.max_tag > 0;
   prior.swap(h);
   h->nb_valid = false;
   migrate_trace("uis_stream_import", h, utt, sc, bytes, timer);

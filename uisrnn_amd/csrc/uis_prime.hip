@@ -115,7 +115,8 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   // (the primed prefix is scored with the model's transition_bias: a pending per-frame table is refused, and dropped --
   // and so is a pending speaker table: both are consumed, whichever is reported)
   const int rcb = refuse_bias(h, "uis_stream_prime");
-  if (int rch = refuse_hint(h, "uis_stream_prime")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  take_stream_tags(h);  // (uis_stream_speakers: the prefix's tags, in this call's frame order; consumed whatever happens below)
+  if (int rch = refuse_hint(h, "uis_stream_prime")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
   if (rcb) return rcb;
   if (!session_of(h, offsets != nullptr, "null handle/offsets")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
@@ -129,7 +130,12 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   const int64_t F = offsets[U];
   if (F > 0 && (!frames || !labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels is null");
   if (F > 0x7fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "more than 2^31 - 1 frames in one call");
+  if (int rct = check_stream_tags_frames(h, F)) return rct;
+  if (h->call_stream_tags_set && (ss.st.flags & UIS_FLAG_PERSISTENT))  // (its pushes could never name the tags again)
+    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
+  const uint8_t* tags = h->call_stream_tags_set ? h->call_stream_tags.data() : nullptr;
   int too_many = -1, too_many_K = 0;
+  std::vector<std::vector<uint8_t>> tag_of_label(U);
   for (int u = 0; u < U; ++u) {
     const int64_t P = offsets[u + 1] - offsets[u];
     if (P == 0) continue;
@@ -137,7 +143,13 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
       return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has already received or been primed with " +
                                            std::to_string((long long)(ss.committed[u] + ss.have[u])) + " frames: a prefix goes in front of everything");
     if (P > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + ": the prefix exceeds the session's max_frames");
+    if (int rct = check_tagged_frames("uis_stream_prime", ss.tagged || h->call_tagged, u, P)) return rct;
     int K = 0;
+    // (the binding hypothesis 0 would hold after these labels under these tags: tag_of_label[u][c], 0 = none; the decode's
+    // rule admits the trace iff tag <-> label is a partial bijection)
+    std::vector<uint8_t>& tag_of = tag_of_label[u];
+    int label_of[128];
+    std::fill(label_of, label_of + 128, -1);
     for (int64_t t = offsets[u]; t < offsets[u + 1]; ++t) {
       const int c = labels[t];
       if (c < 0) return fail(UIS_ERR_INVALID_ARG, "label " + std::to_string(c) + " at frame " + std::to_string(t) + " is negative");
@@ -145,7 +157,14 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
         return fail(UIS_ERR_INVALID_ARG, "label " + std::to_string(c) + " at frame " + std::to_string(t) +
                                              " is not in first-appearance form (at most " + std::to_string(K) + " here): a prefix "
                                              "cannot be an invalid trace");
-      if (c == K) ++K;
+      if (c == K) { ++K; tag_of.push_back(0); }
+      const int g = tags ? tags[t] : 0;
+      if (!g) continue;
+      if ((tag_of[c] && tag_of[c] != g) || (label_of[g] >= 0 && label_of[g] != c))
+        return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + ": the prefix labels contradict its tags (tag " + std::to_string(g) +
+                                             " on label " + std::to_string(c) + " at frame " + std::to_string(t) + ")");
+      tag_of[c] = (uint8_t)g;
+      label_of[g] = c;
     }
     if (K > ss.Kmax && too_many < 0) { too_many = u; too_many_K = K; }
   }
@@ -179,6 +198,11 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
     }
   }
   const int nutt = (int)utts.size();
+  // (uis_stream_speakers: the binding rides in the block-count words, as the selects leave it -- count | tag << 24)
+  std::vector<int32_t> blk_words(s.chain_blk.begin(), s.chain_blk.end());
+  for (const PrimeUtt& p : utts)
+    for (int k = 0; k < p.K; ++k) blk_words[p.blk0 + k] |= (int32_t)tag_of_label[p.utt][k] << UIS_BLK_TAG_SHIFT;
+  ss.tagged = ss.tagged || h->call_tagged;
   ScratchPlan plan;
   const size_t o_chains = plan.take((size_t)nch * sizeof(PrimeChain)), o_utts = plan.take((size_t)nutt * sizeof(PrimeUtt)),
                o_blk = plan.take((size_t)nch * 4), o_lab = plan.take((size_t)F * 4);
@@ -187,7 +211,7 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   hipStream_t st = h->stream;
   HIPCHK(hipMemcpyAsync(base + o_chains, chains.data(), (size_t)nch * sizeof(PrimeChain), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(base + o_utts, utts.data(), (size_t)nutt * sizeof(PrimeUtt), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(base + o_blk, s.chain_blk.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(base + o_blk, blk_words.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(base + o_lab, labels, (size_t)F * 4, hipMemcpyHostToDevice, st));
   PrimeArgs a{};
   a.nch = nch; a.nutt = nutt; a.Fv = (long)s.Fv;

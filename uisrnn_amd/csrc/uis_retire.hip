@@ -6,7 +6,9 @@
 // the live hypotheses = ranks 0 .. live - 1 of the beam tables of parity N & 1, cluster index k is RETIRABLE iff for
 // every live rank r:  k < K_r,  k is not among r's labels of window frames [0, N) (its back-pointer chain, walked as
 // k_nbest walks it),  and k != last_r (a window that a commit emptied has no labels, and its one hypothesis still
-// continues from its last label).  Such a cluster was opened before the window; after a commit or a prime all live
+// continues from its last label),  and k carries no speaker tag in r's block-count words (uis_stream_speakers: the next
+// frame with that tag names it; the words move down whole, so a binding follows its cluster's new index).  Such a
+// cluster was opened before the window; after a commit or a prime all live
 // hypotheses share that history, so index k means the same speaker in each of them.  Retiring a set R:
 //   lists    every live rank's slot / block lists lose the entries in R, the entries above move down in order
 //   scalars  K_r -= |R|,  sum_r -= sum of blk_r[k] over R,  last_r -= #{k in R : k < last_r};  scores stay
@@ -50,6 +52,7 @@ struct RetireArgs {
   int32_t* retired;         // [U][Kmax]
   int32_t* retirable;       // [U][Kmax]
   int32_t* words;           // [U][4]: retired, retirable, largest K afterwards, status
+  int tagged;               // the session holds speaker tags (uis_stream_speakers): the block-count words are scanned for them
 };
 
 // pre[w] = bits set in mask[0 .. w), w <= nw (one thread; nw <= 129)
@@ -103,6 +106,15 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_scan(DecodeState 
     if (last >= 0 && last < Kmax) atomicOr(&s_used[last >> 5], 1u << (last & 31));
     atomicMin(&s_minK, K);
     atomicMax(&s_maxK, K);
+  }
+  // ---- a cluster that carries a tag in any live rank counts as used: the next frame with that tag names it.  Entry
+  // i = (rank i / Kmax, index i % Kmax)
+  if (a.tagged) {
+    for (long i = tid; i < (long)live * Kmax; i += UIS_RETIRE_THREADS) {
+      const int r = (int)(i / Kmax), k = (int)(i - (long)r * Kmax);
+      const int K = st.beam_K[e + r];
+      if (k < K && blk_tag(st.beam_blk[(e + r) * Kmax + k]) != 0) atomicOr(&s_used[k >> 5], 1u << (k & 31));
+    }
   }
   __syncthreads();
   const int minK = live > 0 ? s_minK : 0;
@@ -173,7 +185,7 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
   for (int r = tid; r < live; r += UIS_RETIRE_THREADS) {
     const int32_t* blk = st.beam_blk + (e + r) * Kmax;
     int gone = 0;
-    for (int i = 0; i < n_ret; ++i) gone += blk[retired[i]];
+    for (int i = 0; i < n_ret; ++i) gone += blk_count(blk[retired[i]]);   // (a retired cluster carries no tag; the count all the same)
     const int K = st.beam_K[e + r], last = st.beam_last[e + r];
     s_K[r] = K < 0 ? 0 : (K > Kmax ? Kmax : K);
     st.beam_K[e + r] = K - n_ret;
@@ -289,6 +301,7 @@ UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const 
   a.retired = reinterpret_cast<int32_t*>(base + o_ret);
   a.retirable = reinterpret_cast<int32_t*>(base + o_able);
   a.shift = reinterpret_cast<int32_t*>(base + o_shift);
+  a.tagged = ss.tagged ? 1 : 0;
   // ---- scan, apply
   HIPCHK(timer.begin());
   hipLaunchKernelGGL(k_retire_scan, dim3(U), dim3(UIS_RETIRE_THREADS), nbest_lds_bytes(B), st, stc, a);

@@ -180,7 +180,7 @@ int pm_quit(uis_handle* h) {
 }
 
 // ---- the scaffold of a session call between launches: uis_stream_{labels, nbest, posterior, prime, commit, restart,
-// retire, committed}.  THE ORDER, stated here once:
+// retire, committed, bindings}.  THE ORDER, stated here once:
 //   1. session_of and the call's own checks on the host: nothing of the session is touched, and a call refused here
 //      (or one with nothing to do) costs a UIS_FLAG_PERSISTENT session nothing and touches no device;
 //   2. session_enter: the resident launch leaves (pm_quit -- it occupies every CU and the tables are written between
@@ -484,7 +484,8 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
 
 UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
   take_bias(h);  // (uis_frame_bias: this push's table, in the chunk's own frame order; consumed whatever happens below)
-  if (int rch = refuse_hint(h, "uis_stream_push")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  take_stream_tags(h);  // (uis_stream_speakers: likewise)
+  if (int rch = refuse_hint(h, "uis_stream_push")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
   if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
   uis_handle::Stream& ss = h->stream_state;
   if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
@@ -507,6 +508,12 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   // a table would have to travel through the mailbox, whose layout is a protocol of its own: DESIGN.md section 9, "Open")
   if (h->call_bias_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no per-frame transition_bias (uis_frame_bias): the table is dropped");
+  // (uis_stream_speakers: the same three checks for this push's tags, then the 2^24 bound of a session that holds any)
+  if (int rct = check_stream_tags_frames(h, F)) return rct;
+  if (h->call_stream_tags_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
+  for (int u = 0; u < U; ++u)
+    if (int rct = check_tagged_frames("uis_stream_push", ss.tagged || h->call_tagged, u, ss.committed[u] + ss.have[u] + counts[u])) return rct;
   if (F == 0) return UIS_OK;
   if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
   HIPCHK(hipSetDevice(h->device));
@@ -584,6 +591,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
   if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
   if (h->call_bias_set && (rc = ss.chunk_bias.ensure((size_t)F * 24))) return rc;
+  if (h->call_stream_tags_set && (rc = ss.chunk_hint.ensure((size_t)F))) return rc;
   // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
   // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
   ss.poison = UisPoison::from_env();
@@ -593,10 +601,15 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
     HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
     HIPCHK(ss.poison.device(ss.chunk_bias.p, ss.chunk_bias.cap, h->stream));
+    HIPCHK(ss.poison.device(ss.chunk_hint.p, ss.chunk_hint.cap, h->stream));
   }
   // (the table's rows are the chunk's: row foff[u] + step, as mse0; call_bias3 lives until the synchronize below)
   if (h->call_bias_set)
     HIPCHK(hipMemcpyAsync(ss.chunk_bias.p, h->call_bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
+  // (the tags likewise, one byte per chunk row; the session counts as tagged from here on, whatever becomes of the push)
+  if (h->call_stream_tags_set)
+    HIPCHK(hipMemcpyAsync(ss.chunk_hint.p, h->call_stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
+  ss.tagged = ss.tagged || h->call_tagged;
   int64_t* h_foff = ss.h_stage.as<int64_t>();
   int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + (size_t)U * 8);
   {
@@ -627,6 +640,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   DecodeState st = ss.st;
   st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
   st.bias3 = h->call_bias_set ? ss.chunk_bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
+  st.hint = h->call_stream_tags_set ? ss.chunk_hint.as<uint8_t>() : nullptr;  // (ss.st.hint likewise: the bindings ride in beam_blk)
   const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
   // One-launch path: the chunk's projection fused into the kernel and plain launches after the
   // session's first push make a push one H2D, one memset and ONE kernel.  Measured
@@ -762,6 +776,64 @@ UIS_EXPORT int32_t uis_stream_limits(uis_handle* h, const int32_t* limits) {
   if (int rc = upload_session_limits(h, next, dev)) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   ss.limits = next;
+  return UIS_OK;
+}
+
+namespace {
+
+#define UIS_BINDINGS_WIDTH 128   // tags 0 .. 127: one thread and one output word each
+
+// The binding of the best hypothesis, one workgroup per utterance, between launches: out[u][g] = the cluster index whose
+// block-count word of rank 0 carries tag g (1 .. 127), -1 where none does; out[u][0] = how many tags are bound.  An
+// utterance without a live hypothesis (an emptied beam, the overflow word set): 0 and -1 everywhere.  A window that a
+// commit emptied keeps its one hypothesis, and with it the binding.
+__global__ __launch_bounds__(UIS_BINDINGS_WIDTH) void k_stream_bindings(DecodeState st, int32_t* __restrict__ out) {
+  __shared__ int s_bound[UIS_BINDINGS_WIDTH];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  if (u >= st.U) return;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u, EMPTY_WINDOW_KEEPS_BEAM);
+  s_bound[tid] = -1;
+  __syncthreads();
+  if (live > 0) {
+    int K = st.beam_K[e];
+    K = K < 0 ? 0 : (K > st.Kmax ? st.Kmax : K);
+    const int32_t* row = st.beam_blk + e * st.Kmax;   // rank 0
+    for (int k = tid; k < K; k += UIS_BINDINGS_WIDTH) {
+      const int g = blk_tag(row[k]) & (UIS_BINDINGS_WIDTH - 1);
+      if (g) s_bound[g] = k;   // (a binding is injective: no two threads write one word)
+    }
+  }
+  __syncthreads();
+  const int c = s_bound[tid];
+  const int n = __syncthreads_count(tid > 0 && c >= 0);
+  out[(size_t)u * UIS_BINDINGS_WIDTH + tid] = tid == 0 ? n : c;
+}
+
+}  // namespace
+
+// Who is who right now: see include/uisrnn_hip.h.  The scaffold's order; nothing of the session changes.
+UIS_EXPORT int32_t uis_stream_bindings(uis_handle* h, int32_t* out) {
+  if (int rch = refuse_hint(h, "uis_stream_bindings")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
+  if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
+  uis_handle::Stream& ss = h->stream_state;
+  const int U = ss.U;
+  CallTimer timer{h};
+  int rc;
+  DecodeState stv;
+  if ((rc = session_enter(h, &stv))) return rc;
+  ScratchPlan plan;
+  const size_t bytes = (size_t)U * UIS_BINDINGS_WIDTH * 4, o_out = plan.take(bytes);
+  char* base;
+  if ((rc = session_buffers(h, plan, bytes, &base))) return rc;
+  HIPCHK(timer.begin());
+  hipLaunchKernelGGL(k_stream_bindings, dim3(U), dim3(UIS_BINDINGS_WIDTH), 0, h->stream, stv, reinterpret_cast<int32_t*>(base + o_out));
+  HIPCHK(hipGetLastError());
+  HIPCHK(timer.end());
+  HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_out, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memcpy(out, ss.h_land.p, bytes);
+  if (CallTimer::env("UIS_BINDINGS_TRACE"))
+    fprintf(stderr, "uis_stream_bindings: utterances %d device_ms %.3f call_ms %.3f\n", U, timer.device_ms(), timer.call_ms());
   return UIS_OK;
 }
 

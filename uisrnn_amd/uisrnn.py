@@ -74,7 +74,7 @@ def _check_max_speakers(max_speakers, args, n_utt):
 _MAX_KNOWN_SPEAKERS = 127   # (a cluster's tag is seven bits of its block-count word: include/uisrnn_hip.h)
 
 
-def _check_known_speakers(known_speakers, lengths, single=False):
+def _check_known_speakers(known_speakers, lengths, single=False, tables=None):
   """The known_speakers keyword as the library's table: None (nobody is known) or one uint8 array per utterance of that
   utterance's length, 0 = unknown, 1 .. 127 = the utterance's names in the order they first appear.
 
@@ -83,7 +83,10 @@ def _check_known_speakers(known_speakers, lengths, single=False):
   dict keys are: 1, 1.0 and True are one speaker, 'a' and b'a' two.  A float NaN equals nothing, itself included, so it
   cannot name anybody and is refused.  Raises before any device work: ValueError for a wrong count or length, for more
   than 127 names in one utterance, for a NaN name and for a bool where a sequence is expected, TypeError for an
-  unhashable name."""
+  unhashable name.
+
+  tables (a session's pushes): one {name: tag} dict per utterance that the call goes on numbering from and adds its new
+  names to -- the caller hands in copies and keeps them only if nothing was raised."""
   if known_speakers is None:
     return None
 
@@ -94,14 +97,14 @@ def _check_known_speakers(known_speakers, lengths, single=False):
       raise ValueError('known_speakers of {} must be a sequence of names (None: unknown), not {!r}.'.format(
           who, type(value)))
 
-  def one(value, n, who):
+  def one(value, n, who, tags=None):
     if value is None:
       return np.zeros(n, dtype=np.uint8)
     refuse_kind(value, who)
     names = value.tolist() if isinstance(value, np.ndarray) else list(value)
     if len(names) != n:
       raise ValueError('known_speakers of {} has {} entries for {} frames.'.format(who, len(names), n))
-    tags, table = {}, np.zeros(n, dtype=np.uint8)
+    tags, table = {} if tags is None else tags, np.zeros(n, dtype=np.uint8)
     for t, name in enumerate(names):
       if name is None:
         continue
@@ -126,7 +129,8 @@ def _check_known_speakers(known_speakers, lengths, single=False):
     raise ValueError('known_speakers for a list of sequences must be one sequence of names per sequence.')
   if len(known_speakers) != len(lengths):
     raise ValueError('known_speakers has {} entries for {} utterances.'.format(len(known_speakers), len(lengths)))
-  return [one(v, n, 'utterance {}'.format(u)) for u, (v, n) in enumerate(zip(known_speakers, lengths))]
+  return [one(v, n, 'utterance {}'.format(u), None if tables is None else tables[u])
+          for u, (v, n) in enumerate(zip(known_speakers, lengths))]
 
 
 def _check_transition_bias(transition_bias, lengths, single=False, offline=True):
@@ -1102,6 +1106,12 @@ class OnlineSession:
   itself before a push that could take an utterance past K clusters.  The ids the session hands out never change
   and are never reused: a speaker who returns after retirement is a new id.
 
+  Known speakers: push(..., known_speakers=) names who speaks at some of the chunk's frames -- a
+  corrected segment, an enrolled voice, a channel tag -- and the stream decodes as predict(..., known_speakers=) would:
+
+      session.push([chunk], known_speakers=[['ann', None, None, 'bob']])   # one name (or None) per frame
+      session.speakers()                   # [{'ann': 0, 'bob': 1}]: the label each name's frames carry
+
   persistent=True (UIS_FLAG_PERSISTENT): the decode kernel stays on the GPU between pushes and is
   fed through a mailbox in pinned host memory -- the lowest push latency (no launch, no copy
   engine), at the price of occupying the whole device until the session closes or has been idle
@@ -1115,6 +1125,7 @@ class OnlineSession:
   _retire_to = None
   _bound = None   # per utterance an upper bound of K: K at the last query plus the frames pushed since
   _seen = None    # per utterance {id: stream position of its last committed appearance}
+  _names = None   # per utterance {name: tag}: its known speakers, numbered 1 .. 127 by first appearance across pushes
 
   def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None,
                retire_to=None, limits=None):
@@ -1157,7 +1168,42 @@ class OnlineSession:
     """The slots' bounds: a list with an int or None (no bound) per utterance."""
     return [int(v) if v else None for v in self._decoder.stream_limits()]
 
-  def prime(self, chunks, cluster_ids):
+  def _name_tables(self):
+    if self._names is None:
+      self._names = [{} for _ in range(self._num_utterances)]
+    return self._names
+
+  def _speaker_tags(self, sizes, known_speakers):
+    """A call's known_speakers as (the library's flat uint8 table in the call's frame order, the utterances' name tables
+    with the call's new names added) -- (None, None) without the keyword.  Nothing of the session changes here: the
+    caller keeps the tables once every check of the call has passed."""
+    if known_speakers is None:
+      return None, None
+    if isinstance(known_speakers, np.ndarray) and known_speakers.ndim == 2:
+      known_speakers = list(known_speakers)   # ([U, n] beside [U, n, D]: one row per utterance)
+    tables = [dict(t) for t in self._name_tables()]
+    per_utt = _check_known_speakers(known_speakers, sizes, tables=tables)
+    flat = np.concatenate(per_utt) if per_utt else np.zeros(0, dtype=np.uint8)
+    return (flat if flat.size else None), tables
+
+  def speaker_names(self, utterance):
+    """The known speakers of an utterance in tag order: names[g - 1] is the name with tag g."""
+    names = self._name_tables()[self._utterance(utterance)]
+    return sorted(names, key=names.get)
+
+  def speakers(self):
+    """Who is who right now (uis_stream_bindings): per utterance {name: label} for the known
+    speakers the best hypothesis has bound -- the label labels() gives that speaker's frames.  A name that no frame has
+    carried yet, or whose utterance has no live hypothesis, is absent."""
+    table = self._decoder.stream_bindings()
+    out = []
+    for u, names in enumerate(self._name_tables()):
+      bound = [(name, int(table[u, tag])) for name, tag in names.items() if table[u, tag] >= 0]
+      ids = self._ids(u, [c for _, c in bound])
+      out.append({name: ids[i] for i, (name, _) in enumerate(bound)})
+    return out
+
+  def prime(self, chunks, cluster_ids, known_speakers=None):
     """Start utterances from a labeled prefix (uis_stream_prime; extension).
 
     The session is afterwards in the state it would hold had it received the prefix frames with its beam
@@ -1169,6 +1215,9 @@ class OnlineSession:
       chunks: a list with one [P_u, D] float64 array or None per utterance: the prefix frames.
       cluster_ids: a list with one sequence of P_u ids (any hashable kind; renamed by order of first
         appearance, as score_labels does) or None per utterance.
+      known_speakers: None, or as push's: who speaks at the prefix frames.  The primed hypothesis binds each name to
+        the cluster its frames are labeled with; within one prefix a name must stay on one id and an id under one name
+        (HipLibraryError, UIS_ERR_INVALID_ARG, otherwise).
     Returns:
       a list with the prefix's negative log-likelihood (float) per utterance, None where nothing was primed.
     Raises:
@@ -1206,7 +1255,11 @@ class OnlineSession:
                          'everything.'.format(u, int(received[u])))
       labels[u] = _first_appearance(ids)
       frames[u] = chunk
-    scores = self._decoder.stream_prime(frames, labels)
+    speakers, names = self._speaker_tags([0 if f is None else len(f) for f in frames], known_speakers)
+    extra = {} if speakers is None else {'speakers': speakers}
+    if names is not None:
+      self._names = names
+    scores = self._decoder.stream_prime(frames, labels, **extra)
     if self._bound is not None:
       for u in range(n_utt):   # (a prefix of P frames has at most P clusters)
         self._bound[u] += 0 if labels[u] is None else len(labels[u])
@@ -1222,9 +1275,15 @@ class OnlineSession:
     tables = _check_transition_bias(transition_bias, _chunk_sizes(chunks), offline=False)
     return np.concatenate(tables) if tables else np.zeros(0, dtype=np.float64)
 
-  def push(self, chunks, transition_bias=None):
+  def push(self, chunks, transition_bias=None, known_speakers=None):
     """chunks: a list with one [n, D] float64 array (or None) per utterance, or one [U, n, D]
     float64 array when every utterance received the same number of frames.
+
+    known_speakers: who speaks at some of this push's frames, in the chunk's own layout -- None,
+    or one sequence (or None) per utterance of its chunk's length whose entries are None (unknown) or any hashable name.
+    The session numbers an utterance's names 1 .. 127 by first appearance across its pushes (restart clears them); the
+    128th name is a ValueError before any device work, the other errors are predict's.  The stream is bit for bit
+    predict(..., known_speakers=) of everything received.  A persistent session refuses a table like a bias table.
 
     transition_bias: this push's per-frame probability of a speaker change, in the chunk's own
     layout -- None, a number, one array (or None) per utterance of its chunk's length, or a [U, n] array beside a
@@ -1235,6 +1294,11 @@ class OnlineSession:
     if bias is not None and not bias.size:
       bias = None
     extra = {} if bias is None else {'bias': bias}
+    speakers, names = self._speaker_tags(_chunk_sizes(chunks), known_speakers)
+    if speakers is not None:
+      extra['speakers'] = speakers
+    if names is not None:
+      self._names = names
     if self._retire_at is not None:
       self._keep_under_cap(chunks)
     if self._horizon is not None:
@@ -1491,6 +1555,8 @@ class OnlineSession:
         self._gone[u] = []
       if self._bound is not None:
         self._bound[u], self._seen[u] = 0, {}
+      if self._names is not None:
+        self._names[u] = {}
     return out
 
   # ---- moving and checkpointing utterances
@@ -1517,20 +1583,32 @@ class OnlineSession:
     gone = self._gone[u] if self._gone is not None else []
     return blob + _pack_state_trailer(blob, self._final[u], gone)
 
-  def import_state(self, utterance, blob):
+  def import_state(self, utterance, blob, speaker_names=None):
     """Continue an exported utterance in slot `utterance`, which must have received nothing (uis_stream_import).
     labels(), commit(), nbest(), restart() and retire() hand out the same ids as the source session did, and
     restart() returns the whole stream.  All or nothing.
 
+    speaker_names: the source's speaker_names(utterance) -- names are not serialised; the bindings are.  The slot's
+    name table becomes this list (None: empty).
+
     Raises:
-      ValueError: an index out of range, bytes that are not an exported state.
+      ValueError: an index out of range, bytes that are not an exported state, a state whose hypotheses bind more
+        speaker tags than speaker_names has names (before the library is called).
       _capi.HipLibraryError: the library's refusals (status UIS_ERR_INVALID_ARG: a damaged blob, another model or
         beam size, a window longer than max_frames, a slot that has received frames; UIS_ERR_CLUSTER_CAP: a
         hypothesis with more clusters than this session's max_clusters).  The session is then as it was.
     """
     u = self._utterance(utterance)
     core, final, gone = _unpack_state(blob)
+    names = [] if speaker_names is None else list(speaker_names)
+    if len(names) > _MAX_KNOWN_SPEAKERS or len(set(names)) != len(names):
+      raise ValueError('speaker_names must be at most {} distinct names.'.format(_MAX_KNOWN_SPEAKERS))
+    most = _capi.blob_max_tag(core)
+    if most > len(names):
+      raise ValueError('the state binds speaker tag {} but speaker_names has {} names: pass the source session\'s '
+                       'speaker_names(utterance).'.format(most, len(names)))
     self._decoder.stream_import(u, core)
+    self._name_tables()[u] = {name: g + 1 for g, name in enumerate(names)}
     self._final[u] = final
     if gone:
       if self._gone is None:
@@ -1671,10 +1749,11 @@ class StreamPool:
     self._slot[key] = self._free.pop()
     return self._slot[key]
 
-  def push(self, chunks, transition_bias=None):
+  def push(self, chunks, transition_bias=None, known_speakers=None):
     """chunks: a dict {key: [n, D] float64 array} with the new frames of the streams that received some.
     transition_bias: None, a number, or a dict {key: array of the chunk's length} for the streams that have values of
-    their own (OnlineSession.push)."""
+    their own (OnlineSession.push).  known_speakers: None, or a dict {key: sequence of names (None: unknown) of the
+    chunk's length} for the streams that have some (OnlineSession.push)."""
     per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
     for key, chunk in chunks.items():
       per_slot[self._slot[key]] = chunk
@@ -1683,7 +1762,22 @@ class StreamPool:
       for key, values in transition_bias.items():
         bias_slot[self._slot[key]] = values
       transition_bias = bias_slot
-    self._session.push(per_slot, transition_bias)
+    if known_speakers is not None:
+      if not isinstance(known_speakers, dict):
+        raise ValueError('known_speakers of a pool must be a dict {key: sequence of names}.')
+      names_slot = [None] * len(per_slot)
+      for key, values in known_speakers.items():
+        names_slot[self._slot[key]] = values
+      known_speakers = names_slot
+    self._session.push(per_slot, transition_bias, known_speakers)
+
+  def speakers(self, key):
+    """{name: label} of the stream's known speakers (OnlineSession.speakers for its slot)."""
+    return self._session.speakers()[self._slot[key]]
+
+  def speaker_names(self, key):
+    """The stream's known speakers in tag order (OnlineSession.speaker_names)."""
+    return self._session.speaker_names(self._slot[key])
 
   def labels(self, key):
     """The currently best labels of everything the stream has received."""
@@ -1708,12 +1802,12 @@ class StreamPool:
     """OnlineSession.export_state for the stream's slot.  The key stays open."""
     return self._session.export_state(self._slot[key])
 
-  def adopt(self, key, blob):
+  def adopt(self, key, blob, speaker_names=None):
     """Take a free slot, like open, and continue an exported stream in it (OnlineSession.import_state).  Returns
     the slot's index; a refused blob leaves the pool as it was."""
     slot = self.open(key)
     try:
-      self._session.import_state(slot, blob)
+      self._session.import_state(slot, blob, speaker_names)
     except Exception:
       del self._slot[key]
       self._free.append(slot)
