@@ -559,50 +559,42 @@ class Decoder:
       return rc
     _raise_status(self._lib, rc, what)
 
+  def _set_table(self, what, values, convert):
+    """One per-call table of the library (uis_call_tables.h) through the setter named `what`: None clears, else the
+    array `convert` makes of `values` is handed over with its first dimension as the length."""
+    call = getattr(self._lib, what)
+    if values is None:
+      self._check(call(self._handle, None, 0), what)
+      return
+    arr = convert(values)
+    self._check(call(self._handle, arr.ctypes.data_as(call.argtypes[1]), int(arr.shape[0])), what)
+
+  @staticmethod
+  def _tags(speakers):
+    tags = np.asarray(speakers).reshape(-1)
+    if tags.size and (tags.min() < 0 or tags.max() > 255):
+      raise ValueError('speaker tags must lie in 0 .. 127')
+    return np.ascontiguousarray(tags, dtype=np.uint8)
+
   def set_limits(self, limits):
     """uis_decode_limits: the max_speakers table (ints, 0 = no bound; None clears) of the NEXT decode* /
     stream_begin call on this decoder, which consumes it."""
-    if limits is None:
-      self._check(self._lib.uis_decode_limits(self._handle, None, 0), 'uis_decode_limits')
-      return
-    lim = np.ascontiguousarray(limits, dtype=np.int32)
-    self._check(self._lib.uis_decode_limits(self._handle, _i32(lim), int(lim.shape[0])), 'uis_decode_limits')
+    self._set_table('uis_decode_limits', limits, lambda v: np.ascontiguousarray(v, dtype=np.int32))
 
   def set_frame_bias(self, bias):
     """uis_frame_bias: the per-frame transition_bias (float64, one value per frame in the call's frame order, NaN = the
     model's; None clears) of the NEXT decode* / stream_push / score_* call on this decoder, which consumes it."""
-    if bias is None:
-      self._check(self._lib.uis_frame_bias(self._handle, None, 0), 'uis_frame_bias')
-      return
-    b = np.ascontiguousarray(bias, dtype=np.float64).reshape(-1)
-    self._check(self._lib.uis_frame_bias(
-        self._handle, b.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(b.shape[0])), 'uis_frame_bias')
+    self._set_table('uis_frame_bias', bias, lambda v: np.ascontiguousarray(v, dtype=np.float64).reshape(-1))
 
   def set_frame_speakers(self, speakers):
     """uis_frame_speakers: the known speakers (uint8, one tag per frame in the call's frame order, 0 = unknown, 1 .. 127
     a speaker; None clears) of the NEXT decode* call on this decoder, which consumes it."""
-    if speakers is None:
-      self._check(self._lib.uis_frame_speakers(self._handle, None, 0), 'uis_frame_speakers')
-      return
-    tags = np.asarray(speakers).reshape(-1)
-    if tags.size and (tags.min() < 0 or tags.max() > 255):
-      raise ValueError('speaker tags must lie in 0 .. 127')
-    tags = np.ascontiguousarray(tags, dtype=np.uint8)
-    self._check(self._lib.uis_frame_speakers(
-        self._handle, tags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(tags.shape[0])), 'uis_frame_speakers')
+    self._set_table('uis_frame_speakers', speakers, self._tags)
 
   def set_stream_speakers(self, speakers):
     """uis_stream_speakers: the known speakers (uint8, one tag per frame in the call's own frame order, 0 = unknown,
     1 .. 127 a speaker; None clears) of the NEXT stream_push / stream_prime on this decoder, which consumes it."""
-    if speakers is None:
-      self._check(self._lib.uis_stream_speakers(self._handle, None, 0), 'uis_stream_speakers')
-      return
-    tags = np.asarray(speakers).reshape(-1)
-    if tags.size and (tags.min() < 0 or tags.max() > 255):
-      raise ValueError('speaker tags must lie in 0 .. 127')
-    tags = np.ascontiguousarray(tags, dtype=np.uint8)
-    self._check(self._lib.uis_stream_speakers(
-        self._handle, tags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(tags.shape[0])), 'uis_stream_speakers')
+    self._set_table('uis_stream_speakers', speakers, self._tags)
 
   def _packed(self, frames, offsets, labels=None):
     """Packed utterances, checked: float32 frames [sum N, D], int64 offsets [U + 1] and, if given, int32 labels

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(UIS_COMMIT_THREADS) void k_commit_move(DecodeState 
 
 UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int32_t* labels_out, int64_t capacity,
                                      int32_t* counts_out, int32_t* dropped_out) {
-  if (int rch = refuse_hint(h, "uis_stream_commit")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_commit", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, counts_out != nullptr, "null handle/counts_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U, B = ss.B;
@@ -203,7 +203,7 @@ UIS_EXPORT int32_t uis_stream_commit(uis_handle* h, const int32_t* horizon, int3
 }
 
 UIS_EXPORT int32_t uis_stream_committed(uis_handle* h, int64_t* committed_out) {
-  if (int rch = refuse_hint(h, "uis_stream_committed")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_committed", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, committed_out != nullptr, "null handle/committed_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   std::copy(ss.committed.begin(), ss.committed.end(), committed_out);

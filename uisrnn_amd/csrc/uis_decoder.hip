@@ -31,6 +31,7 @@
 
 #include "uis_poison.h"
 #include "uis_blob.h"
+#include "uis_call_tables.h"
 #include "uis_kernels.hip"
 #include "uis_eval.hip"
 #include "uisrnn_hip.h"
@@ -53,6 +54,9 @@ int fail(int code, const std::string& msg) {
       return fail(e_ == hipErrorOutOfMemory ? UIS_ERR_OOM : UIS_ERR_HIP,               \
                   std::string(#expr) + ": " + hipGetErrorString(e_));                  \
   } while (0)
+
+// (what uis_call_tables.h reports, as this file's calls return it)
+int table_status(const TableStatus& s) { return s.code == UIS_OK ? UIS_OK : fail(s.code, s.msg); }
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -289,24 +293,9 @@ struct uis_handle : HandleMem {
   std::vector<int64_t> io_offsets;  // offsets of the last uis_decode (its labels are still in io_labels)
   std::vector<int32_t> last_overflow;
   std::vector<float> last_beam_scores;
-  // max_speakers: the table uis_decode_limits left for the next decode / uis_stream_begin, and the one the running call
-  // took from it (take_limits, at that call's entry: consumed whether the call succeeds or not)
-  std::vector<int32_t> pending_limits, call_limits;
-  bool pending_limits_set = false, call_limits_set = false;
-  // per-frame transition_bias: {lp_stay, lp_sw, lp_new} per frame as uis_frame_bias formed them for the next call that
-  // takes frames, and the running call's (take_bias, at that call's entry: consumed whether the call succeeds or not)
-  std::vector<double> pending_bias3, call_bias3;
-  bool pending_bias_set = false, call_bias_set = false;
-  // known speakers: one tag per frame (0 unknown, 1 .. 127) as uis_frame_speakers left them for the next decode, and the
-  // running call's (take_hint, at that call's entry: consumed whether the call succeeds or not)
-  std::vector<uint8_t> pending_hint, call_hint;
-  bool pending_hint_set = false, call_hint_set = false;
-  // a session's known speakers: the table uis_stream_speakers left for the next uis_stream_push / uis_stream_prime, in
-  // that call's frame order, and the running call's (take_stream_tags, at that call's entry: consumed whether the call
-  // succeeds or not; every other uis_stream_* call leaves it pending).  call_tagged: the running call's table holds a
-  // non-zero tag
-  std::vector<uint8_t> pending_stream_tags, call_stream_tags;
-  bool pending_stream_tags_set = false, call_stream_tags_set = false, call_tagged = false;
+  // the per-call input tables (max_speakers, per-frame transition_bias, known speakers of a decode and of a session's
+  // calls): as their setters left them, and as the running call took them (uis_call_tables.h)
+  CallTables tables;
   // n-best readout (uis_nbest.hip): what the last decode that returned UIS_OK / UIS_ERR_CLUSTER_CAP left behind --
   // every group's DecodeState (views into the workspace, which only the next decode rewrites), the utterances'
   // offsets, the record format
@@ -318,6 +307,14 @@ struct uis_handle : HandleMem {
 };
 
 namespace {
+
+static_assert(UIS_TAGGED_FRAMES_END == (int64_t)1 << UIS_BLK_TAG_SHIFT, "uis_call_tables.h restates the block-count word's tag shift");
+
+// Every entry point that a table concerns opens with this: its rule over the handle's tables (uis_call_tables.h).  A
+// null handle passes: the call's own check reports it.
+int begin_call(uis_handle* h, const char* who, const TableRule& rule) {
+  return h ? table_status(h->tables.begin(who, rule)) : UIS_OK;
+}
 
 inline volatile uint32_t* pm_ctl(uis_handle::Stream& ss) { return ss.pm_block.as<volatile uint32_t>(); }
 
@@ -1397,9 +1394,7 @@ int derive_shape(DecodeCall& c) {
   h->last_overflow.clear(); h->last_beam_scores.clear();
   h->nb_valid = false;  // (... nor uis_last_decode_nbest its hypotheses)
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
-  if (h->call_limits_set && (int64_t)h->call_limits.size() != (int64_t)n_utt)
-    return fail(UIS_ERR_INVALID_ARG, "uis_decode_limits gave " + std::to_string(h->call_limits.size()) + " limits, this decode has " +
-                                         std::to_string(n_utt) + " utterances");
+  if (int rc = table_status(h->tables.check_limits("decode", n_utt))) return rc;
   h->last_pick = KernelPick{};
   const DevModel& m = h->m;
   const int B = opts->beam_size, L = opts->look_ahead, tau = opts->test_iteration;
@@ -1421,12 +1416,8 @@ int derive_shape(DecodeCall& c) {
     maxN = std::max(maxN, n);
   }
   const int64_t F = n_utt ? offsets[n_utt] : 0;
-  if (h->call_bias_set && (int64_t)h->call_bias3.size() != 3 * F)
-    return fail(UIS_ERR_INVALID_ARG, "uis_frame_bias gave " + std::to_string(h->call_bias3.size() / 3) + " values, this decode has " +
-                                         std::to_string(F) + " frames");
-  if (h->call_hint_set && (int64_t)h->call_hint.size() != F)
-    return fail(UIS_ERR_INVALID_ARG, "uis_frame_speakers gave " + std::to_string(h->call_hint.size()) + " tags, this decode has " +
-                                         std::to_string(F) + " frames");
+  if (int rc = table_status(h->tables.check_bias("decode", F))) return rc;
+  if (int rc = table_status(h->tables.check_hint("decode", F))) return rc;
   bool ragged_list = false;  // (utterances of different lengths)
   for (int u = 1; u < n_utt; ++u) ragged_list = ragged_list || offsets[u + 1] - offsets[u] != offsets[1] - offsets[0];
   if (c.stats) memset(c.stats, 0, sizeof(*c.stats));
@@ -1441,7 +1432,7 @@ int derive_shape(DecodeCall& c) {
   const int64_t maxT = (int64_t)tau * maxN;
   if (maxT > 0x7fffff00LL) return fail(UIS_ERR_UNSUPPORTED, "test_iteration * N too large");
   // (a cluster's tag shares its block-count word: the count keeps bits 0 .. 23)
-  if (h->call_hint_set && maxT >= ((int64_t)1 << 24))
+  if (h->tables.hint.call_set && maxT >= UIS_TAGGED_FRAMES_END)
     return fail(UIS_ERR_UNSUPPORTED, "a decode with known speakers (uis_frame_speakers) needs test_iteration * N below 2^24");
   HIPCHK(hipSetDevice(h->device));
 
@@ -1514,7 +1505,7 @@ int derive_shape(DecodeCall& c) {
     for (int u = 0; u < U; ++u)
       c.bp_base[u + 1] = c.bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
   c.shape = DecodeShape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, c.h_frames != nullptr,
-                        wnd, (size_t)lds.total, c.wsl.total, h->call_bias_set, h->call_hint_set};
+                        wnd, (size_t)lds.total, c.wsl.total, h->tables.bias3.call_set, h->tables.hint.call_set};
   return UIS_OK;
 }
 
@@ -1548,7 +1539,7 @@ int plan_and_place(DecodeCall& c) {
   pick.family = c.plan.decode_kernel & 0xff; pick.Hp = m.Hp; pick.Dp = m.Dp;  // (what stays without a table lookup)
   c.cluster_kern = c.plan.clustered() && !c.rs ? cluster_kernel(c.plan, m, s.L, &pick) : nullptr;
   c.rs_kern = c.rs ? find_kernel(kernels::rs, m.Hp, m.Dp, c.plan.rs_kind, &pick) : nullptr;
-  if (c.rs_kern && h->call_limits_set) c.rs_kern = find_kernel(kernels::rs_lim, m.Hp, m.Dp, c.plan.rs_kind);  // (the same entry's twin)
+  if (c.rs_kern && h->tables.limits.call_set) c.rs_kern = find_kernel(kernels::rs_lim, m.Hp, m.Dp, c.plan.rs_kind);  // (the same entry's twin)
   h->last_pick = pick;
   return UIS_OK;
 }
@@ -1596,14 +1587,14 @@ int upload_tables(DecodeCall& c) {
   HIPCHK(hipMemcpyAsync(h->off.p, c.offsets, (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
   // (max_speakers: the caller's table, if there is one; k_init_state writes DecodeState::limit from it in every decode,
   // so that nothing depends on what an earlier call left there and an unbounded decode pays no copy)
-  if (h->call_limits_set)
-    HIPCHK(hipMemcpyAsync(h->limit_in.p, h->call_limits.data(), (size_t)s.U * 4, hipMemcpyHostToDevice, h->stream));
+  if (h->tables.limits.call_set)
+    HIPCHK(hipMemcpyAsync(h->limit_in.p, h->tables.limits.data(), (size_t)s.U * 4, hipMemcpyHostToDevice, h->stream));
   // (uis_frame_bias: the whole table ahead of the first launch, also of a decode in several)
-  if (h->call_bias_set && s.F > 0)
-    HIPCHK(hipMemcpyAsync(h->bias3.p, h->call_bias3.data(), (size_t)s.F * 24, hipMemcpyHostToDevice, h->stream));
+  if (h->tables.bias3.call_set && s.F > 0)
+    HIPCHK(hipMemcpyAsync(h->bias3.p, h->tables.bias3.data(), (size_t)s.F * 24, hipMemcpyHostToDevice, h->stream));
   // (uis_frame_speakers: likewise the whole tag table)
-  if (h->call_hint_set && s.F > 0)
-    HIPCHK(hipMemcpyAsync(h->hint.p, h->call_hint.data(), (size_t)s.F, hipMemcpyHostToDevice, h->stream));
+  if (h->tables.hint.call_set && s.F > 0)
+    HIPCHK(hipMemcpyAsync(h->hint.p, h->tables.hint.data(), (size_t)s.F, hipMemcpyHostToDevice, h->stream));
   if (int rc = upload_log_tables(h->alpha, c.n_log, c.log_host, h->logblk.p, h->logden.p, h->stream)) return rc;
   if (s.wnd)
     HIPCHK(hipMemcpyAsync(h->bp_base.p, c.bp_base.data(), (size_t)(s.U + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -1843,9 +1834,9 @@ void build_group_states(DecodeCall& c) {
     st.utt_step = h->utt_step.as<int32_t>() + u0;
     st.overflow = h->overflow.as<int32_t>() + u0;
     st.limit = h->limit.as<int32_t>() + u0;
-    st.limit_in = h->call_limits_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
-    st.bias3 = h->call_bias_set ? h->bias3.as<double>() : nullptr;  // (indexed by the packed frame, like mse0)
-    st.hint = h->call_hint_set ? h->hint.as<uint8_t>() : nullptr;   // (likewise)
+    st.limit_in = h->tables.limits.call_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
+    st.bias3 = h->tables.bias3.call_set ? h->bias3.as<double>() : nullptr;  // (indexed by the packed frame, like mse0)
+    st.hint = h->tables.hint.call_set ? h->hint.as<uint8_t>() : nullptr;   // (likewise)
     st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
@@ -2246,160 +2237,42 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
   return UIS_OK;
 }
 
-// The table uis_decode_limits left becomes the running call's (every entry point that consumes it starts here).
-static void take_limits(uis_handle* h) {
-  if (!h) return;
-  h->call_limits.swap(h->pending_limits);
-  h->call_limits_set = h->pending_limits_set;
-  h->pending_limits.clear();
-  h->pending_limits_set = false;
-}
-
+// The setters of the per-call tables: validation and conversion are uis_call_tables.h's.
 UIS_EXPORT int32_t uis_decode_limits(uis_handle* h, const int32_t* limits, int32_t n_utt) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  if (!limits) { h->pending_limits.clear(); h->pending_limits_set = false; return UIS_OK; }
-  if (n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_utt");
-  for (int u = 0; u < n_utt; ++u)
-    if (limits[u] < 0 || limits[u] > 4096) return fail(UIS_ERR_INVALID_ARG, "a limit must be in [0, 4096] (0: no bound)");
-  h->pending_limits.assign(limits, limits + n_utt);
-  h->pending_limits_set = true;
-  return UIS_OK;
-}
-
-// The same for uis_frame_bias' table, at every entry point that takes frames.
-static void take_bias(uis_handle* h) {
-  if (!h) return;
-  h->call_bias3.swap(h->pending_bias3);
-  h->call_bias_set = h->pending_bias_set;
-  h->pending_bias3.clear();
-  h->pending_bias_set = false;
-}
-
-// The running call's table must cover exactly its frames.
-static int check_bias_frames(uis_handle* h, int64_t n_frames) {
-  if (h->call_bias_set && (int64_t)h->call_bias3.size() != 3 * n_frames)
-    return fail(UIS_ERR_INVALID_ARG, "uis_frame_bias gave " + std::to_string(h->call_bias3.size() / 3) + " values, this call has " +
-                                         std::to_string(n_frames) + " frames");
-  return UIS_OK;
-}
-
-// Calls that cannot honour a table refuse a pending one (and consume it).
-static int refuse_bias(uis_handle* h, const char* who) {
-  take_bias(h);
-  if (!h || !h->call_bias_set) return UIS_OK;
-  h->call_bias_set = false;
-  h->call_bias3.clear();
-  return fail(UIS_ERR_UNSUPPORTED, std::string(who) + " takes no per-frame transition_bias (uis_frame_bias): the pending table is dropped");
-}
-
-// The same for uis_frame_speakers' table, at the decode entry points.
-static void take_hint(uis_handle* h) {
-  if (!h) return;
-  h->call_hint.swap(h->pending_hint);
-  h->call_hint_set = h->pending_hint_set;
-  h->pending_hint.clear();
-  h->pending_hint_set = false;
-}
-
-// Calls that cannot honour a speaker table refuse a pending one (and consume it).
-static int refuse_hint(uis_handle* h, const char* who) {
-  take_hint(h);
-  if (!h || !h->call_hint_set) return UIS_OK;
-  h->call_hint_set = false;
-  h->call_hint.clear();
-  return fail(UIS_ERR_UNSUPPORTED, std::string(who) + " takes no known speakers (uis_frame_speakers): the pending table is dropped");
+  return table_status(h->tables.set_limits(limits, n_utt));
 }
 
 UIS_EXPORT int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  if (!tags || n_frames == 0) { h->pending_hint.clear(); h->pending_hint_set = false; return UIS_OK; }
-  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
-  for (int64_t t = 0; t < n_frames; ++t)
-    if (tags[t] > 127)
-      return fail(UIS_ERR_INVALID_ARG, "the speaker tag at frame " + std::to_string(t) + " is above 127 (0: unknown)");
-  h->pending_hint.assign(tags, tags + n_frames);
-  h->pending_hint_set = true;
-  return UIS_OK;
-}
-
-// The same for uis_stream_speakers' table, at the two entry points that take a session's frames (uis_stream_push,
-// uis_stream_prime); no other call touches it.
-static void take_stream_tags(uis_handle* h) {
-  if (!h) return;
-  h->call_stream_tags.swap(h->pending_stream_tags);
-  h->call_stream_tags_set = h->pending_stream_tags_set;
-  h->pending_stream_tags.clear();
-  h->pending_stream_tags_set = false;
-  h->call_tagged = false;
-  for (uint8_t g : h->call_stream_tags) h->call_tagged = h->call_tagged || g != 0;
-}
-
-// The running call's table must cover exactly its frames.
-static int check_stream_tags_frames(uis_handle* h, int64_t n_frames) {
-  if (h->call_stream_tags_set && (int64_t)h->call_stream_tags.size() != n_frames)
-    return fail(UIS_ERR_INVALID_ARG, "uis_stream_speakers gave " + std::to_string(h->call_stream_tags.size()) + " tags, this call has " +
-                                         std::to_string(n_frames) + " frames");
-  return UIS_OK;
-}
-
-// A cluster's tag shares its block-count word (UIS_BLK_*): once a session holds a tag, or the running call brings one,
-// no utterance may have received 2^24 frames or more.  Host arithmetic, before any device work.
-static int check_tagged_frames(const char* who, bool tagged, int utt, int64_t received) {
-  if (tagged && received >= ((int64_t)1 << UIS_BLK_TAG_SHIFT))
-    return fail(UIS_ERR_UNSUPPORTED, std::string(who) + ": utterance " + std::to_string(utt) + " of a session with known speakers would have "
-                                         "received 2^24 frames or more (a cluster's tag shares its block-count word)");
-  return UIS_OK;
+  return table_status(CallTables::set_tags(h->tables.hint, tags, n_frames));
 }
 
 UIS_EXPORT int32_t uis_stream_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames) {
-  if (int rch = refuse_hint(h, "uis_stream_speakers")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes)
+  if (int rc = begin_call(h, "uis_stream_speakers", UIS_RULE_STREAM_OTHER)) return rc;
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  if (!tags || n_frames == 0) { h->pending_stream_tags.clear(); h->pending_stream_tags_set = false; return UIS_OK; }
-  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
-  for (int64_t t = 0; t < n_frames; ++t)
-    if (tags[t] > 127)
-      return fail(UIS_ERR_INVALID_ARG, "the speaker tag at frame " + std::to_string(t) + " is above 127 (0: unknown)");
-  h->pending_stream_tags.assign(tags, tags + n_frames);
-  h->pending_stream_tags_set = true;
-  return UIS_OK;
+  return table_status(CallTables::set_tags(h->tables.stream_tags, tags, n_frames));
 }
 
 UIS_EXPORT int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
-  if (!bias || n_frames == 0) { h->pending_bias3.clear(); h->pending_bias_set = false; return UIS_OK; }
-  if (n_frames < 0) return fail(UIS_ERR_INVALID_ARG, "negative n_frames");
-  for (int64_t t = 0; t < n_frames; ++t)
-    if (!(std::isnan(bias[t]) || (bias[t] >= 0.0 && bias[t] <= 1.0)))
-      return fail(UIS_ERR_INVALID_ARG, "transition_bias at frame " + std::to_string(t) + " is outside [0, 1] (NaN: the model's)");
   const DevModel& m = h->m;
-  std::vector<double>& w = h->pending_bias3;
-  w.resize((size_t)n_frames * 3);
-  for (int64_t t = 0; t < n_frames; ++t) {
-    const double b = bias[t];
-    double* o = w.data() + 3 * t;
-    if (std::isnan(b)) { o[0] = m.lp_stay; o[1] = m.lp_sw; o[2] = m.lp_new; continue; }
-    // uis_create's expressions, with the C library's log (log(0) = -inf: a hard constraint, dropped by every select)
-    o[0] = std::log(1.0 - b);
-    o[1] = std::log(b);
-    o[2] = o[1] + m.l_alpha;
-  }
-  h->pending_bias_set = true;
-  return UIS_OK;
+  const double model3[3] = {m.lp_stay, m.lp_sw, m.lp_new};
+  return table_status(h->tables.set_bias(bias, n_frames, model3, m.l_alpha));
 }
 
 UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const int64_t* offsets, int32_t n_utt,
                                      const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out,
                                      uis_stats* stats) {
-  take_limits(h);
-  take_bias(h);
-  take_hint(h);
+  if (int rc = begin_call(h, "uis_decode_device", UIS_RULE_DECODE)) return rc;
   if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
 }
 
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                               const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
-  if (h && !h->src64) { take_limits(h); take_bias(h); take_hint(h); }  // (uis_decode_f64 has taken them)
+  if (h && !h->src64)  // (uis_decode_f64 has begun the call)
+    if (int rc = begin_call(h, "uis_decode", UIS_RULE_DECODE)) return rc;
   if (!h || !offsets || n_utt < 0) return fail(UIS_ERR_INVALID_ARG, "null handle/offsets or negative n_utt");
   h->nb_valid = false;  // (a decode refused below leaves nothing for uis_last_decode_nbest either)
   const int64_t F = n_utt ? offsets[n_utt] : 0;
@@ -2455,9 +2328,7 @@ UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t*
 
 UIS_EXPORT int32_t uis_decode_f64(uis_handle* h, const double* const* utterances, const int64_t* n_frames, int32_t n_utt,
                                   const uis_decode_opts* opts, int32_t* labels_out, float* scores_out, uis_stats* stats) {
-  take_limits(h);
-  take_bias(h);
-  take_hint(h);
+  if (int rc = begin_call(h, "uis_decode_f64", UIS_RULE_DECODE)) return rc;
   if (!h || n_utt < 0 || (n_utt > 0 && (!utterances || !n_frames)))
     return fail(UIS_ERR_INVALID_ARG, "null handle/utterances/n_frames or negative n_utt");
   h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)

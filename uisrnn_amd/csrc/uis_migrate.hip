@@ -233,7 +233,7 @@ unsigned migrate_grid(const MigrateArgs& a, int64_t window_frames, int B) {
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_export_bound(uis_handle* h, int32_t utt, int64_t* bytes_out) {
-  if (int rch = refuse_hint(h, "uis_stream_export_bound")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_export_bound", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, bytes_out != nullptr, "null handle/bytes_out")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   *bytes_out = migrate_bound(h);
@@ -241,7 +241,7 @@ UIS_EXPORT int32_t uis_stream_export_bound(uis_handle* h, int32_t utt, int64_t* 
 }
 
 UIS_EXPORT int32_t uis_stream_export(uis_handle* h, int32_t utt, void* blob, int64_t capacity, int64_t* bytes_out) {
-  if (int rch = refuse_hint(h, "uis_stream_export")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_export", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, blob && bytes_out, "null handle/blob/bytes_out")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
@@ -313,7 +313,7 @@ UIS_EXPORT int32_t uis_stream_export(uis_handle* h, int32_t utt, void* blob, int
 }
 
 UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blob, int64_t bytes) {
-  if (int rch = refuse_hint(h, "uis_stream_import")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_import", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, blob != nullptr, "null handle/blob")) return UIS_ERR_INVALID_ARG;
   if (!migrate_utt(h, utt)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
@@ -340,7 +340,7 @@ UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blo
   // session's pushes could never name them again; the 2^24 bound of a tagged session holds for what arrives, too)
   if (info.max_tag > 0 && (ss.st.flags & UIS_FLAG_PERSISTENT))
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers: the blob carries speaker tags (uis_stream_speakers)");
-  if (int rct = check_tagged_frames("uis_stream_import", ss.tagged || info.max_tag > 0, utt, sc.committed + sc.N)) return rct;
+  if (int rct = table_status(CallTables::check_tagged_frames("uis_stream_import", ss.tagged || info.max_tag > 0, utt, sc.committed + sc.N))) return rct;
   int rc;
   if ((rc = session_enter(h, nullptr))) return rc;  // (no window table: the target has received nothing)
   hipStream_t st = h->stream;

@@ -232,7 +232,7 @@ UIS_EXPORT int32_t uis_last_decode_nbest(uis_handle* h, int32_t n_best, int32_t*
 
 UIS_EXPORT int32_t uis_stream_nbest(uis_handle* h, int32_t n_best, int32_t* labels_out, int64_t capacity,
                                     float* scores_out, int32_t* counts_out, int64_t* stable_out) {
-  if (int rch = refuse_hint(h, "uis_stream_nbest")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_nbest", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   if (n_best < 1 || n_best > ss.B)

@@ -259,7 +259,7 @@ UIS_EXPORT int32_t uis_last_decode_posterior(uis_handle* h, double temperature, 
 
 UIS_EXPORT int32_t uis_stream_posterior(uis_handle* h, double temperature, float* confidence_out, float* change_out,
                                         int64_t capacity, float* weights_out, int32_t* counts_out) {
-  if (int rch = refuse_hint(h, "uis_stream_posterior")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_posterior", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(UIS_ERR_INVALID_ARG, "temperature must be finite and > 0");

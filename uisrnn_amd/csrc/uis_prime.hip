@@ -112,12 +112,7 @@ __global__ __launch_bounds__(256) void k_prime_bp(DecodeState st, PrimeArgs a) {
 
 UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const int64_t* offsets, const int32_t* labels,
                                     float* scores_out) {
-  // (the primed prefix is scored with the model's transition_bias: a pending per-frame table is refused, and dropped --
-  // and so is a pending speaker table: both are consumed, whichever is reported)
-  const int rcb = refuse_bias(h, "uis_stream_prime");
-  take_stream_tags(h);  // (uis_stream_speakers: the prefix's tags, in this call's frame order; consumed whatever happens below)
-  if (int rch = refuse_hint(h, "uis_stream_prime")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
-  if (rcb) return rcb;
+  if (int rc = begin_call(h, "uis_stream_prime", UIS_RULE_STREAM_PRIME)) return rc;  // (the prefix's tags, in this call's frame order)
   if (!session_of(h, offsets != nullptr, "null handle/offsets")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const DevModel& m = h->m;
@@ -130,10 +125,10 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   const int64_t F = offsets[U];
   if (F > 0 && (!frames || !labels)) return fail(UIS_ERR_INVALID_ARG, "frames/labels is null");
   if (F > 0x7fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "more than 2^31 - 1 frames in one call");
-  if (int rct = check_stream_tags_frames(h, F)) return rct;
-  if (h->call_stream_tags_set && (ss.st.flags & UIS_FLAG_PERSISTENT))  // (its pushes could never name the tags again)
+  if (int rct = table_status(h->tables.check_stream_tags("call", F))) return rct;
+  if (h->tables.stream_tags.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))  // (its pushes could never name the tags again)
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
-  const uint8_t* tags = h->call_stream_tags_set ? h->call_stream_tags.data() : nullptr;
+  const uint8_t* tags = h->tables.stream_tags.data();
   int too_many = -1, too_many_K = 0;
   std::vector<std::vector<uint8_t>> tag_of_label(U);
   for (int u = 0; u < U; ++u) {
@@ -143,7 +138,7 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
       return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has already received or been primed with " +
                                            std::to_string((long long)(ss.committed[u] + ss.have[u])) + " frames: a prefix goes in front of everything");
     if (P > ss.cap) return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + ": the prefix exceeds the session's max_frames");
-    if (int rct = check_tagged_frames("uis_stream_prime", ss.tagged || h->call_tagged, u, P)) return rct;
+    if (int rct = table_status(CallTables::check_tagged_frames("uis_stream_prime", ss.tagged || h->tables.tagged, u, P))) return rct;
     int K = 0;
     // (the binding hypothesis 0 would hold after these labels under these tags: tag_of_label[u][c], 0 = none; the decode's
     // rule admits the trace iff tag <-> label is a partial bijection)
@@ -202,7 +197,7 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   std::vector<int32_t> blk_words(s.chain_blk.begin(), s.chain_blk.end());
   for (const PrimeUtt& p : utts)
     for (int k = 0; k < p.K; ++k) blk_words[p.blk0 + k] |= (int32_t)tag_of_label[p.utt][k] << UIS_BLK_TAG_SHIFT;
-  ss.tagged = ss.tagged || h->call_tagged;
+  ss.tagged = ss.tagged || h->tables.tagged;
   ScratchPlan plan;
   const size_t o_chains = plan.take((size_t)nch * sizeof(PrimeChain)), o_utts = plan.take((size_t)nutt * sizeof(PrimeUtt)),
                o_blk = plan.take((size_t)nch * 4), o_lab = plan.take((size_t)F * 4);

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(UIS_RESTART_THREADS) void k_stream_restart_fill(Dec
 
 UIS_EXPORT int32_t uis_stream_restart(uis_handle* h, const int32_t* which, int32_t* labels_out, int64_t capacity,
                                       int32_t* counts_out, float* scores_out, int32_t* overflow_out) {
-  if (int rch = refuse_hint(h, "uis_stream_restart")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_restart", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, which && counts_out, "null handle/which/counts_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U;

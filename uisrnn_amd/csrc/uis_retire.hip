@@ -242,7 +242,7 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
 UIS_EXPORT int32_t uis_stream_retire(uis_handle* h, const int32_t* which, const int64_t* offsets, const int32_t* clusters,
                                      int32_t* retired_out, int32_t* counts_out, int32_t* k_out, int32_t* retirable_out,
                                      int32_t* retirable_counts_out) {
-  if (int rch = refuse_hint(h, "uis_stream_retire")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_retire", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, counts_out && k_out, "null handle/counts_out/k_out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U, B = ss.B, Kmax = ss.Kmax;

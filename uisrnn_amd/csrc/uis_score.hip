@@ -455,7 +455,7 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
   ScoreSchedule s_own;
   ScoreSchedule& s = keep ? *keep : s_own;
   // (uis_frame_bias: the scoring entry points took the table and checked its length; a priming run never has one)
-  const double* bias3 = (!keep && h->call_bias_set) ? h->call_bias3.data() : nullptr;
+  const double* bias3 = keep ? nullptr : h->tables.bias3.data();
   score_schedule(m, h->alpha, offsets, U, labels, s, bias3);
   const auto t_sched = std::chrono::steady_clock::now();
   const int64_t Fv = s.Fv;
@@ -624,22 +624,20 @@ int score_check(uis_handle* h, const float* frames, const int64_t* offsets, int3
 
 UIS_EXPORT int32_t uis_score_labels(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                     const int32_t* labels, float* scores_out, float* frame_losses_out) {
-  take_bias(h);
-  if (int rch = refuse_hint(h, "uis_score_labels")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_score_labels", UIS_RULE_SCORE)) return rc;
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
-  if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;
+  if (int rc = table_status(h->tables.check_bias("call", n_utt ? offsets[n_utt] : 0))) return rc;
   if (done) return UIS_OK;
   return score_run(h, frames, offsets, n_utt, labels, scores_out, frame_losses_out);
 }
 
 UIS_EXPORT int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
                                       const int32_t* labels, int32_t width, float* losses_out, float* scores_out) {
-  take_bias(h);
-  if (int rch = refuse_hint(h, "uis_score_speakers")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_score_speakers", UIS_RULE_SCORE)) return rc;
   bool done;
   if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
-  if (int rc = check_bias_frames(h, n_utt ? offsets[n_utt] : 0)) return rc;
+  if (int rc = table_status(h->tables.check_bias("call", n_utt ? offsets[n_utt] : 0))) return rc;
   if (width < 1) return fail(UIS_ERR_INVALID_ARG, "width must be at least 1");
   if (done) return UIS_OK;
   const int64_t F = offsets[n_utt];

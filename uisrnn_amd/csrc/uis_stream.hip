@@ -341,14 +341,11 @@ int upload_session_limits(uis_handle* h, const std::vector<int32_t>& limits, std
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
-  take_limits(h);
-  if (int rch = refuse_hint(h, "uis_stream_begin")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_begin", UIS_RULE_STREAM_BEGIN)) return rc;
   if (!h || !opts || n_utt < 1 || max_frames < 1) return fail(UIS_ERR_INVALID_ARG, "null handle/opts, n_utt < 1 or max_frames < 1");
   uis_handle::Stream& ss = h->stream_state;
   if (ss.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is already open on this handle");
-  if (h->call_limits_set && (int64_t)h->call_limits.size() != (int64_t)n_utt)
-    return fail(UIS_ERR_INVALID_ARG, "uis_decode_limits gave " + std::to_string(h->call_limits.size()) + " limits, this session has " +
-                                         std::to_string(n_utt) + " utterances");
+  if (int rc = table_status(h->tables.check_limits("session", n_utt))) return rc;
   const DevModel& m = h->m;
   const int B = opts->beam_size;
   const int Kmax = opts->max_clusters > 0 ? opts->max_clusters : 16;
@@ -470,7 +467,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   std::vector<int32_t> limit_dev;
   HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
   ss.limits.assign((size_t)U, 0);
-  if (h->call_limits_set) ss.limits = h->call_limits;
+  if (h->tables.limits.call_set) ss.limits = h->tables.limits.call;
   if ((rc = upload_log_tables(h->alpha, max_frames + 2, log_host, d_logblk, d_logden, h->stream))) return rc;
   st.off = d_off; st.logblk = d_logblk; st.logden = d_logden;
   st.avail = ss.d_avail; st.foff = ss.d_foff; st.lab_off = ss.d_lab_off;
@@ -483,9 +480,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
 }
 
 UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
-  take_bias(h);  // (uis_frame_bias: this push's table, in the chunk's own frame order; consumed whatever happens below)
-  take_stream_tags(h);  // (uis_stream_speakers: likewise)
-  if (int rch = refuse_hint(h, "uis_stream_push")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_push", UIS_RULE_STREAM_PUSH)) return rc;  // (this push's tables, in the chunk's own frame order)
   if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
   uis_handle::Stream& ss = h->stream_state;
   if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
@@ -503,17 +498,17 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     F += counts[u];
     max_new = std::max<int64_t>(max_new, counts[u]);
   }
-  if (int rcb = check_bias_frames(h, F)) return rcb;
+  if (int rcb = table_status(h->tables.check_bias("call", F))) return rcb;
   // (the resident launch of a UIS_FLAG_PERSISTENT session reads its priors from the kernel arguments it was launched with;
   // a table would have to travel through the mailbox, whose layout is a protocol of its own: DESIGN.md section 9, "Open")
-  if (h->call_bias_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+  if (h->tables.bias3.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no per-frame transition_bias (uis_frame_bias): the table is dropped");
   // (uis_stream_speakers: the same three checks for this push's tags, then the 2^24 bound of a session that holds any)
-  if (int rct = check_stream_tags_frames(h, F)) return rct;
-  if (h->call_stream_tags_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+  if (int rct = table_status(h->tables.check_stream_tags("call", F))) return rct;
+  if (h->tables.stream_tags.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
   for (int u = 0; u < U; ++u)
-    if (int rct = check_tagged_frames("uis_stream_push", ss.tagged || h->call_tagged, u, ss.committed[u] + ss.have[u] + counts[u])) return rct;
+    if (int rct = table_status(CallTables::check_tagged_frames("uis_stream_push", ss.tagged || h->tables.tagged, u, ss.committed[u] + ss.have[u] + counts[u]))) return rct;
   if (F == 0) return UIS_OK;
   if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
   HIPCHK(hipSetDevice(h->device));
@@ -590,8 +585,8 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if ((rc = ss.chunk_x.ensure(need))) return rc;
   if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
   if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
-  if (h->call_bias_set && (rc = ss.chunk_bias.ensure((size_t)F * 24))) return rc;
-  if (h->call_stream_tags_set && (rc = ss.chunk_hint.ensure((size_t)F))) return rc;
+  if (h->tables.bias3.call_set && (rc = ss.chunk_bias.ensure((size_t)F * 24))) return rc;
+  if (h->tables.stream_tags.call_set && (rc = ss.chunk_hint.ensure((size_t)F))) return rc;
   // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
   // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
   ss.poison = UisPoison::from_env();
@@ -603,13 +598,13 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     HIPCHK(ss.poison.device(ss.chunk_bias.p, ss.chunk_bias.cap, h->stream));
     HIPCHK(ss.poison.device(ss.chunk_hint.p, ss.chunk_hint.cap, h->stream));
   }
-  // (the table's rows are the chunk's: row foff[u] + step, as mse0; call_bias3 lives until the synchronize below)
-  if (h->call_bias_set)
-    HIPCHK(hipMemcpyAsync(ss.chunk_bias.p, h->call_bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
+  // (the table's rows are the chunk's: row foff[u] + step, as mse0; the call's table lives until the synchronize below)
+  if (h->tables.bias3.call_set)
+    HIPCHK(hipMemcpyAsync(ss.chunk_bias.p, h->tables.bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
   // (the tags likewise, one byte per chunk row; the session counts as tagged from here on, whatever becomes of the push)
-  if (h->call_stream_tags_set)
-    HIPCHK(hipMemcpyAsync(ss.chunk_hint.p, h->call_stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
-  ss.tagged = ss.tagged || h->call_tagged;
+  if (h->tables.stream_tags.call_set)
+    HIPCHK(hipMemcpyAsync(ss.chunk_hint.p, h->tables.stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
+  ss.tagged = ss.tagged || h->tables.tagged;
   int64_t* h_foff = ss.h_stage.as<int64_t>();
   int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + (size_t)U * 8);
   {
@@ -639,8 +634,8 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   Launcher lch{h, h->stream, false};
   DecodeState st = ss.st;
   st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
-  st.bias3 = h->call_bias_set ? ss.chunk_bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
-  st.hint = h->call_stream_tags_set ? ss.chunk_hint.as<uint8_t>() : nullptr;  // (ss.st.hint likewise: the bindings ride in beam_blk)
+  st.bias3 = h->tables.bias3.call_set ? ss.chunk_bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
+  st.hint = h->tables.stream_tags.call_set ? ss.chunk_hint.as<uint8_t>() : nullptr;  // (ss.st.hint likewise: the bindings ride in beam_blk)
   const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
   // One-launch path: the chunk's projection fused into the kernel and plain launches after the
   // session's first push make a push one H2D, one memset and ONE kernel.  Measured
@@ -698,7 +693,7 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
 }
 
 UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
-  if (int rch = refuse_hint(h, "uis_stream_labels")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_labels", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U;
@@ -752,7 +747,7 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
 }
 
 UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
-  if (int rch = refuse_hint(h, "uis_stream_end")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_end", UIS_RULE_STREAM_OTHER)) return rc;
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
   if (!h->stream_state.active) return UIS_OK;
   HIPCHK(hipSetDevice(h->device));
@@ -765,7 +760,7 @@ UIS_EXPORT int32_t uis_stream_end(uis_handle* h) {
 // max_speakers of an open session.  The table belongs to the slots, not to the streams in them: restarts, imports and
 // retirements leave it alone, blobs do not carry it.  All or nothing: a table with a value out of range changes none.
 UIS_EXPORT int32_t uis_stream_limits(uis_handle* h, const int32_t* limits) {
-  if (int rch = refuse_hint(h, "uis_stream_limits")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_limits", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, limits != nullptr, "null handle/limits")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   for (int u = 0; u < ss.U; ++u)
@@ -813,7 +808,7 @@ __global__ __launch_bounds__(UIS_BINDINGS_WIDTH) void k_stream_bindings(DecodeSt
 
 // Who is who right now: see include/uisrnn_hip.h.  The scaffold's order; nothing of the session changes.
 UIS_EXPORT int32_t uis_stream_bindings(uis_handle* h, int32_t* out) {
-  if (int rch = refuse_hint(h, "uis_stream_bindings")) return rch;  // (uis_frame_speakers' table belongs to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_bindings", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U;
@@ -838,7 +833,7 @@ UIS_EXPORT int32_t uis_stream_bindings(uis_handle* h, int32_t* out) {
 }
 
 UIS_EXPORT int32_t uis_stream_get_limits(uis_handle* h, int32_t* out) {
-  if (int rch = refuse_hint(h, "uis_stream_get_limits")) return rch;  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+  if (int rc = begin_call(h, "uis_stream_get_limits", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
   const uis_handle::Stream& ss = h->stream_state;
   for (int u = 0; u < ss.U; ++u) out[u] = ss.limits[u];

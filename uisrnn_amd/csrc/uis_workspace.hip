@@ -146,7 +146,7 @@ std::vector<WsItem> workspace_list(DecodeCall& c) {
     ENSURE(bp_base, (U + 1) * 8);
   }
   ENSURE(limit, U * 4);  // (last: every view above stays where it was measured)
-  if (h->call_limits_set) ENSURE(limit_in, U * 4);
+  if (h->tables.limits.call_set) ENSURE(limit_in, U * 4);
   if (s.biased) ENSURE(bias3, frames * 24);  // (uis_frame_bias: {lp_stay, lp_sw, lp_new} per frame; behind everything, like the limits)
   if (s.hinted) ENSURE(hint, frames);  // (uis_frame_speakers: one tag per frame; the very last view, so that none above moves)
 #undef ENSURE
