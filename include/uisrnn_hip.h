@@ -494,6 +494,39 @@ int32_t uis_frame_bias(uis_handle* h, const double* bias, int64_t n_frames);
 int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames);
 
 /*
+ * Minimum turn length: decode under "a speaker who takes the floor keeps it for at least m frames".
+ *
+ * min_turn[u] = m is utterance u's bound in decode steps; 0 and 1 mean no rule.  A hypothesis' RUN is the number of
+ * most recent decode steps of its trace that carry its last label -- the whole trace, tiled test_iteration times, so a
+ * run continues across the pass boundary.  At a step, a hypothesis that has a last label l and a run below m keeps the
+ * loss of candidate l only: every other cluster and the new cluster get +inf, which every select drops.  A hypothesis
+ * without a last label (the first step) has every candidate.  The last turn of an utterance may be shorter than m -- the
+ * utterance simply ends -- and with test_iteration >= 2 the first turn of the RETURNED labels (the last N steps of the
+ * trace) may look shorter, because its run began in the pass before.  Sub-step j of a look-ahead window uses the run of
+ * the prefix it extends.  Nothing else changes -- the priors, the ddCRP terms, the float32 accumulation, the prune order,
+ * the tie rules, max_speakers, uis_frame_bias, uis_frame_speakers -- and the rules hold together: a contradiction (two
+ * different tags on an utterance's first two frames under m = 3) leaves an empty beam, reported as ever (labels -1, score +inf).
+ * No table, or one of zeros and ones, gives today's decode bit for bit, device memory included.
+ *
+ *   uis_min_turn   min_turn: host int32 [n_utt], each in [0, 32767] (else UIS_ERR_INVALID_ARG and the pending table is
+ *                  left as it was: the run shares the hypothesis' last-label word, 15 bits); NULL clears a pending
+ *                  table.  The table belongs to the NEXT uis_decode / uis_decode_f64 / uis_decode_device on this
+ *                  handle, which consumes it whether it succeeds or not and must have exactly n_utt utterances (else
+ *                  that call returns UIS_ERR_INVALID_ARG and nothing runs).  A decode without a pending table has no
+ *                  rule, whatever an earlier call used.
+ *
+ * Refused with UIS_ERR_UNSUPPORTED, the table consumed and the handle usable: uis_score_labels, uis_score_speakers and
+ * every uis_stream_* call made while a table is pending (a session's operations read the last-label words as labels,
+ * so a session never holds a run).  The refused call has done nothing but drop the table and whatever other pending
+ * table it would have consumed.  Where several pending tables are refused by one call, the one reported is
+ * uis_frame_speakers', then this one, then uis_frame_bias', then uis_decode_limits', then uis_stream_speakers'.  A
+ * decode in which some utterance has m >= 2 runs the kernels with the owner-side selects, as one with uis_frame_bias
+ * does: where the decode without a table reports k_decode_rs or k_decode_big<WS>, uis_last_decode_instantiation
+ * reports k_decode_resident or k_decode_big.
+ */
+int32_t uis_min_turn(uis_handle* h, const int32_t* min_turn, int32_t n_utt);
+
+/*
  * Known speakers in streaming sessions.
  *
  * The rule is the one above, unchanged: a session pushed under tags, in any chunking and with silent slots, is bit for

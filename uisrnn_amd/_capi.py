@@ -361,6 +361,8 @@ def load_library(path=None):
   lib.uis_frame_bias.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64]
   lib.uis_frame_speakers.restype = i32
   lib.uis_frame_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
+  lib.uis_min_turn.restype = i32
+  lib.uis_min_turn.argtypes = [ctypes.c_void_p, i32p, i32]
   lib.uis_stream_speakers.restype = i32
   lib.uis_stream_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
   lib.uis_stream_bindings.restype = i32
@@ -432,7 +434,7 @@ EXPORTED_SYMBOLS = (
     'uis_stream_labels', 'uis_stream_end', 'uis_stream_prime', 'uis_last_decode_nbest', 'uis_stream_nbest', 'uis_last_decode_posterior', 'uis_stream_posterior', 'uis_stream_commit', 'uis_stream_committed', 'uis_stream_restart', 'uis_stream_retire',
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
-    'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_stream_speakers', 'uis_stream_bindings',
+    'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_min_turn', 'uis_stream_speakers', 'uis_stream_bindings',
     'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -591,6 +593,11 @@ class Decoder:
     a speaker; None clears) of the NEXT decode* call on this decoder, which consumes it."""
     self._set_table('uis_frame_speakers', speakers, self._tags)
 
+  def set_min_turn(self, min_turn):
+    """uis_min_turn: the minimum turn lengths (ints, one per utterance, 0 and 1 = no rule; None clears) of the NEXT
+    decode* call on this decoder, which consumes it."""
+    self._set_table('uis_min_turn', min_turn, lambda v: np.ascontiguousarray(v, dtype=np.int32).reshape(-1))
+
   def set_stream_speakers(self, speakers):
     """uis_stream_speakers: the known speakers (uint8, one tag per frame in the call's own frame order, 0 = unknown,
     1 .. 127 a speaker; None clears) of the NEXT stream_push / stream_prime on this decoder, which consumes it."""
@@ -612,21 +619,24 @@ class Decoder:
       raise ValueError('labels must be [offsets[-1]]')
     return frames, offsets, labels
 
-  def _run_decode(self, call, what, opts, frames, counts, offsets, labels, scores, limits, bias, speakers=None):
+  def _run_decode(self, call, what, opts, frames, counts, offsets, labels, scores, limits, bias, speakers=None,
+                  min_turn=None):
     """One decode call of the library -- uis_decode, uis_decode_f64 and uis_decode_device take the same arguments in
     the same places: `frames`, `labels` and `scores` as ctypes passes them on, `counts` the int64 array in third place
     (the offsets; the lengths for uis_decode_f64).  `offsets` is kept, as it is, as the layout of this decode, for
     last_nbest and last_posterior: an array the caller of the wrapper may still write to comes as a copy.  Returns
     {'stats', 'status'}."""
     stats = Stats()
-    # the tables are those of the NEXT call on the handle, which consumes them: limits, bias, speakers, the decode --
-    # nothing between
+    # the tables are those of the NEXT call on the handle, which consumes them: limits, bias, speakers, min_turn, the
+    # decode -- nothing between
     if limits is not None:
       self.set_limits(limits)
     if bias is not None:
       self.set_frame_bias(bias)
     if speakers is not None:
       self.set_frame_speakers(speakers)
+    if min_turn is not None:
+      self.set_min_turn(min_turn)
     rc = self._check(call(self._handle, frames, _i64(counts), offsets.shape[0] - 1, ctypes.byref(opts), labels, scores,
                           ctypes.byref(stats)), what)
     self._last_offsets = offsets
@@ -643,7 +653,8 @@ class Decoder:
     return out
 
   def decode(self, frames, offsets, beam_size, look_ahead, test_iteration,
-             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None, speakers=None):
+             max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None, speakers=None,
+             min_turn=None):
     """Decode packed host utterances.
 
     Args:
@@ -659,12 +670,13 @@ class Decoder:
     scores = np.empty(n_utt, dtype=np.float32)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
     out = self._run_decode(self._lib.uis_decode, 'uis_decode', opts, _ptr(frames), offsets, offsets.copy(),
-                           _i32(labels), _ptr(scores), limits, bias, speakers)
+                           _i32(labels), _ptr(scores), limits, bias, speakers, min_turn)
     out.update(labels=labels, scores=scores)
     return self._with_decode_info(out, n_utt, beam_size, want_beam_scores)
 
   def decode_f64(self, sequences, beam_size, look_ahead, test_iteration,
-                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None, speakers=None):
+                 max_clusters=0, flags=0, want_beam_scores=False, n_streams=0, level_cap=0, limits=None, bias=None, speakers=None,
+                 min_turn=None):
     """Decode a list of [N_u, D] float64 arrays as predict() receives them (uis_decode_f64:
     the library casts to float32 on its own threads while earlier chunks travel to the device).
 
@@ -682,7 +694,7 @@ class Decoder:
     scores = np.empty(n_utt, dtype=np.float32)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
     out = self._run_decode(self._lib.uis_decode_f64, 'uis_decode_f64', opts, ptrs, lens, offsets,
-                           _i32(labels), _ptr(scores), limits, bias, speakers)
+                           _i32(labels), _ptr(scores), limits, bias, speakers, min_turn)
     out.update(labels=labels, scores=scores)
     return self._with_decode_info(out, n_utt, beam_size, want_beam_scores)
 
@@ -1118,14 +1130,15 @@ class Decoder:
                            _offsets(self._stream_have), self._stream_beam)
 
   def decode_host(self, frames_ptr, offsets, beam_size, look_ahead, test_iteration,
-                  labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None, bias=None, speakers=None):
+                  labels_ptr, scores_ptr, max_clusters=0, flags=0, limits=None, bias=None, speakers=None,
+                  min_turn=None):
     """uis_decode on raw HOST pointers (e.g. pinned buffers from uis_host_alloc or torch)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, 0)
     return self._run_decode(
         self._lib.uis_decode, 'uis_decode', opts, ctypes.cast(ctypes.c_void_p(int(frames_ptr)), _fp), offsets,
         offsets.copy(), ctypes.cast(ctypes.c_void_p(int(labels_ptr)), _i32p),
-        ctypes.cast(ctypes.c_void_p(int(scores_ptr)), _fp) if scores_ptr else None, limits, bias, speakers)
+        ctypes.cast(ctypes.c_void_p(int(scores_ptr)), _fp) if scores_ptr else None, limits, bias, speakers, min_turn)
 
   # ---- evaluation on the device (uis_eval_*)
   @staticmethod
@@ -1164,14 +1177,14 @@ class Decoder:
 
   def decode_device(self, d_frames_ptr, offsets, beam_size, look_ahead,
                     test_iteration, d_labels_ptr, d_scores_ptr, max_clusters=0,
-                    flags=0, n_streams=0, limits=None, bias=None, speakers=None):
+                    flags=0, n_streams=0, limits=None, bias=None, speakers=None, min_turn=None):
     """Decode with frames/labels/scores already resident in HBM (raw pointers)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams)
     return self._run_decode(
         self._lib.uis_decode_device, 'uis_decode_device', opts, ctypes.c_void_p(int(d_frames_ptr)), offsets,
         offsets.copy(), ctypes.c_void_p(int(d_labels_ptr)),
-        ctypes.c_void_p(int(d_scores_ptr) if d_scores_ptr else None), limits, bias, speakers)
+        ctypes.c_void_p(int(d_scores_ptr) if d_scores_ptr else None), limits, bias, speakers, min_turn)
 
 
 def flatten_params(params):

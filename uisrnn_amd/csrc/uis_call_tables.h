@@ -1,16 +1,16 @@
 // uis_call_tables.h -- the per-call input tables of the C ABI: set by one call (uis_decode_limits, uis_frame_bias,
-// uis_frame_speakers, uis_stream_speakers), then taken, refused or left pending by the calls that follow.  Plain C++:
+// uis_frame_speakers, uis_stream_speakers, uis_min_turn), then taken, refused or left pending by the calls that follow.  Plain C++:
 // the tables, the rule of every kind of entry point as data, the setters' validation, the count checks and the 2^24
 // bound of a tagged session -- no HIP type; tests/call_tables_main.cpp builds it with the host compiler alone.
 //
 // Which entry point does what (tests/test_gpu_call_tables.py pins it from outside):
-//   entry points                                  limits  bias    hint    stream_tags
-//   uis_decode, uis_decode_f64, uis_decode_device take    take    take    leave
-//   uis_score_labels, uis_score_speakers          leave   take    refuse  leave
-//   uis_stream_begin                              take    leave   refuse  leave
-//   uis_stream_push                               leave   take    refuse  take
-//   uis_stream_prime                              leave   refuse  refuse  take
-//   every other uis_stream_* call                 leave   leave   refuse  leave
+//   entry points                                  limits  bias    hint    stream_tags  min_turn
+//   uis_decode, uis_decode_f64, uis_decode_device take    take    take    leave        take
+//   uis_score_labels, uis_score_speakers          leave   take    refuse  leave        refuse
+//   uis_stream_begin                              take    leave   refuse  leave        refuse
+//   uis_stream_push                               leave   take    refuse  take         refuse
+//   uis_stream_prime                              leave   refuse  refuse  take         refuse
+//   every other uis_stream_* call                 leave   leave   refuse  leave        refuse
 //   everything else                               begins no call: touches nothing
 // A new entry point picks a rule; a new table adds a column.
 #ifndef UIS_CALL_TABLES_H_
@@ -27,6 +27,8 @@
 // a cluster's tag shares its block-count word (uis_kernels.h's UIS_BLK_TAG_SHIFT, restated because this header stands
 // alone): under known speakers no count may reach 2^24
 #define UIS_TAGGED_FRAMES_END ((int64_t)1 << 24)
+// a hypothesis' run shares its last-label word (uis_kernels.h's UIS_LAST_RUN_SHIFT, likewise restated): 15 bits
+#define UIS_MIN_TURN_MAX 32767
 
 // what a function of this header reports: UIS_OK, or a status of uisrnn_hip.h and the text for uis_last_error
 struct TableStatus {
@@ -53,31 +55,34 @@ struct PendingTable {
 };
 
 enum TableUse : uint8_t { LEAVE, TAKE, REFUSE };
-struct TableRule { TableUse limits, bias, hint, stream_tags; };
-constexpr TableRule UIS_RULE_DECODE{TAKE, TAKE, TAKE, LEAVE};
-constexpr TableRule UIS_RULE_SCORE{LEAVE, TAKE, REFUSE, LEAVE};
-constexpr TableRule UIS_RULE_STREAM_BEGIN{TAKE, LEAVE, REFUSE, LEAVE};
-constexpr TableRule UIS_RULE_STREAM_PUSH{LEAVE, TAKE, REFUSE, TAKE};
-constexpr TableRule UIS_RULE_STREAM_PRIME{LEAVE, REFUSE, REFUSE, TAKE};  // (the prefix is scored with the model's transition_bias)
-constexpr TableRule UIS_RULE_STREAM_OTHER{LEAVE, LEAVE, REFUSE, LEAVE};  // (known speakers belong to the offline decodes: DESIGN.md section 26)
+struct TableRule { TableUse limits, bias, hint, stream_tags, min_turn = LEAVE; };
+constexpr TableRule UIS_RULE_DECODE{TAKE, TAKE, TAKE, LEAVE, TAKE};
+constexpr TableRule UIS_RULE_SCORE{LEAVE, TAKE, REFUSE, LEAVE, REFUSE};
+constexpr TableRule UIS_RULE_STREAM_BEGIN{TAKE, LEAVE, REFUSE, LEAVE, REFUSE};
+constexpr TableRule UIS_RULE_STREAM_PUSH{LEAVE, TAKE, REFUSE, TAKE, REFUSE};
+constexpr TableRule UIS_RULE_STREAM_PRIME{LEAVE, REFUSE, REFUSE, TAKE, REFUSE};  // (the prefix is scored with the model's transition_bias)
+// (known speakers and the minimum turn length belong to the offline decodes: DESIGN.md sections 26 and 29)
+constexpr TableRule UIS_RULE_STREAM_OTHER{LEAVE, LEAVE, REFUSE, LEAVE, REFUSE};
 
 struct CallTables {
   PendingTable<int32_t> limits;      // max_speakers, one per utterance (uis_decode_limits; 0: no bound)
   PendingTable<double> bias3;        // per-frame transition_bias as {lp_stay, lp_sw, lp_new} (uis_frame_bias)
   PendingTable<uint8_t> hint;        // known speakers of a decode, one tag per frame (uis_frame_speakers; 0: unknown)
   PendingTable<uint8_t> stream_tags; // known speakers of a push / a prime, in that call's frame order (uis_stream_speakers)
+  PendingTable<int32_t> min_turn;    // minimum turn length, one per utterance (uis_min_turn; 0 and 1: no rule)
   bool tagged = false;               // the running call's stream_tags hold a non-zero tag
 
   // ---- an entry point begins: every table its rule names is consumed first, whichever refusal is then reported (the
-  // speaker table's before the bias table's)
+  // speaker table's first, then the minimum turn length's, then the bias table's)
   TableStatus begin(const char* who, const TableRule& rule) {
     const bool no_limits = use(limits, rule.limits), no_bias = use(bias3, rule.bias), no_hint = use(hint, rule.hint),
-               no_tags = use(stream_tags, rule.stream_tags);
+               no_tags = use(stream_tags, rule.stream_tags), no_turn = use(min_turn, rule.min_turn);
     if (rule.stream_tags == TAKE) {
       tagged = false;
       for (uint8_t g : stream_tags.call) tagged = tagged || g != 0;
     }
     if (no_hint) return refusal(who, "known speakers (uis_frame_speakers)");
+    if (no_turn) return refusal(who, "minimum turn length (uis_min_turn)");
     if (no_bias) return refusal(who, "per-frame transition_bias (uis_frame_bias)");
     if (no_limits) return refusal(who, "max_speakers (uis_decode_limits)");
     if (no_tags) return refusal(who, "known speakers of a session (uis_stream_speakers)");
@@ -91,6 +96,14 @@ struct CallTables {
     for (int u = 0; u < n_utt; ++u)
       if (v[u] < 0 || v[u] > 4096) return {UIS_ERR_INVALID_ARG, "a limit must be in [0, 4096] (0: no bound)"};
     limits.set(v, (size_t)n_utt);
+    return {};
+  }
+  TableStatus set_min_turn(const int32_t* v, int32_t n_utt) {
+    if (!v) { min_turn.clear(); return {}; }
+    if (n_utt < 0) return {UIS_ERR_INVALID_ARG, "negative n_utt"};
+    for (int u = 0; u < n_utt; ++u)
+      if (v[u] < 0 || v[u] > UIS_MIN_TURN_MAX) return {UIS_ERR_INVALID_ARG, "a minimum turn length must be in [0, 32767] (0 and 1: no rule)"};
+    min_turn.set(v, (size_t)n_utt);
     return {};
   }
   // (hint and stream_tags)
@@ -128,6 +141,7 @@ struct CallTables {
   TableStatus check_limits(const char* scope, int64_t n) const { return check_count(limits, 1, "uis_decode_limits", "limits", scope, n, "utterances"); }
   TableStatus check_bias(const char* scope, int64_t n) const { return check_count(bias3, 3, "uis_frame_bias", "values", scope, n, "frames"); }
   TableStatus check_hint(const char* scope, int64_t n) const { return check_count(hint, 1, "uis_frame_speakers", "tags", scope, n, "frames"); }
+  TableStatus check_min_turn(const char* scope, int64_t n) const { return check_count(min_turn, 1, "uis_min_turn", "values", scope, n, "utterances"); }
   TableStatus check_stream_tags(const char* scope, int64_t n) const { return check_count(stream_tags, 1, "uis_stream_speakers", "tags", scope, n, "frames"); }
 
   // ---- once a session holds a tag, or the running call brings one, no utterance may have received 2^24 frames or more.

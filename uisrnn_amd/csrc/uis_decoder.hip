@@ -181,6 +181,7 @@ struct HandleMem {
   DevBuf limit, limit_in;  // [U] int32 each: DecodeState::limit, written by every decode, and uis_decode_limits' table it is written from
   DevBuf bias3;  // [frames][3] float64: DecodeState::bias3 of a decode with a uis_frame_bias table (the workspace's last view)
   DevBuf hint;   // [frames] uint8: DecodeState::hint of a decode with a uis_frame_speakers table (behind bias3: the workspace's last view)
+  DevBuf min_turn;  // [U] int32: DecodeState::min_turn of a decode whose uis_min_turn table holds a value of 2 or more (behind hint: the workspace's last view)
   DevBuf rs_block;  // UIS_NO_ARENA: the stretch k_decode_rs addresses through one descriptor (pool_mean .. mse_tab), one allocation
   DevBuf arena;  // one allocation behind all of the above: the per-step tables share pages (TLB reach)
   HostBuf h_cast;  // uis_decode_f64: the pinned float32 staging buffer the utterances are cast into, chunk by chunk, ahead of each H2D copy
@@ -839,6 +840,10 @@ struct DecodeShape {
   // replicated selects of k_decode_rs and k_decode_big<WS> keep in a layout of their own: excluded like `biased`
   // 
   bool hinted = false;
+  // the call has a minimum turn length of 2 or more for some utterance (uis_min_turn).  The runs ride in the
+  // last-label words, which those two kernels' selects likewise keep in a layout of their own: excluded like `biased`
+  // 
+  bool turned = false;
 };
 
 enum class DecodePath { STEPWISE, GRAPH, RESIDENT, RS, BIG, BIG_WS, WINDOW, DEEP, SMALL };
@@ -948,7 +953,7 @@ DecodePlan plan_decode(const DevModel& m, const DecodeShape& s, uint32_t flags, 
                    big_win_lds_bytes(m.Hp, S, (int)s.NC, Kmax, B) <= 157 * 1024;
 
   if (resident) {
-    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0 || s.biased || s.hinted;
+    const bool owner = (flags & UIS_FLAG_OWNER_SELECT) != 0 || s.biased || s.hinted || s.turned;
     const int per_xcd = (U + p.ncl - 1) / p.ncl;
     // (k_decode_rs keeps frame numbers in 32 bits and reads the frame stream through 4 GB descriptors with 32-bit byte
     // offsets: a row of gi0 is 3 Hp floats, a row of x Dp)
@@ -1382,6 +1387,14 @@ int cluster_cap_status(int n_over, int Kmax) {
                                        std::to_string(Kmax) + " clusters per hypothesis");
 }
 
+// Whether the running call's uis_min_turn table sets a rule for any utterance (0 and 1 set none: such a decode is
+// planned, laid out and run as one without a table).
+static bool turn_rule(const uis_handle* h) {
+  bool any = false;
+  for (int32_t v : h->tables.min_turn.call) any = any || v >= 2;
+  return h->tables.min_turn.call_set && any;
+}
+
 // Step 1: the arguments checked, the DecodeShape and the utterance groups.  shape.U == 0 with UIS_OK: an empty list,
 // nothing left to do.
 int derive_shape(DecodeCall& c) {
@@ -1395,6 +1408,7 @@ int derive_shape(DecodeCall& c) {
   h->nb_valid = false;  // (... nor uis_last_decode_nbest its hypotheses)
   if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
   if (int rc = table_status(h->tables.check_limits("decode", n_utt))) return rc;
+  if (int rc = table_status(h->tables.check_min_turn("decode", n_utt))) return rc;
   h->last_pick = KernelPick{};
   const DevModel& m = h->m;
   const int B = opts->beam_size, L = opts->look_ahead, tau = opts->test_iteration;
@@ -1505,7 +1519,7 @@ int derive_shape(DecodeCall& c) {
     for (int u = 0; u < U; ++u)
       c.bp_base[u + 1] = c.bp_base[u] + (((int64_t)tau * (offsets[u + 1] - offsets[u]) + L - 1) / L) * B;
   c.shape = DecodeShape{U, G, B, Kmax, L, S, F, maxN, maxT, NC, ragged_list, h->src64 != nullptr, c.h_frames != nullptr,
-                        wnd, (size_t)lds.total, c.wsl.total, h->tables.bias3.call_set, h->tables.hint.call_set};
+                        wnd, (size_t)lds.total, c.wsl.total, h->tables.bias3.call_set, h->tables.hint.call_set, turn_rule(h)};
   return UIS_OK;
 }
 
@@ -1592,6 +1606,9 @@ int upload_tables(DecodeCall& c) {
   // (uis_frame_bias: the whole table ahead of the first launch, also of a decode in several)
   if (h->tables.bias3.call_set && s.F > 0)
     HIPCHK(hipMemcpyAsync(h->bias3.p, h->tables.bias3.data(), (size_t)s.F * 24, hipMemcpyHostToDevice, h->stream));
+  // (uis_min_turn: one value per utterance, where any of them sets a rule)
+  if (s.turned)
+    HIPCHK(hipMemcpyAsync(h->min_turn.p, h->tables.min_turn.data(), (size_t)s.U * 4, hipMemcpyHostToDevice, h->stream));
   // (uis_frame_speakers: likewise the whole tag table)
   if (h->tables.hint.call_set && s.F > 0)
     HIPCHK(hipMemcpyAsync(h->hint.p, h->tables.hint.data(), (size_t)s.F, hipMemcpyHostToDevice, h->stream));
@@ -1837,6 +1854,7 @@ void build_group_states(DecodeCall& c) {
     st.limit_in = h->tables.limits.call_set ? h->limit_in.as<int32_t>() + u0 : nullptr;
     st.bias3 = h->tables.bias3.call_set ? h->bias3.as<double>() : nullptr;  // (indexed by the packed frame, like mse0)
     st.hint = h->tables.hint.call_set ? h->hint.as<uint8_t>() : nullptr;   // (likewise)
+    st.min_turn = c.shape.turned ? h->min_turn.as<int32_t>() + u0 : nullptr;
     st.x = c.d_x; st.gi0 = h->gi0.as<float>(); st.mse0 = h->mse0.as<float>();
     st.logblk = h->logblk.as<double>(); st.logden = h->logden.as<double>();
     st.pool_mean = h->pool_mean.as<float>() + u0 * S * m.Dp;
@@ -2241,6 +2259,11 @@ UIS_EXPORT int32_t uis_create(const uis_model_desc* d, int32_t device, uis_handl
 UIS_EXPORT int32_t uis_decode_limits(uis_handle* h, const int32_t* limits, int32_t n_utt) {
   if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
   return table_status(h->tables.set_limits(limits, n_utt));
+}
+
+UIS_EXPORT int32_t uis_min_turn(uis_handle* h, const int32_t* min_turn, int32_t n_utt) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  return table_status(h->tables.set_min_turn(min_turn, n_utt));
 }
 
 UIS_EXPORT int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames) {

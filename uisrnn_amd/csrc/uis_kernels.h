@@ -233,6 +233,11 @@ struct DecodeState {
   // speaker.  A hypothesis' binding of tags to clusters rides in its block-count words (UIS_BLK_* below), so whatever
   // moves a hypothesis' tables moves its binding.  Null: the call has no table.
   const uint8_t* hint;       // [frames] or null
+
+  // ---- minimum turn length (uis_min_turn): one value per utterance; 0 and 1 = no rule.  A hypothesis' run -- how
+  // many of its most recent steps carry its last label, saturating at the utterance's value -- rides in its last-label
+  // word (UIS_LAST_* below), so whatever moves a hypothesis' tables moves its run.  Null: the call has no table.
+  const int32_t* min_turn;   // [U] or null
 };
 
 // A block-count word (beam_blk / lv_blk and their LDS copies): the count in bits 0 .. 23 (it never exceeds tau * N,
@@ -242,6 +247,31 @@ struct DecodeState {
 #define UIS_BLK_COUNT_MASK 0x00ffffff
 __device__ __forceinline__ int blk_count(int w) { return w & UIS_BLK_COUNT_MASK; }
 __device__ __forceinline__ int blk_tag(int w) { return w >> UIS_BLK_TAG_SHIFT; }
+
+// A last-label word (beam_last / lv_last and their LDS copies): the label in bits 0 .. 15 as a signed 16-bit number (-1:
+// no label yet; max_clusters <= 4096), the hypothesis' run in bits 16 .. 30.  Only a decode whose utterance has a
+// minimum turn length of 2 or more writes run bits; everywhere else the word is the label, and -1 stays -1.
+#define UIS_LAST_RUN_SHIFT 16
+#define UIS_LAST_RUN_MASK 0x7fff
+__device__ __forceinline__ int last_label(int w) { return (int)(int16_t)w; }
+__device__ __forceinline__ int last_run(int w) { return (w >> UIS_LAST_RUN_SHIFT) & UIS_LAST_RUN_MASK; }
+
+// The minimum turn length of utterance u (uniform over the workgroup: one null test, then one load); below 2: no rule.
+__device__ __forceinline__ int utt_min_turn(const DecodeState& st, int u) {
+  return st.min_turn ? st.min_turn[u] : 0;
+}
+// Under a minimum turn length mt >= 2, a hypothesis whose last-label word is w may take candidate c only if it has no
+// label yet, its run has reached mt, or c continues the run.
+__device__ __forceinline__ bool turn_allows(int w, int c, int mt) {
+  return w < 0 || last_run(w) >= mt || c == last_label(w);
+}
+// The child's last-label word: c continues the parent's run (saturating at mt) or begins one; without a rule, c.
+__device__ __forceinline__ int turn_word(int w, int c, int mt) {
+  if (mt < 2) return c;
+  const int grown = last_run(w) + 1;
+  const int run = (w >= 0 && c == last_label(w)) ? (grown < mt ? grown : mt) : 1;
+  return c | (run << UIS_LAST_RUN_SHIFT);
+}
 
 // The three prior words of the step that decides `frame` (uniform over the workgroup: one null test, then scalar loads).
 struct StepPriors { double lp_stay, lp_sw, lp_new; };

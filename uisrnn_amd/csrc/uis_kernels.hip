@@ -1008,13 +1008,14 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
   const float mse_new = st.mse0[frame];
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's)
   const int g = step_tag(st, frame);  // (uis_frame_speakers: this frame's known speaker, 0 = unknown or no table)
+  const int mt = utt_min_turn(st, u);  // (uis_min_turn: this utterance's minimum turn length, below 2 = no rule)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
     while (tid >= sbase[my_b + 1]) ++my_b;
     my_c = tid - sbase[my_b];
     my_ld = st.logden[ssum[my_b]];
-    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
+    if (my_c < sK[my_b] && my_c != last_label(slast[my_b])) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
   }
 
   // ---- A: weighted MSE of the frame against every live cluster state.
@@ -1062,12 +1063,12 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
       while (i >= sbase[b + 1]) ++b;
       c = i - sbase[b];
       ld = st.logden[ssum[b]];
-      lb = (c < sK[b] && c != slast[b]) ? st.logblk[blk_count(sblk[b * Kmax + c])] : 0.0;
+      lb = (c < sK[b] && c != last_label(slast[b])) ? st.logblk[blk_count(sblk[b * Kmax + c])] : 0.0;
     }
     float mse; double prior;
     if (c < sK[b]) {  // existing cluster, uisrnn.py:409-420
       mse = smse[sslot[b * Kmax + c]];
-      prior = (c == slast[b]) ? pr.lp_stay : (pr.lp_sw + lb) - ld;
+      prior = (c == last_label(slast[b])) ? pr.lp_stay : (pr.lp_sw + lb) - ld;
     } else {          // new cluster, uisrnn.py:440-446
       mse = mse_new;
       prior = pr.lp_new - ld;
@@ -1075,6 +1076,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     float sc = sscore[b] + uis_step_loss(mse, prior);  // float32 accumulate, uisrnn.py:452
     if (c >= sK[b] && c >= lim) sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
     if (g && !tag_allows(sblk + b * Kmax, sK[b], c, g)) sc = INFINITY;  // known speakers: g's cluster, or one without a tag
+    if (mt >= 2 && !turn_allows(slast[b], c, mt)) sc = INFINITY;  // minimum turn length: a run below mt goes on
     scscore[i] = sc;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + b) * (Kmax + 1) + c] = sc;
     const bool fin = uis_isfinite(sc);
@@ -1158,7 +1160,7 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     if (c2 < Knew && c2 < Kmax) {
       int slot, blk;
       if (c2 == c) {  // (a tagged frame binds its tag to the cluster that takes it; a bound cluster keeps its tag)
-        slot = sdst[r]; blk = (is_new ? 1 : sblk[b * Kmax + c] + (c != slast[b] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
+        slot = sdst[r]; blk = (is_new ? 1 : sblk[b * Kmax + c] + (c != last_label(slast[b]) ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
       } else { slot = sslot[b * Kmax + c2]; blk = sblk[b * Kmax + c2]; }
       st.beam_slot[(bnxt + r) * Kmax + c2] = slot;
       st.beam_blk[(bnxt + r) * Kmax + c2] = blk;
@@ -1175,8 +1177,8 @@ __global__ __launch_bounds__(256) void k_select(DevModel m, DecodeState st, int 
     int Knew = Kb + (is_new ? 1 : 0);
     if (Knew > Kmax) { Knew = Kmax; st.overflow[u] = 1; }  // cluster cap hit: utterance flagged
     st.beam_K[bnxt + r] = Knew;
-    st.beam_last[bnxt + r] = c;
-    st.beam_sum[bnxt + r] = ssum[b] + ((is_new || c != slast[b]) ? 1 : 0);
+    st.beam_last[bnxt + r] = turn_word(slast[b], c, mt);
+    st.beam_sum[bnxt + r] = ssum[b] + ((is_new || c != last_label(slast[b])) ? 1 : 0);
     st.beam_score[bnxt + r] = scscore[i];
     st.bp[((size_t)st.tau * st.off[u] + step) * B + r] = ((unsigned)b << 16) | (unsigned)c;
     atomicMax(&st.counters[3], (unsigned long long)Knew);
@@ -1447,6 +1449,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   const int lim = st.limit[u];  // (written between launches only)
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: this frame's words, or the model's; uploaded before the launch)
   const int g = step_tag(st, frame);  // (uis_frame_speakers: this frame's known speaker, 0 = unknown or no table; likewise)
+  const int mt = utt_min_turn(st, u);  // (uis_min_turn: this utterance's minimum turn length, below 2 = no rule; likewise)
   int my_b = 0, my_c = 0;
   double my_lb = 0.0, my_ld = 0.0;
   if (tid < C) {
@@ -1454,7 +1457,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     my_b = (int)(bc >> 16);
     my_c = (int)(bc & 0xffffu);
     my_ld = st.logden[ssum[my_b]];
-    if (my_c < sK[my_b] && my_c != slast[my_b]) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
+    if (my_c < sK[my_b] && my_c != last_label(slast[my_b])) my_lb = st.logblk[blk_count(sblk[my_b * Kmax + my_c])];
   }
   const int Dp = DPT ? DPT : m.Dp;
   const float* pmean = st.pool_mean + (size_t)u * S * Dp;
@@ -1540,7 +1543,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     float mse; double prior;
     if (my_c < sK[my_b]) {
       mse = smse[sslot[my_b * Kmax + my_c]];
-      prior = (my_c == slast[my_b]) ? pr.lp_stay : (pr.lp_sw + my_lb) - my_ld;
+      prior = (my_c == last_label(slast[my_b])) ? pr.lp_stay : (pr.lp_sw + my_lb) - my_ld;
     } else {
       mse = mse_new;
       prior = pr.lp_new - my_ld;
@@ -1549,6 +1552,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     if (my_c >= sK[my_b] && my_c >= lim) my_sc = INFINITY;  // max_speakers: a hypothesis at its bound opens no cluster
     // known speakers (tagged frames only): g's cluster, or one without a tag -- read off the hypothesis' own row of sblk
     if (g && !tag_allows(sblk + my_b * Kmax, sK[my_b], my_c, g)) my_sc = INFINITY;
+    if (mt >= 2 && !turn_allows(slast[my_b], my_c, mt)) my_sc = INFINITY;  // minimum turn length: a run below mt goes on
     if (uis_isfinite(my_sc)) my_key = ((unsigned long long)uis_score_key(my_sc) << 32) | (unsigned)tid;
     if (st.dbg_scores) st.dbg_scores[(((size_t)step * U + u) * B + my_b) * (Kmax + 1) + my_c] = my_sc;
   }
@@ -1686,7 +1690,7 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
   if (isw && wc < Kmax) {
     const bool is_new = wc == Kb;
     // (a tagged frame binds its tag to the cluster that takes it; a bound cluster keeps its tag)
-    const int blk_new = (is_new ? 1 : sblk[wb * Kmax + wc] + (wc != slast[wb] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
+    const int blk_new = (is_new ? 1 : sblk[wb * Kmax + wc] + (wc != last_label(slast[wb]) ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT);
     if (KEEP) {
       nslot[r * Kmax + wc] = dst;
       nblk[r * Kmax + wc] = blk_new;
@@ -1701,12 +1705,13 @@ __device__ __forceinline__ void select_fast_body(const DevModel& m, const Decode
     int Knew = Kb + (is_new ? 1 : 0);
     if (Knew > Kmax) { Knew = Kmax; st.overflow[u] = 1; }
     Kmaxseen = Knew;
-    const int sum_new = ssum[wb] + ((is_new || wc != slast[wb]) ? 1 : 0);
+    const int sum_new = ssum[wb] + ((is_new || wc != last_label(slast[wb])) ? 1 : 0);
+    const int last_new = turn_word(slast[wb], wc, mt);  // (the child's label, and under a minimum turn length its run)
     if (KEEP) {
-      nK[r] = Knew; nlast[r] = wc; nsum[r] = sum_new; nscore[r] = swscore[r];
+      nK[r] = Knew; nlast[r] = last_new; nsum[r] = sum_new; nscore[r] = swscore[r];
     } else {
       st.beam_K[bnxt + r] = Knew;
-      st.beam_last[bnxt + r] = wc;
+      st.beam_last[bnxt + r] = last_new;
       st.beam_sum[bnxt + r] = sum_new;
     }
     st.beam_score[bnxt + r] = swscore[r];  // (the final beam's scores are read back by k_backtrace)
@@ -3283,6 +3288,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
   const int lim = st.limit[u];
   const StepPriors pr = step_priors(m, st, frame);  // (uis_frame_bias: the sub-step's own frame)
   const int g = step_tag(st, frame);  // (uis_frame_speakers: the sub-step's own frame; the binding is the extended prefix's)
+  const int mt = utt_min_turn(st, u);  // (uis_min_turn: below 2 = no rule; the run is the extended prefix's)
   auto node_of = [&](int i) {  // largest node with cbase[node] <= i
     int lo = 0, hi = n_in;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cbase[mid] <= i) lo = mid; else hi = mid; }
@@ -3291,7 +3297,8 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
   // a thread per input hypothesis (its table row fetched once), its K_b + 1 candidates in turn --
   // not a thread per candidate, each finding its hypothesis by bisection and re-reading the row
   for (int b = tid; b < n_in; b += NT) {
-    const int Kb = in.K[b], lastb = in.last[b], i0 = cbase[b];
+    const int Kb = in.K[b], lastw = in.last[b], lastb = last_label(lastw), i0 = cbase[b];
+    const bool held = mt >= 2 && lastw >= 0 && last_run(lastw) < mt;  // minimum turn length: only lastb is a candidate
     const float base_score = in.score[b];
     const double ld = st.logden[in.sum[b]];
     const int origin = (st.dbg_scores && last) ? (in.origin ? in.origin[b] : b) : 0;
@@ -3335,12 +3342,13 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
       for (int e = 0; e < 4; ++e) {
         const int c = c0 + e;
         // (known speakers: at a tagged sub-step only g's cluster, or one without a tag, is a candidate)
-        const bool ok = !g || (bound >= 0 ? c == bound : blk_tag(bk[e]) == 0);
+        const bool ok = (!g || (bound >= 0 ? c == bound : blk_tag(bk[e]) == 0)) && (!held || c == lastb);
         if (c < Kb) emit(c, mse[sl[e]], !ok ? -(double)INFINITY : (c == lastb) ? pr.lp_stay : (pr.lp_sw + lb[e]) - ld);
       }
     }
-    // max_speakers: at its bound, a loss of +inf = no candidate; known speakers: neither where g has a cluster already
-    emit(Kb, mse_new, (Kb < lim && bound < 0) ? pr.lp_new - ld : -(double)INFINITY);
+    // max_speakers: at its bound, a loss of +inf = no candidate; known speakers: neither where g has a cluster already;
+    // minimum turn length: nor while the run is below mt
+    emit(Kb, mse_new, (Kb < lim && bound < 0 && !held) ? pr.lp_new - ld : -(double)INFINITY);
   }
   __syncthreads();
   WSTAMP(2);
@@ -3520,7 +3528,7 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
     const int Knew = Kb + (is_new ? 1 : 0);
     if (c2 < Knew) {
       int slot, blk;
-      if (c2 == c) { slot = dstv[r]; blk = (is_new ? 1 : in.blk[(size_t)b * Kmax + c] + (c != in.last[b] ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT); }
+      if (c2 == c) { slot = dstv[r]; blk = (is_new ? 1 : in.blk[(size_t)b * Kmax + c] + (c != last_label(in.last[b]) ? 1 : 0)) | (g << UIS_BLK_TAG_SHIFT); }
       else { slot = in.slot[(size_t)b * Kmax + c2]; blk = in.blk[(size_t)b * Kmax + c2]; }
       out.slot[(size_t)r * Kmax + c2] = slot;
       out.blk[(size_t)r * Kmax + c2] = blk;
@@ -3537,8 +3545,8 @@ __device__ __forceinline__ void window_body(const DevModel& m, const DecodeState
     int Knew = Kb + (is_new ? 1 : 0);
     if (Knew > Kmax) { Knew = Kmax; atomicOr(&st.overflow[u], 1); }
     out.K[r] = Knew;
-    out.last[r] = c;
-    out.sum[r] = in.sum[b] + ((is_new || c != in.last[b]) ? 1 : 0);
+    out.last[r] = turn_word(in.last[b], c, mt);
+    out.sum[r] = in.sum[b] + ((is_new || c != last_label(in.last[b])) ? 1 : 0);
     out.score[r] = cscore[i];
     const int origin = in.origin ? in.origin[b] : b;
     if (!last) {

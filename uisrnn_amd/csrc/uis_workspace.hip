@@ -148,7 +148,8 @@ std::vector<WsItem> workspace_list(DecodeCall& c) {
   ENSURE(limit, U * 4);  // (last: every view above stays where it was measured)
   if (h->tables.limits.call_set) ENSURE(limit_in, U * 4);
   if (s.biased) ENSURE(bias3, frames * 24);  // (uis_frame_bias: {lp_stay, lp_sw, lp_new} per frame; behind everything, like the limits)
-  if (s.hinted) ENSURE(hint, frames);  // (uis_frame_speakers: one tag per frame; the very last view, so that none above moves)
+  if (s.hinted) ENSURE(hint, frames);  // (uis_frame_speakers: one tag per frame; behind everything above, so that none of it moves)
+  if (s.turned) ENSURE(min_turn, U * 4);  // (uis_min_turn: one value per utterance; the very last view, likewise)
 #undef ENSURE
   return want;
 }

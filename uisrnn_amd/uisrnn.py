@@ -71,6 +71,37 @@ def _check_max_speakers(max_speakers, args, n_utt):
   return values if any(values) else None
 
 
+_MAX_MIN_TURN = 32767  # (a hypothesis' run is fifteen bits of its last-label word: include/uisrnn_hip.h)
+
+
+def _check_min_turn(min_turn, n_utt):
+  """The min_turn keyword as the library's table: None (no utterance has a rule) or a list of n_utt ints, 0 and 1 = no
+  rule.  min_turn: None, an integer for every utterance, or a sequence with one integer per utterance.  Raises before
+  any device work: ValueError for a bool, a negative value, a value above 32767 or a sequence of the wrong length,
+  TypeError for a value that is no integer."""
+  if min_turn is None:
+    return None
+
+  def one(value):
+    if isinstance(value, (bool, np.bool_)):
+      raise ValueError('min_turn must be an integer in [0, {}], not a bool.'.format(_MAX_MIN_TURN))
+    if not isinstance(value, (int, np.integer)):
+      raise TypeError('min_turn must be an integer (a number of frames), not {!r}.'.format(value))
+    if not 0 <= int(value) <= _MAX_MIN_TURN:
+      raise ValueError('min_turn must be in [0, {}], not {!r}.'.format(_MAX_MIN_TURN, value))
+    return int(value)
+
+  if isinstance(min_turn, np.ndarray) and min_turn.ndim == 0:
+    min_turn = min_turn.item()   # (a 0-d array is a scalar)
+  if isinstance(min_turn, (list, tuple, np.ndarray)):
+    values = [one(v) for v in (min_turn.tolist() if isinstance(min_turn, np.ndarray) else min_turn)]
+    if len(values) != int(n_utt):
+      raise ValueError('min_turn has {} entries for {} utterances.'.format(len(values), n_utt))
+  else:
+    values = [one(min_turn)] * int(n_utt)
+  return values if any(v >= 2 for v in values) else None
+
+
 _MAX_KNOWN_SPEAKERS = 127   # (a cluster's tag is seven bits of its block-count word: include/uisrnn_hip.h)
 
 
@@ -502,13 +533,14 @@ class UISRNN:
                        'by args.observation_dim.')
 
   def _offline_arguments(self, test_sequences, args, max_speakers, transition_bias, known_speakers=None,
-                         sequences_first=False):
-    """The offline entry points' arguments, checked: (single, sequences, limits, bias, speakers) -- single: one array
-    was given, and the caller hands out result 0; limits, bias and speakers as _decode_batch takes them.
+                         sequences_first=False, min_turn=None):
+    """The offline entry points' arguments, checked: (single, sequences, tables) -- single: one array was given, and the
+    caller hands out result 0; tables: _decode_batch's keywords limits, bias, speakers and min_turn.
 
     The first bad argument is the one reported, and the order is part of the interface: an array's sequence comes
     before its bound (the reference's checks first), a list's bound before its sequences -- except with
-    sequences_first, parallel_predict's order.  transition_bias and then known_speakers need the lengths and come last."""
+    sequences_first, parallel_predict's order.  transition_bias and then known_speakers need the lengths and come after
+    them; min_turn is last."""
     single = isinstance(test_sequences, np.ndarray)
     if not single and not isinstance(test_sequences, list):
       raise TypeError('test_sequences should be either a list or numpy array.')
@@ -521,20 +553,21 @@ class UISRNN:
       limits = _check_max_speakers(max_speakers, args, len(seqs))
     bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single)
     speakers = _check_known_speakers(known_speakers, [s.shape[0] for s in seqs], single=single)
-    return single, seqs, limits, bias, speakers
+    turns = _check_min_turn(min_turn, len(seqs))
+    return single, seqs, {'limits': limits, 'bias': bias, 'speakers': speakers, 'min_turn': turns}
 
-  def _predict(self, test_sequences, args, max_speakers, transition_bias, known_speakers=None, **readout):
+  def _predict(self, test_sequences, args, max_speakers, transition_bias, known_speakers=None, min_turn=None, **readout):
     """predict / predict_nbest / predict_posteriors: the checked arguments through _decode_batch, whose `readout`
     keyword (n_best or posterior) selects what an utterance's result is."""
-    single, seqs, limits, bias, speakers = self._offline_arguments(
-        test_sequences, args, max_speakers, transition_bias, known_speakers)
+    single, seqs, tables = self._offline_arguments(
+        test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn=min_turn)
     if not seqs:
       return []
-    results = self._decode_batch(seqs, args, limits=limits, bias=bias, speakers=speakers, **readout)
+    results = self._decode_batch(seqs, args, **tables, **readout)
     return results[0] if single else results
 
   def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
-                    limits=None, bias=None, speakers=None):
+                    limits=None, bias=None, speakers=None, min_turn=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -548,12 +581,13 @@ class UISRNN:
     bias (_check_transition_bias): None, or one float64 array per sequence: the per-frame transition_bias table, which
     follows the same regroupings.
     speakers (_check_known_speakers): None, or one uint8 array per sequence: the known speakers' tags, likewise.
+    min_turn (_check_min_turn): None, or one int per sequence (0 and 1 = no rule): the minimum turn lengths, likewise.
     """
     decoder = decoder or self._get_decoder(device)
 
     def take(members):
-      """What one decode call is handed for these sequences: the arrays, and their entries of limits, bias and speakers
-      as decode_f64's keywords (a table that is None is no keyword at all)."""
+      """What one decode call is handed for these sequences: the arrays, and their entries of limits, bias, speakers
+      and min_turn as decode_f64's keywords (a table that is None is no keyword at all)."""
       tables = {}
       if limits is not None:
         tables['limits'] = [limits[u] for u in members]
@@ -561,6 +595,8 @@ class UISRNN:
         tables['bias'] = np.concatenate([bias[u] for u in members])
       if speakers is not None:
         tables['speakers'] = np.concatenate([speakers[u] for u in members])
+      if min_turn is not None:
+        tables['min_turn'] = [min_turn[u] for u in members]
       return [sequences[u] for u in members], tables
 
     def decode(members, level_cap):
@@ -756,13 +792,14 @@ class UISRNN:
                          for ids, p in zip(test_cluster_ids, predicted)]
     return predicted, [float(m) / int(n) for m, n in zip(matched, lens)]
 
-  def predict_single(self, test_sequence, args, max_speakers=None, transition_bias=None, known_speakers=None):
+  def predict_single(self, test_sequence, args, max_speakers=None, transition_bias=None, known_speakers=None,
+                     min_turn=None):
     """Predict labels for one test sequence (uisrnn/uisrnn.py:479-562).
 
     Args:
       test_sequence: 2-dim float64 numpy array [N, D].
       args: inference namespace (beam_size, look_ahead, test_iteration).
-      max_speakers, transition_bias, known_speakers: see predict (extensions).
+      max_speakers, transition_bias, known_speakers, min_turn: see predict (extensions).
 
     Returns:
       list of N ints: the predicted cluster id per frame.
@@ -772,7 +809,7 @@ class UISRNN:
       ValueError: wrong rank or observation dimension.
     """
     self._check_sequence(test_sequence)   # (a list too is refused here, in the reference's words)
-    return self._predict(test_sequence, args, max_speakers, transition_bias, known_speakers)
+    return self._predict(test_sequence, args, max_speakers, transition_bias, known_speakers, min_turn)
 
   def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
              max_speakers=None):
@@ -794,7 +831,7 @@ class UISRNN:
     whose streams begin and end independently of each other."""
     return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers))
 
-  def predict(self, test_sequences, args, max_speakers=None, transition_bias=None, known_speakers=None):
+  def predict(self, test_sequences, args, max_speakers=None, transition_bias=None, known_speakers=None, min_turn=None):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
 
     A list is decoded as ONE lock-step batch on the GPU (the reference loops
@@ -822,6 +859,14 @@ class UISRNN:
     speaker).  ValueError, before any device work, for a wrong count or length, more than 127 names, a float NaN as a
     name, or a bool in the place of a sequence; TypeError for an unhashable name.
 
+    min_turn (extension): how short a turn can be -- None, an int for every sequence, or one int
+    per sequence; 0 and 1 mean no rule.  A hypothesis whose last speaker has held the floor for fewer than min_turn
+    frames can only continue that speaker, so every completed turn of the decode has at least min_turn frames.  The
+    last turn may be shorter (the sequence ends), and with args.test_iteration >= 2 so may the first turn of the labels
+    returned, whose run began in the pass before.  A rule that contradicts known_speakers (two names on the first
+    two frames under min_turn 3) empties the beam: EmptyBeamError.  ValueError, before any device work, for a wrong count,
+    a negative value, a value above 32767 or a bool; TypeError for a value that is no integer.
+
     Raises:
       TypeError: test_sequences is neither a list nor a numpy array.
       EmptyBeamError: non-finite scores emptied an utterance's beam (the reference raises
@@ -830,16 +875,16 @@ class UISRNN:
         prefixes inside a window than the device tables hold (a limit the reference does not
         have); the exception names them and carries the other utterances' results.
     """
-    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers)
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn)
 
   def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None,
-                    known_speakers=None):
+                    known_speakers=None, min_turn=None):
     """predict, returning every hypothesis of the final beam instead of the best one (extension).
 
     Args:
       test_sequences, args: as predict.
       n_best: the most hypotheses wanted per sequence, in [1, args.beam_size] (default: beam_size).
-      max_speakers, transition_bias, known_speakers: as predict.
+      max_speakers, transition_bias, known_speakers, min_turn: as predict.
     Returns:
       for an array the pair (labelings, scores): at most n_best label lists -- fewer when the final
       beam holds fewer -- best first, and their scores as floats, ascending; labelings[0] is predict's
@@ -854,10 +899,10 @@ class UISRNN:
       raise ValueError('n_best must be an integer in [1, args.beam_size].')
     if not 1 <= int(n_best) <= int(args.beam_size):
       raise ValueError('n_best must be in [1, args.beam_size = {}].'.format(args.beam_size))
-    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, n_best=int(n_best))
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn, n_best=int(n_best))
 
   def predict_posteriors(self, test_sequences, args, temperature=1.0, max_speakers=None, transition_bias=None,
-                         known_speakers=None):
+                         known_speakers=None, min_turn=None):
     """predict, with the beam's per-frame confidence in its answer (extension).
 
     With w_k = softmax(-score_k / temperature) over the hypotheses of the final beam:
@@ -872,7 +917,7 @@ class UISRNN:
       temperature: a finite number > 0.  1 is the model's own posterior; a sharply peaked model (a trained D = 256
         one puts all but 1e-3, usually all but 1e-11, on the best hypothesis) needs a larger one to rank its
         uncertain frames.
-      max_speakers, transition_bias, known_speakers: as predict.
+      max_speakers, transition_bias, known_speakers, min_turn: as predict.
     Returns:
       for an array the triple (labels, confidence, change): predict's answer and two float32 arrays of its length.
       For a list, a list of such triples.  One decode, with predict's cap and level retries.
@@ -881,7 +926,8 @@ class UISRNN:
       what predict raises; ValueError for a temperature that is not a finite number > 0, before any device work.
     """
     temperature = _check_temperature(temperature)
-    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, posterior=temperature)
+    return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn,
+                         posterior=temperature)
 
   def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
     """predict, with the first frames of every sequence already labeled (extension).
@@ -1834,7 +1880,7 @@ class StreamPool:
 
 
 def parallel_predict(model, test_sequences, args, num_processes=4, devices=None, max_speakers=None, transition_bias=None,
-                     known_speakers=None):
+                     known_speakers=None, min_turn=None):
   """Drop-in for uisrnn.parallel_predict (uisrnn/uisrnn.py:593-623).
 
   The reference maps utterances over a forkserver process pool.  Here the
@@ -1847,24 +1893,23 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
   Args:
     devices: optional explicit list of HIP device indices (repeats allowed --
       used by the tests to exercise the path on a single-GPU box).
-    max_speakers, transition_bias, known_speakers: as UISRNN.predict (extensions); every shard takes its members'
-      entries.
+    max_speakers, transition_bias, known_speakers, min_turn: as UISRNN.predict (extensions); every shard takes its
+      members' entries.
 
   Raises:
     TypeError: test_sequences is not a list.
   """
   if not isinstance(test_sequences, list):
     raise TypeError('test_sequences must be a list.')
-  _, _, limits, bias, speakers = model._offline_arguments(  # pylint: disable=protected-access
-      test_sequences, args, max_speakers, transition_bias, known_speakers, sequences_first=True)
+  _, _, tables = model._offline_arguments(  # pylint: disable=protected-access
+      test_sequences, args, max_speakers, transition_bias, known_speakers, sequences_first=True, min_turn=min_turn)
   if not test_sequences:
     return []
   if devices is None:
     n_dev = max(_capi.load_library().uis_device_count(), 1)
     devices = list(range(max(1, min(int(num_processes), n_dev))))
   if len(devices) == 1:
-    return model._decode_batch(  # pylint: disable=protected-access
-        test_sequences, args, device=devices[0], limits=limits, bias=bias, speakers=speakers)
+    return model._decode_batch(test_sequences, args, device=devices[0], **tables)  # pylint: disable=protected-access
   import threading  # pylint: disable=import-outside-toplevel
   from uisrnn_amd import distributed  # pylint: disable=import-outside-toplevel
   shards = distributed.shard_utterances(
@@ -1879,9 +1924,7 @@ def parallel_predict(model, test_sequences, args, num_processes=4, devices=None,
     try:
       if shard:
         out = worker.decode([test_sequences[i] for i in shard], args,
-                            None if limits is None else [limits[i] for i in shard],
-                            None if bias is None else [bias[i] for i in shard],
-                            None if speakers is None else [speakers[i] for i in shard])
+                            **{name: None if table is None else [table[i] for i in shard] for name, table in tables.items()})
         for i, labels in zip(shard, out):
           results[i] = labels
     except Exception as exc:  # pylint: disable=broad-except
@@ -1911,9 +1954,9 @@ class _Worker:
     self._decoder = (_capi.Decoder(model.params, device) if self._own
                      else model._get_decoder(device))  # pylint: disable=protected-access
 
-  def decode(self, sequences, args, limits=None, bias=None, speakers=None):
+  def decode(self, sequences, args, limits=None, bias=None, speakers=None, min_turn=None):
     return self._model._decode_batch(  # pylint: disable=protected-access
-        sequences, args, decoder=self._decoder, limits=limits, bias=bias, speakers=speakers)
+        sequences, args, decoder=self._decoder, limits=limits, bias=bias, speakers=speakers, min_turn=min_turn)
 
   def close(self):
     if self._own:
