@@ -516,8 +516,8 @@ int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames)
  *                  rule, whatever an earlier call used.
  *
  * Refused with UIS_ERR_UNSUPPORTED, the table consumed and the handle usable: uis_score_labels, uis_score_speakers and
- * every uis_stream_* call made while a table is pending (a session's operations read the last-label words as labels,
- * so a session never holds a run).  The refused call has done nothing but drop the table and whatever other pending
+ * every uis_stream_* call made while a table is pending (the table is a decode's; a session takes its rule per slot,
+ * through uis_session_min_turn below).  The refused call has done nothing but drop the table and whatever other pending
  * table it would have consumed.  Where several pending tables are refused by one call, the one reported is
  * uis_frame_speakers', then this one, then uis_frame_bias', then uis_decode_limits', then uis_stream_speakers'.  A
  * decode in which some utterance has m >= 2 runs the kernels with the owner-side selects, as one with uis_frame_bias
@@ -525,6 +525,46 @@ int32_t uis_frame_speakers(uis_handle* h, const uint8_t* tags, int64_t n_frames)
  * reports k_decode_resident or k_decode_big.
  */
 int32_t uis_min_turn(uis_handle* h, const int32_t* min_turn, int32_t n_utt);
+
+/*
+ * Minimum turn length in streaming sessions.
+ *
+ * The rule is the one above, unchanged: a session whose slot u has the value m, pushed in any chunking and with silent
+ * slots, is bit for bit the uis_decode of the same frames under uis_min_turn's m at look_ahead 1 and test_iteration 1 --
+ * labels, scores, the final beam and the n-best rows.  The value is a property of the session's SLOTS, as max_speakers
+ * is: uis_stream_restart keeps it, blobs do not carry it, an imported utterance decodes on under the target slot's.
+ * A hypothesis' run rides in the last-label word the session already keeps (the label in bits 0 .. 15, the run,
+ * saturating at m, in bits 16 .. 30), so it follows the utterance through uis_stream_commit, uis_stream_retire and
+ * uis_stream_export / _import and ends at uis_stream_restart.  A slot whose value is 0 or 1 never holds run bits, and a
+ * session in which no slot has m >= 2 is the session without the call, to the byte: device tables and blobs.
+ *
+ *   uis_session_min_turn      min_turn: host int32 [n_utt of the session], each in [0, 32767]; 0 and 1: no rule.  A
+ *                             value may differ from the slot's current one only while the slot's utterance has received
+ *                             no frame (after uis_stream_begin or uis_stream_restart: nothing pushed, primed or
+ *                             imported); otherwise, and for a value out of range, UIS_ERR_INVALID_ARG and NO slot
+ *                             changes.  A session call between launches: a UIS_FLAG_PERSISTENT session honours the rule
+ *                             (its resident launch leaves, the next push starts one under the new table).
+ *   uis_session_get_min_turn  out: host int32 [n_utt]: the table as given (all 0 after uis_stream_begin).
+ *   uis_session_turns         out: host int32 [n_utt][2]: {the last label of utterance u's best hypothesis, in the
+ *                             numbering of uis_stream_labels' labels at this moment; its run}.  The run is 0 where the
+ *                             slot has no rule; {-1, 0} without a live hypothesis (an emptied beam, the cluster cap,
+ *                             nothing received).  With m >= 2 the speaker may change at the next frame iff run >= m.
+ *                             Changes nothing.
+ *
+ * All three need an open session and, like every session call, refuse a pending uis_min_turn table.
+ *
+ * uis_stream_prime into a slot with m >= 2 gives the primed hypothesis the run min(trailing run of the prefix labels, m);
+ * turns shorter than m INSIDE the prefix are the caller's and are kept.  uis_stream_retire reads the label of the word:
+ * the cluster a live hypothesis is speaking in is never retirable, whatever its run, and the clusters above a retired
+ * one move down under unchanged run bits.  Blobs: format 1, unchanged; export is verbatim.  uis_stream_import checks the
+ * LABEL of every rank's word against its cluster count (a rank without clusters holds -1 exactly) and normalises the
+ * run against the target slot's m: m < 2 gives the bare label; a word without a run (a blob from a slot without a
+ * rule: nothing is known of the turn, so the past sets no constraint) gets run m; else min(run, m).  So
+ * export(import(b)) == b wherever source and target slots have the same value.
+ */
+int32_t uis_session_min_turn(uis_handle* h, const int32_t* min_turn);
+int32_t uis_session_get_min_turn(uis_handle* h, int32_t* out);
+int32_t uis_session_turns(uis_handle* h, int32_t* out /* [n_utt][2] */);
 
 /*
  * Known speakers in streaming sessions.

@@ -363,6 +363,12 @@ def load_library(path=None):
   lib.uis_frame_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
   lib.uis_min_turn.restype = i32
   lib.uis_min_turn.argtypes = [ctypes.c_void_p, i32p, i32]
+  lib.uis_session_min_turn.restype = i32
+  lib.uis_session_min_turn.argtypes = [ctypes.c_void_p, i32p]
+  lib.uis_session_get_min_turn.restype = i32
+  lib.uis_session_get_min_turn.argtypes = [ctypes.c_void_p, i32p]
+  lib.uis_session_turns.restype = i32
+  lib.uis_session_turns.argtypes = [ctypes.c_void_p, i32p]
   lib.uis_stream_speakers.restype = i32
   lib.uis_stream_speakers.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64]
   lib.uis_stream_bindings.restype = i32
@@ -435,6 +441,7 @@ EXPORTED_SYMBOLS = (
     'uis_stream_export_bound', 'uis_stream_export', 'uis_stream_import', 'uis_eval_accuracy', 'uis_eval_accuracy_device',
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
     'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_min_turn', 'uis_stream_speakers', 'uis_stream_bindings',
+    'uis_session_min_turn', 'uis_session_get_min_turn', 'uis_session_turns',
     'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -810,6 +817,27 @@ class Decoder:
     """uis_stream_get_limits: int32 [n_utt], 0 = no bound."""
     out = np.zeros(self._stream_n, dtype=np.int32)
     self._check(self._lib.uis_stream_get_limits(self._handle, _i32(out)), 'uis_stream_get_limits')
+    return out
+
+  def session_set_min_turn(self, min_turn):
+    """uis_session_min_turn: replace the open session's minimum turn lengths (one int per slot, 0 and 1 = no rule).  A
+    slot that has received frames keeps its value: HipLibraryError (UIS_ERR_INVALID_ARG) and nothing changes."""
+    turns = np.ascontiguousarray(min_turn, dtype=np.int32)
+    if turns.shape != (self._stream_n,):
+      raise ValueError('one minimum turn length per utterance of the session')
+    self._check(self._lib.uis_session_min_turn(self._handle, _i32(turns)), 'uis_session_min_turn')
+
+  def session_min_turn(self):
+    """uis_session_get_min_turn: int32 [n_utt], 0 and 1 = no rule."""
+    out = np.zeros(self._stream_n, dtype=np.int32)
+    self._check(self._lib.uis_session_get_min_turn(self._handle, _i32(out)), 'uis_session_get_min_turn')
+    return out
+
+  def session_turns(self):
+    """uis_session_turns: int32 [n_utt, 2] -- {the best hypothesis' last label in the numbering of stream_labels at this
+    moment, its run}; the run is 0 where the slot has no rule; {-1, 0} without a live hypothesis."""
+    out = np.zeros((self._stream_n, 2), dtype=np.int32)
+    self._check(self._lib.uis_session_turns(self._handle, _i32(out)), 'uis_session_turns', ok=(UIS_OK,))
     return out
 
   def stream_push(self, chunks, bias=None, speakers=None):

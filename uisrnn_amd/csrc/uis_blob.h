@@ -7,7 +7,11 @@
 //             B, D, Dp, H, Hp, depth, the HidMap segment pair, the 64-bit hash of the model's parameters, total bytes
 //   scalars   UisBlobScalars, 32 bytes: committed, N (window frames = utt_step), live, n (distinct pool slots),
 //             lists (= sum of K over the live ranks), win_score
-//   ranks     [live] x {K, last, sum, score bits}: 16 bytes per live rank, best first
+//   ranks     [live] x {K, last, sum, score bits}: 16 bytes per live rank, best first.  `last` is the last-label word:
+//             the label in bits 0 .. 15 (signed; -1 exactly where K = 0), and in bits 16 .. 30 the hypothesis' run under
+//             its slot's minimum turn length (uis_session_min_turn): 0 in a stream from a slot without a rule, whose
+//             blob is unchanged.  The slot's value itself is not in the blob: import normalises the word against the
+//             target slot's (uis_blob_last_word)
 //   lists     rank by rank: K slot indices (renumbered into 0 .. n - 1), then K block-count words (the count, and in
 //             bits 24 .. 30 the cluster's speaker tag: 0 in a stream without known speakers, whose blob is unchanged); int32
 //   cnt       [n] int32: frames each slot's cluster has absorbed
@@ -39,6 +43,23 @@
 // uis_kernels.h's UIS_BLK_*, restated because this header stands alone
 #define UIS_BLOB_BLK_TAG_SHIFT 24
 #define UIS_BLOB_BLK_COUNT_MASK 0x00ffffff
+// a last-label word of the ranks: uis_kernels.h's UIS_LAST_*, restated likewise
+#define UIS_BLOB_LAST_RUN_SHIFT 16
+#define UIS_BLOB_LAST_RUN_MASK 0x7fff
+
+UIS_BLOB_FN int32_t uis_blob_last_label(int32_t w) { return (int32_t)(int16_t)(w & 0xffff); }
+UIS_BLOB_FN int32_t uis_blob_last_run(int32_t w) { return (w >> UIS_BLOB_LAST_RUN_SHIFT) & UIS_BLOB_LAST_RUN_MASK; }
+
+// A blob's last-label word as a slot whose minimum turn length is m holds it (uis_stream_import): no label stays -1; a
+// slot without a rule (m < 2) holds the bare label; a word without a run comes from a slot without a rule -- nothing is
+// known of the turn, so the past sets no constraint: run m --; else the run, saturated at m.
+UIS_BLOB_FN int32_t uis_blob_last_word(int32_t w, int32_t m) {
+  const int32_t label = uis_blob_last_label(w);
+  if (w < 0 || label < 0) return -1;
+  if (m < 2) return label;
+  const int32_t run = uis_blob_last_run(w);
+  return label | ((run == 0 || run > m ? m : run) << UIS_BLOB_LAST_RUN_SHIFT);
+}
 
 struct UisBlobHeader {
   uint32_t magic, format, numerics, look_ahead;
@@ -140,6 +161,7 @@ struct UisBlobInfo {
   UisBlobLayout lay;
   int32_t max_K;
   int32_t max_tag;   // the largest speaker tag a live rank has bound (0: the blob carries none)
+  int32_t max_run;   // the largest run a live rank's last-label word carries (0: the blob comes from a slot without a minimum turn length)
 };
 
 enum {
@@ -186,11 +208,25 @@ inline int uis_blob_validate(const void* blob, int64_t bytes, const UisBlobShape
   int64_t at = 0;
   in.max_K = 0;
   in.max_tag = 0;
+  in.max_run = 0;
+  int runless = 0;   // ranks that have a label and no run
   for (int r = 0; r < sc.live; ++r) {
     UisBlobRank rk;
     memcpy(&rk, b + l.ranks + (int64_t)r * (int64_t)sizeof(rk), sizeof(rk));
     if (rk.K < 0 || rk.K > UIS_BLOB_MAX_CLUSTERS || at + rk.K > sc.lists) { *why = "a rank's cluster count is out of range"; return UIS_BLOB_MALFORMED; }
-    if (rk.K == 0 ? rk.last != -1 : (rk.last < 0 || rk.last >= rk.K)) { *why = "a rank's last label is not one of its clusters"; return UIS_BLOB_MALFORMED; }
+    // (the label of the word; a word without a label is -1 exactly, and a hypothesis that has clusters has a label)
+    if (rk.K == 0 ? rk.last != -1 : (rk.last < 0 || uis_blob_last_label(rk.last) < 0 || uis_blob_last_label(rk.last) >= rk.K))
+      { *why = "a rank's last label is not one of its clusters"; return UIS_BLOB_MALFORMED; }
+    // (all live ranks come from one slot: under its minimum turn length every rank that has a label has a run of 1 or
+    // more, without one none has run bits.  The run itself is not bounded by the stream: a word that arrived without a
+    // run holds the slot's value, however short the stream.  So the run of a LONE rank is unchecked by design: import
+    // clamps it against the target slot's value)
+    if (rk.K > 0) {
+      const int32_t run = uis_blob_last_run(rk.last);
+      if (run > 0 ? runless > 0 : in.max_run > 0) { *why = "the ranks disagree on whether their slot has a minimum turn length"; return UIS_BLOB_MALFORMED; }
+      runless += run == 0;
+      if (run > in.max_run) in.max_run = run;
+    }
     int64_t sum = 0;
     uint64_t seen[2] = {0, 0};   // the tags this rank has bound
     for (int k = 0; k < rk.K; ++k) {

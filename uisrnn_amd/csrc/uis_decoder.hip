@@ -246,6 +246,10 @@ struct uis_handle : HandleMem {
     // last step), its labels are the committed ones and its score is win_score; the readouts' kernels see N = 0
     bool window_emptied(int u) const { return have[u] == 0 && committed[u] > 0; }
     std::vector<int32_t> limits;      // max_speakers per slot as the caller gave them (0: no bound): uis_stream_begin / uis_stream_limits
+    // minimum turn length per slot as the caller gave them (0 and 1: no rule): uis_session_min_turn.  d_min_turn holds
+    // them on the device; st.min_turn points there exactly while some slot has a value of 2 or more, else it is null
+    std::vector<int32_t> min_turn;
+    int32_t* d_min_turn = nullptr;
     DecodeState st{};
     int32_t* d_avail = nullptr;
     int32_t* d_have = nullptr;        // frames received per utterance, refreshed for every back-trace

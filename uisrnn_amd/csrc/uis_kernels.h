@@ -249,8 +249,9 @@ __device__ __forceinline__ int blk_count(int w) { return w & UIS_BLK_COUNT_MASK;
 __device__ __forceinline__ int blk_tag(int w) { return w >> UIS_BLK_TAG_SHIFT; }
 
 // A last-label word (beam_last / lv_last and their LDS copies): the label in bits 0 .. 15 as a signed 16-bit number (-1:
-// no label yet; max_clusters <= 4096), the hypothesis' run in bits 16 .. 30.  Only a decode whose utterance has a
-// minimum turn length of 2 or more writes run bits; everywhere else the word is the label, and -1 stays -1.
+// no label yet; max_clusters <= 4096), the hypothesis' run in bits 16 .. 30.  Only a decode, or a session slot
+// (uis_session_min_turn), whose utterance has a minimum turn length of 2 or more writes run bits; everywhere else the
+// word is the label, and -1 stays -1.  The session operations between pushes read the label through last_label().
 #define UIS_LAST_RUN_SHIFT 16
 #define UIS_LAST_RUN_MASK 0x7fff
 __device__ __forceinline__ int last_label(int w) { return (int)(int16_t)w; }

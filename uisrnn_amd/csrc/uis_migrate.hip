@@ -15,7 +15,8 @@
 //                    so a second export reproduces the blob), the ranks' scalars, their compact slot / block lists,
 //                    the slots' frame counts, and the control words the host reads (live, beam_n, overflow, n, list
 //                    length).  Import: the same sections into ranks 0 .. live - 1 of the beam tables of parity N & 1,
-//                    pool_cnt, beam_n = {live, 0}, utt_step = N, overflow = 0
+//                    pool_cnt, beam_n = {live, 0}, utt_step = N, overflow = 0.  Export is verbatim; import passes each
+//                    rank's last-label word through uis_blob_last_word against the target slot's minimum turn length
 //   k_migrate_copy   workgroups [0, slot groups): the named slots' rows of pool_mean and pool_hid, 16 bytes per thread
 //                    (rows are copied in the pool's padded / HidMap layout, never re-mapped); the rest: one tile of
 //                    UIS_MIGRATE_TILE_WORDS record words each -- 16 bytes per thread where the utterance's records and
@@ -45,6 +46,7 @@ struct MigrateArgs {
   int u;                // the utterance
   int N, live, n, lists;  // import: from the validated blob; export: the kernels read the control words
   int slot_groups;
+  int min_turn;         // import: the target slot's minimum turn length (uis_session_min_turn; below 2: no rule)
   int32_t* ctl;         // export: [0] live (0: overflow word set or beam empty) [1] beam_n [2] overflow [3] n [4] lists [5] N
   char* img;            // the blob's image in the scratch (16-byte aligned)
   int32_t* flags;       // [S] export: slot named by a live rank
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(UIS_MIGRATE_THREADS) void k_migrate_pack(DevModel m
     if (tid < a.live) {
       const UisBlobRank rk = ranks[tid];
       s_K[tid] = rk.K;
-      st.beam_K[e + tid] = rk.K; st.beam_last[e + tid] = rk.last; st.beam_sum[e + tid] = rk.sum; st.beam_score[e + tid] = rk.score;
+      st.beam_K[e + tid] = rk.K; st.beam_last[e + tid] = uis_blob_last_word(rk.last, a.min_turn); st.beam_sum[e + tid] = rk.sum; st.beam_score[e + tid] = rk.score;
     }
     __syncthreads();
     if (tid == 0) {
@@ -359,6 +361,7 @@ UIS_EXPORT int32_t uis_stream_import(uis_handle* h, int32_t utt, const void* blo
   a.u = utt;
   a.N = sc.N; a.live = sc.live; a.n = sc.n; a.lists = sc.lists;
   a.slot_groups = std::max(1, std::min(sc.n, UIS_MIGRATE_SLOT_GROUPS));
+  a.min_turn = ss.min_turn[utt];  // (the run of every rank's last-label word is normalised against the TARGET slot's value)
   a.img = base + o_img;
   // ---- unpack, copy
   HIPCHK(timer.begin());

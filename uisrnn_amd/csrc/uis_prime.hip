@@ -186,7 +186,15 @@ UIS_EXPORT int32_t uis_stream_prime(uis_handle* h, const float* frames, const in
   for (int u = 0; u < U; ++u) {
     const int K = s.chain_base[u + 1] - s.chain_base[u];
     if (K == 0) continue;
-    utts.push_back(PrimeUtt{u, (int32_t)(offsets[u + 1] - offsets[u]), K, s.utt_last[u], s.utt_sum[u], s.chain_base[u]});
+    // (uis_session_min_turn: under a slot's m >= 2 the word carries min(trailing run of the prefix labels, m), as the
+    // selects would have left it; turns shorter than m INSIDE the prefix are the caller's and are kept)
+    int32_t last_word = s.utt_last[u];
+    if (const int32_t mt = ss.min_turn[u]; mt >= 2) {
+      int32_t run = 1;
+      for (int64_t t = offsets[u + 1] - 1; t > offsets[u] && run < mt && labels[t - 1] == labels[t]; --t) ++run;
+      last_word |= run << UIS_LAST_RUN_SHIFT;
+    }
+    utts.push_back(PrimeUtt{u, (int32_t)(offsets[u + 1] - offsets[u]), K, last_word, s.utt_sum[u], s.chain_base[u]});
     for (int k = 0; k < K; ++k) {
       const int i = s.rank[s.chain_base[u] + k], len = s.len[i];
       chains[i] = PrimeChain{s.fbase[len - 1] + i, u, k, len, 0};

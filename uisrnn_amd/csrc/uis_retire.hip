@@ -11,7 +11,9 @@
 // cluster was opened before the window; after a commit or a prime all live
 // hypotheses share that history, so index k means the same speaker in each of them.  Retiring a set R:
 //   lists    every live rank's slot / block lists lose the entries in R, the entries above move down in order
-//   scalars  K_r -= |R|,  sum_r -= sum of blk_r[k] over R,  last_r -= #{k in R : k < last_r};  scores stay
+//   scalars  K_r -= |R|,  sum_r -= sum of blk_r[k] over R,  last_r -= #{k in R : k < last_r};  scores stay.  last_r is
+//            the LABEL of the rank's last-label word (last_label(): a slot with a minimum turn length keeps the run in
+//            bits 16 .. 30, uis_session_min_turn); the run bits stay as they are
 //   records  in every record word of window steps [0, N) the label becomes label - #{k in R : k < label}; the parent
 //            stays.  Words of ranks that are not live are stale (any bit pattern): a label above max_clusters is left
 // and nothing else: a retired cluster's slot is free by itself (the selects find free slots from the live lists at
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_scan(DecodeState 
   for (int r = tid; r < live; r += UIS_RETIRE_THREADS) {
     int K = st.beam_K[e + r];
     K = K < 0 ? 0 : (K > Kmax ? Kmax : K);
-    const int last = st.beam_last[e + r];
+    const int last = last_label(st.beam_last[e + r]);   // (the label, whatever run the word carries: uis_session_min_turn)
     if (last >= 0 && last < Kmax) atomicOr(&s_used[last >> 5], 1u << (last & 31));
     atomicMin(&s_minK, K);
     atomicMax(&s_maxK, K);
@@ -186,11 +188,12 @@ __global__ __launch_bounds__(UIS_RETIRE_THREADS) void k_retire_apply(DecodeState
     const int32_t* blk = st.beam_blk + (e + r) * Kmax;
     int gone = 0;
     for (int i = 0; i < n_ret; ++i) gone += blk_count(blk[retired[i]]);   // (a retired cluster carries no tag; the count all the same)
-    const int K = st.beam_K[e + r], last = st.beam_last[e + r];
+    const int K = st.beam_K[e + r], word = st.beam_last[e + r], last = last_label(word);
     s_K[r] = K < 0 ? 0 : (K > Kmax ? Kmax : K);
     st.beam_K[e + r] = K - n_ret;
     st.beam_sum[e + r] -= gone;
-    if (last > 0 && last <= Kmax) st.beam_last[e + r] = last - s_shift[last];
+    // (the renumbered label under the word's unchanged run bits; a word without run bits is the label, as before)
+    if (word > 0 && last > 0 && last <= Kmax) st.beam_last[e + r] = word - s_shift[last];
   }
   loads_before_stores();  // (the block counts have returned before the barrier lets anyone move them)
   // ---- the lists: entry i = (rank i / Kmax, index i % Kmax), ascending tiles.  An entry moves down inside its row,

@@ -180,7 +180,7 @@ int pm_quit(uis_handle* h) {
 }
 
 // ---- the scaffold of a session call between launches: uis_stream_{labels, nbest, posterior, prime, commit, restart,
-// retire, committed, bindings}.  THE ORDER, stated here once:
+// retire, committed, bindings} and uis_session_{min_turn, turns}.  THE ORDER, stated here once:
 //   1. session_of and the call's own checks on the host: nothing of the session is touched, and a call refused here
 //      (or one with nothing to do) costs a UIS_FLAG_PERSISTENT session nothing and touches no device;
 //   2. session_enter: the resident launch leaves (pm_quit -- it occupies every CU and the tables are written between
@@ -366,6 +366,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   ss.have.assign(U, 0);
   ss.committed.assign(U, 0);
   ss.win_score.assign(U, 0.0f);
+  ss.min_turn.assign(U, 0);
   ss.log_len = max_frames + 2;
   DecodeState& st = ss.st;
   st.U = U; st.B = B; st.Kmax = Kmax; st.S = S; st.L = 1; st.tau = 1; st.flags = opts->flags | (agent_flags_env() ? UIS_FLAG_AGENT_FLAGS : 0u);
@@ -385,6 +386,7 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   SALLOC(st.utt_step, U, false);
   SALLOC(st.overflow, U, false);
   SALLOC(st.limit, U, false);
+  SALLOC(ss.d_min_turn, U, true);  // (uis_session_min_turn: no slot has a rule, and st.min_turn stays null)
   SALLOC(ss.d_avail, U, true);
   SALLOC(ss.d_have, U, true);
   SALLOC(ss.d_foff, U, true);
@@ -837,5 +839,110 @@ UIS_EXPORT int32_t uis_stream_get_limits(uis_handle* h, int32_t* out) {
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
   const uis_handle::Stream& ss = h->stream_state;
   for (int u = 0; u < ss.U; ++u) out[u] = ss.limits[u];
+  return UIS_OK;
+}
+
+// ---- the minimum turn length of an open session's slots.  The table belongs to the slots, as
+// max_speakers does: restarts keep it, blobs do not carry it, an imported utterance decodes on under the target slot's
+// value.  The run rides in the last-label words the session already keeps (uis_kernels.h UIS_LAST_*); the selects of
+// every push read utt_min_turn(st, u), so a push needs nothing but DecodeState::min_turn -- set exactly while some slot
+// has a value of 2 or more: a session without a rule hands its kernels a null pointer, as before.
+
+namespace {
+
+// the opener of the uis_session_* calls: every one of them is a session call under UIS_RULE_STREAM_OTHER (a pending
+// uis_min_turn table is a decode's, and is refused here as by every uis_stream_* call)
+int begin_session_call(uis_handle* h, const char* who) { return begin_call(h, who, UIS_RULE_STREAM_OTHER); }
+
+}  // namespace
+
+// A value may differ from the slot's current one only while the slot's utterance has received nothing: the run of a
+// live hypothesis saturates at the value it was formed under.  All or nothing.  A session call between launches: the
+// resident launch of a UIS_FLAG_PERSISTENT session leaves, and the next push's launch is given the new pointer.
+UIS_EXPORT int32_t uis_session_min_turn(uis_handle* h, const int32_t* min_turn) {
+  if (int rc = begin_session_call(h, "uis_session_min_turn")) return rc;
+  if (!session_of(h, min_turn != nullptr, "null handle/min_turn")) return UIS_ERR_INVALID_ARG;
+  uis_handle::Stream& ss = h->stream_state;
+  bool any = false, changed = false;
+  for (int u = 0; u < ss.U; ++u) {
+    if (min_turn[u] < 0 || min_turn[u] > UIS_MIN_TURN_MAX)
+      return fail(UIS_ERR_INVALID_ARG, "a minimum turn length must be in [0, 32767] (0 and 1: no rule)");
+    if (min_turn[u] != ss.min_turn[u] && ss.committed[u] + ss.have[u] != 0)
+      return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has already received or been primed with " +
+                                           std::to_string((long long)(ss.committed[u] + ss.have[u])) +
+                                           " frames: its slot's minimum turn length changes only before the first frame "
+                                           "(after uis_stream_begin or uis_stream_restart); nothing was changed");
+    any = any || min_turn[u] >= 2;
+    changed = changed || min_turn[u] != ss.min_turn[u];
+  }
+  if (!changed) return UIS_OK;
+  if (int rc = session_enter(h, nullptr)) return rc;  // (the resident launch leaves: the table is written between launches)
+  const std::vector<int32_t> next(min_turn, min_turn + ss.U);
+  HIPCHK(hipMemcpyAsync(ss.d_min_turn, next.data(), (size_t)ss.U * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  ss.min_turn = next;
+  ss.st.min_turn = any ? ss.d_min_turn : nullptr;
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_session_get_min_turn(uis_handle* h, int32_t* out) {
+  if (int rc = begin_session_call(h, "uis_session_get_min_turn")) return rc;
+  if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
+  const uis_handle::Stream& ss = h->stream_state;
+  for (int u = 0; u < ss.U; ++u) out[u] = ss.min_turn[u];
+  return UIS_OK;
+}
+
+namespace {
+
+#define UIS_TURNS_THREADS 64
+
+// The turn the best hypothesis is in, one thread per utterance (two loads and two stores each: a workgroup per
+// utterance, as k_stream_bindings has for its 128 output words, would idle 63 lanes of 64), between launches: out[u] = {the label of rank 0's
+// last-label word -- a cluster index as uis_stream_labels numbers them now --, its run}.  The run is 0 where the slot
+// has no rule (such a word carries none); {-1, 0} for an utterance without a live hypothesis (an emptied beam, the
+// overflow word set) and for one that has received nothing.  A window that a commit emptied keeps its one hypothesis.
+__global__ __launch_bounds__(UIS_TURNS_THREADS) void k_session_turns(DecodeState st, int32_t* __restrict__ out) {
+  const int u = blockIdx.x * UIS_TURNS_THREADS + threadIdx.x;
+  if (u >= st.U) return;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u, EMPTY_WINDOW_KEEPS_BEAM);
+  int label = -1, run = 0;
+  if (live > 0) {
+    const int w = st.beam_last[e];   // rank 0
+    const int K = st.beam_K[e];
+    if (w >= 0 && last_label(w) >= 0 && last_label(w) < K) {
+      label = last_label(w);
+      run = utt_min_turn(st, u) >= 2 ? last_run(w) : 0;
+    }
+  }
+  out[2 * (size_t)u] = label;
+  out[2 * (size_t)u + 1] = run;
+}
+
+}  // namespace
+
+// May the speaker change at the next frame: see include/uisrnn_hip.h.  The scaffold's order; nothing of the session changes.
+UIS_EXPORT int32_t uis_session_turns(uis_handle* h, int32_t* out) {
+  if (int rc = begin_session_call(h, "uis_session_turns")) return rc;
+  if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
+  uis_handle::Stream& ss = h->stream_state;
+  const int U = ss.U;
+  CallTimer timer{h};
+  int rc;
+  DecodeState stv;
+  if ((rc = session_enter(h, &stv))) return rc;
+  ScratchPlan plan;
+  const size_t bytes = (size_t)U * 8, o_out = plan.take(bytes);
+  char* base;
+  if ((rc = session_buffers(h, plan, bytes, &base))) return rc;
+  HIPCHK(timer.begin());
+  hipLaunchKernelGGL(k_session_turns, dim3((U + UIS_TURNS_THREADS - 1) / UIS_TURNS_THREADS), dim3(UIS_TURNS_THREADS), 0, h->stream, stv, reinterpret_cast<int32_t*>(base + o_out));
+  HIPCHK(hipGetLastError());
+  HIPCHK(timer.end());
+  HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_out, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memcpy(out, ss.h_land.p, bytes);
+  if (CallTimer::env("UIS_TURNS_TRACE"))
+    fprintf(stderr, "uis_session_turns: utterances %d device_ms %.3f call_ms %.3f\n", U, timer.device_ms(), timer.call_ms());
   return UIS_OK;
 }

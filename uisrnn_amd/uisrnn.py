@@ -74,6 +74,16 @@ def _check_max_speakers(max_speakers, args, n_utt):
 _MAX_MIN_TURN = 32767  # (a hypothesis' run is fifteen bits of its last-label word: include/uisrnn_hip.h)
 
 
+def _slot_rules(who, rules):
+  """The per-slot rule keywords of the session entries (online, online_pool, predict_primed), which take them as
+  **rules: today min_turn alone.  Returns its value (None: not given); TypeError, in Python's own words, for any other."""
+  rules = dict(rules)
+  value = rules.pop('min_turn', None)
+  for name in rules:
+    raise TypeError("{}() got an unexpected keyword argument '{}'".format(who, name))
+  return value
+
+
 def _check_min_turn(min_turn, n_utt):
   """The min_turn keyword as the library's table: None (no utterance has a rule) or a list of n_utt ints, 0 and 1 = no
   rule.  min_turn: None, an integer for every utterance, or a sequence with one integer per utterance.  Raises before
@@ -812,24 +822,28 @@ class UISRNN:
     return self._predict(test_sequence, args, max_speakers, transition_bias, known_speakers, min_turn)
 
   def online(self, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
-             max_speakers=None):
+             max_speakers=None, **rules):
     """An OnlineSession (streaming decode; extension, see the class).  horizon: None, or the decision
     horizon in frames of a session that commits by itself when a push does not fit its window.  retire_at: None,
     or the cluster count from which the session retires speakers by itself, down to retire_to (default
     retire_at // 2): see OnlineSession.retire.  max_speakers: None, an int or one entry per utterance: the slots'
-    bounds (OnlineSession.set_max_speakers)."""
+    bounds (OnlineSession.set_max_speakers).  min_turn (keyword, among **rules): None, an int or one int per utterance: the slots' minimum turn
+    lengths (OnlineSession.set_min_turn)."""
     limits = _check_max_speakers(max_speakers, args, num_utterances)
+    turns = _check_min_turn(_slot_rules('online', rules), num_utterances)
     if args.look_ahead != 1:
       raise ValueError('online decoding needs look_ahead 1')
     if self.transition_bias is None:
       raise TypeError('transition_bias is None: the model was never fit or loaded')
-    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon, retire_at, retire_to, limits)
+    return OnlineSession(self, num_utterances, args, max_frames, persistent, horizon, retire_at, retire_to, limits,
+                         turns)
 
   def online_pool(self, slots, args, max_frames, persistent=False, horizon=None, retire_at=None, retire_to=None,
-                  max_speakers=None):
+                  max_speakers=None, **rules):
     """A StreamPool over one OnlineSession of `slots` utterances (extension, see the class): for callers
     whose streams begin and end independently of each other."""
-    return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers))
+    return StreamPool(self.online(slots, args, max_frames, persistent, horizon, retire_at, retire_to, max_speakers,
+                                  **rules))
 
   def predict(self, test_sequences, args, max_speakers=None, transition_bias=None, known_speakers=None, min_turn=None):
     """Predict labels for one sequence or a list of them (uisrnn.py:564-590).
@@ -929,7 +943,7 @@ class UISRNN:
     return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn,
                          posterior=temperature)
 
-  def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None):
+  def predict_primed(self, test_sequences, prefix_cluster_ids, args, max_speakers=None, **rules):
     """predict, with the first frames of every sequence already labeled (extension).
 
     The decode of sequence u starts from the state the model holds after prefix_cluster_ids[u] along its
@@ -942,6 +956,8 @@ class UISRNN:
         appearance; may be empty), or a list of such sequences for a list.
       args: inference namespace; look_ahead and test_iteration must be 1 (online decoding).
       max_speakers: as predict.  A prefix with more clusters than its bound is kept: it opens nothing more.
+      min_turn (keyword, among **rules): as predict.  The decode goes on from the run the prefix ends in; turns shorter than min_turn inside a
+        given prefix are the caller's and are kept.
     Returns:
       N ints for an array, a list of such lists for a list; the first P_u are the renamed prefix.
     Raises:
@@ -953,6 +969,7 @@ class UISRNN:
     if int(args.look_ahead) != 1 or int(args.test_iteration) != 1:
       raise ValueError('predict_primed is online decoding: look_ahead and test_iteration must be 1.')
     limits = _check_max_speakers(max_speakers, args, len(seqs))
+    turns = _check_min_turn(_slot_rules('predict_primed', rules), len(seqs))
     for seq in seqs:
       self._check_sequence(seq)
     prefixes = []
@@ -973,6 +990,8 @@ class UISRNN:
       bound = {} if limits is None else {'limits': [limits[u] for u in pending]}
       decoder.stream_begin(len(pending), args.beam_size, max(max(lens), 1), max_clusters=cap, **bound)
       try:
+        if turns is not None:
+          decoder.session_set_min_turn([turns[u] for u in pending])
         try:
           decoder.stream_prime([seqs[u][:len(prefixes[u])] for u in pending], [prefixes[u] for u in pending])
         except _capi.HipLibraryError as err:
@@ -1174,7 +1193,7 @@ class OnlineSession:
   _names = None   # per utterance {name: tag}: its known speakers, numbered 1 .. 127 by first appearance across pushes
 
   def __init__(self, model, num_utterances, args, max_frames, persistent=False, horizon=None, retire_at=None,
-               retire_to=None, limits=None):
+               retire_to=None, limits=None, min_turn=None):
     if horizon is not None and (isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 0):
       raise ValueError('horizon must be None or a non-negative integer.')
     cap = None if args is None else _initial_cluster_cap(args)
@@ -1201,6 +1220,36 @@ class OnlineSession:
       self._decoder.stream_begin(num_utterances, args.beam_size, max_frames, max_clusters=cap, **bound)
     self._open = True
     self._num_utterances = int(num_utterances)
+    if min_turn is not None:
+      self._decoder.session_set_min_turn(min_turn)
+
+  def set_min_turn(self, values):
+    """Replace the slots' minimum turn lengths between two pushes (uis_session_min_turn): None,
+    an int, or one int per utterance; 0 and 1 mean no rule.  A stream pushed under m is bit for bit
+    predict(..., min_turn=m) of everything received.  The values belong to the slots: restart keeps them, an imported
+    stream decodes on under its new slot's, snapshots do not carry them.  A slot's value can change only while its
+    utterance has received nothing (after the session opens or after restart): otherwise _capi.HipLibraryError (status
+    UIS_ERR_INVALID_ARG) and no slot changes.  ValueError / TypeError as predict's min_turn."""
+    turns = _check_min_turn(0 if values is None else values, self._num_utterances)
+    self._decoder.session_set_min_turn(turns if turns is not None else [0] * self._num_utterances)
+
+  def min_turn(self):
+    """The slots' minimum turn lengths: a list with an int per utterance (0 and 1: no rule)."""
+    return [int(v) for v in self._decoder.session_min_turn()]
+
+  def turns(self):
+    """The turn each utterance's best hypothesis is in (uis_session_turns): per utterance (speaker id, run, held) -- the
+    id labels() gives the newest frame, for how many frames it has held the floor (saturating at the slot's min_turn; 0
+    where the slot has no rule), and whether the rule holds the speaker at the next frame (run < min_turn).
+    (-1, 0, False) for an utterance without a live hypothesis or without frames."""
+    table = self._decoder.session_turns()
+    values = self._decoder.session_min_turn()
+    out = []
+    for u in range(self._num_utterances):
+      label, run = int(table[u, 0]), int(table[u, 1])
+      m = int(values[u])
+      out.append((self._ids(u, [label])[0], run, bool(label >= 0 and m >= 2 and run < m)))
+    return out
 
   def set_max_speakers(self, values):
     """Replace the slots' bounds between two pushes (uis_stream_limits): None, an int, or one entry (an int, 0 or
@@ -1780,18 +1829,25 @@ class StreamPool:
     self._slot = {}   # key -> slot
     self._free = list(range(session._num_utterances - 1, -1, -1))  # pylint: disable=protected-access
 
-  def open(self, key, max_speakers=None):
+  def open(self, key, max_speakers=None, min_turn=None):
     """Take a free slot for a new stream.  Returns the slot's index.  max_speakers: None (the slot keeps the bound it
-    has), 0 (no bound) or the bound the slot gets for this stream."""
+    has), 0 (no bound) or the bound the slot gets for this stream.  min_turn: None (the slot keeps the minimum turn
+    length it has) or the value the slot gets for this stream (0 and 1: no rule)."""
     if key in self._slot:
       raise KeyError('stream {!r} is already open'.format(key))
     if not self._free:
       raise RuntimeError('no free slot')
+    if min_turn is not None:
+      _check_min_turn([min_turn], 1)   # (raises before any device work; 0 and 1 are values too)
     if max_speakers is not None:
       limit = _check_max_speakers([max_speakers], None, 1)
       values = self._session.max_speakers()
       values[self._free[-1]] = limit[0] if limit else 0
       self._session.set_max_speakers(values)
+    if min_turn is not None:
+      values = self._session.min_turn()
+      values[self._free[-1]] = int(min_turn)
+      self._session.set_min_turn(values)
     self._slot[key] = self._free.pop()
     return self._slot[key]
 
