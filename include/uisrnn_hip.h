@@ -297,6 +297,57 @@ int32_t uis_decode_device(uis_handle* h, const float* d_frames, const int64_t* o
                           int32_t* d_labels_out, float* d_scores_out, uis_stats* stats);
 
 /*
+ * Device tensors in: decode and push straight from what a speaker encoder left in HBM.
+ *
+ * A uis_tensor describes one block of rows on the handle's device: `rows` rows of observation_dim elements of `dtype`,
+ * the inner dimension contiguous, row r at data + r * row_stride elements (row_stride >= observation_dim: a slice of a
+ * padded [U, T, D] batch, a [:, :D] view of a wider tensor, any base alignment).  One kernel launch (k_ingest,
+ * csrc/uis_ingest.hip) gathers the blocks of a call, in list order, into the packed float32 [F, D] stream the other
+ * entry points receive, converting on the way:
+ *   float64 -> float32  round to nearest even, bit for bit the cast of uis_decode_f64 (and numpy's astype(float32)):
+ *                       results that are float32 subnormals and values that overflow to +-inf included
+ *   float16, bfloat16   exact, subnormal inputs included
+ * Everything behind the packed stream is what it was, so a call here gives the bits of its host sibling on the same
+ * values.
+ *
+ * producer_stream: the HIP stream on which the tensors were written (a hipStream_t, e.g. torch's
+ * torch.cuda.current_stream().cuda_stream), NULL for the default stream.  The call records an event there and its own
+ * stream waits for it before the first read: no synchronisation is needed on the caller's side.  The calls block as
+ * their siblings do: outputs are complete, and the tensors free to be rewritten, on return.
+ *
+ * Checked on the host before any GPU work (UIS_ERR_INVALID_ARG): data NULL with rows > 0, rows < 0, an unknown dtype,
+ * row_stride < observation_dim with rows > 0, data not aligned to its element size, capacity_rows below the rows given.
+ *
+ *   uis_ingest_tensors        the kernel alone: n blocks -> d_frames_out, float32 [sum rows, D] on the device, with room
+ *                             for capacity_rows rows
+ *   uis_tensors_decode        uis_decode_device of the utterances given as one block each (rows 0: an empty utterance):
+ *                             the blocks are gathered into the handle's own frame buffer and decoded from there.
+ *                             d_labels_out / d_scores_out on the device, as there; the per-call tables (uis_decode_limits,
+ *                             uis_frame_bias, uis_frame_speakers, uis_min_turn) belong to it as to every decode, and the
+ *                             uis_last_decode_* readouts are valid after it
+ *   uis_tensors_stream_push   uis_stream_push with utterance u's new frames in chunks[u] (rows 0: none): the same checks
+ *                             in the same order, a pending uis_frame_bias / uis_stream_speakers table applies as there;
+ *                             the frames never leave the device.  A UIS_FLAG_PERSISTENT session returns
+ *                             UIS_ERR_UNSUPPORTED before touching anything (its frames would have to travel through the
+ *                             host mailbox) and stays usable and unchanged
+ * (The latter two are named tensors-first: the prefixes uis_decode / uis_stream_ are enumerated by the call-table test.)
+ */
+enum { UIS_DTYPE_F32 = 0, UIS_DTYPE_F64 = 1, UIS_DTYPE_F16 = 2, UIS_DTYPE_BF16 = 3 };
+typedef struct uis_tensor {
+  const void* data;    /* device pointer to the first row (may be NULL where rows == 0) */
+  int64_t rows;
+  int64_t row_stride;  /* elements between two rows, >= observation_dim */
+  int32_t dtype;       /* UIS_DTYPE_* */
+  int32_t reserved;    /* 0 */
+} uis_tensor;
+int32_t uis_ingest_tensors(uis_handle* h, const uis_tensor* blocks, int32_t n, void* producer_stream,
+                           float* d_frames_out, int64_t capacity_rows);
+int32_t uis_tensors_decode(uis_handle* h, const uis_tensor* utterances, int32_t n_utt, void* producer_stream,
+                           const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out, uis_stats* stats);
+int32_t uis_tensors_stream_push(uis_handle* h, const uis_tensor* chunks /* [n_utt of the session] */,
+                                void* producer_stream);
+
+/*
  * After a decode: per-utterance overflow flags (1 = hit the cluster cap) and
  * the full final beam scores, for the host-side retry loop and the parity tests.
  *   overflow_out : host int32 [n_utt] or NULL

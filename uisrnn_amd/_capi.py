@@ -176,6 +176,138 @@ def _offsets(counts):
   return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
 
 
+# ---- device tensors in (uis_ingest_tensors, uis_tensors_decode, uis_tensors_stream_push; csrc/uis_ingest.hip)
+
+UIS_DTYPE_F32, UIS_DTYPE_F64, UIS_DTYPE_F16, UIS_DTYPE_BF16 = 0, 1, 2, 3
+DTYPE_BYTES = {UIS_DTYPE_F32: 4, UIS_DTYPE_F64: 8, UIS_DTYPE_F16: 2, UIS_DTYPE_BF16: 2}
+# struct uis_tensor, one record per block: a table is a numpy array of these, handed over by its address
+TENSOR_RECORD = np.dtype([('data', np.uint64), ('rows', np.int64), ('row_stride', np.int64), ('dtype', np.int32),
+                          ('reserved', np.int32)])
+INGEST_WORKGROUP_ITEMS = 512   # items (8 consecutive floats of one row) a workgroup of k_ingest takes
+
+
+def ingest_workgroup_rows(dim):
+  """Rows of the packed stream one workgroup of k_ingest covers (the last one possibly in part)."""
+  return INGEST_WORKGROUP_ITEMS // ((int(dim) + 7) // 8)
+
+
+_dtype_codes = None   # {torch dtype: UIS_DTYPE_*}, made by the first tensor call (torch is imported no earlier)
+_ELEM_BYTES = np.array([DTYPE_BYTES[c] for c in range(4)], dtype=np.int64)
+
+
+def _torch_dtype_codes():
+  global _dtype_codes
+  if _dtype_codes is None:
+    import torch  # pylint: disable=import-outside-toplevel
+    _dtype_codes = {torch.float32: UIS_DTYPE_F32, torch.float64: UIS_DTYPE_F64, torch.float16: UIS_DTYPE_F16,
+                    torch.bfloat16: UIS_DTYPE_BF16}
+  return _dtype_codes
+
+
+def _checked_tensor(t, ndim, dim, device, who):
+  """One tensor of a tensor entry point, checked before the library is called: TypeError for what is no floating-point
+  torch tensor on a GPU, ValueError for a wrong device index, rank or observation dimension.  device None: any device,
+  the CPU included (descriptor building is plain arithmetic; the tests use it).  Returns (tensor, dtype code): the
+  tensor itself, or a contiguous copy where its inner stride is not 1 or its rows overlap."""
+  codes = _torch_dtype_codes()
+  if type(t).__module__.split('.')[0] != 'torch' or not hasattr(t, 'data_ptr'):
+    raise TypeError('{} should be a torch tensor, not {}.'.format(who, type(t).__name__))
+  code = codes.get(t.dtype)
+  if code is None:
+    raise TypeError('{} should be of dtype float64, float32, float16 or bfloat16, not {}.'.format(who, t.dtype))
+  if device is not None:
+    if t.device.type != 'cuda':
+      raise TypeError('{} is on the {}: tensors must be on the model\'s device (cuda:{}).'.format(who, t.device, device))
+    if t.device.index != device:
+      raise ValueError('{} is on {}, the model is on cuda:{}.'.format(who, t.device, device))
+  if t.ndim != ndim:
+    raise ValueError('{} must be a {}-dim tensor.'.format(who, ndim))
+  if t.shape[-1] != dim:
+    raise ValueError('{} does not match observation_dim ({} against {}).'.format(who, t.shape[-1], dim))
+  rows_overlap = t.shape[-2] > 1 and t.stride(-2) < dim
+  if (dim > 1 and t.stride(-1) != 1) or rows_overlap:
+    t = t.contiguous()
+  return t, code
+
+
+def tensor_table(source, dim, lengths=None, device=None, who='test_sequences'):
+  """The uis_tensor table of `source`: a list of [N_u, D] tensors (None: no rows), or one [U, T, D] tensor whose
+  utterance u holds `lengths[u]` rows (None: T).  Returns (table, keep): a TENSOR_RECORD array with one record per
+  utterance and whatever has to outlive the call that reads it.  A block of at most one row is given row_stride D
+  where its own is smaller (a stride nothing is ever multiplied by)."""
+  dim = int(dim)
+  if hasattr(source, 'ndim') and not isinstance(source, (list, tuple)):
+    batch, code = _checked_tensor(source, 3, dim, device, who)
+    n_utt, most = int(batch.shape[0]), int(batch.shape[1])
+    rows = np.full(n_utt, most, dtype=np.int64)
+    if lengths is not None:
+      rows = np.asarray(lengths.cpu() if hasattr(lengths, 'cpu') else lengths).astype(np.int64).reshape(-1)
+      if rows.shape[0] != n_utt or (n_utt and (rows.min() < 0 or rows.max() > most)):
+        raise ValueError('lengths must hold one value in [0, {}] per utterance.'.format(most))
+    table = np.zeros(n_utt, dtype=TENSOR_RECORD)
+    # (addresses lie below 2^63: int64 arithmetic)
+    table['data'] = np.int64(batch.data_ptr()) + np.arange(n_utt, dtype=np.int64) * (int(batch.stride(0)) * DTYPE_BYTES[code])
+    table['rows'] = rows
+    table['row_stride'] = max(int(batch.stride(1)), dim) if most <= 1 else int(batch.stride(1))
+    table['dtype'] = code
+    return table, [batch]
+  if lengths is not None:
+    raise ValueError('lengths belongs to a [U, T, D] tensor.')
+  table = np.zeros(len(source), dtype=TENSOR_RECORD)
+  keep = []
+  for u, t in enumerate(source):
+    if t is None:
+      table[u] = (0, 0, dim, UIS_DTYPE_F32, 0)
+      continue
+    t, code = _checked_tensor(t, 2, dim, device, '{}[{}]'.format(who, u))
+    keep.append(t)
+    rows = int(t.shape[0])
+    table[u] = (t.data_ptr() if rows else 0, rows, max(int(t.stride(0)), dim) if rows <= 1 else int(t.stride(0)), code, 0)
+  return table, keep
+
+
+def check_tensor_table(table, dim, capacity_rows=None):
+  """The library's checks of a uis_tensor list (uisrnn_hip.h), in its order, as ValueError: they hold before the
+  library is called, whoever built the table."""
+  codes, rows = table['dtype'], table['rows']
+  if len(table) and ((codes >= 0) & (codes <= 3)).all():   # (the usual case in a few array operations: nothing to report)
+    live, address = rows > 0, table['data'].view(np.int64)
+    if not ((rows < 0) | (live & ((address == 0) | (table['row_stride'] < dim) | (address % _ELEM_BYTES[codes] != 0)))).any():
+      total = int(rows.sum())
+      if capacity_rows is None or total <= capacity_rows:
+        return total
+  for u, rec in enumerate(table):
+    esz = DTYPE_BYTES.get(int(rec['dtype']))
+    if esz is None:
+      raise ValueError('tensor {} has an unknown dtype code {}.'.format(u, int(rec['dtype'])))
+    if rec['rows'] < 0:
+      raise ValueError('tensor {} has a negative row count.'.format(u))
+    if rec['rows'] == 0:
+      continue
+    if not rec['data']:
+      raise ValueError('tensor {} has rows but no data.'.format(u))
+    if rec['row_stride'] < dim:
+      raise ValueError('tensor {}: row_stride {} is below observation_dim {}.'.format(u, int(rec['row_stride']), dim))
+    if int(rec['data']) % esz:
+      raise ValueError('tensor {}: data is not aligned to its element size.'.format(u))
+  total = int(table['rows'].sum()) if len(table) else 0
+  if capacity_rows is not None and total > capacity_rows:
+    raise ValueError('{} rows given, capacity_rows is {}.'.format(total, capacity_rows))
+  return total
+
+
+def tensor_vector_flags(table, dim, out_ptr=0):
+  """Per block: whether k_ingest moves it with 16-byte loads and stores -- D a multiple of 4, the output base, the
+  block's base and its row pitch in bytes all multiples of 16 (the rule of ingest_vec_ok in csrc/uis_ingest.hip)."""
+  esz = np.array([DTYPE_BYTES[int(c)] for c in table['dtype']], dtype=np.int64)
+  return ((dim % 4 == 0) & (int(out_ptr) % 16 == 0) & (table['data'].astype(np.int64) % 16 == 0) &
+          ((table['row_stride'] * esz) % 16 == 0) & (table['rows'] > 0))
+
+
+def _table_ptr(table):
+  return ctypes.c_void_p(table.ctypes.data) if len(table) else None
+
+
 def _cut(flat, offsets):
   """A packed buffer as one array (a copy) per utterance."""
   return [flat[offsets[u]:offsets[u + 1]].copy() for u in range(len(offsets) - 1)]
@@ -329,6 +461,14 @@ def load_library(path=None):
   lib.uis_decode_f64.argtypes = [
       ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), i64p, i32, ctypes.POINTER(DecodeOpts),
       i32p, _fp, ctypes.POINTER(Stats)]
+  lib.uis_ingest_tensors.restype = i32
+  lib.uis_ingest_tensors.argtypes = [ctypes.c_void_p, ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+  lib.uis_tensors_decode.restype = i32
+  lib.uis_tensors_decode.argtypes = [
+      ctypes.c_void_p, ctypes.c_void_p, i32, ctypes.c_void_p, ctypes.POINTER(DecodeOpts), ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.POINTER(Stats)]
+  lib.uis_tensors_stream_push.restype = i32
+  lib.uis_tensors_stream_push.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
   lib.uis_last_decode_info.restype = i32
   lib.uis_last_decode_info.argtypes = [ctypes.c_void_p, i32p, _fp]
   lib.uis_last_decode_shape.restype = i32
@@ -442,6 +582,7 @@ EXPORTED_SYMBOLS = (
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
     'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_min_turn', 'uis_stream_speakers', 'uis_stream_bindings',
     'uis_session_min_turn', 'uis_session_get_min_turn', 'uis_session_turns',
+    'uis_ingest_tensors', 'uis_tensors_decode', 'uis_tensors_stream_push',
     'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
     'uis_train_get_params', 'uis_train_get_grads', 'uis_train_destroy')
@@ -896,6 +1037,81 @@ class Decoder:
     rc = self._lib.uis_stream_push(self._handle, frames.ctypes.data_as(_fp) if len(frames) else None, self._stream_counts_ptr)
     self._check(rc, 'uis_stream_push')
     self._stream_have += counts
+
+  def _producer(self, stream):
+    """producer_stream of the tensor entry points: `stream` (a raw hipStream_t as an int, 0: the default stream), or,
+    for None, the stream torch is issuing work to on this device at this moment."""
+    if stream is None:
+      import torch  # pylint: disable=import-outside-toplevel
+      stream = torch.cuda.current_stream(self.device).cuda_stream
+    return ctypes.c_void_p(int(stream) or None)
+
+  def ingest_tensors(self, source, lengths=None, out=None, stream=None):
+    """uis_ingest_tensors, the gather kernel alone: `source` as tensor_table takes it -> the packed float32
+    [sum rows, D] device tensor (`out`: written from its first row, must be contiguous and hold that many)."""
+    import torch  # pylint: disable=import-outside-toplevel
+    table, keep = tensor_table(source, self.observation_dim, lengths, self.device, 'tensors')
+    total = check_tensor_table(table, self.observation_dim, None if out is None else int(out.shape[0]))
+    if out is None:
+      out = torch.empty((total, self.observation_dim), dtype=torch.float32, device='cuda:{}'.format(self.device))
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.ndim != 2 or out.shape[1] != self.observation_dim:
+      raise ValueError('out must be a contiguous float32 [rows, D] tensor')
+    self._check(self._lib.uis_ingest_tensors(self._handle, _table_ptr(table), len(table), self._producer(stream),
+                                             ctypes.c_void_p(out.data_ptr() or None), int(out.shape[0])),
+                'uis_ingest_tensors', ok=(UIS_OK,))
+    del keep
+    return out[:total]
+
+  def decode_tensors(self, source, beam_size, look_ahead, test_iteration, max_clusters=0, flags=0, want_beam_scores=False,
+                     n_streams=0, level_cap=0, limits=None, bias=None, speakers=None, min_turn=None, lengths=None,
+                     stream=None):
+    """Decode utterances that live in device tensors (uis_tensors_decode): `source` and `lengths` as tensor_table
+    takes them, everything else as decode_f64.
+
+    Returns the dict of decode() with `labels` an int32 DEVICE tensor (packed in utterance order) and `scores` on the
+    host (float32 [U]; `scores_device`: the tensor they came from), and `empty` (bool [U]): the utterances whose beam
+    became empty -- their score is not finite, which no surviving hypothesis' is (every select drops such candidates)."""
+    import torch  # pylint: disable=import-outside-toplevel
+    table, keep = tensor_table(source, self.observation_dim, lengths, self.device)
+    total = check_tensor_table(table, self.observation_dim)
+    n_utt = len(table)
+    offsets = _offsets(table['rows'])
+    where = 'cuda:{}'.format(self.device)
+    labels = torch.empty(max(total, 1), dtype=torch.int32, device=where)
+    scores = torch.empty(max(n_utt, 1), dtype=torch.float32, device=where)
+    opts = make_opts(beam_size, look_ahead, test_iteration, max_clusters, flags, n_streams, level_cap)
+    producer = self._producer(stream)
+
+    def call(handle, blocks, _, count, *rest):   # (_run_decode's argument order, with the table in the frames' place)
+      return self._lib.uis_tensors_decode(handle, blocks, count, producer, *rest)
+
+    out = self._run_decode(call, 'uis_tensors_decode', opts, _table_ptr(table), offsets, offsets,
+                           ctypes.c_void_p(labels.data_ptr()), ctypes.c_void_p(scores.data_ptr()), limits, bias, speakers,
+                           min_turn)
+    del keep
+    host_scores = scores[:n_utt].cpu().numpy()
+    out.update(labels=labels[:total], scores=host_scores, scores_device=scores[:n_utt],
+               empty=~np.isfinite(host_scores) & (table['rows'] > 0))
+    return self._with_decode_info(out, n_utt, beam_size, want_beam_scores)
+
+  def stream_push_tensors(self, chunks, bias=None, speakers=None, stream=None, table=None):
+    """stream_push with the new frames in device tensors (uis_tensors_stream_push): a list with one [n_u, D] tensor
+    (or None) per utterance, or ONE [n_utt, n, D] tensor; float64, float32, float16 or bfloat16, any row stride.  The
+    frames never leave the device.  bias, speakers: as stream_push.  table: tensor_table's result for these chunks, where
+    the caller has already made it."""
+    if len(chunks) != self._stream_n:
+      raise ValueError('one chunk (or None) per utterance')
+    table, keep = table or tensor_table(chunks, self.observation_dim, None, self.device, 'chunks')
+    if isinstance(chunks, (list, tuple)):   # (the table of one checked [U, n, D] tensor holds nothing a check could find)
+      check_tensor_table(table, self.observation_dim)
+    if bias is not None:
+      self.set_frame_bias(bias)
+    if speakers is not None:
+      self.set_stream_speakers(speakers)
+    rc = self._lib.uis_tensors_stream_push(self._handle, _table_ptr(table), self._producer(stream))
+    self._check(rc, 'uis_tensors_stream_push')
+    del keep
+    self._stream_have += table['rows']
 
   def stream_received(self):
     """Frames per utterance the open session holds (pushed or primed, not yet committed): int64 [n_utt]."""

@@ -32,6 +32,7 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_blob.h'),
     os.path.join(_HERE, 'csrc', 'uis_call_tables.h'),
     os.path.join(_HERE, 'csrc', 'uis_stream.hip'),
+    os.path.join(_HERE, 'csrc', 'uis_ingest.hip'),
     os.path.join(_HERE, 'csrc', 'uis_workspace.hip'),
     os.path.join(_ROOT, 'include', 'uis_numerics.h'),
     os.path.join(_ROOT, 'include', 'uisrnn_hip.h'),

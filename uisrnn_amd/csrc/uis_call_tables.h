@@ -5,13 +5,14 @@
 //
 // Which entry point does what (tests/test_gpu_call_tables.py pins it from outside):
 //   entry points                                  limits  bias    hint    stream_tags  min_turn
-//   uis_decode, uis_decode_f64, uis_decode_device take    take    take    leave        take
+//   uis_decode, uis_decode_f64, uis_decode_device,
+//   uis_tensors_decode                            take    take    take    leave        take
 //   uis_score_labels, uis_score_speakers          leave   take    refuse  leave        refuse
 //   uis_stream_begin                              take    leave   refuse  leave        refuse
-//   uis_stream_push                               leave   take    refuse  take         refuse
+//   uis_stream_push, uis_tensors_stream_push      leave   take    refuse  take         refuse
 //   uis_stream_prime                              leave   refuse  refuse  take         refuse
 //   every other uis_stream_* call                 leave   leave   refuse  leave        refuse
-//   everything else                               begins no call: touches nothing
+//   everything else (uis_ingest_tensors too)      begins no call: touches nothing
 // A new entry point picks a rule; a new table adds a column.
 #ifndef UIS_CALL_TABLES_H_
 #define UIS_CALL_TABLES_H_

@@ -199,6 +199,9 @@ struct HandleMem {
   // the posterior readout's own (a following n-best readout finds its buffers as it left them): results, offset tables,
   // the per-group partial rows of k_posterior; the label table and scores k_nbest_window fills for k_posterior_window
   DevBuf ps_conf, ps_change, ps_weights, ps_counts, ps_off, ps_part, ps_labels, ps_scores;
+  // k_ingest's descriptor table (uis_ingest.hip): the pinned block it is built in and its device copy, one H2D per call
+  DevBuf ingest_tab;
+  HostBuf h_ingest;
 };
 
 // Which kernel-table entry a lookup returned (find_kernel fills it from the entry it found): the record behind
@@ -288,6 +291,7 @@ struct uis_handle : HandleMem {
   void* cast_pool = nullptr;  // CastPool: the threads that cast (created by the first uis_decode_f64)
   ProfileEvents prof;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_pre = nullptr;
+  hipEvent_t ev_producer = nullptr;  // recorded on the caller's stream by the tensor entry points (created by the first of them)
   // utterance groups: one stream + one cached step graph each
   std::vector<hipStream_t> gstreams;
   std::vector<hipEvent_t> gdone;
@@ -2133,6 +2137,7 @@ UIS_EXPORT void uis_destroy(uis_handle* h) {
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
   if (h->ev_pre) (void)hipEventDestroy(h->ev_pre);
+  if (h->ev_producer) (void)hipEventDestroy(h->ev_producer);
   for (GraphCache& gc : h->gcache) if (gc.exec) (void)hipGraphExecDestroy(gc.exec);
   for (hipEvent_t e : h->gdone) (void)hipEventDestroy(e);
   for (hipStream_t sg : h->gstreams) { (void)hipStreamSynchronize(sg); (void)hipStreamDestroy(sg); }
@@ -2294,6 +2299,49 @@ UIS_EXPORT int32_t uis_decode_device(uis_handle* h, const float* d_frames, const
   if (int rc = begin_call(h, "uis_decode_device", UIS_RULE_DECODE)) return rc;
   if (h) h->poison = UisPoison::from_env();
   return decode_impl(h, d_frames, offsets, n_utt, opts, d_labels_out, d_scores_out, stats);
+}
+
+// ------------------------------------------------------------------ device tensors in
+#include "uis_ingest.hip"
+
+UIS_EXPORT int32_t uis_ingest_tensors(uis_handle* h, const uis_tensor* blocks, int32_t n, void* producer_stream,
+                                      float* d_frames_out, int64_t capacity_rows) {
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  int64_t F = 0;
+  if (int rc = ingest_validate("uis_ingest_tensors", blocks, n, h->m.D, &F)) return rc;
+  if (F > capacity_rows) return fail(UIS_ERR_INVALID_ARG, "uis_ingest_tensors: " + std::to_string((long long)F) + " rows given, capacity_rows is " + std::to_string((long long)capacity_rows));
+  if (F > 0 && !d_frames_out) return fail(UIS_ERR_INVALID_ARG, "uis_ingest_tensors: d_frames_out is null");
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = ingest_enqueue(h, blocks, n, F, producer_stream, d_frames_out, UisPoison::from_env())) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return UIS_OK;
+}
+
+UIS_EXPORT int32_t uis_tensors_decode(uis_handle* h, const uis_tensor* utterances, int32_t n_utt, void* producer_stream,
+                                      const uis_decode_opts* opts, int32_t* d_labels_out, float* d_scores_out,
+                                      uis_stats* stats) {
+  static const char who[] = "uis_tensors_decode";
+  if (int rc = begin_call(h, who, UIS_RULE_DECODE)) return rc;  // (the rule of every decode)
+  if (!h) return fail(UIS_ERR_INVALID_ARG, "null handle");
+  h->nb_valid = false;  // (as uis_decode: a decode refused below leaves nothing for uis_last_decode_nbest)
+  h->last_U = 0; h->last_B = 0;
+  int64_t F = 0;
+  if (int rc = ingest_validate(who, utterances, n_utt, h->m.D, &F)) return rc;
+  if (!opts) return fail(UIS_ERR_INVALID_ARG, "null opts");
+  if (h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "a streaming session is open on this handle (uis_stream_end first)");
+  std::vector<int64_t> offsets((size_t)n_utt + 1, 0);
+  for (int u = 0; u < n_utt; ++u) offsets[u + 1] = offsets[u] + utterances[u].rows;
+  HIPCHK(hipSetDevice(h->device));
+  if (int rc = h->io_frames.ensure((size_t)std::max<int64_t>(F, 1) * h->m.D * 4)) return rc;
+  h->poison = UisPoison::from_env();
+  HIPCHK(h->poison.device(h->io_frames.p, h->io_frames.cap, h->stream));
+  h->io_offsets.clear();  // (the labels go to the caller's tensor: nothing for uis_eval_last_decode)
+  // the gather runs on the handle's stream, where the decode's first kernels follow it
+  if (int rc = ingest_enqueue(h, utterances, n_utt, F, producer_stream, h->io_frames.as<float>(), h->poison)) return rc;
+  const int rc = decode_impl(h, h->io_frames.as<float>(), offsets.data(), n_utt, opts, d_labels_out, d_scores_out, stats);
+  // (a decode refused for its arguments has not waited for the gather: the caller's tensors are free on return)
+  if (rc != UIS_OK && rc != UIS_ERR_CLUSTER_CAP) (void)hipStreamSynchronize(h->stream);
+  return rc;
 }
 
 UIS_EXPORT int32_t uis_decode(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,

@@ -403,7 +403,11 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   SALLOC(st.beam_score, n.beam, false);
   SALLOC(st.beam_slot, n.beam_lists, false);
   SALLOC(st.beam_blk, n.beam_lists, false);
-  SALLOC(st.bp, (size_t)U * max_frames * B, false);  // (a record per frame of the session's capacity; a decode's: per step of the frames given)
+  // (a record per frame of the session's capacity; a decode's: per step of the frames given.  The table starts as zeros
+  // -- under UIS_POISON_WORKSPACE as the poison word: the record word of a dead rank is never written, and
+  // uis_stream_export copies the records verbatim, so without a defined start two sessions with the same history could
+  // export different bytes)
+  SALLOC(st.bp, (size_t)U * max_frames * B, !ss.poison.on);
   SALLOC(st.rows, n.rows, true);
   SALLOC(st.nrows, n.nrows, true);
   SALLOC(st.gi_up, n.gi_up, false);
@@ -481,11 +485,14 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   return UIS_OK;
 }
 
-UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
-  if (int rc = begin_call(h, "uis_stream_push", UIS_RULE_STREAM_PUSH)) return rc;  // (this push's tables, in the chunk's own frame order)
-  if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
+namespace {
+
+// One push, whoever brings the frames: `frames` (uis_stream_push: host float32, utterance after utterance) or `chunks`
+// (uis_tensors_stream_push: one device tensor per utterance, gathered by k_ingest into the chunk's frame area) -- exactly
+// one of the two is given.  The caller has begun the call and checked the handle and the session.
+int stream_push_impl(uis_handle* h, const char* who, const float* frames, const uis_tensor* chunks, void* producer_stream,
+                     const int32_t* counts) {
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   const DevModel& m = h->m;
   const int U = ss.U;
   int64_t F = 0, max_new = 0;
@@ -510,15 +517,15 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if (h->tables.stream_tags.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
   for (int u = 0; u < U; ++u)
-    if (int rct = table_status(CallTables::check_tagged_frames("uis_stream_push", ss.tagged || h->tables.tagged, u, ss.committed[u] + ss.have[u] + counts[u]))) return rct;
+    if (int rct = table_status(CallTables::check_tagged_frames(who, ss.tagged || h->tables.tagged, u, ss.committed[u] + ss.have[u] + counts[u]))) return rct;
   if (F == 0) return UIS_OK;
-  if (!frames) return fail(UIS_ERR_INVALID_ARG, "frames is null");
+  if (!frames && !chunks) return fail(UIS_ERR_INVALID_ARG, "frames is null");
   HIPCHK(hipSetDevice(h->device));
   int rc;
 #if defined(UIS_PM_TIMING)
   const double t_enter = pm_now_s();
 #endif
-  bool pm_fits = ss.persist && !h->resident_off;
+  bool pm_fits = ss.persist && !h->resident_off && !chunks;  // (tensors never reach a persistent session)
   if (pm_fits) {  // every cluster's new frames must fit its fixed row range
     const int ncl = ss.st.ncl;
     for (int c = 0; c < ncl && pm_fits; ++c) {
@@ -577,11 +584,14 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
     ss.persist = false;  // the cooperative launch was refused: ordinary launches from here on
   }
   if (ss.pm_running && (rc = pm_quit(h))) return rc;
-  // ---- one staging block, one H2D: [foff][avail][frames]
-  const size_t hdr = (size_t)U * 8 + (((size_t)U * 4 + 15) & ~(size_t)15);
+  // ---- one staging block, one H2D: [foff][avail][frames]; tensors: [k_ingest's table][foff][avail] travel, and the
+  // frame area behind them is written by the gather (the table is a multiple of 16 bytes: the rest lies as it did)
+  const size_t lead = chunks ? (size_t)U * sizeof(IngestBlock) : 0;
+  const size_t hdr = lead + (size_t)U * 8 + (((size_t)U * 4 + 15) & ~(size_t)15);
   const size_t need = hdr + (size_t)F * m.D * 4;
-  if (need > ss.h_stage.cap) {  // (with head-room: pushes of a session vary in size)
-    hipError_t e = ss.h_stage.ensure(need + need / 4 + 4096, hipHostMallocDefault);
+  const size_t staged = chunks ? hdr : need;
+  if (staged > ss.h_stage.cap) {  // (with head-room: pushes of a session vary in size)
+    hipError_t e = ss.h_stage.ensure(staged + staged / 4 + 4096, hipHostMallocDefault);
     if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
   }
   if ((rc = ss.chunk_x.ensure(need))) return rc;
@@ -607,8 +617,8 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   if (h->tables.stream_tags.call_set)
     HIPCHK(hipMemcpyAsync(ss.chunk_hint.p, h->tables.stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
   ss.tagged = ss.tagged || h->tables.tagged;
-  int64_t* h_foff = ss.h_stage.as<int64_t>();
-  int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + (size_t)U * 8);
+  int64_t* h_foff = reinterpret_cast<int64_t*>(ss.h_stage.as<char>() + lead);
+  int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + lead + (size_t)U * 8);
   {
     int64_t pos = 0;
     for (int u = 0; u < U; ++u) {
@@ -617,10 +627,13 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
       h_avail[u] = ss.have[u] + counts[u];
     }
   }
-  memcpy(ss.h_stage.as<char>() + hdr, frames, (size_t)F * m.D * 4);
-  HIPCHK(hipMemcpyAsync(ss.chunk_x.p, ss.h_stage.p, need, hipMemcpyHostToDevice, h->stream));
-  ss.d_foff = ss.chunk_x.as<int64_t>();
-  ss.d_avail = reinterpret_cast<int32_t*>(ss.chunk_x.as<char>() + (size_t)U * 8);
+  if (frames) memcpy(ss.h_stage.as<char>() + hdr, frames, (size_t)F * m.D * 4);
+  else ingest_fill_table(ss.h_stage.as<IngestBlock>(), chunks, U, m.D, reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr));
+  HIPCHK(hipMemcpyAsync(ss.chunk_x.p, ss.h_stage.p, staged, hipMemcpyHostToDevice, h->stream));
+  if (chunks && (rc = ingest_launch(h, ss.chunk_x.as<IngestBlock>(), U, F, producer_stream, reinterpret_cast<float*>(ss.chunk_x.as<char>() + hdr))))
+    return rc;
+  ss.d_foff = reinterpret_cast<int64_t*>(ss.chunk_x.as<char>() + lead);
+  ss.d_avail = reinterpret_cast<int32_t*>(ss.chunk_x.as<char>() + lead + (size_t)U * 8);
   ss.st.foff = ss.d_foff;
   ss.st.avail = ss.d_avail;
   const float* d_x = reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr);
@@ -692,6 +705,35 @@ UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int
   for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
   ss.steps_run += max_new;
   return UIS_OK;
+}
+
+}  // namespace
+
+UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
+  if (int rc = begin_call(h, "uis_stream_push", UIS_RULE_STREAM_PUSH)) return rc;  // (this push's tables, in the chunk's own frame order)
+  if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
+  if (!h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
+  return stream_push_impl(h, "uis_stream_push", frames, nullptr, nullptr, counts);
+}
+
+UIS_EXPORT int32_t uis_tensors_stream_push(uis_handle* h, const uis_tensor* chunks, void* producer_stream) {
+  static const char who[] = "uis_tensors_stream_push";
+  if (int rc = begin_call(h, who, UIS_RULE_STREAM_PUSH)) return rc;  // (uis_stream_push's rule: this push's tables)
+  if (!h || !chunks) return fail(UIS_ERR_INVALID_ARG, "null handle/chunks");
+  uis_handle::Stream& ss = h->stream_state;
+  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
+  // (the resident launch of a UIS_FLAG_PERSISTENT session takes its frames from the host mailbox)
+  if (ss.st.flags & UIS_FLAG_PERSISTENT)
+    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no device tensors (uis_tensors_stream_push): its frames travel "
+                                     "through the host mailbox; use uis_stream_push");
+  int64_t F = 0;
+  if (int rc = ingest_validate(who, chunks, ss.U, h->m.D, &F)) return rc;
+  std::vector<int32_t> counts((size_t)ss.U);
+  for (int u = 0; u < ss.U; ++u) {
+    if (chunks[u].rows > 0x7fffff00LL) return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames");
+    counts[u] = (int32_t)chunks[u].rows;
+  }
+  return stream_push_impl(h, who, nullptr, chunks, producer_stream, counts.data());
 }
 
 UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {

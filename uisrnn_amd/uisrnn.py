@@ -289,8 +289,9 @@ def _sequences_with_ids(test_sequences, cluster_ids, name):
 
 
 def _chunk_sizes(chunks):
-  """Frames per utterance of a push: of one [U, n, D] array, or of a list with an array (or None) per utterance."""
-  if isinstance(chunks, np.ndarray) and chunks.ndim == 3:
+  """Frames per utterance of a push: of one [U, n, D] array (or device tensor), or of a list with an array (or None)
+  per utterance."""
+  if not isinstance(chunks, (list, tuple)) and getattr(chunks, 'ndim', 0) == 3:
     return [int(chunks.shape[1])] * len(chunks)
   return [0 if c is None else len(c) for c in chunks]
 
@@ -577,7 +578,7 @@ class UISRNN:
     return results[0] if single else results
 
   def _decode_batch(self, sequences, args, flags=0, device=None, decoder=None, level_cap=0, n_best=0, posterior=None,
-                    limits=None, bias=None, speakers=None, min_turn=None):
+                    limits=None, bias=None, speakers=None, min_turn=None, tensors=False, scores_out=None):
     """Decode a list of validated sequences in one lock-step batch.
 
     `decoder` (a _capi.Decoder built from self.params) overrides the model's own handle for
@@ -592,8 +593,12 @@ class UISRNN:
     follows the same regroupings.
     speakers (_check_known_speakers): None, or one uint8 array per sequence: the known speakers' tags, likewise.
     min_turn (_check_min_turn): None, or one int per sequence (0 and 1 = no rule): the minimum turn lengths, likewise.
+    tensors (predict_tensors): the sequences are [N_u, D] device tensors; every decode call is decoder.decode_tensors in
+    the place of decode_f64 and an utterance's result is its int32 device tensor, a view of that call's label tensor.
+    scores_out: None, or a list with one slot per sequence that receives each utterance's score (a numpy float32).
     """
     decoder = decoder or self._get_decoder(device)
+    decode_call = decoder.decode_tensors if tensors else decoder.decode_f64
 
     def take(members):
       """What one decode call is handed for these sequences: the arrays, and their entries of limits, bias, speakers
@@ -651,8 +656,8 @@ class UISRNN:
         sub_off = np.zeros(len(pending) + 1, dtype=np.int64)
         sub_off[1:] = np.cumsum([s.shape[0] for s in sub])
         try:
-          out = decoder.decode_f64(sub, args.beam_size, args.look_ahead, args.test_iteration,
-                                   max_clusters=cap, flags=flags, level_cap=level_cap, **tables)
+          out = decode_call(sub, args.beam_size, args.look_ahead, args.test_iteration,
+                            max_clusters=cap, flags=flags, level_cap=level_cap, **tables)
         except _capi.HipLibraryError as err:
           if err.status == _capi.UIS_ERR_OOM and len(pending) > 1:
             # the decode state of this many utterances does not fit the device (or the pinned staging
@@ -721,14 +726,17 @@ class UISRNN:
             still.append(u)
           else:
             labels = out['labels'][sub_off[k]:sub_off[k + 1]]
-            if labels.size and labels[0] < 0:
+            # (device labels are not read back for this: decode_tensors names the emptied beams by their scores)
+            if out['empty'][k] if tensors else (labels.size and labels[0] < 0):
               # every candidate of some step was non-finite (nan/inf in the input or the
               # weights): the reference ends up indexing an empty beam_set
               # (uisrnn/uisrnn.py:561) and raises the same exception type
               raise EmptyBeamError('the beam became empty (max() arg is an empty sequence / list '
                                    'index out of range in the reference): non-finite scores in '
                                    'utterance {}'.format(u))
-            results[u] = labels.tolist()
+            results[u] = labels if tensors else labels.tolist()
+            if scores_out is not None:
+              scores_out[members[u]] = out['scores'][k]
             if hyps is not None and labels.size:
               live = int(hyps['counts'][k])
               results[u] = ([row.tolist() for row in hyps['labels'][k][:live]],
@@ -890,6 +898,62 @@ class UISRNN:
         have); the exception names them and carries the other utterances' results.
     """
     return self._predict(test_sequences, args, max_speakers, transition_bias, known_speakers, min_turn)
+
+  def predict_tensors(self, test_sequences, args, lengths=None, max_speakers=None, transition_bias=None,
+                      known_speakers=None, min_turn=None, return_scores=False):
+    """predict for embeddings that already live on the model's GPU (extension): no copy to the
+    host, no cast there, no copy back.
+
+    Args:
+      test_sequences: one [N, D] torch tensor, a list of [N_u, D] tensors, or one [U, T, D] tensor with `lengths`
+        (one int per utterance, its frames; None: T) -- on the model's device, of dtype float64, float32, float16 or
+        bfloat16, with any row stride (a slice of a padded batch, a [:, :D] view); a non-unit inner stride is made
+        contiguous here.  The tensors may have been written on torch's current stream just before: the library orders
+        itself behind that stream.
+      args, max_speakers, transition_bias, known_speakers, min_turn: as predict.
+      return_scores: also return each utterance's score (the best hypothesis' negative log-likelihood).
+
+    Returns:
+      int32 device tensors of labels, one per utterance (views of one label tensor unless a retry decoded some
+      utterances again); for a single [N, D] tensor its one tensor.  With return_scores: (labels, scores), scores a
+      float32 numpy array (for a single tensor: its one number).  Bit for bit what predict returns for
+      t.double().cpu().numpy().
+
+    Raises:
+      TypeError: something that is no torch tensor, an integer or other unsupported dtype, a CPU tensor.
+      ValueError: a tensor on another device, a wrong rank or observation dimension, bad lengths; the table errors of
+        predict.  All before the library is called.  EmptyBeamError, LookAheadWindowError: as predict.
+    """
+    import torch  # pylint: disable=import-outside-toplevel
+    dim, device = self.observation_dim, self.device_index
+    single = isinstance(test_sequences, torch.Tensor) and test_sequences.ndim == 2
+    if isinstance(test_sequences, torch.Tensor):
+      if single:
+        if lengths is not None:
+          raise ValueError('lengths belongs to a [U, T, D] tensor.')
+        seqs = [_capi._checked_tensor(test_sequences, 2, dim, device, 'test_sequences')[0]]  # pylint: disable=protected-access
+      else:
+        table, _ = _capi.tensor_table(test_sequences, dim, lengths, device)
+        seqs = [test_sequences[u, :int(n)] for u, n in enumerate(table['rows'])]
+    elif isinstance(test_sequences, list):
+      if lengths is not None:
+        raise ValueError('lengths belongs to a [U, T, D] tensor.')
+      seqs = [_capi._checked_tensor(t, 2, dim, device, 'test_sequences[{}]'.format(u))[0]  # pylint: disable=protected-access
+              for u, t in enumerate(test_sequences)]
+    else:
+      raise TypeError('test_sequences should be either a list of torch tensors or a torch tensor.')
+    sizes = [int(s.shape[0]) for s in seqs]
+    tables = {'limits': _check_max_speakers(max_speakers, args, len(seqs)),
+              'bias': _check_transition_bias(transition_bias, sizes, single=single),
+              'speakers': _check_known_speakers(known_speakers, sizes, single=single),
+              'min_turn': _check_min_turn(min_turn, len(seqs))}
+    if not seqs:
+      return ([], np.zeros(0, dtype=np.float32)) if return_scores else []
+    scores = [None] * len(seqs) if return_scores else None
+    results = self._decode_batch(seqs, args, tensors=True, scores_out=scores, **tables)
+    if single:
+      return (results[0], scores[0]) if return_scores else results[0]
+    return (results, np.array(scores, dtype=np.float32)) if return_scores else results
 
   def predict_nbest(self, test_sequences, args, n_best=None, max_speakers=None, transition_bias=None,
                     known_speakers=None, min_turn=None):
@@ -1364,7 +1428,7 @@ class OnlineSession:
     """push's transition_bias as the library's flat table: the chunk's frames, utterance by utterance."""
     if transition_bias is None:
       return None
-    if (isinstance(chunks, np.ndarray) and chunks.ndim == 3 and
+    if (not isinstance(chunks, (list, tuple)) and getattr(chunks, 'ndim', 0) == 3 and
         isinstance(transition_bias, np.ndarray) and transition_bias.ndim == 2):
       transition_bias = list(transition_bias)   # ([U, n] beside [U, n, D]: one row per utterance)
     tables = _check_transition_bias(transition_bias, _chunk_sizes(chunks), offline=False)
@@ -1422,6 +1486,33 @@ class OnlineSession:
         raise
       return
     self._decoder.stream_push(chunks, **extra)
+
+  def push_tensors(self, chunks, transition_bias=None, known_speakers=None):
+    """push for frames that already live on the model's GPU: a list with one [n, D] torch tensor
+    (or None) per utterance, or one [U, n, D] tensor -- float64, float32, float16 or bfloat16, any row stride.  The
+    frames never leave the device; room-making, the retire policy, transition_bias and known_speakers work as in push,
+    and the stream is bit for bit the one push gives for the same values.  A persistent session takes its frames
+    through the host: ValueError at once, the session untouched.  TypeError / ValueError as predict_tensors, before the
+    library is called."""
+    if self.persistent:
+      raise ValueError('a persistent session takes no device tensors (its frames travel through the host mailbox): use '
+                       'push, or open the session with persistent=False.')
+    if len(chunks) != self._num_utterances:
+      raise ValueError('one chunk (or None) per utterance')
+    # (the checks of every tensor, before any table is built or any room is made)
+    table = _capi.tensor_table(chunks, self._model.observation_dim, None, self._model.device_index, 'chunks')
+    bias = self._push_bias(chunks, transition_bias)
+    extra = {} if bias is None or not bias.size else {'bias': bias}
+    speakers, names = self._speaker_tags(_chunk_sizes(chunks), known_speakers)
+    if speakers is not None:
+      extra['speakers'] = speakers
+    if names is not None:
+      self._names = names
+    if self._retire_at is not None:
+      self._keep_under_cap(chunks)
+    if self._horizon is not None:
+      self._make_room(chunks)
+    self._decoder.stream_push_tensors(chunks, table=table, **extra)
 
   def _make_room(self, chunks):
     """horizon given: a push whose chunk does not fit the window commits first."""
@@ -1856,6 +1947,10 @@ class StreamPool:
     transition_bias: None, a number, or a dict {key: array of the chunk's length} for the streams that have values of
     their own (OnlineSession.push).  known_speakers: None, or a dict {key: sequence of names (None: unknown) of the
     chunk's length} for the streams that have some (OnlineSession.push)."""
+    self._per_slot_push(self._session.push, chunks, transition_bias, known_speakers)
+
+  def _per_slot_push(self, push, chunks, transition_bias, known_speakers):
+    """push / push_tensors: the dicts by key as the session's lists by slot, then the session's own call."""
     per_slot = [None] * self._session._num_utterances  # pylint: disable=protected-access
     for key, chunk in chunks.items():
       per_slot[self._slot[key]] = chunk
@@ -1871,7 +1966,12 @@ class StreamPool:
       for key, values in known_speakers.items():
         names_slot[self._slot[key]] = values
       known_speakers = names_slot
-    self._session.push(per_slot, transition_bias, known_speakers)
+    push(per_slot, transition_bias, known_speakers)
+
+  def push_tensors(self, chunks, transition_bias=None, known_speakers=None):
+    """push with the streams' new frames in device tensors: a dict {key: [n, D] torch tensor}; transition_bias and
+    known_speakers as push (OnlineSession.push_tensors)."""
+    self._per_slot_push(self._session.push_tensors, chunks, transition_bias, known_speakers)
 
   def speakers(self, key):
     """{name: label} of the stream's known speakers (OnlineSession.speakers for its slot)."""
