@@ -18,6 +18,7 @@ DEPENDS = SOURCES + [
     os.path.join(_HERE, 'csrc', 'uis_kernels.hip'),
     os.path.join(_HERE, 'csrc', 'uis_kernels.h'),
     os.path.join(_HERE, 'csrc', 'uis_poison.h'),
+    os.path.join(_HERE, 'csrc', 'uis_push_layout.h'),
     os.path.join(_HERE, 'csrc', 'uis_select_rs.hip'),
     os.path.join(_HERE, 'csrc', 'uis_eval.hip'),
     os.path.join(_HERE, 'csrc', 'uis_score.hip'),

@@ -32,6 +32,7 @@
 #include "uis_poison.h"
 #include "uis_blob.h"
 #include "uis_call_tables.h"
+#include "uis_push_layout.h"
 #include "uis_kernels.hip"
 #include "uis_eval.hip"
 #include "uisrnn_hip.h"
@@ -158,17 +159,41 @@ struct ProfileEvents {
   size_t used = 0;
 };
 
+// The chunk of a streaming push: the frames it brings and what is formed of them once per chunk, a row per frame.  Grow only; a UIS_FLAG_PERSISTENT session takes it at full size when it opens.
+struct Chunk {
+  // one push = one H2D copy: the block ChunkLayout describes ([k_ingest's table, tensors only][foff][avail][frames]) is
+  // built in `stage` (pinned; for tensors without the frames, which the gather writes) and mirrored at the front of `x`
+  HostBuf stage;
+  // pad [rows][Dp] float32: the frames padded, where D != Dp; gi0 [rows][G], mse0 [rows] float32: the chunk's input
+  // projection; bias [rows][3] float64: DecodeState::bias3 of a push with a uis_frame_bias table; hint [rows] uint8:
+  // DecodeState::hint of a push with a uis_stream_speakers table
+  DevBuf x, pad, gi0, mse0, bias, hint;
+  // what a push of this layout needs; bias / hint where it has that table, the staging block (with head-room: pushes of
+  // a session vary in size) unless the frames travel through the mailbox
+  int ensure(const ChunkLayout& lay, size_t F, const DevModel& m, bool with_bias, bool with_hint, bool staged = true) {
+    const size_t travel = staged && lay.travel_bytes > stage.cap ? lay.travel_bytes + lay.travel_bytes / 4 + 4096 : 0;
+    if (hipError_t e = stage.ensure(travel, hipHostMallocDefault)) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    int rc;
+    if ((rc = x.ensure(lay.total_bytes)) || (rc = gi0.ensure(F * m.G * 4)) || (rc = mse0.ensure(F * 4)) ||
+        (with_bias && (rc = bias.ensure(F * 24))) || (with_hint && (rc = hint.ensure(F)))) return rc;
+    return m.D != m.Dp ? pad.ensure(F * m.Dp * 4) : UIS_OK;
+  }
+  // UIS_POISON_WORKSPACE: all of it, ahead of the defining writes
+  hipError_t poison(const UisPoison& p, hipStream_t stream) {
+    p.host(stage.p, stage.cap);
+    for (DevBuf* b : {&x, &gi0, &mse0, &bias, &hint, &pad})
+      if (hipError_t e = p.device(b->p, b->cap, stream)) return e;
+    return hipSuccess;
+  }
+};
+
 // What a streaming session owns: one move-assignment of a fresh one frees it all.
 struct StreamMem {
   std::vector<DevBuf> allocs;  // the session's state, one allocation per table (uis_stream_begin)
-  DevBuf chunk_x, chunk_pad, chunk_gi0, chunk_mse0, labels, scores;
-  DevBuf chunk_bias;  // [chunk frames][3] float64: DecodeState::bias3 of a push with a uis_frame_bias table
-  DevBuf chunk_hint;  // [chunk frames] uint8: DecodeState::hint of a push with a uis_stream_speakers table
-  // one push = one H2D copy: [foff U x int64][avail U x int32, padded][frames] staged in pinned
-  // host memory (h_stage) and mirrored in chunk_x
-  HostBuf h_stage;
-  HostBuf pm_block;  // the persistent launch's mailbox (host-coherent)
-  HostBuf h_land;    // uis_stream_commit's pinned landing block
+  Chunk chunk;
+  DevBuf labels, scores;  // uis_stream_labels' back-trace
+  HostBuf pm_block;  // the persistent launch's mailbox (host-coherent; MailboxLayout)
+  HostBuf h_land;    // the pinned landing block of every scaffold call's one download (session_buffers)
 };
 
 // Every device and pinned buffer of a handle outside its session, likewise.
@@ -254,12 +279,9 @@ struct uis_handle : HandleMem {
     std::vector<int32_t> min_turn;
     int32_t* d_min_turn = nullptr;
     DecodeState st{};
-    int32_t* d_avail = nullptr;
     int32_t* d_have = nullptr;        // frames received per utterance, refreshed for every back-trace
-    int64_t* d_foff = nullptr;
     int64_t* d_lab_off = nullptr;
     float* d_beam_scores = nullptr;
-    int64_t steps_run = 0;
     // one-launch steps (k_decode_resident per push) where the shape allows it
     bool resident = false;
     bool coop_checked = false;        // one push of this session already went through the cooperative launch
@@ -270,16 +292,12 @@ struct uis_handle : HandleMem {
     bool persist = false;             // the session asked for it and its shape allows it
     bool pm_running = false;          // the launch is on the device
     uint32_t pm_seq = 0;              // commands issued to the running launch
-    int64_t pm_cap_frames = 0;        // rows of the mailbox's frame area = ncl * pm_cluster_rows
-    int64_t pm_cluster_rows = 0;      // each cluster's FIXED share of the chunk buffers (rows), see uis_stream_begin
-    size_t pm_o_foff = 0, pm_o_avail = 0, pm_o_laboff = 0, pm_o_frames = 0, pm_o_labels = 0, pm_o_scores = 0,
-           pm_o_bscores = 0, pm_o_overflow = 0;
+    MailboxLayout mailbox;            // where everything lies in pm_block, and each cluster's fixed share of the chunk's rows
     unsigned long long* d_go = nullptr;
     unsigned char* d_hdr = nullptr;
     PersistArgs pm_args{};            // host copy of what d_pm_args holds
     PersistArgs* d_pm_args = nullptr;
-    size_t hdr_stride = 0;
-    int64_t pm_launches = 0, pm_commands = 0;
+    int64_t pm_launches = 0;
     UisPoison poison;                 // UIS_POISON_WORKSPACE as uis_stream_begin / the running uis_stream_push read it
     // a push, a prime or an import has given the session a non-zero speaker tag (uis_stream_speakers): from then on, and
     // until uis_stream_end, no utterance may reach 2^24 frames received (the tag shares the block-count word)

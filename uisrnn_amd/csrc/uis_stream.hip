@@ -13,16 +13,17 @@
 namespace {
 
 // One table of the session's state: an allocation of its own (the persistent launch's fixed row ranges and the L2
-// note in uis_stream_begin are why a session's addresses are left alone: no arena here).
+// note in alloc_persistent are why a session's addresses are left alone: no arena here).
 template <typename T>
 int stream_alloc(uis_handle* h, T** out, size_t count, bool zero = false) {
   DevBuf b;
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
   if (int rc = b.alloc(bytes)) return rc;
-  *out = b.as<T>();
+  void* const p = b.p;
+  *out = static_cast<T*>(p);  // (T may be const: a table DecodeState's kernels only read)
   h->stream_state.allocs.push_back(std::move(b));
-  HIPCHK(h->stream_state.poison.device(*out, bytes, h->stream));  // (UIS_POISON_WORKSPACE: ahead of the block's defining writes)
-  if (zero) HIPCHK(hipMemsetAsync(*out, 0, bytes, h->stream));
+  HIPCHK(h->stream_state.poison.device(p, bytes, h->stream));  // (UIS_POISON_WORKSPACE: ahead of the block's defining writes)
+  if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, h->stream));
   return UIS_OK;
 }
 
@@ -47,6 +48,23 @@ unsigned long long pm_idle_ticks() {
   return (unsigned long long)(ms * 1e5);  // s_memrealtime ticks of 10 ns
 }
 
+// The abort word of the one-launch kernels (DecodeState::cl_abort = d_ctl + 16): non-zero once an in-launch barrier gave
+// up, after which the session's state is not trustworthy any more.  Read behind the launch on the handle's stream and
+// waited for (a push: its one synchronisation), or by a blocking copy where the stream is known to be drained
+// (pm_reap, which then also gives the launch that stays up for this handle); `where` completes the message.
+int launch_aborted(uis_handle* h, bool behind_launch, const char* where) {
+  uint32_t word = 0;
+  if (behind_launch) {
+    HIPCHK(hipMemcpyAsync(&word, h->stream_state.d_ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  } else {
+    HIPCHK(hipMemcpy(&word, h->stream_state.d_ctl + 16, 4, hipMemcpyDeviceToHost));
+  }
+  if (!word) return UIS_OK;
+  if (!behind_launch) { h->stream_state.persist = false; h->resident_off = true; }
+  return fail(UIS_ERR_HIP, std::string("in-launch barrier failed ") + where + "; close the session (uis_stream_end) and reopen it with UIS_FLAG_STEPWISE");
+}
+
 // After the launch has ended (every cluster left, or an in-launch barrier gave up): look at the abort word.
 int pm_reap(uis_handle* h) {
   uis_handle::Stream& ss = h->stream_state;
@@ -67,15 +85,7 @@ int pm_reap(uis_handle* h) {
     if (q != hipSuccess) return fail(UIS_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
   }
   ss.pm_running = false;
-  uint32_t abort_word = 0;
-  HIPCHK(hipMemcpy(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost));
-  if (abort_word) {
-    ss.persist = false;
-    h->resident_off = true;
-    return fail(UIS_ERR_HIP, "in-launch barrier failed inside the persistent streaming launch; close the session "
-                             "(uis_stream_end) and reopen it with UIS_FLAG_STEPWISE");
-  }
-  return UIS_OK;
+  return launch_aborted(h, false, "inside the persistent streaming launch");
 }
 
 int pm_launch(uis_handle* h) {
@@ -83,26 +93,26 @@ int pm_launch(uis_handle* h) {
   const DevModel& m = h->m;
   DecodeState st = ss.st;
   // the mailbox as the device sees it (the same address under unified addressing; asked for anyway)
-  void* blk_dev = nullptr;
-  HIPCHK(hipHostGetDevicePointer(&blk_dev, ss.pm_block.p, 0));
-  unsigned char* blk = static_cast<unsigned char*>(blk_dev);
-  st.x = reinterpret_cast<const float*>(ss.chunk_x.as<char>());
-  st.gi0 = ss.chunk_gi0.as<float>();
-  st.mse0 = ss.chunk_mse0.as<float>();
+  void* blk = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&blk, ss.pm_block.p, 0));
+  const MailboxLayout& box = ss.mailbox;
+  st.x = ss.chunk.x.as<float>();  // (no header in front: the tables travel through the mailbox)
+  st.gi0 = ss.chunk.gi0.as<float>();
+  st.mse0 = ss.chunk.mse0.as<float>();
   st.push_F = 0;
   PersistArgs& pa = ss.pm_args;
-  pa.ctl = reinterpret_cast<uint32_t*>(blk);
-  pa.foff = reinterpret_cast<const int64_t*>(blk + ss.pm_o_foff);
-  pa.avail = reinterpret_cast<const int32_t*>(blk + ss.pm_o_avail);
-  pa.lab_off = reinterpret_cast<const int64_t*>(blk + ss.pm_o_laboff);
-  pa.frames = reinterpret_cast<const float*>(blk + ss.pm_o_frames);
-  pa.labels = reinterpret_cast<int32_t*>(blk + ss.pm_o_labels);
-  pa.scores = reinterpret_cast<float*>(blk + ss.pm_o_scores);
-  pa.beam_scores = reinterpret_cast<float*>(blk + ss.pm_o_bscores);
-  pa.overflow = reinterpret_cast<int32_t*>(blk + ss.pm_o_overflow);
+  pa.ctl = static_cast<uint32_t*>(blk);
+  pa.foff = uis_block_at<int64_t>(blk, box.o_foff);
+  pa.avail = uis_block_at<int32_t>(blk, box.o_avail);
+  pa.lab_off = uis_block_at<int64_t>(blk, box.o_lab_off);
+  pa.frames = uis_block_at<float>(blk, box.o_frames);
+  pa.labels = uis_block_at<int32_t>(blk, box.o_labels);
+  pa.scores = uis_block_at<float>(blk, box.o_scores);
+  pa.beam_scores = uis_block_at<float>(blk, box.o_beam_scores);
+  pa.overflow = uis_block_at<int32_t>(blk, box.o_overflow);
   pa.go = ss.d_go;
   pa.hdr = ss.d_hdr;
-  pa.hdr_stride = ss.hdr_stride;
+  pa.hdr_stride = box.hdr_stride;
   pa.idle_ticks = pm_idle_ticks();
   HIPCHK(hipMemcpyAsync(ss.d_pm_args, &pa, sizeof(pa), hipMemcpyHostToDevice, h->stream));
   st.pm = ss.d_pm_args;
@@ -126,7 +136,8 @@ int pm_launch(uis_handle* h) {
 // device (never started, or left because it was idle) is started first when `may_launch`; a
 // launch that left while the command was on its way is reaped and the command issued again to a
 // new one -- harmless: a cluster that did take a push has nothing left to do for it.
-// Returns UIS_OK, an error, or 1 = not running and may_launch was false.
+// Returns UIS_OK, an error, or PM_NOT_TAKEN = not running and may_launch was false.
+constexpr int PM_NOT_TAKEN = 1;  // (no error: the caller goes through ordinary launches)
 int pm_command(uis_handle* h, uint32_t type, uint32_t frames, bool may_launch, const uint32_t* row0 = nullptr,
                const uint32_t* nrow = nullptr) {
   uis_handle::Stream& ss = h->stream_state;
@@ -135,7 +146,7 @@ int pm_command(uis_handle* h, uint32_t type, uint32_t frames, bool may_launch, c
   for (int attempt = 0; attempt < 3; ++attempt) {
     int rc;
     if (!ss.pm_running) {
-      if (!may_launch) return 1;
+      if (!may_launch) return PM_NOT_TAKEN;
       for (int i = 0; i < UIS_PM_CTL_WORDS; ++i) ctl[i] = 0;
       ss.pm_seq = 1;
       pm_ring(ss, 1, type, frames, row0, nrow);
@@ -144,7 +155,6 @@ int pm_command(uis_handle* h, uint32_t type, uint32_t frames, bool may_launch, c
       ss.pm_seq += 1;
       pm_ring(ss, ss.pm_seq, type, frames, row0, nrow);
     }
-    ss.pm_commands += 1;
     const double t0 = pm_now_s();
     bool left = false;
     unsigned spins = 0;
@@ -180,7 +190,8 @@ int pm_quit(uis_handle* h) {
 }
 
 // ---- the scaffold of a session call between launches: uis_stream_{labels, nbest, posterior, prime, commit, restart,
-// retire, committed, bindings} and uis_session_{min_turn, turns}.  THE ORDER, stated here once:
+// retire, committed, limits, bindings, export, import} and uis_session_{min_turn, turns} (the getters stop after
+// step 1; a push has an order of its own, above struct Push).  THE ORDER, stated here once:
 //   1. session_of and the call's own checks on the host: nothing of the session is touched, and a call refused here
 //      (or one with nothing to do) costs a UIS_FLAG_PERSISTENT session nothing and touches no device;
 //   2. session_enter: the resident launch leaves (pm_quit -- it occupies every CU and the tables are written between
@@ -256,6 +267,31 @@ struct CallTimer {
   double device_ms() const { float ms = 0.0f; if (device_work) (void)hipEventElapsedTime(&ms, h->ev_begin, h->ev_end); return (double)ms; }
   double call_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
 };
+
+// A call that asks one kernel about the session and changes nothing (uis_stream_bindings, uis_session_turns), after
+// its checks: enter, one output block of `bytes` in the scratch plan, launch(view, block) between the timer's begin /
+// end, one download, one synchronisation, the copy to `out`, the trace line where the call's knob asks for it.
+template <typename Launch>
+int session_query(uis_handle* h, const char* who, const char* trace_knob, size_t bytes, void* out, Launch launch) {
+  uis_handle::Stream& ss = h->stream_state;
+  CallTimer timer{h};
+  DecodeState stv;
+  if (int rc = session_enter(h, &stv)) return rc;
+  ScratchPlan plan;
+  const size_t o_out = plan.take(bytes);
+  char* base;
+  if (int rc = session_buffers(h, plan, bytes, &base)) return rc;
+  HIPCHK(timer.begin());
+  launch(stv, reinterpret_cast<int32_t*>(base + o_out));
+  HIPCHK(hipGetLastError());
+  HIPCHK(timer.end());
+  HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_out, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  memcpy(out, ss.h_land.p, bytes);
+  if (CallTimer::env(trace_knob))
+    fprintf(stderr, "%s: utterances %d device_ms %.3f call_ms %.3f\n", who, ss.U, timer.device_ms(), timer.call_ms());
+  return UIS_OK;
+}
 
 // The prior tables logblk / logden of a session that must reach further (uis_stream_commit, uis_stream_import): they
 // are indexed by block counts and their sum, which go on growing with the stream.  reserve() BEFORE any scratch (an
@@ -338,6 +374,14 @@ int upload_session_limits(uis_handle* h, const std::vector<int32_t>& limits, std
   return UIS_OK;
 }
 
+// uis_stream_begin's: a session that is not opened to the end is released (stream_free) on every failing return, behind
+// the stream (no upload may still be reading the call's host vectors)
+struct SessionGuard {
+  uis_handle* h;
+  bool opened = false;
+  ~SessionGuard() { if (!opened) { (void)hipStreamSynchronize(h->stream); stream_free(h); } }
+};
+
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_decode_opts* opts, int64_t max_frames) {
@@ -378,193 +422,174 @@ UIS_EXPORT int32_t uis_stream_begin(uis_handle* h, int32_t n_utt, const uis_deco
   ss.resident = m.Hp != 128 && !(opts->flags & (UIS_FLAG_STEPWISE | UIS_FLAG_GENERIC_SELECT)) && resident_fits(m, U, B, Kmax, S, geo);
   if ((opts->flags & UIS_FLAG_RESIDENT) && !ss.resident)
     { ss = uis_handle::Stream{}; return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_RESIDENT: the one-launch decode does not apply to this session's shape"); }
-  int rc = UIS_OK;
-  int64_t* d_off = nullptr; double *d_logblk = nullptr, *d_logden = nullptr;
-#define SALLOC(ptr, count, zero) if ((rc = stream_alloc(h, &(ptr), (size_t)(count), zero))) { stream_free(h); return rc; }
+  std::vector<int64_t> off(U + 1);
+  std::vector<double> log_host;
+  std::vector<int32_t> limit_dev;
+  SessionGuard guard{h};
+  // ---- the session's state: one allocation per table (stream_alloc), ss.st pointed at them
   const StateCounts n = state_counts(m, U, B, Kmax, S, geo.rows_cap, 1);  // (one group)
-  SALLOC(d_off, U + 1, false);
-  SALLOC(st.utt_step, U, false);
-  SALLOC(st.overflow, U, false);
-  SALLOC(st.limit, U, false);
-  SALLOC(ss.d_min_turn, U, true);  // (uis_session_min_turn: no slot has a rule, and st.min_turn stays null)
-  SALLOC(ss.d_avail, U, true);
-  SALLOC(ss.d_have, U, true);
-  SALLOC(ss.d_foff, U, true);
-  SALLOC(ss.d_lab_off, U, true);
-  SALLOC(d_logblk, max_frames + 2, false);
-  SALLOC(d_logden, max_frames + 2, false);
-  SALLOC(st.pool_mean, n.pool_mean, false);
-  SALLOC(st.pool_hid, n.pool_hid, false);
-  SALLOC(st.pool_cnt, n.pool_cnt, false);
-  SALLOC(st.beam_n, n.beam_n, false);
-  SALLOC(st.beam_K, n.beam, false);
-  SALLOC(st.beam_last, n.beam, false);
-  SALLOC(st.beam_sum, n.beam, false);
-  SALLOC(st.beam_score, n.beam, false);
-  SALLOC(st.beam_slot, n.beam_lists, false);
-  SALLOC(st.beam_blk, n.beam_lists, false);
+  int rc = UIS_OK;
+  const auto take = [&](auto** ptr, size_t count, bool zero = false) { if (!rc) rc = stream_alloc(h, ptr, count, zero); };
+  take(&st.off, U + 1);
+  take(&st.utt_step, U);
+  take(&st.overflow, U);
+  take(&st.limit, U);
+  take(&ss.d_min_turn, U, true);  // (uis_session_min_turn: no slot has a rule, and st.min_turn stays null)
+  take(&st.avail, U, true);  // (until the first push through ordinary launches points both into its chunk)
+  take(&ss.d_have, U, true);
+  take(&st.foff, U, true);
+  take(&ss.d_lab_off, U, true);
+  st.lab_off = ss.d_lab_off;
+  take(&st.logblk, (size_t)ss.log_len);
+  take(&st.logden, (size_t)ss.log_len);
+  take(&st.pool_mean, n.pool_mean);
+  take(&st.pool_hid, n.pool_hid);
+  take(&st.pool_cnt, n.pool_cnt);
+  take(&st.beam_n, n.beam_n);
+  take(&st.beam_K, n.beam);
+  take(&st.beam_last, n.beam);
+  take(&st.beam_sum, n.beam);
+  take(&st.beam_score, n.beam);
+  take(&st.beam_slot, n.beam_lists);
+  take(&st.beam_blk, n.beam_lists);
   // (a record per frame of the session's capacity; a decode's: per step of the frames given.  The table starts as zeros
   // -- under UIS_POISON_WORKSPACE as the poison word: the record word of a dead rank is never written, and
   // uis_stream_export copies the records verbatim, so without a defined start two sessions with the same history could
   // export different bytes)
-  SALLOC(st.bp, (size_t)U * max_frames * B, !ss.poison.on);
-  SALLOC(st.rows, n.rows, true);
-  SALLOC(st.nrows, n.nrows, true);
-  SALLOC(st.gi_up, n.gi_up, false);
-  SALLOC(st.a1, n.a1, true);
-  SALLOC(st.counters, 96, true);  // (one group's statistics words and room to spare; a decode's: every group's plus the diagnostic builds' clocks)
+  take(&st.bp, (size_t)U * max_frames * B, !ss.poison.on);
+  take(&st.rows, n.rows, true);
+  take(&st.nrows, n.nrows, true);
+  take(&st.gi_up, n.gi_up);
+  take(&st.a1, n.a1, true);
+  take(&st.counters, 96, true);  // (one group's statistics words and room to spare; a decode's: every group's plus the diagnostic builds' clocks)
   ss.ctl_words = n.ctl_words;
-  SALLOC(ss.d_ctl, ss.ctl_words, true);
+  take(&ss.d_ctl, ss.ctl_words, true);
+  take(&ss.d_beam_scores, (size_t)U * B);
+  if (rc) return rc;
   wire_cluster_ctl(st, ss.d_ctl, ss.resident ? &geo : nullptr);
-  SALLOC(ss.d_beam_scores, (size_t)U * B, false);
   if (opts->flags & UIS_FLAG_PERSISTENT) {
-    // the launch that stays: needs the one-launch shape with the beam in LDS (at most one utterance
+    // ---- the launch that stays: needs the one-launch shape with the beam in LDS (at most one utterance
     // per workgroup), unpadded frames, and a mailbox that holds every label of the session
     const bool shape = find_kernel(kernels::persist, m.Hp, m.Dp, CLS_NONE) != nullptr;
     const double label_bytes = (double)U * (double)max_frames * 4.0;
-    if (!(ss.resident && shape && U <= 32 * geo.ncl && m.D == m.Dp && label_bytes <= 256e6)) {
-      stream_free(h);
+    if (!(ss.resident && shape && U <= 32 * geo.ncl && m.D == m.Dp && label_bytes <= 256e6))
       return fail(UIS_ERR_UNSUPPORTED, "UIS_FLAG_PERSISTENT needs the one-launch shape (rnn_depth 1, rnn_hidden_size 512 with "
                                        "observation_dim 256 / 512 or 256 with 256, unpadded), at most one utterance per compute "
                                        "unit and n_utt * max_frames <= 64 M labels");
-    }
-    // Every cluster gets a FIXED row range of the chunk buffers (x, gi0, mse0) and of the mailbox's
-    // frame area: room for 16 frames of each of its utterances.  Fixed, because the launch never
-    // ends between pushes: a row that changed hands from one push to the next would leave a stale
-    // dirty line in the previous owner's XCD-private L2, free to be written back over the new
-    // owner's data at any time (seen as rare score differences before the ranges were fixed).
-    ss.pm_cluster_rows = std::min<int64_t>(round_up(((U + geo.ncl - 1) / geo.ncl) * 16, 32), (int64_t)UIS_RES_HEAD_TILES * 16 * 6);
-    ss.pm_cap_frames = ss.pm_cluster_rows * geo.ncl;
-    size_t o = (size_t)UIS_PM_CTL_WORDS * 4;
-    auto take = [&](size_t bytes) { o = (o + 127) & ~(size_t)127; const size_t r = o; o += bytes; return r; };
-    ss.pm_o_foff = take((size_t)U * 8);
-    ss.pm_o_avail = take((size_t)U * 4);
-    ss.pm_o_laboff = take((size_t)U * 8);
-    ss.pm_o_scores = take((size_t)U * 4);
-    ss.pm_o_bscores = take((size_t)U * B * 4);
-    ss.pm_o_overflow = take((size_t)U * 4);
-    ss.pm_o_frames = take((size_t)ss.pm_cap_frames * m.D * 4);
-    ss.pm_o_labels = take((size_t)U * (size_t)max_frames * 4);
-    hipError_t e = ss.pm_block.ensure(o, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) { stream_free(h); return fail(UIS_ERR_OOM, std::string("hipHostMalloc (mailbox): ") + hipGetErrorString(e)); }
-    ss.poison.host(ss.pm_block.p, o);  // (... and then the mailbox's initial state)
-    memset(ss.pm_block.p, 0, o);
-    ss.hdr_stride = (((size_t)U * 12) + 127) & ~(size_t)127;
-    SALLOC(ss.d_go, (size_t)UIS_PM_MAX_CLUSTERS * 16, true);
-    SALLOC(ss.d_hdr, (size_t)geo.ncl * ss.hdr_stride, true);
-    SALLOC(ss.d_pm_args, 1, false);
+    // Every cluster gets a FIXED row range of the chunk buffers (x, gi0, mse0) and of the mailbox's frame area
+    // (MailboxLayout::cluster_rows).  Fixed, because the launch never ends between pushes: a row that changed hands from
+    // one push to the next would leave a stale dirty line in the previous owner's XCD-private L2, free to be written back
+    // over the new owner's data at any time (seen as rare score differences before the ranges were fixed).
+    const MailboxLayout& box = ss.mailbox = MailboxLayout(U, B, m.D, max_frames, geo.ncl, UIS_PM_CTL_WORDS, UIS_RES_HEAD_TILES * 16 * 6);
+    hipError_t e = ss.pm_block.ensure(box.total, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc (mailbox): ") + hipGetErrorString(e));
+    ss.poison.host(ss.pm_block.p, box.total);  // (... and then the mailbox's initial state)
+    memset(ss.pm_block.p, 0, box.total);
+    take(&ss.d_go, (size_t)UIS_PM_MAX_CLUSTERS * 16, true);
+    take(&ss.d_hdr, (size_t)geo.ncl * box.hdr_stride, true);
+    take(&ss.d_pm_args, 1);
     // everything a push through the mailbox touches, now: no allocation while the launch is resident
-    if ((rc = ss.chunk_x.ensure((size_t)U * 16 + (size_t)ss.pm_cap_frames * m.Dp * 4)) ||
-        (rc = ss.chunk_gi0.ensure((size_t)ss.pm_cap_frames * m.G * 4)) || (rc = ss.chunk_mse0.ensure((size_t)ss.pm_cap_frames * 4))) {
-      stream_free(h);
-      return rc;
-    }
-    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
+    if (rc || (rc = ss.chunk.ensure(ChunkLayout(U, box.cap_frames, m.D, false, 0), box.cap_frames, m, false, false, false))) return rc;
+    HIPCHK(ss.chunk.poison(ss.poison, h->stream));
     ss.persist = true;
   }
-#undef SALLOC
+  // ---- the initial uploads
   if (ss.resident)  // the extra slot every GRU source row of a fresh cluster reads
     HIPCHK(hipMemcpyAsync(st.pool_hid + (size_t)U * S * m.Hp, m.h1, (size_t)m.Hp * 4, hipMemcpyDeviceToDevice, h->stream));
-  std::vector<int64_t> off(U + 1);
   for (int u = 0; u <= U; ++u) off[u] = (int64_t)u * max_frames;  // capacity offsets: they address the back-pointers
-  std::vector<double> log_host;
-  std::vector<int32_t> limit_dev;
-  HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
+  // (the host fills three of the tables that the kernels, and so DecodeState, only read)
+  HIPCHK(hipMemcpyAsync(const_cast<int64_t*>(st.off), off.data(), off.size() * 8, hipMemcpyHostToDevice, h->stream));
   ss.limits.assign((size_t)U, 0);
   if (h->tables.limits.call_set) ss.limits = h->tables.limits.call;
-  if ((rc = upload_log_tables(h->alpha, max_frames + 2, log_host, d_logblk, d_logden, h->stream))) return rc;
-  st.off = d_off; st.logblk = d_logblk; st.logden = d_logden;
-  st.avail = ss.d_avail; st.foff = ss.d_foff; st.lab_off = ss.d_lab_off;
+  if ((rc = upload_log_tables(h->alpha, ss.log_len, log_host, const_cast<double*>(st.logblk), const_cast<double*>(st.logden), h->stream))) return rc;
   hipLaunchKernelGGL(k_init_state, dim3((U + 255) / 256), dim3(256), 0, h->stream, st);
   HIPCHK(hipGetLastError());
   if ((rc = upload_session_limits(h, ss.limits, limit_dev))) return rc;  // (behind k_init_state, which has written "no bound")
-  HIPCHK(hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
-  ss.active = true;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the host vectors go out of scope)
+  ss.active = guard.opened = true;
   return UIS_OK;
 }
 
 namespace {
 
-// One push, whoever brings the frames: `frames` (uis_stream_push: host float32, utterance after utterance) or `chunks`
+// ---- a push (uis_stream_push, uis_tensors_stream_push).  THE ORDER, stated here once (the steps of struct Push):
+//   1. checks, on the host: the counts against the window's capacity and the 2^31 - 256 bound, this push's tables,
+//      what a UIS_FLAG_PERSISTENT session cannot take, the 2^24 bound of a tagged session.  Nothing of the session is
+//      touched; a push that brings no frame ends here;
+//   2. through_mailbox: a persistent session whose clusters' shares fit their fixed row ranges -- tables and frames
+//      into the mailbox, ring, wait.  No HIP call unless the launch has to be started.  Every other push goes on:
+//   3. upload: a resident launch leaves; the chunk's layout, its growth and fills, the bias and tag tables, the
+//      staging block and its ONE H2D, the gather for tensors, the pad kernel;
+//   4. launch: stepwise / one launch / fused, the cooperative launch and its refusal's fallback, enqueue_steps;
+//   5. in run(): the ONE hipStreamSynchronize, behind a one-launch kernel with the abort word and its
+//      verdict (launch_aborted); and the bookkeeping (have), once for both ways.
+// Who brings the frames: `frames` (uis_stream_push: host float32, utterance after utterance) or `chunks`
 // (uis_tensors_stream_push: one device tensor per utterance, gathered by k_ingest into the chunk's frame area) -- exactly
 // one of the two is given.  The caller has begun the call and checked the handle and the session.
-int stream_push_impl(uis_handle* h, const char* who, const float* frames, const uis_tensor* chunks, void* producer_stream,
-                     const int32_t* counts) {
+struct Push {
+  uis_handle* const h;
+  const char* who;
+  const float* frames;
+  const uis_tensor* chunks;
+  void* producer_stream;
+  const int32_t* counts;
   uis_handle::Stream& ss = h->stream_state;
-  const DevModel& m = h->m;
-  const int U = ss.U;
-  int64_t F = 0, max_new = 0;
-  for (int u = 0; u < U; ++u) {
-    if (counts[u] < 0) return fail(UIS_ERR_INVALID_ARG, "negative frame count");
-    if ((int64_t)ss.have[u] + counts[u] > ss.cap)
-      return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames (the window of frames not yet committed: "
-                                       "uis_stream_commit makes room)");
-    // (pool_cnt / beam_sum count everything an utterance ever received, in int32)
-    if (ss.committed[u] + ss.have[u] + counts[u] > 0x7fffff00LL)
-      return fail(UIS_ERR_UNSUPPORTED, "utterance would have received more than 2^31 - 256 frames in this session");
-    F += counts[u];
-    max_new = std::max<int64_t>(max_new, counts[u]);
+  int64_t F = 0, max_new = 0;  // (1) the frames of the push; the most any utterance brings = the steps to run
+  const float* d_x = nullptr;  // (3) the chunk's frames as the kernels read them (padded where D != Dp)
+  bool ran_resident = false;   // (4) a one-launch kernel took the push
+
+  int checks() {
+    for (int u = 0; u < ss.U; ++u) {
+      if (counts[u] < 0) return fail(UIS_ERR_INVALID_ARG, "negative frame count");
+      if ((int64_t)ss.have[u] + counts[u] > ss.cap)
+        return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames (the window of frames not yet committed: "
+                                         "uis_stream_commit makes room)");
+      // (pool_cnt / beam_sum count everything an utterance ever received, in int32)
+      if (ss.committed[u] + ss.have[u] + counts[u] > 0x7fffff00LL)
+        return fail(UIS_ERR_UNSUPPORTED, "utterance would have received more than 2^31 - 256 frames in this session");
+      F += counts[u];
+      max_new = std::max<int64_t>(max_new, counts[u]);
+    }
+    if (int rc = table_status(h->tables.check_bias("call", F))) return rc;
+    // (the resident launch of a UIS_FLAG_PERSISTENT session reads its priors from the kernel arguments it was launched with;
+    // a table would have to travel through the mailbox, whose layout is a protocol of its own: DESIGN.md section 9, "Open")
+    if (h->tables.bias3.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+      return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no per-frame transition_bias (uis_frame_bias): the table is dropped");
+    // (uis_stream_speakers: the same three checks for this push's tags, then the 2^24 bound of a session that holds any)
+    if (int rc = table_status(h->tables.check_stream_tags("call", F))) return rc;
+    if (h->tables.stream_tags.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
+      return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
+    for (int u = 0; u < ss.U; ++u)
+      if (int rc = table_status(CallTables::check_tagged_frames(who, ss.tagged || h->tables.tagged, u, ss.committed[u] + ss.have[u] + counts[u]))) return rc;
+    return UIS_OK;
   }
-  if (int rcb = table_status(h->tables.check_bias("call", F))) return rcb;
-  // (the resident launch of a UIS_FLAG_PERSISTENT session reads its priors from the kernel arguments it was launched with;
-  // a table would have to travel through the mailbox, whose layout is a protocol of its own: DESIGN.md section 9, "Open")
-  if (h->tables.bias3.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
-    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no per-frame transition_bias (uis_frame_bias): the table is dropped");
-  // (uis_stream_speakers: the same three checks for this push's tags, then the 2^24 bound of a session that holds any)
-  if (int rct = table_status(h->tables.check_stream_tags("call", F))) return rct;
-  if (h->tables.stream_tags.call_set && (ss.st.flags & UIS_FLAG_PERSISTENT))
-    return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no known speakers (uis_stream_speakers): the table is dropped");
-  for (int u = 0; u < U; ++u)
-    if (int rct = table_status(CallTables::check_tagged_frames(who, ss.tagged || h->tables.tagged, u, ss.committed[u] + ss.have[u] + counts[u]))) return rct;
-  if (F == 0) return UIS_OK;
-  if (!frames && !chunks) return fail(UIS_ERR_INVALID_ARG, "frames is null");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
+
+  // The launch that stays on the device.  Returns UIS_OK: the push is done; an error; or PM_NOT_TAKEN: this push goes through
+  // ordinary launches (no persistent session, tensors -- they never reach one --, a cluster's share that does not fit,
+  // or the cooperative launch was refused: ordinary launches from here on).
+  int through_mailbox() {
+    const MailboxLayout& box = ss.mailbox;
+    const int D = h->m.D, ncl = ss.st.ncl;
 #if defined(UIS_PM_TIMING)
-  const double t_enter = pm_now_s();
+    const double t_enter = pm_now_s();
 #endif
-  bool pm_fits = ss.persist && !h->resident_off && !chunks;  // (tensors never reach a persistent session)
-  if (pm_fits) {  // every cluster's new frames must fit its fixed row range
-    const int ncl = ss.st.ncl;
-    for (int c = 0; c < ncl && pm_fits; ++c) {
-      int64_t rows = 0;
-      for (int u = c; u < U; u += ncl) rows += counts[u];
-      pm_fits = rows <= ss.pm_cluster_rows;
-    }
-  }
-  if (pm_fits) {
-    // ---- the launch that stays on the device: tables and frames into the mailbox, ring, wait
-    unsigned char* const pm = ss.pm_block.as<unsigned char>();
-    int64_t* p_foff = reinterpret_cast<int64_t*>(pm + ss.pm_o_foff);
-    int32_t* p_avail = reinterpret_cast<int32_t*>(pm + ss.pm_o_avail);
-    // frames cluster by cluster (cluster c owns utterances c, c + ncl, ...): each cluster's rank 0
-    // fetches ONE contiguous row range
-    const int ncl = ss.st.ncl;
-    uint32_t row0[UIS_PM_MAX_CLUSTERS + 1];
-    std::vector<int64_t> src(U + 1, 0);  // where utterance u's frames start in the caller's buffer
-    for (int u = 0; u < U; ++u) src[u + 1] = src[u] + counts[u];
-    uint32_t nrow[UIS_PM_MAX_CLUSTERS];
-    float* dst = reinterpret_cast<float*>(pm + ss.pm_o_frames);
-    for (int c = 0; c < ncl; ++c) {
-      int64_t pos = (int64_t)c * ss.pm_cluster_rows;  // the cluster's fixed range
-      row0[c] = (uint32_t)pos;
-      for (int u = c; u < U; u += ncl) {
-        p_foff[u] = pos - ss.have[u];
-        p_avail[u] = ss.have[u] + counts[u];
-        if (counts[u]) memcpy(dst + (size_t)pos * m.D, frames + (size_t)src[u] * m.D, (size_t)counts[u] * m.D * 4);
-        pos += counts[u];
-      }
-      nrow[c] = (uint32_t)(pos - (int64_t)c * ss.pm_cluster_rows);
-    }
+    if (!ss.persist || h->resident_off || chunks || !chunk_rows(ss.U, ncl, box.cluster_rows, counts, nullptr, nullptr, nullptr, nullptr, nullptr))
+      return PM_NOT_TAKEN;
+    // frames cluster by cluster: each cluster's rank 0 fetches ONE contiguous row range
+    void* const pm = ss.pm_block.p;
+    uint32_t row0[UIS_PM_MAX_CLUSTERS], nrow[UIS_PM_MAX_CLUSTERS];
+    int64_t* foff = uis_block_at<int64_t>(pm, box.o_foff);
+    chunk_rows(ss.U, ncl, box.cluster_rows, counts, ss.have.data(), foff, uis_block_at<int32_t>(pm, box.o_avail), row0, nrow);
+    const float* src = frames;  // (utterance after utterance in the caller's buffer)
+    for (int u = 0; u < ss.U; src += (size_t)counts[u] * D, ++u)
+      if (counts[u]) memcpy(uis_block_at<float>(pm, box.o_frames) + (size_t)(foff[u] + ss.have[u]) * D, src, (size_t)counts[u] * D * 4);
     h->inlaunch_failed = false;
 #if defined(UIS_PM_TIMING)
     static double fill_s = 0.0, wait_s = 0.0; static long n_push = 0;
     const double t_mid = pm_now_s();
     fill_s += t_mid - t_enter;
 #endif
-    rc = pm_command(h, UIS_PM_PUSH, (uint32_t)std::min<int64_t>(F, 4095), true, row0, nrow);
+    const int rc = pm_command(h, UIS_PM_PUSH, (uint32_t)std::min<int64_t>(F, 4095), true, row0, nrow);
 #if defined(UIS_PM_TIMING)
     wait_s += pm_now_s() - t_mid;
     if (++n_push % 100 == 0) {
@@ -575,153 +600,130 @@ int stream_push_impl(uis_handle* h, const char* who, const float* frames, const 
               k[2] * 0.01 / n, k[3] * 0.01 / n);
     }
 #endif
-    if (rc == UIS_OK) {
-      for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
-      ss.steps_run += max_new;
-      return UIS_OK;
+    if (rc == UIS_OK || !h->inlaunch_failed) return rc;
+    ss.persist = false;
+    return PM_NOT_TAKEN;
+  }
+
+  int upload() {
+    const bool with_bias = h->tables.bias3.call_set, with_tags = h->tables.stream_tags.call_set;
+    int rc;
+    if (ss.pm_running && (rc = pm_quit(h))) return rc;
+    Chunk& ck = ss.chunk;
+    const ChunkLayout lay(ss.U, F, h->m.D, chunks != nullptr, sizeof(IngestBlock));
+    if ((rc = ck.ensure(lay, F, h->m, with_bias, with_tags))) return rc;
+    // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its chunk from nothing (the session's state lives
+    // elsewhere) -- all on the handle's stream, idle since the last call
+    ss.poison = UisPoison::from_env();
+    if (ss.poison.on) HIPCHK(ck.poison(ss.poison, h->stream));
+    // (the table's rows are the chunk's: row foff[u] + step, as mse0; the call's table lives until the synchronize below)
+    if (with_bias) HIPCHK(hipMemcpyAsync(ck.bias.p, h->tables.bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
+    // (the tags likewise, one byte per chunk row; the session counts as tagged from here on, whatever becomes of the push)
+    if (with_tags) HIPCHK(hipMemcpyAsync(ck.hint.p, h->tables.stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
+    ss.tagged = ss.tagged || h->tables.tagged;
+    // one staging block, one H2D; for tensors the frame area behind the header is written by the gather
+    chunk_rows(ss.U, 1, 0, counts, ss.have.data(), uis_block_at<int64_t>(ck.stage.p, lay.o_foff), uis_block_at<int32_t>(ck.stage.p, lay.o_avail), nullptr, nullptr);
+    float* const d_frames = uis_block_at<float>(ck.x.p, lay.o_frames);
+    if (frames) memcpy(uis_block_at<float>(ck.stage.p, lay.o_frames), frames, (size_t)F * h->m.D * 4);
+    else ingest_fill_table(ck.stage.as<IngestBlock>(), chunks, ss.U, h->m.D, d_frames);
+    HIPCHK(hipMemcpyAsync(ck.x.p, ck.stage.p, lay.travel_bytes, hipMemcpyHostToDevice, h->stream));
+    if (chunks && (rc = ingest_launch(h, ck.x.as<IngestBlock>(), ss.U, F, producer_stream, d_frames))) return rc;
+    ss.st.foff = uis_block_at<int64_t>(ck.x.p, lay.o_foff);
+    ss.st.avail = uis_block_at<int32_t>(ck.x.p, lay.o_avail);
+    d_x = d_frames;
+    if (h->m.D != h->m.Dp) {
+      hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)(((long)F * h->m.Dp + 255) / 256)), dim3(256), 0, h->stream, d_x, ck.pad.as<float>(), (long)F, h->m.D, h->m.Dp);
+      HIPCHK(hipGetLastError());
+      d_x = ck.pad.as<float>();
     }
-    if (!h->inlaunch_failed) return rc;
-    ss.persist = false;  // the cooperative launch was refused: ordinary launches from here on
+    return UIS_OK;
   }
-  if (ss.pm_running && (rc = pm_quit(h))) return rc;
-  // ---- one staging block, one H2D: [foff][avail][frames]; tensors: [k_ingest's table][foff][avail] travel, and the
-  // frame area behind them is written by the gather (the table is a multiple of 16 bytes: the rest lies as it did)
-  const size_t lead = chunks ? (size_t)U * sizeof(IngestBlock) : 0;
-  const size_t hdr = lead + (size_t)U * 8 + (((size_t)U * 4 + 15) & ~(size_t)15);
-  const size_t need = hdr + (size_t)F * m.D * 4;
-  const size_t staged = chunks ? hdr : need;
-  if (staged > ss.h_stage.cap) {  // (with head-room: pushes of a session vary in size)
-    hipError_t e = ss.h_stage.ensure(staged + staged / 4 + 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(UIS_ERR_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  }
-  if ((rc = ss.chunk_x.ensure(need))) return rc;
-  if ((rc = ss.chunk_gi0.ensure((size_t)F * m.G * 4))) return rc;
-  if ((rc = ss.chunk_mse0.ensure((size_t)F * 4))) return rc;
-  if (h->tables.bias3.call_set && (rc = ss.chunk_bias.ensure((size_t)F * 24))) return rc;
-  if (h->tables.stream_tags.call_set && (rc = ss.chunk_hint.ensure((size_t)F))) return rc;
-  // UIS_POISON_WORKSPACE: a push through ordinary launches rebuilds its staging block and the chunk's x / gi0 / mse0
-  // from nothing (the session's state lives elsewhere) -- all on the handle's stream, idle since the last call
-  ss.poison = UisPoison::from_env();
-  if (ss.poison.on) {
-    ss.poison.host(ss.h_stage.p, ss.h_stage.cap);
-    HIPCHK(ss.poison.device(ss.chunk_x.p, ss.chunk_x.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_gi0.p, ss.chunk_gi0.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_mse0.p, ss.chunk_mse0.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_bias.p, ss.chunk_bias.cap, h->stream));
-    HIPCHK(ss.poison.device(ss.chunk_hint.p, ss.chunk_hint.cap, h->stream));
-  }
-  // (the table's rows are the chunk's: row foff[u] + step, as mse0; the call's table lives until the synchronize below)
-  if (h->tables.bias3.call_set)
-    HIPCHK(hipMemcpyAsync(ss.chunk_bias.p, h->tables.bias3.data(), (size_t)F * 24, hipMemcpyHostToDevice, h->stream));
-  // (the tags likewise, one byte per chunk row; the session counts as tagged from here on, whatever becomes of the push)
-  if (h->tables.stream_tags.call_set)
-    HIPCHK(hipMemcpyAsync(ss.chunk_hint.p, h->tables.stream_tags.data(), (size_t)F, hipMemcpyHostToDevice, h->stream));
-  ss.tagged = ss.tagged || h->tables.tagged;
-  int64_t* h_foff = reinterpret_cast<int64_t*>(ss.h_stage.as<char>() + lead);
-  int32_t* h_avail = reinterpret_cast<int32_t*>(ss.h_stage.as<char>() + lead + (size_t)U * 8);
-  {
-    int64_t pos = 0;
-    for (int u = 0; u < U; ++u) {
-      h_foff[u] = pos - ss.have[u];  // row of step s's frame in this chunk = foff + s
-      pos += counts[u];
-      h_avail[u] = ss.have[u] + counts[u];
+
+  int launch() {
+    float *const gi0 = ss.chunk.gi0.as<float>(), *const mse0 = ss.chunk.mse0.as<float>();
+    int rc;
+    Launcher lch{h, h->stream, false};
+    DecodeState st = ss.st;
+    st.x = d_x; st.gi0 = gi0; st.mse0 = mse0;
+    st.bias3 = h->tables.bias3.call_set ? ss.chunk.bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
+    st.hint = h->tables.stream_tags.call_set ? ss.chunk.hint.as<uint8_t>() : nullptr;  // (ss.st.hint likewise: the bindings ride in beam_blk)
+    // One-launch path: the chunk's projection fused into the kernel and plain launches after the
+    // session's first push make a push one H2D, one memset and ONE kernel.  Measured
+    // (tools/stream_latency.py, profiles/): that kernel re-reads its weights into registers / LDS at
+    // every launch (~10 us), so for 1-3 steps per push the four small kernels per step are still
+    // quicker (79 vs 96 us for one frame of 64 utterances); from 4 steps on the single launch wins
+    // (16 frames: 690 vs 880 us).  UIS_FLAG_RESIDENT forces it, UIS_FLAG_STEPWISE forbids it.
+    bool stepwise = !ss.resident || h->resident_off || (max_new < UIS_STREAM_RESIDENT_MIN_STEPS && !(ss.st.flags & UIS_FLAG_RESIDENT));
+    // the chunk's gi0 / mse0: inside the one-launch kernel when the frames need no padding and the
+    // chunk's rows fit the kernel's LDS list, else by the two once-per-chunk kernels
+    const bool fused = !stepwise && h->m.D == h->m.Dp && F <= (int64_t)UIS_RES_HEAD_TILES * 16 * 6;
+    if (!fused && (rc = plain_input_proj(lch, h->m, d_x, gi0, mse0, (long)F))) return rc;
+    HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
+    st.push_F = fused ? (int)F : 0;
+    if (!stepwise) {
+      // every step of this push in ONE launch (the kernel runs max over utterances of
+      // avail - utt_step steps; utterances without new frames sit them out)
+      HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
+      h->inlaunch_failed = false;
+      // Every push is a COOPERATIVE launch: the kernel spins on in-launch barriers and needs all its
+      // workgroups co-resident, which only that launch path checks against whatever else runs on the
+      // device at that moment (another handle's decode, a second session).  A plain launch of the
+      // same grid saves 15-19 us of host time per push; it is opt-in (UIS_STREAM_PLAIN_LAUNCH=1) for
+      // callers that own the device, and used only after the session's first push went through the
+      // cooperative path.
+      static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
+      rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, h->m.Hp, h->m.Dp, CLS_NONE, &h->last_pick), h->n_cu, st.ncl,
+                                 one_launch_lds(resident_lds_bytes(h->m.Hp, h->m.Dp, ss.B, ss.Kmax, ss.S)), h->m, st,
+                                 !(ss.coop_checked && plain_ok));
+      if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
+        h->resident_off = true; stepwise = true;
+        if (fused) {  // ... and they need the chunk's gi0 / mse0
+          if ((rc = plain_input_proj(lch, h->m, d_x, gi0, mse0, (long)F))) return rc;
+          st.push_F = 0;
+        }
+      } else if (rc) return rc;
+      else { ran_resident = true; ss.coop_checked = true; }
     }
+    if (stepwise) {
+      h->last_pick = KernelPick{};
+      h->last_pick.family = UIS_DK_STEPWISE; h->last_pick.Hp = h->m.Hp; h->last_pick.Dp = h->m.Dp;
+      if ((rc = enqueue_steps(h, lch, st, select_lds_layout(h->m.Dp, ss.B, ss.Kmax, ss.S).total, (int)max_new))) return rc;
+    }
+    return UIS_OK;
   }
-  if (frames) memcpy(ss.h_stage.as<char>() + hdr, frames, (size_t)F * m.D * 4);
-  else ingest_fill_table(ss.h_stage.as<IngestBlock>(), chunks, U, m.D, reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr));
-  HIPCHK(hipMemcpyAsync(ss.chunk_x.p, ss.h_stage.p, staged, hipMemcpyHostToDevice, h->stream));
-  if (chunks && (rc = ingest_launch(h, ss.chunk_x.as<IngestBlock>(), U, F, producer_stream, reinterpret_cast<float*>(ss.chunk_x.as<char>() + hdr))))
-    return rc;
-  ss.d_foff = reinterpret_cast<int64_t*>(ss.chunk_x.as<char>() + lead);
-  ss.d_avail = reinterpret_cast<int32_t*>(ss.chunk_x.as<char>() + lead + (size_t)U * 8);
-  ss.st.foff = ss.d_foff;
-  ss.st.avail = ss.d_avail;
-  const float* d_x = reinterpret_cast<const float*>(ss.chunk_x.as<char>() + hdr);
-  if (m.D != m.Dp) {
-    if ((rc = ss.chunk_pad.ensure((size_t)F * m.Dp * 4))) return rc;
-    HIPCHK(ss.poison.device(ss.chunk_pad.p, ss.chunk_pad.cap, h->stream));
-    const long total = (long)F * m.Dp;
-    hipLaunchKernelGGL(k_pad_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_x,
-                       ss.chunk_pad.as<float>(), (long)F, m.D, m.Dp);
-    HIPCHK(hipGetLastError());
-    d_x = ss.chunk_pad.as<float>();
+
+  int run() {
+    if (int rc = checks()) return rc;
+    if (F == 0) return UIS_OK;
+    if (!frames && !chunks) return fail(UIS_ERR_INVALID_ARG, "frames is null");
+    HIPCHK(hipSetDevice(h->device));
+    int rc = through_mailbox();
+    if (rc == PM_NOT_TAKEN) {
+      if ((rc = upload())) return rc;
+      if ((rc = launch())) return rc;
+      // (5: after the synchronisation the staging block and the caller's frames may be reused)
+      if (ran_resident) rc = launch_aborted(h, true, "during uis_stream_push");
+      else HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (rc) return rc;
+    for (int u = 0; u < ss.U; ++u) ss.have[u] += counts[u];
+    return UIS_OK;
   }
-  Launcher lch{h, h->stream, false};
-  DecodeState st = ss.st;
-  st.x = d_x; st.gi0 = ss.chunk_gi0.as<float>(); st.mse0 = ss.chunk_mse0.as<float>();
-  st.bias3 = h->tables.bias3.call_set ? ss.chunk_bias.as<double>() : nullptr;  // (ss.st.bias3 stays null: no other session call forms a prior)
-  st.hint = h->tables.stream_tags.call_set ? ss.chunk_hint.as<uint8_t>() : nullptr;  // (ss.st.hint likewise: the bindings ride in beam_blk)
-  const SelectLds lds = select_lds_layout(m.Dp, ss.B, ss.Kmax, ss.S);
-  // One-launch path: the chunk's projection fused into the kernel and plain launches after the
-  // session's first push make a push one H2D, one memset and ONE kernel.  Measured
-  // (tools/stream_latency.py, profiles/): that kernel re-reads its weights into registers / LDS at
-  // every launch (~10 us), so for 1-3 steps per push the four small kernels per step are still
-  // quicker (79 vs 96 us for one frame of 64 utterances); from 4 steps on the single launch wins
-  // (16 frames: 690 vs 880 us).  UIS_FLAG_RESIDENT forces it, UIS_FLAG_STEPWISE forbids it.
-  bool stepwise = !ss.resident || h->resident_off ||
-                  (max_new < UIS_STREAM_RESIDENT_MIN_STEPS && !(ss.st.flags & UIS_FLAG_RESIDENT));
-  // the chunk's gi0 / mse0: inside the one-launch kernel when the frames need no padding and the
-  // chunk's rows fit the kernel's LDS list, else by the two once-per-chunk kernels
-  const bool fused = !stepwise && m.D == m.Dp && F <= (int64_t)UIS_RES_HEAD_TILES * 16 * 6;
-  if (!fused && (rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
-  HIPCHK(hipMemsetAsync(ss.st.nrows, 0, 8, h->stream));
-  st.push_F = fused ? (int)F : 0;
-  bool ran_resident = false;
-  if (!stepwise) {
-    // every step of this push in ONE launch (the kernel runs max over utterances of
-    // avail - utt_step steps; utterances without new frames sit them out)
-    HIPCHK(hipMemsetAsync(ss.d_ctl, 0, ss.ctl_words * 4, h->stream));
-    h->inlaunch_failed = false;
-    // Every push is a COOPERATIVE launch: the kernel spins on in-launch barriers and needs all its
-    // workgroups co-resident, which only that launch path checks against whatever else runs on the
-    // device at that moment (another handle's decode, a second session).  A plain launch of the
-    // same grid saves 15-19 us of host time per push; it is opt-in (UIS_STREAM_PLAIN_LAUNCH=1) for
-    // callers that own the device, and used only after the session's first push went through the
-    // cooperative path.
-    static const bool plain_ok = getenv("UIS_STREAM_PLAIN_LAUNCH") != nullptr && atoi(getenv("UIS_STREAM_PLAIN_LAUNCH")) != 0;
-    rc = launch_cluster_kernel(lch, find_kernel(kernels::resident, m.Hp, m.Dp, CLS_NONE, &h->last_pick), h->n_cu, st.ncl,
-                               one_launch_lds(resident_lds_bytes(m.Hp, m.Dp, ss.B, ss.Kmax, ss.S)), m, st,
-                               !(ss.coop_checked && plain_ok));
-    if (rc && h->inlaunch_failed) {  // refused before anything ran: the per-step kernels take over
-      h->resident_off = true; stepwise = true;
-      if (fused) {  // ... and they need the chunk's gi0 / mse0
-        if ((rc = plain_input_proj(lch, m, d_x, ss.chunk_gi0.as<float>(), ss.chunk_mse0.as<float>(), (long)F))) return rc;
-        st.push_F = 0;
-      }
-    } else if (rc) return rc;
-    else { ran_resident = true; ss.coop_checked = true; }
-  }
-  if (stepwise) {
-    h->last_pick = KernelPick{};
-    h->last_pick.family = UIS_DK_STEPWISE; h->last_pick.Hp = m.Hp; h->last_pick.Dp = m.Dp;
-    if ((rc = enqueue_steps(h, lch, st, lds.total, (int)max_new))) return rc;
-  }
-  uint32_t abort_word = 0;
-  if (ran_resident) HIPCHK(hipMemcpyAsync(&abort_word, ss.d_ctl + 16, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // the staging block and the caller's frames may be reused
-  if (abort_word)  // an in-launch barrier gave up mid-push: the session's state is not trustworthy any more
-    return fail(UIS_ERR_HIP, "in-launch barrier failed during uis_stream_push; close the session (uis_stream_end) and reopen it "
-                             "with UIS_FLAG_STEPWISE");
-  for (int u = 0; u < U; ++u) ss.have[u] += counts[u];
-  ss.steps_run += max_new;
-  return UIS_OK;
-}
+};
 
 }  // namespace
 
 UIS_EXPORT int32_t uis_stream_push(uis_handle* h, const float* frames, const int32_t* counts) {
   if (int rc = begin_call(h, "uis_stream_push", UIS_RULE_STREAM_PUSH)) return rc;  // (this push's tables, in the chunk's own frame order)
-  if (!h || !counts) return fail(UIS_ERR_INVALID_ARG, "null handle/counts");
-  if (!h->stream_state.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
-  return stream_push_impl(h, "uis_stream_push", frames, nullptr, nullptr, counts);
+  if (!session_of(h, counts != nullptr, "null handle/counts")) return UIS_ERR_INVALID_ARG;
+  return Push{h, "uis_stream_push", frames, nullptr, nullptr, counts}.run();
 }
 
 UIS_EXPORT int32_t uis_tensors_stream_push(uis_handle* h, const uis_tensor* chunks, void* producer_stream) {
   static const char who[] = "uis_tensors_stream_push";
   if (int rc = begin_call(h, who, UIS_RULE_STREAM_PUSH)) return rc;  // (uis_stream_push's rule: this push's tables)
-  if (!h || !chunks) return fail(UIS_ERR_INVALID_ARG, "null handle/chunks");
+  if (!session_of(h, chunks != nullptr, "null handle/chunks")) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
-  if (!ss.active) return fail(UIS_ERR_INVALID_ARG, "no streaming session (uis_stream_begin first)");
   // (the resident launch of a UIS_FLAG_PERSISTENT session takes its frames from the host mailbox)
   if (ss.st.flags & UIS_FLAG_PERSISTENT)
     return fail(UIS_ERR_UNSUPPORTED, "a UIS_FLAG_PERSISTENT session takes no device tensors (uis_tensors_stream_push): its frames travel "
@@ -733,7 +735,7 @@ UIS_EXPORT int32_t uis_tensors_stream_push(uis_handle* h, const uis_tensor* chun
     if (chunks[u].rows > 0x7fffff00LL) return fail(UIS_ERR_INVALID_ARG, "utterance exceeds the session's max_frames");
     counts[u] = (int32_t)chunks[u].rows;
   }
-  return stream_push_impl(h, who, nullptr, chunks, producer_stream, counts.data());
+  return Push{h, who, nullptr, chunks, producer_stream, counts.data()}.run();
 }
 
 UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* scores_out, int32_t* overflow_out) {
@@ -741,50 +743,49 @@ UIS_EXPORT int32_t uis_stream_labels(uis_handle* h, int32_t* labels_out, float* 
   if (!session_of(h)) return UIS_ERR_INVALID_ARG;
   uis_handle::Stream& ss = h->stream_state;
   const int U = ss.U;
+  const size_t nb = (size_t)U * ss.B;
   const std::vector<int64_t> lab_off = window_offsets(ss);
   const int64_t F = lab_off[U];
   if (F > 0 && !labels_out) return fail(UIS_ERR_INVALID_ARG, "labels_out is null");
   HIPCHK(hipSetDevice(h->device));
-  int rc;
+  int rc = PM_NOT_TAKEN;  // (no resident launch to ask)
+  const MailboxLayout& box = ss.mailbox;
+  void* const pm = ss.pm_block.p;
   if (ss.persist && ss.pm_running) {
     // the resident launch back-traces every utterance and writes into the mailbox
-    unsigned char* const pm = ss.pm_block.as<unsigned char>();
-    memcpy(pm + ss.pm_o_laboff, lab_off.data(), (size_t)U * 8);
+    memcpy(uis_block_at<int64_t>(pm, box.o_lab_off), lab_off.data(), (size_t)U * 8);
     rc = pm_command(h, UIS_PM_LABELS, 0, false);
-    if (rc == UIS_OK) {
-      if (F > 0) memcpy(labels_out, pm + ss.pm_o_labels, (size_t)F * 4);
-      if (scores_out) memcpy(scores_out, pm + ss.pm_o_scores, (size_t)U * 4);
-      h->last_U = U; h->last_B = ss.B; h->nb_valid = false;
-      h->last_overflow.assign(reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow),
-                              reinterpret_cast<const int32_t*>(pm + ss.pm_o_overflow) + U);
-      h->last_beam_scores.assign(reinterpret_cast<const float*>(pm + ss.pm_o_bscores),
-                                 reinterpret_cast<const float*>(pm + ss.pm_o_bscores) + (size_t)U * ss.B);
-      emptied_windows(ss, nullptr, scores_out, 1, nullptr);
-      emptied_windows(ss, nullptr, h->last_beam_scores.data(), ss.B, nullptr, ss.B - 1);
-      return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
-    }
-    if (rc != 1) return rc;  // (1: the launch had left -- its tables are back in global memory)
+    if (rc != UIS_OK && rc != PM_NOT_TAKEN) return rc;  // (not taken: the launch had left -- its tables are back in global memory)
   }
-  DecodeState stl;
-  if ((rc = session_enter(h, &stl))) return rc;  // (no launch is running here: the mailbox path above took it or found it gone)
-  if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
-  if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
-  const UisPoison poison = UisPoison::from_env();
-  HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
-  HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
-  HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, h->stream, stl, ss.labels.as<int32_t>(),
-                     ss.scores.as<float>(), ss.d_beam_scores);
-  HIPCHK(hipGetLastError());
-  if (F > 0) HIPCHK(hipMemcpyAsync(labels_out, ss.labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-  if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, ss.scores.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
+  if (rc == UIS_OK) {
+    if (F > 0) memcpy(labels_out, uis_block_at<int32_t>(pm, box.o_labels), (size_t)F * 4);
+    if (scores_out) memcpy(scores_out, uis_block_at<float>(pm, box.o_scores), (size_t)U * 4);
+    h->last_overflow.assign(uis_block_at<int32_t>(pm, box.o_overflow), uis_block_at<int32_t>(pm, box.o_overflow) + U);
+    h->last_beam_scores.assign(uis_block_at<float>(pm, box.o_beam_scores), uis_block_at<float>(pm, box.o_beam_scores) + nb);
+  } else {
+    DecodeState stl;
+    if ((rc = session_enter(h, &stl))) return rc;  // (no launch is running here: the mailbox path above took it or found it gone)
+    if ((rc = ss.labels.ensure((size_t)std::max<int64_t>(F, 1) * 4))) return rc;
+    if ((rc = ss.scores.ensure((size_t)U * 4))) return rc;
+    const UisPoison poison = UisPoison::from_env();
+    HIPCHK(poison.device(ss.labels.p, ss.labels.cap, h->stream));
+    HIPCHK(poison.device(ss.scores.p, ss.scores.cap, h->stream));
+    HIPCHK(hipMemcpyAsync(ss.d_lab_off, lab_off.data(), (size_t)U * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_backtrace, dim3(U), dim3(64), (size_t)64 * ss.B, h->stream, stl, ss.labels.as<int32_t>(),
+                       ss.scores.as<float>(), ss.d_beam_scores);
+    HIPCHK(hipGetLastError());
+    if (F > 0) HIPCHK(hipMemcpyAsync(labels_out, ss.labels.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+    if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, ss.scores.p, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
+    h->last_overflow.assign(U, 0);
+    h->last_beam_scores.assign(nb, INFINITY);
+    HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, nb * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  // ---- the tail of both ways: the "last decode" of uis_last_decode_info / _shape is this session from here on (the
+  // readout follows); what is shown of a window that a commit emptied; the overflow words' verdict
   h->last_U = U; h->last_B = ss.B;
-  h->nb_valid = false;  // (the "last decode" of uis_last_decode_info / _shape is this session from here on: the readout follows)
-  h->last_overflow.assign(U, 0);
-  h->last_beam_scores.assign((size_t)U * ss.B, INFINITY);
-  HIPCHK(hipMemcpyAsync(h->last_overflow.data(), ss.st.overflow, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(h->last_beam_scores.data(), ss.d_beam_scores, (size_t)U * ss.B * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  h->nb_valid = false;
   emptied_windows(ss, nullptr, scores_out, 1, nullptr);
   emptied_windows(ss, nullptr, h->last_beam_scores.data(), ss.B, nullptr, ss.B - 1);
   return cluster_cap_status(count_cluster_cap(h->last_overflow, overflow_out), ss.Kmax);
@@ -854,26 +855,10 @@ __global__ __launch_bounds__(UIS_BINDINGS_WIDTH) void k_stream_bindings(DecodeSt
 UIS_EXPORT int32_t uis_stream_bindings(uis_handle* h, int32_t* out) {
   if (int rc = begin_call(h, "uis_stream_bindings", UIS_RULE_STREAM_OTHER)) return rc;
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
-  uis_handle::Stream& ss = h->stream_state;
-  const int U = ss.U;
-  CallTimer timer{h};
-  int rc;
-  DecodeState stv;
-  if ((rc = session_enter(h, &stv))) return rc;
-  ScratchPlan plan;
-  const size_t bytes = (size_t)U * UIS_BINDINGS_WIDTH * 4, o_out = plan.take(bytes);
-  char* base;
-  if ((rc = session_buffers(h, plan, bytes, &base))) return rc;
-  HIPCHK(timer.begin());
-  hipLaunchKernelGGL(k_stream_bindings, dim3(U), dim3(UIS_BINDINGS_WIDTH), 0, h->stream, stv, reinterpret_cast<int32_t*>(base + o_out));
-  HIPCHK(hipGetLastError());
-  HIPCHK(timer.end());
-  HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_out, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  memcpy(out, ss.h_land.p, bytes);
-  if (CallTimer::env("UIS_BINDINGS_TRACE"))
-    fprintf(stderr, "uis_stream_bindings: utterances %d device_ms %.3f call_ms %.3f\n", U, timer.device_ms(), timer.call_ms());
-  return UIS_OK;
+  const int U = h->stream_state.U;
+  return session_query(h, "uis_stream_bindings", "UIS_BINDINGS_TRACE", (size_t)U * UIS_BINDINGS_WIDTH * 4, out, [&](const DecodeState& stv, int32_t* d_out) {
+    hipLaunchKernelGGL(k_stream_bindings, dim3(U), dim3(UIS_BINDINGS_WIDTH), 0, h->stream, stv, d_out);
+  });
 }
 
 UIS_EXPORT int32_t uis_stream_get_limits(uis_handle* h, int32_t* out) {
@@ -967,24 +952,8 @@ __global__ __launch_bounds__(UIS_TURNS_THREADS) void k_session_turns(DecodeState
 UIS_EXPORT int32_t uis_session_turns(uis_handle* h, int32_t* out) {
   if (int rc = begin_session_call(h, "uis_session_turns")) return rc;
   if (!session_of(h, out != nullptr, "null handle/out")) return UIS_ERR_INVALID_ARG;
-  uis_handle::Stream& ss = h->stream_state;
-  const int U = ss.U;
-  CallTimer timer{h};
-  int rc;
-  DecodeState stv;
-  if ((rc = session_enter(h, &stv))) return rc;
-  ScratchPlan plan;
-  const size_t bytes = (size_t)U * 8, o_out = plan.take(bytes);
-  char* base;
-  if ((rc = session_buffers(h, plan, bytes, &base))) return rc;
-  HIPCHK(timer.begin());
-  hipLaunchKernelGGL(k_session_turns, dim3((U + UIS_TURNS_THREADS - 1) / UIS_TURNS_THREADS), dim3(UIS_TURNS_THREADS), 0, h->stream, stv, reinterpret_cast<int32_t*>(base + o_out));
-  HIPCHK(hipGetLastError());
-  HIPCHK(timer.end());
-  HIPCHK(hipMemcpyAsync(ss.h_land.p, base + o_out, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  memcpy(out, ss.h_land.p, bytes);
-  if (CallTimer::env("UIS_TURNS_TRACE"))
-    fprintf(stderr, "uis_session_turns: utterances %d device_ms %.3f call_ms %.3f\n", U, timer.device_ms(), timer.call_ms());
-  return UIS_OK;
+  const int U = h->stream_state.U;
+  return session_query(h, "uis_session_turns", "UIS_TURNS_TRACE", (size_t)U * 8, out, [&](const DecodeState& stv, int32_t* d_out) {
+    hipLaunchKernelGGL(k_session_turns, dim3((U + UIS_TURNS_THREADS - 1) / UIS_TURNS_THREADS), dim3(UIS_TURNS_THREADS), 0, h->stream, stv, d_out);
+  });
 }
