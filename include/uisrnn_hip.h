@@ -764,6 +764,52 @@ int32_t uis_score_speakers(uis_handle* h, const float* frames, const int64_t* of
                            const int32_t* labels, int32_t width, float* losses_out, float* scores_out);
 
 /*
+ * Speaker profiles: who the speakers of a GIVEN labeling are.  Utterance u has K_u clusters;
+ * cluster k holds frames t_1 < ... < t_n, counted from the utterance's first frame.
+ *   frames, offsets, labels : as uis_score_labels
+ *   width          : rows per utterance, at least every utterance's cluster count (of its valid trace) and at least 1
+ *                    -- otherwise UIS_ERR_INVALID_ARG, before any device work, and the handle stays usable
+ *   n_clusters_out : host int32 [n_utt]: K_u; -1 for an invalid trace (a label past the allowed range, the trace
+ *                    uis_score_labels scores +inf)
+ *   stats_out      : host int32 [n_utt][width][4]: {n, blocks, t_1, t_n}; blocks = the maximal runs of k in the labels
+ *                    (the ddCRP block count)
+ *   mean_out       : host float32 [n_utt][width][D]: the cluster's running mean of linear_mean2 outputs after its last
+ *                    frame -- what every later frame of the speaker would be scored against, and the bits
+ *                    uis_stream_prime leaves in the session's pool for that cluster
+ *   sum_x_out      : host float32 [n_utt][width][D] or NULL: ((0 + x[t_1]) + x[t_2]) + ..., float32, frame order
+ *   sum_r2_out     : host float32 [n_utt][width][D] or NULL: acc = +0; for j = 1 .. n: r = x[t_j] - P_j, acc = acc + r * r,
+ *                    each operation rounded to float32; P_1 = the mean of a fresh cluster (what a new speaker's MSE is
+ *                    measured against), P_j = the running mean after frame t_{j-1}: the mean uis_score_labels charged
+ *                    frame t_j against.  Summed over clusters and divided by the frame count it is the closed-form
+ *                    maximum-likelihood sigma2 under the model's own means
+ *   scores_out     : host float32 [n_utt] or NULL: what uis_score_labels gives, bit for bit (+inf for an invalid trace)
+ * Only the D real dimensions are written.  Rows k >= K_u, and every row of an invalid trace, hold stats {0, 0, -1, -1}
+ * and +0.0 in every float.  Non-finite observations propagate as the arithmetic above propagates them.  A pending
+ * uis_frame_bias table is taken and reaches scores_out only.  Refusals and side effects as uis_score_labels; on top,
+ * UIS_ERR_UNSUPPORTED, before any device work, when the utterances of one call hold more than 65535 clusters in all
+ * (one grid row per cluster chain): profile the list in parts.
+ */
+int32_t uis_speaker_profiles(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                             const int32_t* labels, int32_t width, int32_t* n_clusters_out, int32_t* stats_out,
+                             float* mean_out, float* sum_x_out, float* sum_r2_out, float* scores_out);
+
+/*
+ * Speaker profiles of an open session: the speakers of each utterance's best hypothesis right now.  A session call
+ * between launches, as uis_stream_bindings and uis_session_turns (the resident launch of a UIS_FLAG_PERSISTENT session
+ * leaves and the next push starts it again); no bit of the session changes.  (Named uis_session_*, as uis_session_turns:
+ * every other uis_stream_* call's rule applies -- pending limit / bias / stream-speaker tables stay pending, a pending
+ * uis_frame_speakers or uis_min_turn table is refused.)
+ *   width          : rows per utterance, at least the session's max_clusters -- otherwise UIS_ERR_INVALID_ARG
+ *   n_clusters_out : host int32 [n_utt]: the clusters K of the rank-0 hypothesis; 0 for a slot that has received
+ *                    nothing; -1 for an utterance without a live hypothesis (cluster-cap overflow, an emptied beam)
+ *   stats_out      : host int32 [n_utt][width][4]: {frames the cluster has absorbed, its block count, its known-speaker
+ *                    tag (0: none), 0}; cluster indices are uis_stream_labels' numbering at this moment
+ *   mean_out       : host float32 [n_utt][width][D]: the cluster's running mean, from the session's pool
+ * Rows past K (every row where K = -1): stats {0, 0, -1, -1}, +0.0 in every float.
+ */
+int32_t uis_session_profiles(uis_handle* h, int32_t width, int32_t* n_clusters_out, int32_t* stats_out, float* mean_out);
+
+/*
  * N-best readout: the labels of EVERY hypothesis of the final beam, not only of rank 0.  A decode
  * leaves the back-pointers of all beam_size ranks and the final beam's scores on the device; these
  * calls only read them (no decode kernel is involved).

@@ -17,5 +17,7 @@ parallel_predict = _uisrnn.parallel_predict
 OnlineSession = _uisrnn.OnlineSession  # extension: streaming decode
 StreamPool = _uisrnn.StreamPool  # extension: an open-ended set of streams over one session's slots
 speaker_posteriors = _uisrnn.speaker_posteriors  # extension: soft assignments from UISRNN.score_speakers' rows
+speaker_distances = _uisrnn.speaker_distances  # extension: weighted MSE between the speakers of two profiles
+SpeakerProfile = _uisrnn.SpeakerProfile  # extension: what UISRNN.speaker_profiles returns per sequence
 EmptyBeamError = _uisrnn.EmptyBeamError
 LookAheadWindowError = _uisrnn.LookAheadWindowError

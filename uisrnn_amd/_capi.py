@@ -545,6 +545,10 @@ def load_library(path=None):
   lib.uis_score_labels.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, _fp, _fp]
   lib.uis_score_speakers.restype = i32
   lib.uis_score_speakers.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, i32, _fp, _fp]
+  lib.uis_speaker_profiles.restype = i32
+  lib.uis_speaker_profiles.argtypes = [ctypes.c_void_p, _fp, i64p, i32, i32p, i32, i32p, i32p, _fp, _fp, _fp, _fp]
+  lib.uis_session_profiles.restype = i32
+  lib.uis_session_profiles.argtypes = [ctypes.c_void_p, i32, i32p, i32p, _fp]
   lib.uis_eval_last_decode.restype = i32
   lib.uis_eval_last_decode.argtypes = [ctypes.c_void_p, i32p, i32, i64p]
   lib.uis_host_alloc.restype = i32
@@ -582,6 +586,7 @@ EXPORTED_SYMBOLS = (
     'uis_eval_last_decode', 'uis_score_labels', 'uis_score_speakers', 'uis_decode_limits', 'uis_stream_limits',
     'uis_stream_get_limits', 'uis_frame_bias', 'uis_frame_speakers', 'uis_min_turn', 'uis_stream_speakers', 'uis_stream_bindings',
     'uis_session_min_turn', 'uis_session_get_min_turn', 'uis_session_turns',
+    'uis_speaker_profiles', 'uis_session_profiles',
     'uis_ingest_tensors', 'uis_tensors_decode', 'uis_tensors_stream_push',
     'uis_host_alloc', 'uis_host_free', 'uis_last_error',
     'uis_train_create', 'uis_train_set_data', 'uis_train_step', 'uis_train_param_count',
@@ -895,6 +900,34 @@ class Decoder:
     self._check(rc, 'uis_score_speakers')
     return scores, losses
 
+  def speaker_profiles(self, frames, offsets, labels, width, bias=None):
+    """The speakers of given labelings (uis_speaker_profiles).
+
+    Args:
+      frames, offsets, labels: as score_labels.
+      width: rows per utterance: at least the largest cluster count of the utterances.
+      bias: a per-frame transition_bias table; it reaches `scores` only.
+    Returns:
+      dict(n_clusters int32 [U] (-1: an invalid trace), stats int32 [U, width, 4] {frames, blocks, first, last},
+      mean / sum_x / sum_r2 float32 [U, width, D], scores float32 [U] -- score_labels' bits).  Rows past an utterance's
+      cluster count, and every row of an invalid trace: stats {0, 0, -1, -1} and +0.0.
+    """
+    frames, offsets, labels = self._packed(frames, offsets, labels)
+    n_utt = offsets.shape[0] - 1
+    width = int(width)
+    rows = (n_utt, max(width, 0))
+    dim = self.observation_dim
+    out = {'n_clusters': np.zeros(n_utt, dtype=np.int32), 'stats': np.zeros(rows + (4,), dtype=np.int32),
+           'mean': np.zeros(rows + (dim,), dtype=np.float32), 'sum_x': np.zeros(rows + (dim,), dtype=np.float32),
+           'sum_r2': np.zeros(rows + (dim,), dtype=np.float32), 'scores': np.zeros(n_utt, dtype=np.float32)}
+    if bias is not None:
+      self.set_frame_bias(bias)
+    rc = self._lib.uis_speaker_profiles(
+        self._handle, _ptr(frames), _i64(offsets), n_utt, _i32(labels), width, _i32(out['n_clusters']), _i32(out['stats']),
+        _ptr(out['mean']), _ptr(out['sum_x']), _ptr(out['sum_r2']), _ptr(out['scores']))
+    self._check(rc, 'uis_speaker_profiles')
+    return out
+
   def last_instantiation(self):
     """(family, Hp, Dp, variant, persist) of the kernel-table entry behind the last decode, or behind the last
     launch of a stream_push: uis_last_decode_instantiation, family as a name of DECODE_KERNELS."""
@@ -979,6 +1012,19 @@ class Decoder:
     moment, its run}; the run is 0 where the slot has no rule; {-1, 0} without a live hypothesis."""
     out = np.zeros((self._stream_n, 2), dtype=np.int32)
     self._check(self._lib.uis_session_turns(self._handle, _i32(out)), 'uis_session_turns', ok=(UIS_OK,))
+    return out
+
+  def stream_profiles(self, width=None):
+    """uis_session_profiles: the speakers of each utterance's best hypothesis right now -- dict(n_clusters int32 [U]
+    (0: nothing received, -1: no live hypothesis), stats int32 [U, width, 4] {frames, blocks, tag, 0}, mean float32
+    [U, width, D]); cluster indices in the numbering of stream_labels at this moment; rows past the cluster count hold
+    {0, 0, -1, -1} and +0.0.  width defaults to the session's max_clusters and may not be smaller."""
+    width = self._stream_cap if width is None else int(width)
+    rows = (self._stream_n, max(width, 0))
+    out = {'n_clusters': np.zeros(self._stream_n, dtype=np.int32), 'stats': np.zeros(rows + (4,), dtype=np.int32),
+           'mean': np.zeros(rows + (self.observation_dim,), dtype=np.float32)}
+    rc = self._lib.uis_session_profiles(self._handle, width, _i32(out['n_clusters']), _i32(out['stats']), _ptr(out['mean']))
+    self._check(rc, 'uis_session_profiles', ok=(UIS_OK,))
     return out
 
   def stream_push(self, chunks, bias=None, speakers=None):

@@ -7,7 +7,8 @@
 //   entry points                                  limits  bias    hint    stream_tags  min_turn
 //   uis_decode, uis_decode_f64, uis_decode_device,
 //   uis_tensors_decode                            take    take    take    leave        take
-//   uis_score_labels, uis_score_speakers          leave   take    refuse  leave        refuse
+//   uis_score_labels, uis_score_speakers,
+//   uis_speaker_profiles                          leave   take    refuse  leave        refuse
 //   uis_stream_begin                              take    leave   refuse  leave        refuse
 //   uis_stream_push, uis_tensors_stream_push      leave   take    refuse  take         refuse
 //   uis_stream_prime                              leave   refuse  refuse  take         refuse

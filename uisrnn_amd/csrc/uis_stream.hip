@@ -957,3 +957,76 @@ UIS_EXPORT int32_t uis_session_turns(uis_handle* h, int32_t* out) {
     hipLaunchKernelGGL(k_session_turns, dim3((U + UIS_TURNS_THREADS - 1) / UIS_TURNS_THREADS), dim3(UIS_TURNS_THREADS), 0, h->stream, stv, d_out);
   });
 }
+
+namespace {
+
+#define UIS_PROFILES_THREADS 256
+
+// The speakers of the best hypothesis, one workgroup per utterance, threads over (cluster,
+// dimension), between launches.  Rank 0 of the final beam holds K clusters; cluster k -- the numbering uis_stream_labels
+// uses right now -- lives in pool slot beam_slot[k]: n[u] = K, stats[u][k] = {pool_cnt of the slot, the count and the
+// tag of the block-count word, 0}, mean[u][k] = the D real dimensions of the slot's pool_mean row.  Rows k >= K:
+// {0, 0, -1, -1} and +0.0.  n[u] = -1 and every row absent for an utterance without a live hypothesis (an emptied beam,
+// the overflow word set); 0 for one that has received nothing.  A window that a commit emptied keeps its one hypothesis.
+__global__ __launch_bounds__(UIS_PROFILES_THREADS) void k_session_profiles(DevModel m, DecodeState st, int width, int32_t* __restrict__ n_out,
+                                                                           int4* __restrict__ stats, float* __restrict__ mean) {
+  const int u = blockIdx.x, tid = threadIdx.x;
+  if (u >= st.U) return;
+  const auto [N, T, par, nb, live, e, bp] = beam_view(st, u, EMPTY_WINDOW_KEEPS_BEAM);
+  int K = -1;
+  if (live > 0) {
+    K = st.beam_K[e];   // rank 0
+    const int cap = st.Kmax < width ? st.Kmax : width;
+    K = K < 0 ? 0 : (K > cap ? cap : K);
+  }
+  if (tid == 0) n_out[u] = K;
+  const int32_t* slot = st.beam_slot + e * st.Kmax;
+  const int32_t* blk = st.beam_blk + e * st.Kmax;
+  for (int k = tid; k < width; k += UIS_PROFILES_THREADS) {
+    int4 v = make_int4(0, 0, -1, -1);
+    if (k < K) {
+      const int sl = slot[k], w = blk[k];
+      v = make_int4(sl >= 0 && sl < st.S ? st.pool_cnt[(size_t)u * st.S + sl] : 0, blk_count(w), blk_tag(w), 0);
+    }
+    stats[(size_t)u * width + k] = v;
+  }
+  const int total = width * m.D;
+  for (int idx = tid; idx < total; idx += UIS_PROFILES_THREADS) {
+    const int k = idx / m.D, d = idx - k * m.D;
+    float v = 0.0f;
+    if (k < K) {
+      const int sl = slot[k];
+      if (sl >= 0 && sl < st.S) v = st.pool_mean[((size_t)u * st.S + sl) * m.Dp + d];
+    }
+    mean[(size_t)u * total + idx] = v;
+  }
+}
+
+}  // namespace
+
+// Who the best hypothesis' speakers are right now: see include/uisrnn_hip.h.  The scaffold's order; nothing of the
+// session changes.  One output block {n [U], stats [U][width][4], mean [U][width][D]}, split on the host.
+UIS_EXPORT int32_t uis_session_profiles(uis_handle* h, int32_t width, int32_t* n_clusters_out, int32_t* stats_out, float* mean_out) {
+  if (int rc = begin_session_call(h, "uis_session_profiles")) return rc;
+  if (!session_of(h, n_clusters_out && stats_out && mean_out, "null handle/n_clusters_out/stats_out/mean_out")) return UIS_ERR_INVALID_ARG;
+  const uis_handle::Stream& ss = h->stream_state;
+  const int U = ss.U, D = h->m.D;
+  if (width < ss.Kmax)
+    return fail(UIS_ERR_INVALID_ARG, "width must be at least the session's max_clusters (" + std::to_string(ss.Kmax) + "), not " +
+                                         std::to_string(width));
+  if ((int64_t)U * width * (D + 4) > 0x1fffffffLL) return fail(UIS_ERR_UNSUPPORTED, "the profiles of one call exceed 2 GB: a smaller width");
+  const size_t rows = (size_t)U * width;
+  const size_t o_stats = ((size_t)U * 4 + 15) & ~(size_t)15, o_mean = o_stats + rows * 16, bytes = o_mean + rows * D * 4;
+  std::vector<char> block(bytes);
+  const DevModel m = h->m;
+  int rc = session_query(h, "uis_session_profiles", "UIS_PROFILES_TRACE", bytes, block.data(), [&](const DecodeState& stv, int32_t* d_out) {
+    char* base = reinterpret_cast<char*>(d_out);
+    hipLaunchKernelGGL(k_session_profiles, dim3(U), dim3(UIS_PROFILES_THREADS), 0, h->stream, m, stv, (int)width, d_out,
+                       reinterpret_cast<int4*>(base + o_stats), reinterpret_cast<float*>(base + o_mean));
+  });
+  if (rc) return rc;
+  memcpy(n_clusters_out, block.data(), (size_t)U * 4);
+  memcpy(stats_out, block.data() + o_stats, rows * 16);
+  memcpy(mean_out, block.data() + o_mean, rows * D * 4);
+  return UIS_OK;
+}

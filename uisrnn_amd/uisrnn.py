@@ -1184,6 +1184,110 @@ class UISRNN:
         lambda losses, k, u, rows: losses[rows, :widths[u]].copy())
     return out[0] if single else out
 
+  def speaker_profiles(self, test_sequences, test_cluster_ids, transition_bias=None):
+    """Who the speakers of given labelings are (extension; uis_speaker_profiles).
+
+    Per speaker of a sequence: how many frames and turns it has, where it first and last speaks, the model's mean for
+    it -- the running mean of linear_mean2 outputs that any later frame of the speaker would be scored against --, the
+    sum of its frames, and the per-dimension sum of squared residuals of its frames against the mean each was charged
+    against.  The mean is what speaker_distances compares across sequences or with enrolled vectors; the residual sums
+    are what sigma2_estimate adds up.
+
+    Args:
+      test_sequences, test_cluster_ids, transition_bias: as score_labels (the bias reaches `score` only).
+    Returns:
+      a SpeakerProfile (array) or a list of them (list).  A labeling that is a list of ids is valid by construction.
+    """
+    single, seqs, labels = self._labeled_sequences(test_sequences, test_cluster_ids)
+    _, _, raw_ids = _sequences_with_ids(test_sequences, test_cluster_ids, 'test_cluster_ids')
+    names = [list(dict.fromkeys(i.tolist() if isinstance(i, np.ndarray) else list(i))) for i in raw_ids]
+    widths = [max(len(n), 1) for n in names]
+    bias = _check_transition_bias(transition_bias, [s.shape[0] for s in seqs], single=single, offline=False)
+
+    def cut(result, k, u, rows):
+      del rows
+      count = len(names[u])
+      stats = result['stats'][k, :count]
+      return SpeakerProfile(names[u], stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy(), stats[:, 3].copy(),
+                            result['mean'][k, :count].copy(), result['sum_x'][k, :count].copy(),
+                            result['sum_r2'][k, :count].copy(), float(result['scores'][k]))
+
+    out = self._score_in_halves(
+        seqs, labels, bias,
+        lambda decoder, members, *packed, bias: decoder.speaker_profiles(
+            *packed, max(widths[u] for u in members), bias=bias),
+        cut)
+    return out[0] if single else out
+
+  def sigma2_estimate(self, test_sequences, test_cluster_ids):
+    """The closed-form maximum-likelihood sigma2 of labeled sequences under the model's OWN means (extension).
+
+    sigma2[d] = sum over sequences and speakers of sum_r2[d] / total frames, where sum_r2 is speaker_profiles': the
+    squared residual of every frame against the mean the model charged it against (the running mean of its speaker
+    before the frame; the fresh-cluster mean at a speaker's first frame).  Summed on the host in float64, in list
+    order.  No training is involved and nothing of the model changes: whether to use the estimate on a new domain is
+    the caller's decision (`model.sigma2 = model.sigma2_estimate(...)`).  (The name `estimate_sigma2` is the
+    reference's boolean training flag on this class.)
+
+    Returns:
+      float64 [observation_dim]; NaN everywhere when the sequences hold no frame.
+    """
+    profiles = self.speaker_profiles(test_sequences, test_cluster_ids)
+    if isinstance(profiles, SpeakerProfile):
+      profiles = [profiles]
+    total = np.zeros(self.observation_dim, dtype=np.float64)
+    frames = 0
+    for profile in profiles:
+      for k in range(len(profile.ids)):
+        total = total + profile.sum_r2[k].astype(np.float64)
+        frames += int(profile.frames[k])
+    with np.errstate(invalid='ignore', divide='ignore'):
+      return total / np.float64(frames)
+
+
+class SpeakerProfile(object):
+  """The speakers of one labeled sequence (UISRNN.speaker_profiles), K of them, in first-appearance order:
+    ids      the caller's ids
+    frames   int32 [K] frames per speaker;  blocks  int32 [K] turns (maximal runs) per speaker
+    first, last  int32 [K] the speaker's first and last frame
+    mean     float32 [K, D] the model's running mean for the speaker after its last frame
+    sum_x    float32 [K, D] the float32 sum of its frames, in frame order
+    sum_r2   float32 [K, D] the float32 sum of squared residuals against the means its frames were charged against
+    centroid float64 [K, D] sum_x / frames
+    score    the labeling's negative log-likelihood (score_labels')"""
+
+  __slots__ = ('ids', 'frames', 'blocks', 'first', 'last', 'mean', 'sum_x', 'sum_r2', 'score')
+
+  def __init__(self, ids, frames, blocks, first, last, mean, sum_x, sum_r2, score):
+    self.ids, self.frames, self.blocks, self.first, self.last = list(ids), frames, blocks, first, last
+    self.mean, self.sum_x, self.sum_r2, self.score = mean, sum_x, sum_r2, score
+
+  @property
+  def centroid(self):
+    return self.sum_x.astype(np.float64) / np.asarray(self.frames, dtype=np.float64)[:, None]
+
+
+def speaker_distances(model, a, b):
+  """The model's distance between every speaker of `a` and every speaker of `b`: float64 [K_a, K_b] of
+  sum_d (mean_a[d] - mean_b[d])^2 / (2 sigma2[d]) -- the weighted MSE the decode itself uses between a frame and a
+  speaker's mean, here between two means.  On the host.
+
+  Args:
+    model: a UISRNN (its sigma2 weighs the dimensions).
+    a, b: SpeakerProfiles, session profiles (dicts with 'mean') or [K, D] arrays -- enrolled vectors, say.
+  Which speakers are the same person (a threshold, an assignment) is left to the caller.
+  """
+  def means(p):
+    m = p.mean if isinstance(p, SpeakerProfile) else (p['mean'] if isinstance(p, dict) else p)
+    m = np.asarray(m, dtype=np.float64)
+    if m.ndim != 2 or m.shape[1] != model.observation_dim:
+      raise ValueError('speaker means must be [K, observation_dim] arrays.')
+    return m
+  ma, mb = means(a), means(b)
+  weight = 1.0 / (2.0 * np.asarray(model.sigma2, dtype=np.float64).reshape(-1))
+  diff = ma[:, None, :] - mb[None, :, :]
+  return (diff * diff * weight).sum(axis=2)
+
 
 def speaker_posteriors(losses, temperature=1.0):
   """Soft speaker assignments from UISRNN.score_speakers' rows: the row-wise softmax of -losses / temperature.
@@ -1360,6 +1464,26 @@ class OnlineSession:
       bound = [(name, int(table[u, tag])) for name, tag in names.items() if table[u, tag] >= 0]
       ids = self._ids(u, [c for _, c in bound])
       out.append({name: ids[i] for i, (name, _) in enumerate(bound)})
+    return out
+
+  def profiles(self):
+    """Who the speakers of each utterance's best hypothesis are right now (uis_session_profiles):
+    per utterance a dict(ids, frames, blocks, names, mean) -- ids: the speakers' ids as labels() gives them (retired ids
+    stay gone, handed-out ids never change); frames / blocks: int32 [K], the frames and turns each has over the whole
+    stream; names: the known speaker bound to each, or None; mean: float32 [K, D], the model's running mean for each --
+    or None for an utterance without a live hypothesis.  Nothing of the session changes."""
+    table = self._decoder.stream_profiles()
+    out = []
+    for u in range(self._num_utterances):
+      count = int(table['n_clusters'][u])
+      if count < 0:
+        out.append(None)
+        continue
+      stats = table['stats'][u, :count]
+      by_tag = {tag: name for name, tag in self._name_tables()[u].items()}
+      out.append({'ids': self._ids(u, list(range(count))), 'frames': stats[:, 0].copy(), 'blocks': stats[:, 1].copy(),
+                  'names': [by_tag.get(int(tag)) if tag > 0 else None for tag in stats[:, 2]],
+                  'mean': table['mean'][u, :count].copy()})
     return out
 
   def prime(self, chunks, cluster_ids, known_speakers=None):
@@ -1976,6 +2100,12 @@ class StreamPool:
   def speakers(self, key):
     """{name: label} of the stream's known speakers (OnlineSession.speakers for its slot)."""
     return self._session.speakers()[self._slot[key]]
+
+  def profiles(self, key):
+    """The stream's speakers right now (OnlineSession.profiles for its slot): dict(ids, frames, blocks, names, mean), or
+    None without a live hypothesis.  The library call answers for every slot of the session at once, so each key pays
+    the whole session's query: a caller that wants many keys at one moment reads OnlineSession.profiles() once."""
+    return self._session.profiles()[self._slot[key]]
 
   def speaker_names(self, key):
     """The stream's known speakers in tag order (OnlineSession.speaker_names)."""
